@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — residues/s of the NA-MPNN encoder+decoder forward on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1|cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1|cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -73,6 +73,7 @@ TRAFFIC_ALGO = {"enc_message": 1000 * (24_576 + 192 + 4 * 512), "dec_message": 1
 KERNEL_OF = {"encdec_persistent": "encdec_persistent_kernel"}      # launch kind -> kernel name when it is not edge_mlp_kernel
 # executed FLOP / residue of the hoisted formulation (three 128x128 GEMMs per edge)
 EXEC_FLOP_EDGE = 48 * 3 * 2 * 128 * 128
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: array bytes in all (the .npy files stay under 64 MB)
 
 
 class Runner:
@@ -837,13 +838,41 @@ class ClockSampler:
         return round(sum(self.samples) / len(self.samples)) if self.samples else None
 
 
+def capture_outputs(runner):
+    """Host float32 copies of what one step hands its caller (log_probs, h_V, h_E), at most DUMP_BUDGET_BYTES in all.  An array
+    that does not fit the rest of the budget is replaced by a fixed, seeded sample of its rows (last axis kept whole), stored
+    with the flat row indices beside it as `<name>_rows` (float64, exact)."""
+    out, left = {}, DUMP_BUDGET_BYTES
+    for name, t in (("log_probs", runner.logp), ("h_V", runner.hV), ("h_E", runner.hE)):
+        rows = t.reshape(-1, t.shape[-1])
+        row_bytes = rows.shape[1] * 4
+        if rows.shape[0] * row_bytes <= left:
+            out[name] = t.float().cpu().numpy()
+            left -= out[name].nbytes
+            continue
+        n = min(rows.shape[0], left // (row_bytes + 8))
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=n, replace=False))
+        out[name] = rows[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+        out[name + "_rows"] = idx.astype(np.float64)
+        left -= out[name].nbytes + out[name + "_rows"].nbytes
+    return out
+
+
+def write_outputs(outputs, directory):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def coll_device(dev, dist):
     """Device of the collectives' buffers: the GPU under RCCL; host memory when the harness is exercised over gloo."""
     return torch.device("cpu") if (dist is not None and dist.get_backend() == "gloo") else dev
 
 
-def encdec_bench(args, dev, rank, world, dist, workload, precision, steps, warmup, profile_steps=None):
-    """Time `steps` passes of the encoder+decoder forward (one namp_encdec_fwd call each) at `precision`."""
+def encdec_bench(args, dev, rank, world, dist, workload, precision, steps, warmup, profile_steps=None, capture=False):
+    """Time `steps` passes of the encoder+decoder forward (one namp_encdec_fwd call each) at `precision`.  capture=True keeps
+    host copies of the last timed step's outputs in `runner.outputs` (see capture_outputs)."""
     cfg = WORKLOADS[workload]
     B, N, K = cfg["B"], cfg["N"], cfg["K"]
     cfg_idx = 1 if workload == "cfg2" else 2
@@ -871,6 +900,8 @@ def encdec_bench(args, dev, rank, world, dist, workload, precision, steps, warmu
         torch.cuda.synchronize()
         barrier()
         elapsed = time.perf_counter() - t0
+    if capture:
+        runner.outputs = capture_outputs(runner)         # outside the timed region, before any further step
     if dist is not None:
         t = torch.tensor([elapsed], device=coll_device(dev, dist), dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1142,7 +1173,12 @@ def main():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short cfg3 / cfg5 / cfg1 runs appended to the default line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="cfg2 / cfg3: write what the headline's last timed step computed (log_probs, h_V, h_E of rank 0; float32, "
+                         "< 64 MB in all, a seeded row sample of what does not fit) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("cfg2", "cfg3"):
+        raise SystemExit(f"bench.py: --dump-outputs covers the encoder+decoder workloads cfg2 / cfg3, not {args.workload}")
     # default step counts per workload: the timed region is >= ~0.2 s everywhere (cfg5: a training step is ~100x a cfg2 forward)
     if args.steps is None:
         args.steps = {"cfg2": 500, "cfg3": 50, "cfg1": 20, "cfg4": 2, "cfg5": 10}.get(args.workload, 50)
@@ -1216,7 +1252,11 @@ def main():
         return finish(train_bench(args, dev, rank, world, dist))
 
     precision = args.precision or ("bf16" if args.workload == "cfg3" else "fp32")
-    out, runner = encdec_bench(args, dev, rank, world, dist, args.workload, precision, args.steps, args.warmup)
+    out, runner = encdec_bench(args, dev, rank, world, dist, args.workload, precision, args.steps, args.warmup,
+                               capture=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        write_outputs(runner.outputs, args.dump_outputs)
+        del runner.outputs
     ref_out = None
     traffic = None
     if rank == 0 and world == 1:

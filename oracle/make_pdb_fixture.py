@@ -7,12 +7,14 @@
   locations, zero occupancy, a HETATM amino acid of ProDy's non-standard table (MSE), an amino acid without CA, residue names
   outside ProDy's tables (UNK, PSU), insertion codes, a 5'-terminal nucleotide without phosphate, waters, a second MODEL;
 * tests/golden/pdb/{4oqu,1am9}_expected.npz — the same arrays for the reference's two example inputs
-  (/root/reference/inference/examples: present in the build container only; the files themselves are not copied).
+  (public PDB entries 4OQU and 1AM9, stored beside them xz-compressed as tests/golden/pdb/{4oqu,1am9}.pdb.xz).
 
     python oracle/make_pdb_fixture.py
 """
+import lzma
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -106,15 +108,17 @@ def main():
         d = expected(pdb, **kw)
         np.savez_compressed(os.path.join(OUT, f"edge_cases_expected_{tag}.npz"), **d)
         print(tag, "L =", len(d["S"]), "S =", d["S"].tolist(), "chain_labels =", d["chain_labels"].tolist(), "mask =", d["mask"].tolist())
-    ex = "/root/reference/inference/examples"
-    if os.path.isdir(ex):
-        for name in ("4oqu", "1am9"):
-            d = expected(os.path.join(ex, name + ".pdb"), na_shared_tokens=True)
-            d.pop("X")                                  # coordinates stay with the reference's file; a digest pins them
-            d["X_checksum"] = np.float64(pdb_ref.parse_PDB(os.path.join(ex, name + ".pdb"), na_shared_tokens=True)["X"].astype(np.float64).sum())
-            np.savez_compressed(os.path.join(OUT, f"{name}_expected.npz"), **d)
-            print(name, "L =", len(d["S"]), "protein/dna/rna/masked =", int(d["protein_mask"].sum()), int(d["dna_mask"].sum()),
-                  int(d["rna_mask"].sum()), int((d["mask"] == 0).sum()), "chains =", sorted(set(d["chain_letters"].tolist())))
+    for name in ("4oqu", "1am9"):
+        with tempfile.TemporaryDirectory() as tmp:
+            src = os.path.join(tmp, name + ".pdb")
+            with lzma.open(os.path.join(OUT, name + ".pdb.xz")) as fi, open(src, "wb") as fo:
+                fo.write(fi.read())
+            d = expected(src, na_shared_tokens=True)
+            d.pop("X")                              # coordinates stay in the .pdb file; a digest pins them
+            d["X_checksum"] = np.float64(pdb_ref.parse_PDB(src, na_shared_tokens=True)["X"].astype(np.float64).sum())
+        np.savez_compressed(os.path.join(OUT, f"{name}_expected.npz"), **d)
+        print(name, "L =", len(d["S"]), "protein/dna/rna/masked =", int(d["protein_mask"].sum()), int(d["dna_mask"].sum()),
+              int(d["rna_mask"].sum()), int((d["mask"] == 0).sum()), "chains =", sorted(set(d["chain_letters"].tolist())))
 
 
 if __name__ == "__main__":

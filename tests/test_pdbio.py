@@ -1,5 +1,7 @@
-"""f3: the prody-free PDB reader (na_mpnn_amd/pdbio.py) — write/read round trips of synthetic complexes and,
-in the build container only, the facts SURVEY App. B records for the reference's two example files."""
+"""f3: the prody-free PDB reader (na_mpnn_amd/pdbio.py) — write/read round trips of synthetic complexes and the facts
+SURVEY App. B records for the reference's two example files (public PDB entries 4OQU and 1AM9, stored xz-compressed in
+tests/golden/pdb)."""
+import lzma
 import os
 
 import numpy as np
@@ -7,8 +9,15 @@ import pytest
 
 from na_mpnn_amd import pdbio, spec, synth
 
-REF_EXAMPLES = "/root/reference/inference/examples"
 INT_TO_RES = {v: k for k, v in spec.restype_to_int().items()}
+
+
+def _example(golden_dir, tmp_path, name):
+    """Path of the unpacked example file `name`.pdb (stored as tests/golden/pdb/<name>.pdb.xz)."""
+    path = os.path.join(tmp_path, name + ".pdb")
+    with lzma.open(os.path.join(golden_dir, "pdb", name + ".pdb.xz")) as src, open(path, "wb") as dst:
+        dst.write(src.read())
+    return path
 
 
 def _write(tmp_path, cx, chain_letters="ABCDEFGH"):
@@ -60,12 +69,11 @@ def test_renumber_insertion_codes():
     assert pdbio.renumber(np.array([5, 6, 6, 6, 7, 10])).tolist() == [5, 6, 7, 8, 9, 12]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLES), reason="reference example files only exist in the build container")
-def test_reference_example_files():
-    p = pdbio.parse_pdb(os.path.join(REF_EXAMPLES, "4oqu.pdb"))
+def test_reference_example_files(golden_dir, tmp_path):
+    p = pdbio.parse_pdb(_example(golden_dir, tmp_path, "4oqu"))
     assert len(p["S"]) == 97 and set(p["chain_letters"]) == {"A"}            # 97-nt RNA, one chain
     assert p["rna_mask"].sum() == 97 and p["mask"].sum() == 97
-    q = pdbio.parse_pdb(os.path.join(REF_EXAMPLES, "1am9.pdb"))
+    q = pdbio.parse_pdb(_example(golden_dir, tmp_path, "1am9"))
     assert len(q["S"]) == 389 and len(set(q["chain_letters"])) == 8          # 313 aa + 76 nt, 8 chains
     assert q["protein_mask"].sum() == 313 and q["dna_mask"].sum() == 72 and q["mask"].sum() == 385
 
@@ -200,16 +208,13 @@ def test_oracle_restatement_reproduces_its_fixture(golden_dir):
 
 @pytest.mark.parametrize("name,facts", [("4oqu", dict(L=97, protein=0, dna=0, rna=97, masked=0, chains=1)),
                                         ("1am9", dict(L=389, protein=313, dna=72, rna=0, masked=4, chains=8))])
-def test_reference_examples_match_the_oracle_arrays(golden_dir, name, facts):
-    """The reference's two example inputs (inference/examples, build container only: the files are not copied into the repo):
+def test_reference_examples_match_the_oracle_arrays(golden_dir, tmp_path, name, facts):
+    """The reference's two example inputs (public PDB entries, stored in tests/golden/pdb):
     the product's reader against the oracle-made arrays of tests/golden/pdb, and those against SURVEY App. B's facts."""
     g = np.load(os.path.join(golden_dir, "pdb", f"{name}_expected.npz"))
     assert len(g["S"]) == facts["L"] and int(g["protein_mask"].sum()) == facts["protein"] and int(g["dna_mask"].sum()) == facts["dna"]
     assert int(g["rna_mask"].sum()) == facts["rna"] and int((g["mask"] == 0).sum()) == facts["masked"]
     assert len(set(g["chain_letters"].tolist())) == facts["chains"]
-    path = f"/root/reference/inference/examples/{name}.pdb"
-    if not os.path.exists(path):
-        pytest.skip("the reference's example files exist in the build container only")
-    P = pdbio.parse_pdb(path, na_shared_tokens=True)
+    P = pdbio.parse_pdb(_example(golden_dir, tmp_path, name), na_shared_tokens=True)
     _check_against(g, P, with_X=False)
     assert abs(float(P["X"].astype(np.float64).sum()) - float(g["X_checksum"])) < 1e-6

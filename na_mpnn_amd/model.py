@@ -15,8 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import sys
-
-import os
+import warnings
 import weakref
 
 import numpy as np
@@ -125,6 +124,88 @@ def level_work_lists(level, group_first, group_last, order0, E_idx0, split):
     flat = level.reshape(-1)[head_pos].long()
     perm = torch.argsort(flat, stable=True)
     return head_pos[perm], flat[perm], sizes[perm].contiguous(), close, close_off
+
+
+def symmetry_visits(groups, weights, order0, L):
+    """Visit plan of symmetry-tied sampling (model_utils.py:220-235): tied residues are visited together, in the order stream 0's
+    decoding order `order0` (a list of the L residues) reaches their first member; every stream then uses that one order.  A residue
+    listed in several groups belongs to the FIRST listed one (as in the reference).  groups / weights: the feature_dict's
+    symmetry_residues / symmetry_weights.  Returns lists of L: (visits, group_first, group_last, w) = the residues in visit order, the
+    first visit of each visit's group, 1 on a group's last visit (else 0), and the weight of each residue (1 outside the groups)."""
+    w = [1.0] * L
+    for i1, group in enumerate(groups):
+        for i2, item in enumerate(group):
+            w[item] = float(weights[i1][i2])
+    group_of = {}
+    for g in groups:
+        for item in g:
+            group_of.setdefault(int(item), g)
+    seen, visit_groups = set(), []
+    for t in order0:
+        if t in seen:
+            continue
+        visit_groups.append(list(group_of.get(t, (t,))))
+        seen.update(visit_groups[-1])
+    visits = [t for g in visit_groups for t in g]
+    if sorted(visits) != list(range(L)):
+        raise ValueError("symmetry_residues groups must be disjoint")
+    gf, gl, v = [], [], 0
+    for g in visit_groups:
+        gf += [v] * len(g); gl += [0] * (len(g) - 1) + [1]; v += len(g)
+    return visits, gf, gl, w
+
+
+def pair_bias_dependencies(pair_bias, max_deps=64):
+    """Extra dependencies of the sampler's levels from pair_bias [B, L, A, L, A] (model_utils.py:116,169-172): the bias of residue i
+    reads the token of every residue j whose block pair_bias[:, i, :, j, :] is not all zero — the sequence neighbours for run.py's
+    --pair_bias_AA (data_utils.py:7-16).  A non-finite entry counts as a dependency.  Returns (dep_idx, n_dep): n_dep = the most partners
+    of any residue, dep_idx [B, L, n_dep] int32 their indices padded with -1 (None when n_dep == 0); None when some residue has more than
+    `max_deps` partners (namp_sample_levels_dep's limit: a dense bias keeps the sequential walk)."""
+    B, L, A = pair_bias.shape[:3]
+    dev = pair_bias.device
+    # (row block by row block: one amax over the whole [B, L, 33, L, 33] tensor would materialise a second copy of it — 4.4 GB at L = 1000)
+    nz = torch.empty(B, L, L, dtype=torch.bool, device=dev)
+    step = max(1, (1 << 26) // max(1, A * L * A))
+    for i0 in range(0, L, step):
+        blk = pair_bias[:, i0:i0 + step]
+        nz[:, i0:i0 + step] = ((blk != 0) | ~torch.isfinite(blk)).any(dim=4).any(dim=2)
+    n_dep = int(nz.sum(-1).max())
+    if n_dep > max_deps:
+        return None
+    if n_dep == 0:
+        return None, 0
+    cols = torch.where(nz, torch.arange(L, device=dev)[None, None, :], torch.full((), L, device=dev))
+    cols = cols.sort(dim=-1).values[:, :, :n_dep]
+    return torch.where(cols < L, cols, torch.full((), -1, device=dev)).to(torch.int32).contiguous(), n_dep
+
+
+class _DecodingOrder:
+    """The decoding order of ONE score / forward / sample call: order int64, order32 / rank int32 [B', L].  With the HIP sort
+    (namp_decoding_order) the three tensors are allocated but not yet written while `pending`: the call's featuriser launch takes the
+    sort along as the first workgroups of its edge-feature launch (`_featurize_hip(order=...)`, namp_featurize_ordered), and `wait()`
+    launches it in the calling stream if none did.  The call holds this object, so nothing pending outlives it."""
+
+    def __init__(self, order, rank, order32=None, inputs=None):
+        self.order, self.order32, self.rank = order, order32, rank
+        self.inputs = inputs                    # (mask, chain_mask or None, randn) as the sort reads them
+        self.pending = inputs is not None
+        self.event = None                       # side-stream work the decoder must wait for (sample()'s early levels)
+
+    def sort_args(self):
+        m, cm, r = self.inputs
+        return (m.data_ptr(), hip.ptr(cm), r.data_ptr(), self.order.data_ptr(), self.order32.data_ptr(), self.rank.data_ptr(),
+                self.order.shape[0])
+
+    def wait(self):
+        """Order the calling stream behind the sort — launching it here if no featuriser launch took it — and behind `event`
+        (no host synchronisation)."""
+        if self.pending:
+            self.pending = False
+            Bm, L = self.inputs[0].shape
+            hip.check(hip.lib().namp_decoding_order(*self.sort_args(), Bm, L, hip.current_stream()), "decoding_order")
+        if self.event is not None:
+            torch.cuda.current_stream().wait_event(self.event)
+            self.event = None
 
 
 class ProteinMPNN(nn.Module):
@@ -243,24 +324,28 @@ class ProteinMPNN(nn.Module):
         where the reference's nn.Embedding raises (model_utils.py:402).  One device reduction + host read per NEW tensor
         OBJECT (identity through a weak reference + its version counter, one slot per argument name — never the address: the
         caching allocator hands a fresh `S.to(device)` the block of the previous batch), so steady-state calls on a resident
-        feature_dict stay asynchronous."""
+        feature_dict stay asynchronous.  An inference tensor has no version counter: it is checked on every call."""
+        cached = not S.is_inference()
         slot = self._tokens_ok.get(what)
-        if slot is not None and slot[0]() is S and slot[1] == S._version:
+        if cached and slot is not None and slot[0]() is S and slot[1] == S._version:
             return
         lo, hi = torch.aminmax(S)
         if int(lo) < 0 or int(hi) >= self.vocab:
             raise IndexError(f"na_mpnn_amd: token ids in '{what}' must lie in [0, {self.vocab}); got [{int(lo)}, {int(hi)}]")
-        self._tokens_ok[what] = (weakref.ref(S), S._version)
+        if cached:
+            self._tokens_ok[what] = (weakref.ref(S), S._version)
 
     def _as(self, t, kind):
         """`t` in the dtype / layout the kernels read ("i32": int32, "f32": float32; contiguous), converted ONCE per tensor object: a
         feature_dict that stays resident (run.py scores / samples the same parsed complex many times; bench.py's shards) costs its ~12
         cast launches on the first call only.  Keyed on the tensor's identity through a weak reference and on its version counter — never on
         its address (the caching allocator hands a new tensor the block of a freed one) — so an in-place edit or a new tensor converts afresh;
-        the converted copy lives as long as its source."""
+        the converted copy lives as long as its source.  An inference tensor has no version counter: it is converted on every call."""
         dt = torch.int32 if kind == "i32" else torch.float32
         if t.dtype == dt and t.is_contiguous():
             return t
+        if t.is_inference():
+            return t.to(dt).contiguous()
         key = (id(t), kind)
         e = self._conv.get(key)
         if e is not None and e[0]() is t and e[1] == t._version:
@@ -272,10 +357,9 @@ class ProteinMPNN(nn.Module):
         self._conv[key] = (weakref.ref(t, lambda _r, k=key: conv.pop(k, None)), t._version, c)
         return c
 
-    def order_and_rank(self, mask, chain_mask, randn, defer=False):
-        """Decoding order argsort((mask * chain_mask + 1e-4) * |randn|) (model_utils.py:389; na_model_utils.py:623) and its inverse permutation
-        in one HIP launch (namp_decoding_order): order int64 [B', L], rank int32 [B', L], B' = rows of randn; mask / chain_mask [B, L] with
-        B' % B == 0 (chain_mask None = ones).  Shapes the kernel does not take (L > 8192, mismatched rows) run the stock ops."""
+    def _decoding_order(self, mask, chain_mask, randn):
+        """The decoding order of one call (see _DecodingOrder): the HIP sort still pending, or — for shapes the kernel does not take
+        (L > 8192, mismatched rows) and off the device — the stock ops' result."""
         Bm, L = mask.shape
         Br = randn.shape[0]
         if mask.is_cuda and L <= 8192 and Br % Bm == 0 and tuple(randn.shape) == (Br, L) and (chain_mask is None or chain_mask.shape == mask.shape):
@@ -284,57 +368,23 @@ class ProteinMPNN(nn.Module):
             order = torch.empty(Br, L, dtype=torch.int64, device=mask.device)
             order32 = torch.empty(Br, L, dtype=torch.int32, device=mask.device)        # (what the sampler's launches read: no cast launch)
             rank = torch.empty(Br, L, dtype=torch.int32, device=mask.device)
-            # The sort depends on (mask, chain_mask, randn) only and its first consumer is the decoder: it runs on a side stream beside the
-            # featuriser / encoder launches enqueued after this call (one workgroup per stream: 20-80 us that would otherwise sit in front of
-            # them).  The calling stream waits for it at once — a wait in the stream, not on the host —, so everything enqueued later is ordered
-            # behind it... which would serialise again: the wait is therefore deferred to `wait_order()` (score / sample / forward call it
-            # right before their decoder launch).
-            self._order_job = None
-            if defer and self.order_fold:
-                # The sort depends on (mask, chain_mask, randn) only and its first consumer is the decoder: the featuriser call that follows
-                # (score / forward / sample) takes it along as the first workgroups of its edge-feature launch (namp_featurize_ordered); a caller
-                # that never featurises gets it from `wait_order()`.  (A side stream, below, cost two cross-stream hand-overs: ~12 us per score().)
-                self._order_job = (m, cm, r, order, order32, rank, Br, Bm, L)
-                self._order32 = (order, order32)
-                self._order_event = None
-                return order, rank
-            main = torch.cuda.current_stream(mask.device)
-            side = self._side_stream(mask.device) if (defer and self.order_side_stream) else main
-            if side is not main:
-                side.wait_stream(main)                              # the inputs' producers
-            hip.check(hip.lib().namp_decoding_order(m.data_ptr(), hip.ptr(cm), r.data_ptr(), order.data_ptr(), order32.data_ptr(), rank.data_ptr(),
-                                                    Br, Bm, L, side.cuda_stream), "decoding_order")
-            self._order32 = (order, order32)
-            ev = torch.cuda.Event()
-            ev.record(side)
-            self._order_event = ev
-            for t_ in (m, r, cm, order, order32, rank):             # the caching allocator must not recycle these before the side stream is done
-                if t_ is not None:
-                    t_.record_stream(side)
-            if not defer:
-                self.wait_order()
-            return order, rank
+            return _DecodingOrder(order, rank, order32, (m, cm, r))
         order = self.decoding_order(mask if chain_mask is None else mask * chain_mask, randn)
-        return order, self.ranks_of(order).to(torch.int32)
+        return _DecodingOrder(order, self.ranks_of(order).to(torch.int32))
+
+    def order_and_rank(self, mask, chain_mask, randn):
+        """Decoding order argsort((mask * chain_mask + 1e-4) * |randn|) (model_utils.py:389; na_model_utils.py:623) and its inverse permutation
+        in one HIP launch in the calling stream (namp_decoding_order): order int64 [B', L], rank int32 [B', L], B' = rows of randn; mask /
+        chain_mask [B, L] with B' % B == 0 (chain_mask None = ones).  Shapes the kernel does not take (L > 8192, mismatched rows) run the stock ops."""
+        o = self._decoding_order(mask, chain_mask, randn)
+        o.wait()
+        return o.order, o.rank
 
     def _side_stream(self, device):
         st = getattr(self, "_side", None)
         if st is None or st.device != device:
             st = self._side = torch.cuda.Stream(device=device)
         return st
-
-    def wait_order(self):
-        """Order the calling stream behind the decoding-order launch of the last `order_and_rank` (no host synchronisation)."""
-        job = getattr(self, "_order_job", None)
-        if job is not None:                                     # no featuriser call took the sort along: here, in the calling stream
-            m, cm, r, order, order32, rank, Br, Bm, L = job
-            self._order_job = None
-            hip.check(hip.lib().namp_decoding_order(m.data_ptr(), hip.ptr(cm), r.data_ptr(), order.data_ptr(), order32.data_ptr(), rank.data_ptr(),
-                                                    Br, Bm, L, hip.current_stream()), "decoding_order")
-        ev = getattr(self, "_order_event", None)
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
-            self._order_event = None
 
     def _workspace(self, B_enc, B_dec, N, K, device):
         need = hip.lib().namp_workspace_bytes(B_enc, B_dec, N, K)
@@ -369,20 +419,23 @@ class ProteinMPNN(nn.Module):
     def _node_features(self, fd):
         fp = self.features
         rp = fd["R_polymer_type"]
-        if not torch.is_grad_enabled():                      # inference: V depends on the polymer types and three small parameters only
+        # inference: V depends on the polymer types and three small parameters only (an inference tensor has no version counter: no cache)
+        cached = not torch.is_grad_enabled() and not rp.is_inference()
+        if cached:
             c = self._v_cache
             sig = tuple((p.data_ptr(), p._version) for p in (fp.node_embedding.weight, fp.norm_nodes.weight, fp.norm_nodes.bias))
             if c is not None and c[0]() is rp and c[1] == rp._version and c[2] == sig:
                 return c[3]
         V = fp.node_embedding.weight.t()[rp.long()]      # one-hot @ W^T == row select (6 rows)
         V = nn.functional.layer_norm(V, (self.node_features,), fp.norm_nodes.weight, fp.norm_nodes.bias, 1e-5)
-        if not torch.is_grad_enabled():
+        if cached:
             self._v_cache = (weakref.ref(rp), rp._version, sig, V)
         return V
 
     @torch.no_grad()
-    def _featurize_hip(self, fd, want_E=True, want_hE=False):
-        """a11 on the HIP kernels (prep_atoms, knn, edge_features): returns V, E (or None), h_E0 (or None), E_idx."""
+    def _featurize_hip(self, fd, want_E=True, want_hE=False, order=None):
+        """a11 on the HIP kernels (prep_atoms, knn, edge_features): returns V, E (or None), h_E0 (or None), E_idx.  A pending
+        decoding-order sort of the same (B, L) (`order`, a _DecodingOrder) rides in the edge-feature launch."""
         self._require_reference_atom_order()
         X = self._noised_X(fd)
         X = self._as(X, "f32") if X is fd["X"] else X.float().contiguous()
@@ -399,14 +452,11 @@ class ProteinMPNN(nn.Module):
                          dtype=torch.uint8, device=dev)
         dna_m, rna_m = self._na_masks(fd)
         t = [self._as(fd[k], "i32") for k in ("X_m", "mask", "R_idx", "chain_labels", "protein_mask")] + [self._as(dna_m, "i32"), self._as(rna_m, "i32")]
-        job = getattr(self, "_order_job", None)
-        if job is not None and job[7] == B and job[8] == L and job[0].device == dev:
-            om, ocm, orn, order, order32, rank, Br = job[:7]      # the pending decoding-order sort rides in the edge-feature launch
-            self._order_job = None
+        if order is not None and order.pending and order.inputs[0].shape == (B, L) and order.inputs[0].device == dev:
+            order.pending = False
             hip.check(Lb.namp_featurize_ordered(W.model(), X.data_ptr(), *[x.data_ptr() for x in t], int(self.k_neighbors),
                                                 int(self.atom_dict[self.na_ref_atom]), E_idx.data_ptr(), hip.ptr(E), hip.ptr(hE),
-                                                ws.data_ptr(), ws.numel(), B, L, om.data_ptr(), hip.ptr(ocm), orn.data_ptr(), order.data_ptr(),
-                                                order32.data_ptr(), rank.data_ptr(), Br, hip.current_stream()), "featurize_ordered")
+                                                ws.data_ptr(), ws.numel(), B, L, *order.sort_args(), hip.current_stream()), "featurize_ordered")
         else:
             hip.check(Lb.namp_featurize(W.model(), X.data_ptr(), *[x.data_ptr() for x in t], int(self.k_neighbors),
                                         int(self.atom_dict[self.na_ref_atom]), E_idx.data_ptr(), hip.ptr(E), hip.ptr(hE),
@@ -417,9 +467,10 @@ class ProteinMPNN(nn.Module):
 
     @torch.no_grad()
     def featurize(self, fd):
-        """ProteinFeaturesNA.forward (model_utils.py:528-593) -> V, E, E_idx (int64 like the reference)."""
+        """ProteinFeaturesNA.forward (model_utils.py:528-593) -> V, E, E_idx (int64 like the reference).  V is the caller's own
+        copy, not the model's cached one."""
         V, E, _, E_idx = self._featurize_hip(fd, want_E=True, want_hE=False)
-        return V, E, E_idx.long()
+        return V.clone(), E, E_idx.long()
 
     # ---------------------------------------------------------------------------------------
     # a7: encoder
@@ -443,10 +494,10 @@ class ProteinMPNN(nn.Module):
         return h_V, h_E
 
     @torch.no_grad()
-    def encode(self, feature_dict):
+    def encode(self, feature_dict, order=None):
         """ProteinMPNN.encode (model_utils.py:71-99).  With the HIP featuriser W_e is applied inside the feature
-        kernel, so E itself is never written."""
-        V, _, h_E, E_idx = self._featurize_hip(feature_dict, want_E=False, want_hE=True)
+        kernel, so E itself is never written.  `order`: a pending decoding-order sort for the featuriser to take along."""
+        V, _, h_E, E_idx = self._featurize_hip(feature_dict, want_E=False, want_hE=True, order=order)
         h_V, h_E = self.encode_graph(V, None, E_idx, feature_dict["mask"], h_E_embedded=h_E)
         return h_V, h_E, E_idx.long()
 
@@ -478,7 +529,6 @@ class ProteinMPNN(nn.Module):
         log_probs = torch.empty(B_dec, N, self.num_letters, device=h_V.device)
         logits = torch.empty_like(log_probs) if want_logits else None
         ws = self._workspace(B_enc, B_dec, N, K, h_V.device)
-        self.wait_order()
         hip.check(hip.lib().namp_decoder_fwd(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(),
                                              m32.data_ptr(), r32.data_ptr(), log_probs.data_ptr(), hip.ptr(logits), None,
                                              ws.data_ptr(), ws.numel(), B_dec, B_enc, N, K, hip.current_stream()),
@@ -486,13 +536,14 @@ class ProteinMPNN(nn.Module):
         return (log_probs, logits) if want_logits else log_probs
 
     @torch.no_grad()
-    def encode_decode(self, feature_dict, S, rank, want_logits=False, idx_long=True):
+    def encode_decode(self, feature_dict, S, rank, want_logits=False, idx_long=True, order=None):
         """encode() + decode_graph() for one decoder batch per complex, as ONE library call (namp_encdec_fwd): lets the
         kernels fuse across the encoder/decoder boundary.  Returns h_V, h_E, E_idx, log_probs(, logits); E_idx is int64 like the
-        reference's unless idx_long=False (score() does not return it: no cast launch)."""
+        reference's unless idx_long=False (score() does not return it: no cast launch).  `order`: the _DecodingOrder that `rank`
+        comes from, while its sort may still be pending."""
         mask = feature_dict["mask"]
         self._check_tokens(S)
-        V, E, h_E, E_idx = self._featurize_hip(feature_dict, want_E=False, want_hE=True)
+        V, E, h_E, E_idx = self._featurize_hip(feature_dict, want_E=False, want_hE=True, order=order)
         W = self._weights()
         B, N, K = E_idx.shape
         V = V.float().contiguous()
@@ -503,7 +554,8 @@ class ProteinMPNN(nn.Module):
         need = 2 * hip.lib().namp_workspace_bytes(B, B, N, K)
         if self._ws is None or self._ws.numel() < need or self._ws.device != V.device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=V.device)
-        self.wait_order()                               # (rank: behind the side-stream sort, see order_and_rank)
+        if order is not None:
+            order.wait()
         hip.check(hip.lib().namp_encdec_fwd(W.model(), V.data_ptr(), hip.ptr(E.float().contiguous() if E is not None else None),
                                             E32.data_ptr(), m32.data_ptr(), S32.data_ptr(), r32.data_ptr(), h_V.data_ptr(),
                                             h_E.data_ptr(), log_probs.data_ptr(), hip.ptr(logits), self._ws.data_ptr(),
@@ -516,16 +568,16 @@ class ProteinMPNN(nn.Module):
         bs = feature_dict["batch_size"]
         S_true, mask = feature_dict["S"], feature_dict["mask"]
         B, L = S_true.shape
-        order, rank = self.order_and_rank(mask, feature_dict["chain_mask"], feature_dict["randn"], defer=True)
-        rank = rank[:B]                          # the reference's gather keeps only E_idx's batch rows (:393)
+        o = self._decoding_order(mask, feature_dict["chain_mask"], feature_dict["randn"])
+        rank = o.rank[:B]                        # the reference's gather keeps only E_idx's batch rows (:393)
         if bs == 1:
-            log_probs = self.encode_decode(feature_dict, S_true, rank, idx_long=False)[3]
-            return {"S": S_true, "log_probs": log_probs, "decoding_order": order[0]}
-        h_V, h_E, E_idx = self.encode(feature_dict)
-        self.wait_order()
+            log_probs = self.encode_decode(feature_dict, S_true, rank, idx_long=False, order=o)[3]
+            return {"S": S_true, "log_probs": log_probs, "decoding_order": o.order[0]}
+        h_V, h_E, E_idx = self.encode(feature_dict, order=o)
+        o.wait()
         rep = lambda t: t.repeat(bs, *([1] * (t.dim() - 1)))
         log_probs = self.decode_graph(h_V, h_E, E_idx, rep(S_true), rep(mask), rep(rank))
-        return {"S": rep(S_true), "log_probs": log_probs, "decoding_order": order[0]}
+        return {"S": rep(S_true), "log_probs": log_probs, "decoding_order": o.order[0]}
 
     @torch.no_grad()
     def unconditional_probs(self, feature_dict):
@@ -552,18 +604,15 @@ class ProteinMPNN(nn.Module):
                 chain_M = chain_M.masked_fill(feature_dict["protein_mask"].to(torch.bool), 0.0)
             if decoding_randn is None:
                 decoding_randn = torch.randn(chain_M.shape, device=mask.device)
-            rank = self.order_and_rank(chain_M, None, decoding_randn, defer=True)[1]
-            _, _, _, log_probs, logits = self.encode_decode(feature_dict, feature_dict["S"], rank, want_logits=True, idx_long=False)
+            o = self._decoding_order(chain_M, None, decoding_randn)
+            _, _, _, log_probs, logits = self.encode_decode(feature_dict, feature_dict["S"], o.rank, want_logits=True, idx_long=False,
+                                                            order=o)
             return log_probs, torch.softmax(logits, dim=-1)
 
     # reference quirk (model_utils.py:186): DecLayer receives mask_t of shape [B], which broadcasts so that
     # every stream is masked with STREAM 0's mask at that step.  True reproduces it; it only matters when
     # batch_size > 1 and masked residues coexist with fixed (chain_mask = 0) ones.
     reference_sample_mask_quirk = True
-    # the decoding-order sort on a side stream beside the featuriser launches (False: in the calling stream; A/B switch)
-    order_side_stream = os.environ.get("NAMP_ORDER_SIDE", "1") != "0"
-    # the decoding-order sort inside the featuriser's edge-feature launch (False: a launch of its own, on the side stream if enabled; A/B switch)
-    order_fold = os.environ.get("NAMP_ORDER_FOLD", "1") != "0"
     # decode the plain sampling branch by dependency level (False: the one-launch sequential walk; same results)
     sample_level_parallel = True
     # ... as ONE persistent launch walking the levels (no host read-back, warm L2); False: one launch per level
@@ -582,7 +631,10 @@ class ProteinMPNN(nn.Module):
         ``pair_bias``) as one persistent HIP launch.
         The categorical draw uses torch.rand on the device (seed with torch.manual_seed) through an inverse
         CDF instead of torch.multinomial; ``feature_dict["S_forced"]`` (optional, [batch,L]) teacher-forces."""
-        fd = feature_dict
+        return self._sample(feature_dict, self.sample_level_walk)
+
+    def _sample(self, fd, walk, uniform=None):
+        """sample() with the persistent level walk on or off (`walk`) and the uniforms of the draws given (None: torch.rand)."""
         bs = fd["batch_size"]
         S_true, mask, bias = fd["S"], fd["mask"], fd["bias"]
         sym = fd.get("symmetry_residues", [[]])
@@ -592,17 +644,16 @@ class ProteinMPNN(nn.Module):
         self._check_tokens(S_true)
         if fd.get("S_forced") is not None:
             self._check_tokens(fd["S_forced"], "S_forced")
-        order, rank = self.order_and_rank(mask, fd["chain_mask"], fd["randn"], defer=True)       # [max(B, bs), L]; beside the launches below
-        V, _, h_E, E_idx = self._featurize_hip(fd, want_E=False, want_hE=True)       # (E_idx stays int32: the kernels' dtype)
+        o = self._decoding_order(mask, fd["chain_mask"], fd["randn"])               # [max(B, bs), L]; sorted by the featuriser launch
+        order, rank = o.order, o.rank
+        V, _, h_E, E_idx = self._featurize_hip(fd, want_E=False, want_hE=True, order=o)   # (E_idx stays int32: the kernels' dtype)
         K = E_idx.shape[-1]
         B_dec = B * bs
         # Plain branch: the dependency levels and the walk's work lists need the neighbour lists and the decoding order only — enqueued on
-        # the side stream behind the sort, beside the encoder launches (sample_levels_kernel is a serial walk of one wave per stream: 62 us at
-        # 97 residues in front of the walk otherwise).
+        # the side stream behind the featuriser launch, beside the encoder launches (sample_levels_kernel is a serial walk of one wave per
+        # stream: 62 us at 97 residues in front of the walk otherwise).
         early = None
-        o32_pair = getattr(self, "_order32", None)
-        if (not symmetric and "pair_bias" not in fd and self.sample_level_parallel and self.sample_level_walk and self.order_side_stream
-                and getattr(self, "_order_job", None) is None and o32_pair is not None and o32_pair[0] is order
+        if (not symmetric and "pair_bias" not in fd and self.sample_level_parallel and walk and not o.pending and o.order32 is not None
                 and order.shape[0] == B_dec and L <= 16000 and E_idx.dtype == torch.int32 and E_idx.is_contiguous()
                 and hip.lib().namp_decoder_sample_walk_grid(B_dec, L, K) > 0):
             Lb_ = hip.lib()
@@ -611,51 +662,28 @@ class ProteinMPNN(nn.Module):
             work = torch.empty(B_dec * L, 2, dtype=torch.int32, device=dev)
             level_off = torch.empty(L + 2, dtype=torch.int32, device=dev)
             n_levels = torch.empty(1, dtype=torch.int32, device=dev)
-            ev_ = torch.cuda.Event(); ev_.record(main_)                              # the neighbour lists are out
+            ev_ = torch.cuda.Event(); ev_.record(main_)                              # the neighbour lists and the order are out
             side_.wait_event(ev_)
-            hip.check(Lb_.namp_sample_levels_dep(E_idx.data_ptr(), o32_pair[1].data_ptr(), rank.data_ptr(), None, 0, None, None, level.data_ptr(),
+            hip.check(Lb_.namp_sample_levels_dep(E_idx.data_ptr(), o.order32.data_ptr(), rank.data_ptr(), None, 0, None, None, level.data_ptr(),
                                                  B_dec, B, L, K, side_.cuda_stream), "sample_levels")
             hip.check(Lb_.namp_sample_work_lists(level.data_ptr(), work.data_ptr(), level_off.data_ptr(), n_levels.data_ptr(), B_dec, L,
                                                  side_.cuda_stream), "sample_work_lists")
-            ev2_ = torch.cuda.Event(); ev2_.record(side_)
-            self._order_event = ev2_                                                 # wait_order() now orders behind all three launches
-            for t_ in (E_idx, level, work, level_off, n_levels):
+            o.event = torch.cuda.Event(); o.event.record(side_)                      # o.wait() orders the decoder behind both launches
+            for t_ in (E_idx, o.order32, rank, level, work, level_off, n_levels):    # (not recycled before the side stream is done)
                 t_.record_stream(side_)
-            early = (level, work, level_off, n_levels, o32_pair[1])
+            early = (level, work, level_off, n_levels)
         h_V, h_E = self.encode_graph(V, None, E_idx, mask, h_E_embedded=h_E)
-        self.wait_order()
+        o.wait()
         chain_mask = mask * fd["chain_mask"]
         group_first = group_last = sym_w = None
         if symmetric:
-            # model_utils.py:220-235: tied residues are visited together, in the order stream 0 reaches their first
-            # member; every stream then uses that one order
             if B != 1:
                 raise ValueError("symmetry-tied sampling expects one input complex (B == 1)")
-            wl = [1.0] * L
-            for i1, group in enumerate(sym):
-                for i2, item in enumerate(group):
-                    wl[item] = float(fd["symmetry_weights"][i1][i2])
-            weights = torch.tensor(wl, dtype=torch.float32)
-            group_of = {}
-            for g_ in sym:                                     # (the reference takes the FIRST listed group that holds a residue)
-                for item in g_:
-                    group_of.setdefault(int(item), g_)
-            visited, groups = set(), []
-            for t_dec in order[0].tolist():
-                if t_dec in visited:
-                    continue
-                groups.append(list(group_of.get(t_dec, (t_dec,))))
-                visited.update(groups[-1])
-            flat = [t for g in groups for t in g]
-            if sorted(flat) != list(range(L)):
-                raise ValueError("symmetry_residues groups must be disjoint")
-            gf, gl, v = [], [], 0
-            for g in groups:
-                gf += [v] * len(g); gl += [0] * (len(g) - 1) + [1]; v += len(g)
-            order = torch.tensor(flat, device=dev).unsqueeze(0).repeat(B_dec, 1)
+            visits, gf, gl, wl = symmetry_visits(sym, fd["symmetry_weights"], order[0].tolist(), L)
+            order = torch.tensor(visits, device=dev).unsqueeze(0).repeat(B_dec, 1)
             group_first = torch.tensor(gf, dtype=torch.int32, device=dev).repeat(B_dec, 1).contiguous()
             group_last = torch.tensor(gl, dtype=torch.int32, device=dev).repeat(B_dec, 1).contiguous()
-            sym_w = weights.to(dev).contiguous()
+            sym_w = torch.tensor(wl, dtype=torch.float32).to(dev).contiguous()
             rank = self.ranks_of(order)
         if order.shape[0] != B_dec:
             raise ValueError(f"randn has {fd['randn'].shape[0]} rows; expected batch_size*B = {B_dec}")
@@ -664,7 +692,8 @@ class ProteinMPNN(nn.Module):
             m0 = mask[0][order[0]]                                             # stream 0's mask along the steps
             mask_dec = torch.empty_like(mask_dec).scatter_(1, order, m0.expand(B_dec, L).contiguous())
         pair_bias = fd["pair_bias"].float().contiguous() if "pair_bias" in fd else None
-        uniform = fd["_uniform"] if fd.get("_uniform") is not None else torch.rand(B_dec, L, device=dev)   # (_uniform: the re-run below)
+        if uniform is None:
+            uniform = torch.rand(B_dec, L, device=dev)
         special = 0
         for name in ("UNK", "DX", "RX", "MAS", "PAD"):                        # model_utils.py:199-203
             special |= 1 << int(self.restype_to_int[name])
@@ -677,129 +706,81 @@ class ProteinMPNN(nn.Module):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         E32, cm32, St32 = _i32(E_idx), _i32(chain_mask), self._as(S_true, "i32")
         m32 = self._as(mask, "i32")
-        md32, o32, r32 = (m32 if mask_dec is mask else _i32(mask_dec)), (early[4] if early is not None else _i32(order)), _i32(rank)
+        md32, o32, r32 = (m32 if mask_dec is mask else _i32(mask_dec)), (o.order32 if early is not None else _i32(order)), _i32(rank)
         bias_f = bias.float().expand(B, L, self.num_letters).contiguous()
         forced = _i32(fd["S_forced"]) if fd.get("S_forced") is not None else None
         h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
-        dep_idx, n_dep = None, 0
-        pb_levels = pair_bias is None
+        deps = (None, 0) if pair_bias is None else None                       # (dep_idx, n_dep) of the levels; None: sequential walk
         if pair_bias is not None and self.sample_level_parallel:
-            # pair_bias (model_utils.py:116,169-172): the bias of residue i reads the token of every residue j whose block
-            # pair_bias[i, :, j, :] is not all zero — the sequence neighbours for run.py's --pair_bias_AA (data_utils.py:7-16).  Those
-            # j become extra dependencies of the levels; a dense bias (more than 64 partners for some residue) keeps the sequential walk.
             if tuple(pair_bias.shape) != (B, L, self.num_letters, L, self.num_letters):
                 raise ValueError(f"pair_bias must be [B, L, {self.num_letters}, L, {self.num_letters}]; got {tuple(pair_bias.shape)}")
-            # (row block by row block: one amax over the whole [B, L, 33, L, 33] tensor would materialise a second copy of it — 4.4 GB at
-            # L = 1000; a non-finite entry counts as a dependency: NaN > 0 is False and would silently drop it from the levels)
-            nz = torch.empty(B, L, L, dtype=torch.bool, device=dev)
-            step_ = max(1, (1 << 26) // max(1, self.num_letters * L * self.num_letters))
-            for i0 in range(0, L, step_):
-                blk = pair_bias[:, i0:i0 + step_]
-                nz[:, i0:i0 + step_] = ((blk != 0) | ~torch.isfinite(blk)).any(dim=4).any(dim=2)
-            n_dep = int(nz.sum(-1).max())
-            if n_dep <= 64:
-                pb_levels = True
-                if n_dep > 0:
-                    cols = torch.where(nz, torch.arange(L, device=dev)[None, None, :], torch.full((), L, device=dev))
-                    cols = cols.sort(dim=-1).values[:, :, :n_dep]
-                    dep_idx = torch.where(cols < L, cols, torch.full((), -1, device=dev)).to(torch.int32).contiguous()
-        if self.sample_level_parallel and pb_levels:
-            # residue i depends only on the neighbours decoded before it -> decode by dependency level (one launch per level over all
-            # streams, ~64 levels at L = 1000 instead of 1000 sequential steps).  Symmetry-tied: the unit of work is a GROUP (its members
-            # run one after the other in the group's workgroup slot and share one draw); its level follows its members' dependencies
+            deps = pair_bias_dependencies(pair_bias)
+        common = (W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), m32.data_ptr(), md32.data_ptr(), cm32.data_ptr(),
+                  St32.data_ptr(), bias_f.data_ptr(), o32.data_ptr(), r32.data_ptr(), uniform.data_ptr(), hip.ptr(forced),
+                  hip.ptr(group_first), hip.ptr(group_last), hip.ptr(sym_w), hip.ptr(pair_bias))
+        tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
+                B_dec, B, L, K, hip.current_stream())
+        out = {"S": None, "sampling_probs": probs, "log_probs": logp, "decoding_order": order, "uniform": uniform}   # (S: after the launch)
+        if not (self.sample_level_parallel and deps is not None):
+            hip.check(Lb.namp_decoder_sample(*common, *tail), "decoder_sample")
+            # (no host sync needed: temporaries are stream-ordered allocations, see _featurize_hip)
+            out["S"] = S_out.long()
+            return out
+        # residue i depends only on the neighbours decoded before it -> decode by dependency level (one launch per level over all
+        # streams, ~64 levels at L = 1000 instead of 1000 sequential steps).  Symmetry-tied: the unit of work is a GROUP (its members
+        # run one after the other in the group's workgroup slot and share one draw); its level follows its members' dependencies
+        dep_idx, n_dep = deps
+        if early is not None:
+            level = early[0]
+        else:
+            level = torch.empty(B_dec, L, dtype=torch.int32, device=dev)
+            hip.check(Lb.namp_sample_levels_dep(E32.data_ptr(), o32.data_ptr(), r32.data_ptr(), hip.ptr(dep_idx), n_dep,
+                                                hip.ptr(group_first), hip.ptr(group_last), level.data_ptr(),
+                                                B_dec, B, L, K, hip.current_stream()), "sample_levels")
+        walk = walk and Lb.namp_decoder_sample_walk_grid(B_dec, L, K) > 0
+        work_n = close = close_off = zbuf = hist = None
+        if walk and not symmetric and L <= 16000:
+            # plain branch: the walk's work lists are built on the device as well (one launch instead of a stable argsort, gathers,
+            # divisions, a histogram and its prefix sums) — the whole design is enqueued with ~a dozen launches
+            nwork = B_dec * L
             if early is not None:
-                level = early[0]
+                _, work, level_off, n_levels = early
             else:
-                level = torch.empty(B_dec, L, dtype=torch.int32, device=dev)
-                hip.check(Lb.namp_sample_levels_dep(E32.data_ptr(), o32.data_ptr(), r32.data_ptr(), hip.ptr(dep_idx), n_dep,
-                                                    hip.ptr(group_first), hip.ptr(group_last), level.data_ptr(),
-                                                    B_dec, B, L, K, hip.current_stream()), "sample_levels")
-            walk = self.sample_level_walk and Lb.namp_decoder_sample_walk_grid(B_dec, L, K) > 0
-            zbuf = None
-            if walk and not symmetric and L <= 16000:
-                # plain branch: the walk's work lists are built on the device as well (one launch instead of a stable argsort, gathers,
-                # divisions, a histogram and its prefix sums) — the whole design is enqueued with ~a dozen launches
-                nwork = B_dec * L
-                if early is not None:
-                    _, work, level_off, n_levels, _ = early
-                else:
-                    work = torch.empty(nwork, 2, dtype=torch.int32, device=dev)
-                    level_off = torch.empty(L + 2, dtype=torch.int32, device=dev)
-                    n_levels = torch.empty(1, dtype=torch.int32, device=dev)
-                    hip.check(Lb.namp_sample_work_lists(level.data_ptr(), work.data_ptr(), level_off.data_ptr(), n_levels.data_ptr(), B_dec, L,
-                                                        hip.current_stream()), "sample_work_lists")
-                hip.check(Lb.namp_decoder_sample_walk(
-                    W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), m32.data_ptr(), md32.data_ptr(), cm32.data_ptr(),
-                    St32.data_ptr(), bias_f.data_ptr(), o32.data_ptr(), r32.data_ptr(), uniform.data_ptr(), hip.ptr(forced),
-                    None, None, None, hip.ptr(pair_bias), work.data_ptr(), None, nwork, level_off.data_ptr(), None, None, None,
-                    float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
-                    B_dec, B, L, K, hip.current_stream()), "decoder_sample_walk")
-                self._walk_sync = ws[ws_bytes - 4096:][:256].view(torch.int32).clone()
-                out = {"S": S_out.long(), "sampling_probs": probs, "log_probs": logp, "decoding_order": order,
-                       "uniform": uniform, "levels": n_levels[0], "work_items": nwork}
-                if self.sample_check_walk and self.sample_walk_status() != 0:
-                    import warnings
-                    warnings.warn(f"persistent level walk timed out (code {self.sample_walk_status():#x}); re-running with per-level launches")
-                    prev, self.sample_level_walk = self.sample_level_walk, False
-                    try:
-                        fd2 = dict(feature_dict)
-                        fd2["S_forced"] = fd.get("S_forced")
-                        fd2["_uniform"] = uniform
-                        out = self.sample(fd2)
-                    finally:
-                        self.sample_level_walk = prev
-                return out
-            sel, flat, work_n, close, close_off = level_work_lists(
-                level, group_first if symmetric else None, group_last if symmetric else None, order[0], E_idx[0].long(),
-                split=bool(symmetric and walk and self.sample_split_groups))
+                work = torch.empty(nwork, 2, dtype=torch.int32, device=dev)
+                level_off = torch.empty(L + 2, dtype=torch.int32, device=dev)
+                n_levels = torch.empty(1, dtype=torch.int32, device=dev)
+                hip.check(Lb.namp_sample_work_lists(level.data_ptr(), work.data_ptr(), level_off.data_ptr(), n_levels.data_ptr(), B_dec, L,
+                                                    hip.current_stream()), "sample_work_lists")
+        else:
+            sel, flat, work_n, close, close_off = level_work_lists(level, group_first, group_last, order[0], E_idx[0].long(),
+                                                                   split=bool(symmetric and walk and self.sample_split_groups))
             if close is not None:
                 zbuf = torch.empty(B_dec, L, self.num_letters, device=dev)
             nwork = int(sel.numel())
             work = torch.stack((sel // L, sel % L), 1).to(torch.int32).contiguous()
-            common = (W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), m32.data_ptr(), md32.data_ptr(), cm32.data_ptr(),
-                      St32.data_ptr(), bias_f.data_ptr(), o32.data_ptr(), r32.data_ptr(), uniform.data_ptr(), hip.ptr(forced),
-                      hip.ptr(group_first), hip.ptr(group_last), hip.ptr(sym_w), hip.ptr(pair_bias), work.data_ptr(), hip.ptr(work_n))
-            tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
-                    B_dec, B, L, K, hip.current_stream())
-            if walk:
-                # one persistent launch: the level histogram stays on the device (levels < L, so L + 2 offsets; everything behind
-                # the last level equals nwork) — nothing is read back, the call returns with the whole design enqueued
-                hist = torch.zeros(L + 1, dtype=torch.int64, device=dev).scatter_add_(0, flat, torch.ones_like(flat))
-                level_off = torch.cat((hist.new_zeros(1), hist.cumsum(0))).to(torch.int32).contiguous()
-                hip.check(Lb.namp_decoder_sample_walk(*common, nwork, level_off.data_ptr(), hip.ptr(close), hip.ptr(close_off), hip.ptr(zbuf),
-                                                      *tail), "decoder_sample_walk")
-                # the 64 barrier words, copied out of the per-call workspace (a view would keep the whole workspace alive on the model)
-                self._walk_sync = ws[ws_bytes - 4096:][:256].view(torch.int32).clone()
-                out = {"S": S_out.long(), "sampling_probs": probs, "log_probs": logp, "decoding_order": order,
-                       "uniform": uniform, "levels": (hist > 0).sum(), "work_items": nwork}   # "levels": a device scalar (no read-back here)
-                if self.sample_check_walk and self.sample_walk_status() != 0:
-                    # the walk's grid barriers gave up (its workgroups were not all resident: a shared or partitioned device) — that
-                    # call's outputs are poisoned; decode again with one launch per level, which needs no co-residency
-                    import warnings
-                    warnings.warn(f"persistent level walk timed out (code {self.sample_walk_status():#x}); re-running with per-level launches")
-                    prev, self.sample_level_walk = self.sample_level_walk, False
-                    try:
-                        fd2 = dict(feature_dict)
-                        fd2["S_forced"] = fd.get("S_forced")
-                        fd2["_uniform"] = uniform
-                        out = self.sample(fd2)
-                    finally:
-                        self.sample_level_walk = prev
+            if not walk:
+                counts = torch.bincount(flat).cpu().tolist()                   # per-level launches: the one host sync of the sampler
+                counts_c = (C.c_int32 * len(counts))(*counts)
+                hip.check(Lb.namp_decoder_sample_levels(*common, work.data_ptr(), hip.ptr(work_n), counts_c, len(counts), *tail),
+                          "decoder_sample_levels")
+                out.update(S=S_out.long(), levels=len(counts))
                 return out
-            counts = torch.bincount(flat).cpu().tolist()                       # per-level launches: the one host sync of the sampler
-            counts_c = (C.c_int32 * len(counts))(*counts)
-            hip.check(Lb.namp_decoder_sample_levels(*common, counts_c, len(counts), *tail), "decoder_sample_levels")
-            return {"S": S_out.long(), "sampling_probs": probs, "log_probs": logp, "decoding_order": order,
-                    "uniform": uniform, "levels": len(counts)}
-        hip.check(Lb.namp_decoder_sample(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), m32.data_ptr(), md32.data_ptr(),
-                                         cm32.data_ptr(), St32.data_ptr(), bias_f.data_ptr(), o32.data_ptr(), r32.data_ptr(),
-                                         uniform.data_ptr(), hip.ptr(forced), hip.ptr(group_first), hip.ptr(group_last),
-                                         hip.ptr(sym_w), hip.ptr(pair_bias), float(fd["temperature"]), special,
-                                         S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         B_dec, B, L, K, hip.current_stream()), "decoder_sample")
-        # (no host sync needed: temporaries are stream-ordered allocations, see _featurize_hip)
-        return {"S": S_out.long(), "sampling_probs": probs, "log_probs": logp, "decoding_order": order,
-                "uniform": uniform}
+            # the level histogram stays on the device (levels < L, so L + 2 offsets; everything behind the last level equals nwork)
+            hist = torch.zeros(L + 1, dtype=torch.int64, device=dev).scatter_add_(0, flat, torch.ones_like(flat))
+            level_off = torch.cat((hist.new_zeros(1), hist.cumsum(0))).to(torch.int32).contiguous()
+        # one persistent launch walking the levels: nothing is read back, the call returns with the whole design enqueued
+        hip.check(Lb.namp_decoder_sample_walk(*common, work.data_ptr(), hip.ptr(work_n), nwork, level_off.data_ptr(), hip.ptr(close),
+                                              hip.ptr(close_off), hip.ptr(zbuf), *tail), "decoder_sample_walk")
+        # the 64 barrier words, copied out of the per-call workspace (a view would keep the whole workspace alive on the model)
+        self._walk_sync = ws[ws_bytes - 4096:][:256].view(torch.int32).clone()
+        out.update(S=S_out.long(), levels=n_levels[0] if hist is None else (hist > 0).sum(), work_items=nwork)   # (levels: a device scalar)
+        code = self.sample_walk_status() if self.sample_check_walk else 0
+        if code != 0:
+            # the walk's grid barriers gave up (its workgroups were not all resident: a shared or partitioned device) — that call's
+            # outputs are poisoned; decode again with one launch per level, which needs no co-residency
+            warnings.warn(f"persistent level walk timed out (code {code:#x}); re-running with per-level launches")
+            return self._sample(fd, walk=False, uniform=uniform)
+        return out
 
     def sample_walk_status(self):
         """Barrier state of the last persistent level walk (synchronises): 0 = every grid barrier completed; otherwise the code of the barrier

@@ -604,6 +604,79 @@ def test_sampler_with_more_than_three_decoder_layers():
     assert maxdiff(outs[0]["sampling_probs"][:, valid], ref["sampling_probs"][:, valid]) < 1e-3
 
 
+@pytest.mark.parametrize("symmetric", [False, True])
+def test_walk_fallback_equals_the_per_level_sampler(weights_np, symmetric):
+    """With `sample_check_walk`, a persistent level walk whose grid barrier gave up (reported here by a patched
+    `sample_walk_status`; no real timeout is provoked) is decoded again with one launch per level and the same uniforms:
+    the result is the per-level sampler's, with a warning, and the model's switches are left as they were."""
+    dev = torch.device("cuda:0")
+    n, k, bs = 60, 16, 2
+    cx = synth.make_complex(seed=611, n=n, n_chains=2)
+    cx["chain_mask"][::9] = 0
+    rng = np.random.default_rng(61)
+    fd = _sample_fd(cx, dev, bs, 0.5, torch.from_numpy(rng.standard_normal((bs, n)).astype(np.float32)))
+    if symmetric:
+        fd.update({"symmetry_residues": [[1, 2, 3], [10, 50], [20, 40]], "symmetry_weights": [[1., 1., 1.], [.5, .5], [1., 2.]]})
+    m = make_model(weights_np, k, dev)
+    m.sample_level_walk = False
+    torch.manual_seed(8)
+    ref = m.sample(fd)
+    m.sample_level_walk, m.sample_check_walk = True, True
+    codes, real_status = [0x102], m.sample_walk_status
+    m.sample_walk_status = lambda: codes.pop() if codes else real_status()
+    torch.manual_seed(8)
+    with pytest.warns(UserWarning, match="timed out"):
+        out = m.sample(fd)
+    assert not codes and m.sample_level_walk and "work_items" not in out and out["levels"] == ref["levels"]
+    for key in ("uniform", "decoding_order", "S", "sampling_probs", "log_probs"):
+        assert torch.equal(out[key], ref[key]), key
+
+
+def test_a_failed_call_leaves_no_decoding_order_pending(weights_np, monkeypatch):
+    """The decoding-order sort rides in the featuriser launch of the call that asked for it: a score() that raises on bad tokens
+    leaves nothing behind on the model, so the next featurize() runs the plain featuriser (namp_featurize, not
+    namp_featurize_ordered) and the next score() returns the oracle's decoding order."""
+    from na_mpnn_amd import hip
+    dev = torch.device("cuda:0")
+    cx = synth.make_complex(seed=613, n=50)
+    fd = fd_of(cx, dev)
+    m = make_model(weights_np, 16, dev)
+    real, calls = hip.lib(), []
+
+    class Recording:
+        def __getattr__(self, name):
+            fn = getattr(real, name)
+            return lambda *a: (calls.append(name), fn(*a))[1]
+
+    monkeypatch.setattr(hip, "lib", lambda: Recording())
+    bad = dict(fd, S=fd["S"].clone())
+    bad["S"][0, 7] = 33
+    with pytest.raises(IndexError):
+        m.score(bad)
+    calls.clear()
+    m.featurize(fd)
+    assert [c for c in calls if c.startswith("namp_featurize") and not c.endswith("_bytes")] == ["namp_featurize"]
+    out = m.score(fd)
+    fdc = {k_: (v.cpu() if isinstance(v, torch.Tensor) else v) for k_, v in fd.items()}
+    assert torch.equal(out["decoding_order"].cpu(), ProteinMPNN.decoding_order(fdc["mask"] * fdc["chain_mask"], fdc["randn"])[0])
+
+
+def test_inference_mode_and_featurize_returns_its_own_V(weights_np):
+    """score() on a feature_dict made under torch.inference_mode() (no version counters to key the conversion caches on) gives
+    the same log-probs as outside it, and the V that featurize() returns is the caller's: editing it changes no later score()."""
+    dev = torch.device("cuda:0")
+    cx = synth.make_complex(seed=617, n=50)
+    fd = fd_of(cx, dev)
+    m = make_model(weights_np, 16, dev)
+    ref = m.score(fd)["log_probs"].clone()
+    with torch.inference_mode():
+        fdi = {k_: (v.clone() if isinstance(v, torch.Tensor) else v) for k_, v in fd.items()}
+        for _ in range(2):
+            assert torch.equal(m.score(fdi)["log_probs"], ref)
+    m.featurize(fd)[0].add_(1.0)
+    assert torch.equal(m.score(fd)["log_probs"], ref)
+
+
 def test_cpu_tensors_are_rejected(weights_np):
     m = ProteinMPNN(num_letters=33, vocab=33, k_neighbors=8, atom_dict=spec.atom_dict(),
                     restype_to_int=spec.restype_to_int(), polytype_to_int=spec.polytype_to_int())

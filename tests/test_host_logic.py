@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from na_mpnn_amd import hip, spec, synth
-from na_mpnn_amd.model import ProteinMPNN
+from na_mpnn_amd.model import ProteinMPNN, pair_bias_dependencies, symmetry_visits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -126,6 +126,65 @@ def test_order_and_rank_stock_path_and_cast_cache():
     del t, a, b
     gc.collect()
     assert len(m._conv) < n                                                     # the weak reference's callback removed the entry
+
+
+def test_conversion_caches_take_inference_tensors():
+    """Tensors made under torch.inference_mode() have no version counter: `_as`, `_check_tokens` and the V cache convert / check them
+    on every call instead of caching them (score() converts the float mask, so caching them made every inference-mode call raise)."""
+    m = ProteinMPNN(num_letters=33, vocab=33, k_neighbors=8, atom_dict=spec.atom_dict(), restype_to_int=spec.restype_to_int(),
+                    polytype_to_int=spec.polytype_to_int())
+    rp = torch.tensor([[0, 1, 2, 5]])
+    V_ref = m._node_features({"R_polymer_type": rp})
+    m._v_cache = None
+    with torch.inference_mode():
+        t = torch.arange(6)
+        a = m._as(t, "i32")
+        assert a.dtype == torch.int32 and torch.equal(a.long(), t)
+        assert m._as(t, "i32") is not a                                          # converted afresh, not cached
+        m._check_tokens(torch.tensor([[0, 5, 32]]))
+        with pytest.raises(IndexError, match=r"\[0, 33\)"):
+            m._check_tokens(torch.tensor([[0, 33]]))
+        rpi = rp.clone()
+        V = m._node_features({"R_polymer_type": rpi})
+        assert torch.equal(V, V_ref) and m._node_features({"R_polymer_type": rpi}) is not V
+    assert not m._conv and not m._tokens_ok and m._v_cache is None
+
+
+def test_symmetry_visits():
+    """Symmetry-tied visit plan: groups are visited in the order stream 0 reaches their first member, members in listed order; a
+    residue listed in several groups belongs to the first one; groups that cover a residue twice raise."""
+    visits, gf, gl, w = symmetry_visits([[1, 3]], [[0.5, 0.25]], [3, 0, 1, 4, 2], 5)
+    assert visits == [1, 3, 0, 4, 2]
+    assert gf == [0, 0, 2, 3, 4] and gl == [0, 1, 1, 1, 1]
+    assert w == [1.0, 0.5, 1.0, 0.25, 1.0]                                       # by residue; 1 outside the groups
+    # residue 1 is listed in [0, 1] and in [1, 2]; residue 2 in [2, 3] first: the third group never forms
+    visits, gf, gl, w = symmetry_visits([[0, 1], [2, 3], [1, 2]], [[1, 2], [3, 4], [5, 6]], [2, 1, 0, 3], 4)
+    assert visits == [2, 3, 0, 1] and gf == [0, 0, 2, 2] and gl == [0, 1, 0, 1]
+    assert w == [1.0, 5.0, 6.0, 4.0]                                             # (weights: the last listed one, as in the reference)
+    assert symmetry_visits([[]], [[]], [2, 0, 1], 3)[:3] == ([2, 0, 1], [0, 1, 2], [1, 1, 1])
+    with pytest.raises(ValueError, match="disjoint"):
+        symmetry_visits([[0, 1], [1, 2]], [[1, 1], [1, 1]], [0, 1, 2], 3)
+
+
+def test_pair_bias_dependencies():
+    """The residues whose tokens a residue's pair_bias row reads: any non-zero or non-finite entry of block [i, :, j, :]; indices in
+    ascending order padded with -1; none at all -> (None, 0); more than 64 partners for some residue -> None (no levels)."""
+    B, L, A = 2, 6, 3
+    pb = torch.zeros(B, L, A, L, A)
+    pb[0, 0, 1, 4, 2] = -1.0
+    pb[0, 0, 2, 2, 0] = 0.5
+    pb[1, 3, 0, 5, 0] = float("nan")
+    pb[1, 1, 0, 0, 1] = float("inf")
+    dep_idx, n_dep = pair_bias_dependencies(pb)
+    assert n_dep == 2 and dep_idx.dtype == torch.int32 and dep_idx.is_contiguous()
+    none = [-1, -1]
+    assert dep_idx.tolist() == [[[2, 4], none, none, none, none, none], [none, [0, -1], none, [5, -1], none, none]]
+    assert pair_bias_dependencies(torch.zeros(1, L, A, L, A)) == (None, 0)
+    dense = torch.zeros(1, 70, 1, 70, 1)
+    dense[0, 3, 0, :64, 0] = 1.0
+    assert pair_bias_dependencies(dense)[1] == 64                                # 64 partners: still levels
+    dense[0, 3, 0, 64, 0] = 1.0
+    assert pair_bias_dependencies(dense) is None
 
 
 def test_synthetic_generators_are_deterministic():

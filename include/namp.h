@@ -535,6 +535,47 @@ int namp_train_loss_smoothed(int backward, const int32_t* S, const float* log_pr
                              const float* rna_mask, const float* protein_restypes, const float* dna_restypes, const float* rna_restypes,
                              const float* eps_scale3, double weight, const int32_t* ppm_mask, const double* aligned_ppm,
                              double* loss, const double* g_loss, float* g_log_probs, long G, int V, void* stream);
+/* ---- training / validation metrics (MetricManager of na_metric_manager.py, na_run.py:240-326) -------------------------------
+ * One batch of G = B*L tokens reduced into a caller-owned fp64 table [rows][ncols] with no host synchronisation.  Per-token inputs
+ * are NampTensorRef: a device pointer to G contiguous elements and its element type (NAMP_DT_*); masks are read as values, never
+ * thresholded.  Rows: (no polymer mask, then each of the n_polymer row masks) x (no interface mask, then each of the n_interface
+ * masks), polymer outer; the mask of a row is mask_for_loss * polymer * interface.  Quantities per row, in order:
+ *   sum mask, sum mask*cbp_mask, sum loss*mask, sum accuracy*mask, sum cbp_accuracy*mask*cbp_mask,
+ *   sum (S == res[k])*mask for k < n_res, then sum (S_pred == res[k])*mask for k < n_res.
+ * Modes: log_probs != NULL (fp32 [G][V], V <= 64): S_pred = argmax (first maximum, first NaN), accuracy = (S == S_pred), loss = the
+ * per-token label-smoothed loss of namp_train_loss_smoothed (loss_polymer / restypes / eps_scale / weight / ppm_mask / aligned_ppm as
+ * there), cbp_accuracy = [(S_pred[i], S_pred[b*L + cbp_index[i]]) is a pair of pair_bits] * cbp_mask (bit b of pair_bits[a] marks the
+ * pair (a, b)).  log_probs == NULL: loss (fp64), accuracy, cbp_accuracy and S_pred are given.  A cbp_index outside [0, L) contributes 0
+ * and sets err[0] = 1.
+ * namp_train_metrics: two launches — per-128-token partial slabs, then a fixed-order sum of the slabs per cell added into
+ *   table[row_of[r] * ncols + col_of[q]] (col_of[q] < 0: quantity q is dropped).  row_of / col_of are HOST arrays of the row count
+ *   and of 5 + 2 n_res entries.  Bit-reproducible: no atomics.  workspace: namp_train_metrics_workspace() doubles.
+ * namp_canonical_pair_accuracy: compute_canonical_base_pair_accuracy (na_model_utils.py:148-166) per token: out[G] int64 = the
+ *   pair hit * cbp_mask (log_probs required); err may be NULL. */
+#define NAMP_DT_BOOL 1
+#define NAMP_DT_I32 2
+#define NAMP_DT_I64 3
+#define NAMP_DT_F32 4
+#define NAMP_DT_F64 5
+#define NAMP_METRIC_MAX_RES 8
+typedef struct NampTensorRef { const void* ptr; int32_t dtype; int32_t reserved; } NampTensorRef;
+typedef struct NampMetricBatch {
+  long long G; int32_t L, V;
+  const float* log_probs;
+  NampTensorRef S, mask_for_loss, cbp_mask, cbp_index;
+  NampTensorRef row_polymer[3], row_interface[2];
+  int32_t n_polymer, n_interface;
+  NampTensorRef loss, accuracy, cbp_accuracy, S_pred;                         /* given mode */
+  NampTensorRef loss_polymer[3], ppm_mask;                                     /* fused mode: the loss's inputs */
+  const float* restypes[3]; const double* aligned_ppm; float eps_scale[3]; int32_t n_res; double weight;
+  int32_t res[NAMP_METRIC_MAX_RES];
+  unsigned long long pair_bits[64];
+} NampMetricBatch;
+long namp_train_metrics_workspace(long long G, int rows, int n_res);
+int namp_train_metrics(const NampMetricBatch* m, double* table, int ncols, const int32_t* row_of, const int32_t* col_of, double* workspace,
+                       int32_t* err, void* stream);
+int namp_canonical_pair_accuracy(const NampMetricBatch* m, long long* out, int32_t* err, void* stream);
+
 int namp_train_adam_chunk(void);
 int namp_train_adam_step(const int32_t* blk_tensor, const long long* blk_off, const long long* numel, const unsigned long long* ptrs,
                          int ntensors, int nblocks, float max_norm, double beta1, double beta2, float step_size, float bias_correction2_sqrt,

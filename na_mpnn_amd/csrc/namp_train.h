@@ -1754,26 +1754,36 @@ struct LossArgs {
   const int32_t* S; const float* log_probs; const float* pm[3]; const float* rm[3]; float eps_scale[3];   // weight / |list| as float32
   double one_minus_w; const int32_t* ppm_mask; const double* aligned_ppm; long G; int V;
 };
+// Target of vocabulary entry v for one residue (S = s_i, ppm_row = its aligned_ppm row or NULL, polymer masks p0..p2).  Shared by
+// loss_smoothed_kernel and the metric kernels of namp_metrics.h, so both evaluate the loss with the same arithmetic.
+__device__ __forceinline__ double loss_smoothed_target(const LossArgs& a, int v, int s_i, const double* ppm_row, float p0, float p1, float p2) {
+  const float r0 = a.rm[0][v], r1 = a.rm[1][v], r2 = a.rm[2][v];
+  double t = ppm_row ? ppm_row[v] : (v == s_i ? 1.0 : 0.0);
+  if ((r0 + r1 + r2) != 0.f) t *= a.one_minus_w;
+  const float eps = ((p0 * r0) * a.eps_scale[0] + (p1 * r1) * a.eps_scale[1]) + (p2 * r2) * a.eps_scale[2];
+  return t + (double)eps;
+}
+// loss_i = -sum_v target_v * lp_row[v] (lp_row: global or LDS)
+__device__ __forceinline__ double loss_smoothed_token(const LossArgs& a, const float* lp_row, int s_i, const double* ppm_row, float p0, float p1,
+                                                      float p2) {
+  double acc = 0.0;
+  for (int v = 0; v < a.V; ++v) acc += loss_smoothed_target(a, v, s_i, ppm_row, p0, p1, p2) * (double)lp_row[v];
+  return -acc;
+}
 template <bool BWD>
 __global__ __launch_bounds__(256) void loss_smoothed_kernel(const LossArgs a, double* __restrict__ loss, const double* __restrict__ g_loss,
                                                             float* __restrict__ g_lp) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.G) return;
   const int s_i = a.S[i];
-  const bool ppm = a.ppm_mask && a.ppm_mask[i] != 0;
+  const double* ppm_row = (a.ppm_mask && a.ppm_mask[i] != 0) ? a.aligned_ppm + i * a.V : nullptr;
   const float p0 = a.pm[0][i], p1 = a.pm[1][i], p2 = a.pm[2][i];
-  const double gi = BWD ? g_loss[i] : 0.0;
-  double acc = 0.0;
-  for (int v = 0; v < a.V; ++v) {
-    const float r0 = a.rm[0][v], r1 = a.rm[1][v], r2 = a.rm[2][v];
-    double t = ppm ? a.aligned_ppm[i * a.V + v] : (v == s_i ? 1.0 : 0.0);
-    if ((r0 + r1 + r2) != 0.f) t *= a.one_minus_w;
-    const float eps = ((p0 * r0) * a.eps_scale[0] + (p1 * r1) * a.eps_scale[1]) + (p2 * r2) * a.eps_scale[2];
-    t += (double)eps;
-    if (BWD) g_lp[i * a.V + v] = (float)(-t * gi);
-    else acc += t * (double)a.log_probs[i * a.V + v];
+  if (BWD) {
+    const double gi = g_loss[i];
+    for (int v = 0; v < a.V; ++v) g_lp[i * a.V + v] = (float)(-loss_smoothed_target(a, v, s_i, ppm_row, p0, p1, p2) * gi);
+  } else {
+    loss[i] = loss_smoothed_token(a, a.log_probs + i * a.V, s_i, ppm_row, p0, p1, p2);
   }
-  if (!BWD) loss[i] = -acc;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 #include "../../include/namp.h"
 #include "namp_train.h"
 #include "namp_train_dw.h"
+#include "namp_metrics.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -650,6 +651,102 @@ int namp_train_adam_step(const int32_t* blk_tensor, const long long* blk_off, co
   }
   hipLaunchKernelGGL(adam_step_kernel, dim3(nblocks), dim3(256), 0, s, p, coef2, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), step_size,
                      bias_correction2_sqrt, eps);
+  CHECK_LAUNCH();
+  return NAMP_OK;
+}
+
+}  // extern "C"
+
+// ---- training / validation metrics (namp_metrics.h) ------------------------------------------------------------------------
+namespace {
+
+static_assert(sizeof(NampMetricBatch) == 904, "NampMetricBatch layout is mirrored by na_mpnn_amd/hip.py");
+
+bool metric_ref_ok(const NampTensorRef& r) { return r.ptr != nullptr && r.dtype >= NAMP_DT_BOOL && r.dtype <= NAMP_DT_F64; }
+MetricRef metric_ref(const NampTensorRef& r) { return MetricRef{r.ptr, r.dtype}; }
+
+// checks shared by both entry points; fills everything but the outputs
+int metric_args(const NampMetricBatch* m, bool need_log_probs, MetricArgs& a, const char* fn) {
+  if (!m) return fail(NAMP_EINVAL, "%s: null batch", fn);
+  REQUIRE(m->G >= 1 && m->L >= 1 && m->G % m->L == 0, "%s: G=%lld is not a multiple of L=%d", fn, m->G, m->L);
+  REQUIRE(m->V >= 1 && m->V <= METRIC_VMAX, "%s: V=%d outside [1, %d]", fn, m->V, METRIC_VMAX);
+  REQUIRE(m->n_polymer >= 0 && m->n_polymer <= 3 && m->n_interface >= 0 && m->n_interface <= 2, "%s: %d polymer / %d interface masks",
+          fn, m->n_polymer, m->n_interface);
+  REQUIRE(m->n_res >= 0 && m->n_res <= NAMP_METRIC_MAX_RES, "%s: n_res=%d", fn, m->n_res);
+  REQUIRE(metric_ref_ok(m->S) && metric_ref_ok(m->cbp_mask), "%s: S and cbp_mask are required", fn);
+  const bool fused = m->log_probs != nullptr;
+  REQUIRE(fused || !need_log_probs, "%s: log_probs is required", fn);
+  a = MetricArgs{};
+  a.log_probs = m->log_probs; a.G = m->G; a.L = m->L; a.V = m->V;
+  a.S = metric_ref(m->S); a.cbp_mask = metric_ref(m->cbp_mask);
+  if (fused) {
+    REQUIRE(metric_ref_ok(m->cbp_index), "%s: cbp_index is required with log_probs", fn);
+    a.cbp_idx = metric_ref(m->cbp_index);
+  }
+  for (int b = 0; b < 64; ++b) a.pair_bits[b] = m->pair_bits[b];
+  return NAMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+long namp_train_metrics_workspace(long long G, int rows, int n_res) {
+  if (G < 1 || rows < 1 || n_res < 0) return 0;
+  return (long)((G + METRIC_TOK - 1) / METRIC_TOK) * rows * (METRIC_BASE_Q + 2 * n_res);
+}
+
+int namp_train_metrics(const NampMetricBatch* m, double* table, int ncols, const int32_t* row_of, const int32_t* col_of, double* workspace,
+                       int32_t* err, void* stream) {
+  MetricArgs a;
+  if (int rc = metric_args(m, false, a, __func__)) return rc;
+  REQUIRE_PTR(table); REQUIRE_PTR(workspace);
+  REQUIRE(row_of && col_of && ncols >= 1, "%s: row_of / col_of / ncols", __func__);
+  const bool fused = m->log_probs != nullptr;
+  REQUIRE(metric_ref_ok(m->mask_for_loss), "%s: null mask_for_loss", __func__);
+  a.mfl = metric_ref(m->mask_for_loss);
+  a.npm = m->n_polymer; a.nim = m->n_interface; a.nres = m->n_res;
+  for (int k = 0; k < a.npm; ++k) { REQUIRE(metric_ref_ok(m->row_polymer[k]), "%s: row polymer mask %d", __func__, k); a.pm[k] = metric_ref(m->row_polymer[k]); }
+  for (int k = 0; k < a.nim; ++k) { REQUIRE(metric_ref_ok(m->row_interface[k]), "%s: row interface mask %d", __func__, k); a.im[k] = metric_ref(m->row_interface[k]); }
+  for (int k = 0; k < a.nres; ++k) a.res[k] = m->res[k];
+  if (fused) {
+    for (int k = 0; k < 3; ++k) {
+      REQUIRE(metric_ref_ok(m->loss_polymer[k]) && m->restypes[k], "%s: the loss needs three polymer masks and restype tables", __func__);
+      a.lpm[k] = metric_ref(m->loss_polymer[k]);
+      a.la.rm[k] = m->restypes[k]; a.la.eps_scale[k] = m->eps_scale[k];
+    }
+    REQUIRE((m->ppm_mask.ptr == nullptr) == (m->aligned_ppm == nullptr), "%s: ppm_mask and aligned_ppm go together", __func__);
+    if (m->ppm_mask.ptr) { REQUIRE(metric_ref_ok(m->ppm_mask), "%s: ppm_mask dtype", __func__); a.ppm_mask = metric_ref(m->ppm_mask); }
+    a.la.aligned_ppm = m->aligned_ppm; a.la.one_minus_w = 1.0 - m->weight; a.la.V = m->V; a.la.G = m->G;
+    a.err = err;
+  } else {
+    REQUIRE(metric_ref_ok(m->loss) && metric_ref_ok(m->accuracy) && metric_ref_ok(m->cbp_accuracy) && metric_ref_ok(m->S_pred),
+            "%s: given mode needs loss, accuracy, cbp_accuracy and S_pred", __func__);
+    a.loss = metric_ref(m->loss); a.acc = metric_ref(m->accuracy); a.cbp_acc = metric_ref(m->cbp_accuracy); a.S_pred = metric_ref(m->S_pred);
+  }
+  const int rows = (1 + a.npm) * (1 + a.nim), Q = METRIC_BASE_Q + 2 * a.nres;
+  MetricFinish f = {};
+  for (int r = 0; r < rows; ++r) { REQUIRE(row_of[r] >= 0, "%s: row_of[%d] < 0", __func__, r); f.row_of[r] = row_of[r]; }
+  for (int q = 0; q < Q; ++q) { REQUIRE(col_of[q] < ncols, "%s: col_of[%d] >= ncols", __func__, q); f.col_of[q] = col_of[q]; }
+  const long nblk = (m->G + METRIC_TOK - 1) / METRIC_TOK;
+  REQUIRE(nblk <= INT32_MAX, "%s: G too large", __func__);
+  f.Q = Q; f.ncols = ncols; f.nblk = (int)nblk; f.P = rows * Q;
+  a.partial = workspace;
+  hipStream_t s = (hipStream_t)stream;
+  if (fused) hipLaunchKernelGGL(metrics_partial_kernel<0>, dim3((unsigned)nblk), dim3(METRIC_TOK), 0, s, a);
+  else hipLaunchKernelGGL(metrics_partial_kernel<1>, dim3((unsigned)nblk), dim3(METRIC_TOK), 0, s, a);
+  hipLaunchKernelGGL(metrics_finish_kernel, dim3((unsigned)f.P), dim3(256), 0, s, (const double*)workspace, f, table);
+  CHECK_LAUNCH();
+  return NAMP_OK;
+}
+
+int namp_canonical_pair_accuracy(const NampMetricBatch* m, long long* out, int32_t* err, void* stream) {
+  MetricArgs a;
+  if (int rc = metric_args(m, true, a, __func__)) return rc;
+  REQUIRE_PTR(out);
+  a.cbp_out = out; a.err = err;
+  const long nblk = (m->G + METRIC_TOK - 1) / METRIC_TOK;
+  hipLaunchKernelGGL(metrics_partial_kernel<2>, dim3((unsigned)nblk), dim3(METRIC_TOK), 0, (hipStream_t)stream, a);
   CHECK_LAUNCH();
   return NAMP_OK;
 }

@@ -71,6 +71,24 @@ class NampReduce(C.Structure):
                 ("n", C.c_int), ("reserved", C.c_int)]
 
 
+NAMP_DT = {"bool": 1, "uint8": 1, "int32": 2, "int64": 3, "float32": 4, "float64": 5}   # NAMP_DT_* element types of NampTensorRef
+NAMP_METRIC_MAX_RES = 8
+
+
+class NampTensorRef(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+class NampMetricBatch(C.Structure):
+    _fields_ = [("G", C.c_longlong), ("L", C.c_int32), ("V", C.c_int32), ("log_probs", c_fp),
+                ("S", NampTensorRef), ("mask_for_loss", NampTensorRef), ("cbp_mask", NampTensorRef), ("cbp_index", NampTensorRef),
+                ("row_polymer", NampTensorRef * 3), ("row_interface", NampTensorRef * 2), ("n_polymer", C.c_int32), ("n_interface", C.c_int32),
+                ("loss", NampTensorRef), ("accuracy", NampTensorRef), ("cbp_accuracy", NampTensorRef), ("S_pred", NampTensorRef),
+                ("loss_polymer", NampTensorRef * 3), ("ppm_mask", NampTensorRef),
+                ("restypes", c_fp * 3), ("aligned_ppm", c_fp), ("eps_scale", C.c_float * 3), ("n_res", C.c_int32), ("weight", C.c_double),
+                ("res", C.c_int32 * NAMP_METRIC_MAX_RES), ("pair_bits", C.c_ulonglong * 64)]
+
+
 i32, vp, sz = C.c_int, C.c_void_p, C.c_size_t
 _PROTOTYPES = {
     # name: (restype, argtypes)      — must list every symbol include/namp.h declares
@@ -159,6 +177,9 @@ _PROTOTYPES = {
     "namp_train_g16_elems": (C.c_long, [C.c_long]),
     "namp_train_loss_smoothed": (i32, [i32, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.POINTER(C.c_float), C.c_double, c_ip, vp,
                                        vp, vp, c_fp, C.c_long, i32, vp]),
+    "namp_train_metrics_workspace": (C.c_long, [C.c_longlong, i32, i32]),
+    "namp_train_metrics": (i32, [C.POINTER(NampMetricBatch), vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp]),
+    "namp_canonical_pair_accuracy": (i32, [C.POINTER(NampMetricBatch), vp, vp, vp]),
     "namp_train_adam_chunk": (i32, []),
     "namp_train_adam_step": (i32, [vp, vp, vp, vp, i32, i32, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_float, c_fp, vp]),
     "namp_sample_levels": (i32, [c_ip, c_ip, c_ip, c_ip, i32, i32, i32, i32, vp]),

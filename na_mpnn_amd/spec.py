@@ -48,6 +48,17 @@ def restype_to_int(na_shared_tokens: bool = False):
     return d
 
 
+# the 16 Watson-Crick pairs a canonical base pair may form, DNA and RNA mixed (na_data_utils.py:286-303)
+NA_CANONICAL_BASE_PAIRS = [("DA", "DT"), ("DA", "U"), ("DC", "DG"), ("DC", "G"), ("DG", "DC"), ("DG", "C"), ("DT", "DA"), ("DT", "A"),
+                           ("A", "DT"), ("A", "U"), ("C", "DG"), ("C", "G"), ("G", "DC"), ("G", "C"), ("U", "DA"), ("U", "A")]
+
+
+def na_canonical_base_pair_ints(restype_to_int):
+    """``PDBDataset.na_canonical_base_pair_ints`` (na_data_utils.py:305-308): the pairs as token ids.  Under the shared DNA/RNA
+    tokens of ``restype_to_int(na_shared_tokens=True)`` the list holds duplicates, as the reference's does."""
+    return [(restype_to_int[a], restype_to_int[b]) for a, b in NA_CANONICAL_BASE_PAIRS]
+
+
 def state_dict_spec(num_encoder_layers: int = 3, num_decoder_layers: int = 3,
                     hidden: int = H, vocab: int = VOCAB, num_letters: int = VOCAB):
     """Ordered {key: shape} of the reference ``ProteinMPNN.state_dict()``.

@@ -1303,19 +1303,58 @@ def polymer_restype_tables(restype_to_int, num_letters, device):
     return masks, nums
 
 
+def featurize(batch, polytype_to_int, restype_to_int, atom_dict, device):
+    """The training loop's batch featurize (na_model_utils.py:8-98): ``batch`` = [(out_dict, L), ...] (items whose out_dict is a
+    list are dropped); every key padded to the longest L with the reference's dtypes and pad values (S = PAD, R_polymer_type = PAD,
+    R_idx = -100, chain_labels = -1, zeros elsewhere, mask = 1 on the residues).  Returns "pass" for an empty batch.  (shard.pad_batch
+    keeps each input's dtype and the fixed pad ids of the default vocabulary, so the per-key table below is spelt out here.)"""
+    batch = [b for b in batch if not isinstance(b[0], list)]
+    if not batch:
+        return "pass"
+    B = len(batch)
+    lengths = [int(b[1]) for b in batch]
+    L = max(lengths)
+    A, V = len(atom_dict), len(restype_to_int)
+    i32, i64 = torch.int32, torch.int64
+    spec_ = {   # key: (shape after [B, L], dtype, pad value)
+        "X": ((A, 3), torch.float32, 0), "X_m": ((A,), i32, 0), "S": ((), i64, restype_to_int["PAD"]), "R_idx": ((), i32, -100),
+        "chain_labels": ((), i64, -1), "protein_mask": ((), i32, 0), "dna_mask": ((), i32, 0), "rna_mask": ((), i32, 0),
+        "R_polymer_type": ((), i64, polytype_to_int["PAD"]), "interface_mask": ((), i32, 0), "base_pair_mask": ((), i32, 0),
+        "base_pair_index": ((), i64, 0), "canonical_base_pair_mask": ((), i32, 0), "canonical_base_pair_index": ((), i64, 0),
+        "aligned_ppm": ((V,), torch.float64, 0), "ppm_mask": ((), i32, 0)}
+    out = {k: torch.full((B, L) + shape, pad, dtype=dt) for k, (shape, dt, pad) in spec_.items()}
+    out["mask"] = torch.zeros(B, L, dtype=i32)
+    for i, (d, n) in enumerate(zip((b[0] for b in batch), lengths)):
+        for k in spec_:
+            out[k][i, :n] = torch.as_tensor(d[k])
+        out["mask"][i, :n] = 1
+    order = ["X", "X_m", "mask", "S", "R_idx", "chain_labels", "protein_mask", "dna_mask", "rna_mask", "R_polymer_type", "interface_mask",
+             "base_pair_mask", "base_pair_index", "canonical_base_pair_mask", "canonical_base_pair_index", "aligned_ppm", "ppm_mask"]
+    fd = {k: out[k].to(device) for k in order}
+    fd["structure_path"] = [b[0]["structure_path"] for b in batch]
+    fd["assembly_id"] = [b[0]["assembly_id"] for b in batch]
+    return fd
+
+
+def _mask_for_loss(fd, tokens_with_no_loss):
+    S, mask = fd["S"].long(), fd["mask"]
+    S_mask = 1 - torch.any(S[:, :, None] == tokens_with_no_loss[None, None, :], dim=-1).long()
+    return S, mask * S_mask
+
+
 def train_step(model, optimizer, fd, polymer_restype_masks, polymer_restype_nums, tokens_with_no_loss, label_smoothing=0.1,
-               loss_tokens=2000.0, gradient_norm=0.0, decoding_randn=None, data_parallel=False, scaler=None):
+               loss_tokens=2000.0, gradient_norm=0.0, decoding_randn=None, data_parallel=False, scaler=None, metrics=None):
     """One optimisation step of na_run.py:198-238: forward, label-smoothed loss, backward, clip, Noam/Adam.
     Mixed precision (the reference's MIXED_PRECISION branch, :216-238): set ``model.message_precision = "bf16"`` — the
     per-edge GEMMs of forward, backward and weight gradients then run as plain bf16 products with fp32 accumulation, master
     weights / residue-level math / loss / optimiser stay fp32 — and optionally pass the reference's ``scaler``
     (torch GradScaler): ``scaler.scale(loss).backward(); clip; scaler.step(optimizer); scaler.update()`` like :232-238.
     ``data_parallel`` (an extension; torch.distributed initialised, one process per GPU): gradients are averaged over
-    the ranks with one all-reduce before clipping, so every rank applies the same update."""
+    the ranks with one all-reduce before clipping, so every rank applies the same update.
+    ``metrics`` (a metrics.MetricManager): the step's log_probs are added to its "train" rows with the step's own loss parameters
+    (na_run.py:240-273) — two more launches, no host synchronisation; None leaves the step exactly as it is."""
     optimizer.zero_grad()
-    S, mask = fd["S"].long(), fd["mask"]
-    S_mask = 1 - torch.any(S[:, :, None] == tokens_with_no_loss[None, None, :], dim=-1).long()
-    mask_for_loss = mask * S_mask
+    S, mask_for_loss = _mask_for_loss(fd, tokens_with_no_loss)
     polymer_masks = {"protein": fd["protein_mask"], "dna": fd["dna_mask"], "rna": fd["rna_mask"]}
     log_probs, _ = forward_train(model, fd, decoding_randn)
     # position-probability targets of the specificity model (na_run.py:229-230), when the batch carries them
@@ -1338,4 +1377,20 @@ def train_step(model, optimizer, fd, polymer_restype_masks, polymer_restype_nums
         scaler.update()
     else:
         optimizer.step()
+    if metrics is not None:
+        metrics.accumulate_from_log_probs(log_probs.detach(), fd, "train", mask_for_loss, *metrics.masks_for(fd),
+                                          polymer_restype_masks=polymer_restype_masks, polymer_restype_nums=polymer_restype_nums,
+                                          weight=label_smoothing)
     return loss.detach(), log_probs.detach()
+
+
+def valid_step(model, fd, metrics, polymer_restype_masks, polymer_restype_nums, tokens_with_no_loss, label_smoothing=0.1,
+               decoding_randn=None):
+    """One validation batch of na_run.py:276-326: a no-grad forward, mask_for_loss as in train_step, and the batch added to the
+    "valid" rows of ``metrics`` (two launches, no host synchronisation).  Returns log_probs."""
+    S, mask_for_loss = _mask_for_loss(fd, tokens_with_no_loss)
+    with torch.no_grad():
+        log_probs, _ = model(fd, decoding_randn)
+    metrics.accumulate_from_log_probs(log_probs, fd, "valid", mask_for_loss, *metrics.masks_for(fd), polymer_restype_masks=polymer_restype_masks,
+                                      polymer_restype_nums=polymer_restype_nums, weight=label_smoothing)
+    return log_probs

@@ -1,25 +1,29 @@
 #!/usr/bin/env python
 """bench.py — residues/s of the NA-MPNN encoder+decoder forward on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1|cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1|cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-           --master-port P bench.py --gpus N --steps K --warmup W
+           --master-port P bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path — (V, E, E_idx, S, mask, decoding ranks) -> log_probs, i.e.
 W_v/W_e + 3 x EncLayer + decoder context + 3 x DecLayer + W_out + log_softmax — over
 one batch of synthetic graphs already resident in HBM.  Default workload = BASELINE.json configs[1]
 ("cfg2": B=1, N=1000, K=48, H=128, 3+3 layers).  Every rank runs its own independent
-complexes (weak scaling, no data-path collective); one RCCL all-gather of the arg-max sequences at
-the end collates results for reporting, outside the timed region.
+complexes (weak scaling, no data-path collective); with --full, one RCCL all-gather of the arg-max
+sequences at the end collates results for reporting, outside the timed region.
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes
+--dump-outputs if given and prints the result line (the contract keys: `metric`, `value`, `unit`,
+`ms_per_step`, `dtype`, ...).  Everything else below is measured only with `--full`.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes this file under
 `torch.distributed.run` with N ranks (one per GPU, backend nccl = RCCL); under a launcher it uses
 the launcher's ranks and refuses a WORLD_SIZE that contradicts --gpus.
 
-The default cfg2 run times the path TWICE with the same K / W: the headline (`value`, `dtype` "f32")
-is the EXACT fp32 evaluation (v_mfma_f32_16x16x4_f32, what BASELINE configs[1] states); the `x3`
-object beside it is the split-bf16 evaluation (three bf16 products per fp32 product, fp32-equivalent
-to ~2^-16), the model's default.  Rank 0 prints ONE COMPACT JSON line (< 6 KB) with the driver's contract keys plus
+The headline of cfg2 (`value`, `dtype` "f32") is the EXACT fp32 evaluation (v_mfma_f32_16x16x4_f32, what
+BASELINE configs[1] states).  A --full cfg2 run times the path again with the same K / W: the `x3`
+object beside the headline is the split-bf16 evaluation (three bf16 products per fp32 product, fp32-equivalent
+to ~2^-16), the model's default.  With --full, rank 0 prints ONE COMPACT JSON line (< 6 KB) with the driver's contract keys plus
   roofline      – dominant kernel: EXECUTED FLOPs / HIP-event-measured duration vs the MFMA peak of its dtype (`frac`); the
                   rate of the reference's dense formulation (the launch executes about half of it) beside it as
                   `algorithmic_*`; `traffic` = HBM bytes per launch from two live rocprofv3 PMC passes of this very workload
@@ -429,56 +433,10 @@ BWD_FLOP_EDGE_ALGO = 3 * 2 * 128 * 128
 BWD_FLOP_EDGE_EXEC = 5 * 2 * 128 * 128
 
 
-def train_bench(args, dev, rank, world, dist):
-    """BASELINE configs[4] ("cfg5"): one optimisation step of na_run.py:198-238 — featurise, forward, label-smoothed loss,
-    backward, gradient clip, Noam/Adam — on B x N synthetic residues per rank, dropout 0.1, coordinate noise 0.1 A."""
+def train_step_profile(m, step, B, N, K):
+    """--full, cfg5: one more training step under the device profiler -> the roofline of the per-edge backward launches and the
+    per-kernel table of the step."""
     from na_mpnn_amd import train
-    from na_mpnn_amd.model import ProteinMPNN
-    cfg = WORKLOADS["cfg5"]
-    B, N, K = cfg["B"], cfg["N"], cfg["K"]
-    rti = spec.restype_to_int()
-    torch.manual_seed(1234 + rank)
-    m = ProteinMPNN(num_letters=33, vocab=33, k_neighbors=K, dropout=0.1, augment_eps=0.1, atom_dict=spec.atom_dict(),
-                    restype_to_int=rti, polytype_to_int=spec.polytype_to_int())
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_weights(0).items()})
-    m.to(dev).train()
-    if getattr(args, "precision", None):
-        m.message_precision = args.precision          # "bf16" = the mixed-precision mode (na_run.py MIXED_PRECISION)
-    cxs = [synth.make_complex(seed=5000 + 100 * rank + b, n=N, n_chains=4) for b in range(B)]
-    fd = {k: torch.from_numpy(np.stack([c[k] for c in cxs])).to(dev) for k in cxs[0]}
-    fd["S"] = fd["S"].long()
-    opt = train.get_std_opt(m.parameters(), 128, 0)
-    rm, rn = train.polymer_restype_tables(rti, 33, dev)
-    no_loss = torch.tensor([rti[t] for t in ("UNK", "DX", "RX", "MAS", "PAD")], device=dev)
-    torch.set_grad_enabled(True)
-
-    def step():
-        return train.train_step(m, opt, fd, rm, rn, no_loss, label_smoothing=0.1, loss_tokens=6000.0, gradient_norm=1.0,
-                                data_parallel=dist is not None)
-
-    def barrier():
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    quiet_gc.collect()
-    torch.cuda.reset_peak_memory_stats()                 # peak_mem_gib is this workload's own peak (the secondary runs share the process)
-    for _ in range(args.warmup):
-        step()
-    barrier()
-    with quiet_gc():
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loss, _ = step()
-        torch.cuda.synchronize()
-        barrier()
-        elapsed = time.perf_counter() - t0
-    if dist is not None:
-        t = torch.tensor([elapsed], device=coll_device(dev, dist), dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * B * N * args.steps / elapsed
     # dominant kernel, timed live with HIP events on the launch stream (torch's current stream)
     from na_mpnn_amd import hip as H_
     from torch.profiler import profile, ProfilerActivity
@@ -533,6 +491,64 @@ def train_bench(args, dev, rank, world, dist):
                 "note": "all per-edge backward launches of the step together; algorithmic = data- and weight-gradient GEMMs per edge, "
                         "executed adds the recomputed forward GEMMs (the reference's checkpoint-recompute policy) and counts the "
                         "three bf16 products of a split product; durations from the device trace of one step"}
+    return {"roofline": roofline,
+            "per_kernel_ms_per_step": {k: round(v[0], 3) for k, v in sorted(ours.items(), key=lambda kv: -kv[1][0])},
+            "device_ms_per_step": round(total_dev_ms, 3), "hip_kernel_share": round(sum(v[0] for v in ours.values()) / total_dev_ms, 3),
+            "other_kernels_ms_per_step": {k[:90]: [round(v[0], 3), v[1]] for k, v in sorted(((k, v) for k, v in kern.items() if k not in ours),
+                                                                                     key=lambda kv: -kv[1][0])[:16]}}
+
+
+def train_bench(args, dev, rank, world, dist):
+    """BASELINE configs[4] ("cfg5"): one optimisation step of na_run.py:198-238 — featurise, forward, label-smoothed loss,
+    backward, gradient clip, Noam/Adam — on B x N synthetic residues per rank, dropout 0.1, coordinate noise 0.1 A."""
+    from na_mpnn_amd import train
+    from na_mpnn_amd.model import ProteinMPNN
+    cfg = WORKLOADS["cfg5"]
+    B, N, K = cfg["B"], cfg["N"], cfg["K"]
+    rti = spec.restype_to_int()
+    torch.manual_seed(1234 + rank)
+    m = ProteinMPNN(num_letters=33, vocab=33, k_neighbors=K, dropout=0.1, augment_eps=0.1, atom_dict=spec.atom_dict(),
+                    restype_to_int=rti, polytype_to_int=spec.polytype_to_int())
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_weights(0).items()})
+    m.to(dev).train()
+    if getattr(args, "precision", None):
+        m.message_precision = args.precision          # "bf16" = the mixed-precision mode (na_run.py MIXED_PRECISION)
+    cxs = [synth.make_complex(seed=5000 + 100 * rank + b, n=N, n_chains=4) for b in range(B)]
+    fd = {k: torch.from_numpy(np.stack([c[k] for c in cxs])).to(dev) for k in cxs[0]}
+    fd["S"] = fd["S"].long()
+    opt = train.get_std_opt(m.parameters(), 128, 0)
+    rm, rn = train.polymer_restype_tables(rti, 33, dev)
+    no_loss = torch.tensor([rti[t] for t in ("UNK", "DX", "RX", "MAS", "PAD")], device=dev)
+    torch.set_grad_enabled(True)
+
+    def step():
+        return train.train_step(m, opt, fd, rm, rn, no_loss, label_smoothing=0.1, loss_tokens=6000.0, gradient_norm=1.0,
+                                data_parallel=dist is not None)
+
+    def barrier():
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    quiet_gc.collect()
+    torch.cuda.reset_peak_memory_stats()                 # peak_mem_gib is this workload's own peak (the secondary runs share the process)
+    for _ in range(args.warmup):
+        step()
+    barrier()
+    with quiet_gc():
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            loss, _ = step()
+        torch.cuda.synchronize()
+        barrier()
+        elapsed = time.perf_counter() - t0
+    if dist is not None:
+        t = torch.tensor([elapsed], device=coll_device(dev, dist), dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * B * N * args.steps / elapsed
+    mp = getattr(m, "message_precision", "x3")
     out = {"metric": "residues/sec trained (featurise + fwd + bwd + clip + Noam/Adam), N=1500 K=48 h=128", "value": round(value, 1),
            "unit": "residues/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -543,16 +559,13 @@ def train_bench(args, dev, rank, world, dist):
            "config": {"workload": f"cfg5: B={B} x N={N} residues per rank, K={K}, H=128, 3+3 layers, dropout 0.1, coordinate noise 0.1, "
                                   "label smoothing 0.1, seeded random-init weights; N > 1: data parallel, one RCCL "
                                   "all-reduce of the 9.2 MB gradient bucket per step (the reference trains single-GPU)",
-                      "global_batch": B * world, "seq_len": N, "parallelism": f"dp{world}"},
-           "roofline": roofline,
-           "per_kernel_ms_per_step": {k: round(v[0], 3) for k, v in sorted(ours.items(), key=lambda kv: -kv[1][0])},
-           "device_ms_per_step": round(total_dev_ms, 3), "hip_kernel_share": round(sum(v[0] for v in ours.values()) / total_dev_ms, 3),
-           "other_kernels_ms_per_step": {k[:90]: [round(v[0], 3), v[1]] for k, v in sorted(((k, v) for k, v in kern.items() if k not in ours),
-                                                                                    key=lambda kv: -kv[1][0])[:16]},
-           "whole_step": {"algorithmic_tflops": round(TRAIN_FLOP_STEP * B * N / (ms_per_step * 1e-3) / 1e12, 2),
-                          "final_loss": round(float(loss), 5),
-                          "peak_mem_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}}
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+                      "global_batch": B * world, "seq_len": N, "parallelism": f"dp{world}"}}
+    if args.full:
+        out.update(train_step_profile(m, step, B, N, K))
+    out["whole_step"] = {"algorithmic_tflops": round(TRAIN_FLOP_STEP * B * N / (ms_per_step * 1e-3) / 1e12, 2),
+                         "final_loss": round(float(loss), 5),
+                         "peak_mem_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
+    if rank == 0 and not args.no_cpu_baseline and world == 1 and args.full:
         out["cpu_baseline"] = cpu_train_baseline(cxs[0], K, rti)
     torch.set_grad_enabled(False)
     return out
@@ -621,37 +634,41 @@ def split_bench(args, dev, rank, world, dist):
         barrier()
         elapsed = time.perf_counter() - t0
     my_res = int(sum(lengths[i] for i in mine))
-    per_rank = [[float(my_res), my_elapsed]]
     if dist is not None:
         t = torch.tensor([elapsed], device=coll_device(dev, dist), dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        mine_t = torch.tensor([float(my_res), my_elapsed], device=coll_device(dev, dist), dtype=torch.float64)
-        allr = [torch.empty_like(mine_t) for _ in range(world)]
-        dist.all_gather(allr, mine_t)
-        per_rank = [[float(a[0]), float(a[1])] for a in allr]
     total_res = int(lengths.sum())
-    t1 = time.perf_counter()
-    collated = shard.all_gather_ragged(result, len(lengths), device=coll_device(dev, dist))
-    torch.cuda.synchronize()
-    gather_ms = (time.perf_counter() - t1) * 1e3
-    n_coll = sum(int(x.numel()) for x in collated if x is not None)
-    rr, rs = [a[0] for a in per_rank], [a[1] for a in per_rank]
     out = {"metric": "residues/sec (featurise + enc + dec forward from coordinates), design_test-sized split", "unit": "residues/s",
            "value": round(total_res * args.steps / elapsed, 1), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
            "dtype": "bf16x3 (GEMMs as split-bf16 products, fp32 accumulate: fp32-equivalent to 2^-16; fp32 elsewhere)" if getattr(m, "message_precision", "x3") == "x3" else "f32", "data": "synthetic",
            "config": {"workload": f"cfg4: {len(lengths)} complexes, {total_res} residues (N_i log-uniform 50..3000), K=48, one "
                                   "score() from coordinates per token-bucket batch, LPT shards, no data-path collective",
-                      "global_batch": len(lengths), "seq_len": int(np.median(lengths)), "parallelism": f"independent complexes x{world}"},
-           "shard": {"rank0_complexes": len(mine), "rank0_batches": len(batches), "batch_tokens": args.batch_tokens, "rank0_residues": my_res,
-                     "ideal_residues_per_rank": total_res // world, "steps_requested": steps_requested, "calibration_pass_s": round(t_pass, 4),
-                     "per_rank_residues": {"min": int(min(rr)), "mean": round(sum(rr) / len(rr), 1), "max": int(max(rr))},
-                     "per_rank_seconds": {"min": round(min(rs), 4), "mean": round(sum(rs) / len(rs), 4), "max": round(max(rs), 4)},
-                     "lpt_imbalance": round(max(rr) / (sum(rr) / len(rr)), 4)},
-           "collation": {"collective": "all_reduce(lengths) + all_gather(padded int32 sequences)", "ms": round(gather_ms, 3),
-                         "backend": (dist.get_backend() if dist is not None else None),
-                         "ranks": (dist.get_world_size() if dist is not None else 1), "residues_collated": n_coll}}
+                      "global_batch": len(lengths), "seq_len": int(np.median(lengths)), "parallelism": f"independent complexes x{world}"}}
+    if not args.full:
+        return out
+    # --full: the shard's per-rank figures and the collation of the designed sequences
+    per_rank = [[float(my_res), my_elapsed]]
+    if dist is not None:
+        mine_t = torch.tensor([float(my_res), my_elapsed], device=coll_device(dev, dist), dtype=torch.float64)
+        allr = [torch.empty_like(mine_t) for _ in range(world)]
+        dist.all_gather(allr, mine_t)
+        per_rank = [[float(a[0]), float(a[1])] for a in allr]
+    t1 = time.perf_counter()
+    collated = shard.all_gather_ragged(result, len(lengths), device=coll_device(dev, dist))
+    torch.cuda.synchronize()
+    gather_ms = (time.perf_counter() - t1) * 1e3
+    n_coll = sum(int(x.numel()) for x in collated if x is not None)
+    rr, rs = [a[0] for a in per_rank], [a[1] for a in per_rank]
+    out["shard"] = {"rank0_complexes": len(mine), "rank0_batches": len(batches), "batch_tokens": args.batch_tokens, "rank0_residues": my_res,
+                    "ideal_residues_per_rank": total_res // world, "steps_requested": steps_requested, "calibration_pass_s": round(t_pass, 4),
+                    "per_rank_residues": {"min": int(min(rr)), "mean": round(sum(rr) / len(rr), 1), "max": int(max(rr))},
+                    "per_rank_seconds": {"min": round(min(rs), 4), "mean": round(sum(rs) / len(rs), 4), "max": round(max(rs), 4)},
+                    "lpt_imbalance": round(max(rr) / (sum(rr) / len(rr)), 4)}
+    out["collation"] = {"collective": "all_reduce(lengths) + all_gather(padded int32 sequences)", "ms": round(gather_ms, 3),
+                        "backend": (dist.get_backend() if dist is not None else None),
+                        "ranks": (dist.get_world_size() if dist is not None else 1), "residues_collated": n_coll}
     assert n_coll == total_res, (n_coll, total_res)
     return out
 
@@ -702,19 +719,20 @@ def design_bench(args, dev, rank, world, dist, specificity=False):
         t = torch.tensor([elapsed], device=coll_device(dev, dist), dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # latency of ONE synchronised design call (the timed region above issues the calls back to back: pipelined throughput — the host enqueues
-    # call i + 1 while call i runs): median of 20 calls, each bracketed by device syncs
+    # --full: latency of ONE synchronised design call (the timed region above issues the calls back to back: pipelined throughput — the
+    # host enqueues call i + 1 while call i runs): median of 20 calls, each bracketed by device syncs
     lat = []
-    with quiet_gc():
-        for _ in range(20):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            step()
-            torch.cuda.synchronize()
-            lat.append(time.perf_counter() - t1)
-    lat.sort()
+    if args.full:
+        with quiet_gc():
+            for _ in range(20):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                step()
+                torch.cuda.synchronize()
+                lat.append(time.perf_counter() - t1)
+        lat.sort()
     res = {"metric": "sampled residues/sec (design: featurise + encode + autoregressive sample), " + ("1am9-sized complex, specificity mode" if specificity else "4oqu-sized complex"),
-           "latency_ms": round(lat[len(lat) // 2] * 1e3, 3), "latency_ms_min": round(lat[0] * 1e3, 3),
+           **({"latency_ms": round(lat[len(lat) // 2] * 1e3, 3), "latency_ms_min": round(lat[0] * 1e3, 3)} if lat else {}),
            "value": round(world * bs * n * args.steps / elapsed, 1), "unit": "residues/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "bf16x3 (GEMMs as split-bf16 products, fp32 accumulate: fp32-equivalent to 2^-16; fp32 elsewhere)" if getattr(m, "message_precision", "x3") == "x3" else "f32", "data": "synthetic",
@@ -724,7 +742,7 @@ def design_bench(args, dev, rank, world, dist, specificity=False):
                                    "coordinates; level-parallel decoding"), "global_batch": bs * world, "seq_len": n,
                       "parallelism": f"replicas x{world}"},
            "levels": (int(out["levels"]) if out.get("levels") is not None else None)}
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and not args.no_cpu_baseline and world == 1 and args.full:
         if True:
             from oracle import cpu_ref
             torch.set_num_threads(min(8, os.cpu_count() or 1))
@@ -870,9 +888,11 @@ def coll_device(dev, dist):
     return torch.device("cpu") if (dist is not None and dist.get_backend() == "gloo") else dev
 
 
-def encdec_bench(args, dev, rank, world, dist, workload, precision, steps, warmup, profile_steps=None, capture=False):
+def encdec_bench(args, dev, rank, world, dist, workload, precision, steps, warmup, profile_steps=None, capture=False, full=True):
     """Time `steps` passes of the encoder+decoder forward (one namp_encdec_fwd call each) at `precision`.  capture=True keeps
-    host copies of the last timed step's outputs in `runner.outputs` (see capture_outputs)."""
+    host copies of the last timed step's outputs in `runner.outputs` (see capture_outputs).  full=False returns the headline keys
+    only; full=True adds the polled clock, the collation of the arg-max sequences and the event-instrumented per-kernel pass
+    behind `roofline` / `per_kernel`."""
     cfg = WORKLOADS[workload]
     B, N, K = cfg["B"], cfg["N"], cfg["K"]
     cfg_idx = 1 if workload == "cfg2" else 2
@@ -908,6 +928,18 @@ def encdec_bench(args, dev, rank, world, dist, workload, precision, steps, warmu
         elapsed = float(t.item())
     ms_per_step = elapsed / steps * 1e3
     value = world * B * N * steps / elapsed
+    dtype = {"fp32": "f32", "x3": "bf16x3 (per-edge GEMMs as three bf16 products of split fp32 operands, fp32 accumulate: "
+                                   "fp32-equivalent to 2^-16; fp32 everywhere else)",
+             "bf16": "bf16 (per-edge GEMMs; fp32 accumulate, fp32 elsewhere)"}[precision]
+    out = {"metric": "residues/sec (enc+dec fwd), N~1000 K=48 h=128; seq-recovery vs CPU ref", "value": round(value, 1),
+           "unit": "residues/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(ms_per_step, 4),
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": dtype, "data": "synthetic",
+           "config": {"workload": f"{workload}: B={B} x N={N} residues per rank, K={K}, H=128, 3 enc + 3 dec layers, "
+                                  f"per-edge GEMMs {precision}, seeded random-init weights, independent complexes per rank",
+                      "precision": precision, "global_batch": B * world, "seq_len": N, "parallelism": f"replicas x{world}"}}
+    if not full:
+        return out, runner
     # the clock under this workload (outside the timed region: ~0.2 s of the same steps with a poller thread beside them)
     clock_mhz = None
     if rank == 0:
@@ -958,24 +990,14 @@ def encdec_bench(args, dev, rank, world, dist, workload, precision, steps, warmu
     if clock_mhz:
         roofline["clock_mhz"] = clock_mhz
         roofline["frac_at_measured_clock"] = round(roofline["frac"] * 2400.0 / max(float(clock_mhz), 1.0), 4)
-    dtype = {"fp32": "f32", "x3": "bf16x3 (per-edge GEMMs as three bf16 products of split fp32 operands, fp32 accumulate: "
-                                   "fp32-equivalent to 2^-16; fp32 everywhere else)",
-             "bf16": "bf16 (per-edge GEMMs; fp32 accumulate, fp32 elsewhere)"}[precision]
-    out = {"metric": "residues/sec (enc+dec fwd), N~1000 K=48 h=128; seq-recovery vs CPU ref", "value": round(value, 1),
-           "unit": "residues/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(ms_per_step, 4),
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": dtype, "data": "synthetic",
-           "config": {"workload": f"{workload}: B={B} x N={N} residues per rank, K={K}, H=128, 3 enc + 3 dec layers, "
-                                  f"per-edge GEMMs {precision}, seeded random-init weights, independent complexes per rank",
-                      "precision": precision, "global_batch": B * world, "seq_len": N, "parallelism": f"replicas x{world}"},
-           "roofline": roofline, "per_kernel": per_kernel,
-           "per_kernel_note": f"separate event-instrumented pass of {psteps} steps (HIP events around every launch)",
-           "whole_path": {"algorithmic_tflops": round(ALGO_FLOP_TOTAL * B * N / (ms_per_step * 1e-3) / 1e12, 3),
-                          "ms_per_step_instrumented_pass": round(sum(v["ms_per_step"] for v in per_kernel.values()), 5)},
-           "collation": {"collective": "all_reduce(lengths) + all_gather(padded int32 arg-max sequences), outside the timed region",
-                         "backend": (dist.get_backend() if dist is not None else None),
-                         "ranks": (dist.get_world_size() if dist is not None else 1),
-                         "collated_residues": n_collated, "expected_residues": world * B * N, "ms": round(gather_ms, 3)}}
+    out.update({"roofline": roofline, "per_kernel": per_kernel,
+                "per_kernel_note": f"separate event-instrumented pass of {psteps} steps (HIP events around every launch)",
+                "whole_path": {"algorithmic_tflops": round(ALGO_FLOP_TOTAL * B * N / (ms_per_step * 1e-3) / 1e12, 3),
+                               "ms_per_step_instrumented_pass": round(sum(v["ms_per_step"] for v in per_kernel.values()), 5)},
+                "collation": {"collective": "all_reduce(lengths) + all_gather(padded int32 arg-max sequences), outside the timed region",
+                              "backend": (dist.get_backend() if dist is not None else None),
+                              "ranks": (dist.get_world_size() if dist is not None else 1),
+                              "collated_residues": n_collated, "expected_residues": world * B * N, "ms": round(gather_ms, 3)}})
     return out, runner
 
 
@@ -1157,8 +1179,8 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg2")
     ap.add_argument("--specificity", action="store_true", help="with --workload cfg1: the specificity-mode call (cfg1s: batch_size 30, T 0.6, 389 residues)")
     ap.add_argument("--precision", choices=["x3", "fp32", "bf16"], default=None,
-                    help="per-edge GEMM evaluation of the headline: default fp32 for cfg2 (exact fp32 MFMA, BASELINE configs[1]; the "
-                         "x3 evaluation is timed beside it), bf16 for cfg3 (BASELINE configs[2]); x3 = split-bf16 products")
+                    help="per-edge GEMM evaluation of the headline: default fp32 for cfg2 (exact fp32 MFMA, BASELINE configs[1]; with "
+                         "--full the x3 evaluation is timed beside it), bf16 for cfg3 (BASELINE configs[2]); x3 = split-bf16 products")
     ap.add_argument("--design-batch", type=int, default=1, help="cfg1: batch_size of the design call")
     ap.add_argument("--split-limit", type=int, default=0, help="cfg4: use only the first n complexes of the split")
     ap.add_argument("--batch-tokens", type=int, default=32000,
@@ -1166,13 +1188,18 @@ def main():
                          "measured 2.66 / 2.76 / 2.91 / 2.85 M residues/s at 8,000 / 16,000 / 32,000 / 64,000)")
     ap.add_argument("--min-seconds", type=float, default=1.0,
                     help="cfg4: the pass count is raised until the timed region lasts at least this long on the slowest rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two live rocprofv3 PMC passes behind roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline: per-kernel / roofline pass, clock, collation, PMC traffic, gather and "
+                         "featuriser figures, CPU baselines and parity, the x3 evaluation, design-call latency, the secondary workloads "
+                         "(N = 1) or cfg4_strong (N > 1).  Off: set-up, warm-up, the timed steps, --dump-outputs and the result line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the parity against the CPU oracle")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the two live rocprofv3 PMC passes behind roofline.traffic")
     ap.add_argument("--verbose", action="store_true", help="print the full detail (per-kernel tables, every secondary line) instead of the compact line")
     ap.add_argument("--detail-out", default=None, help="file for the full detail (default: gpurun_out/bench_detail.json when gpurun_out/ exists)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-gather", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short cfg3 / cfg5 / cfg1 runs appended to the default line")
+    ap.add_argument("--no-gather", action="store_true", help="with --full: skip the gather and featuriser figures")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the persistent-launch run and the short cfg3 / cfg5 / cfg1 / cfg4 runs (N = 1), cfg4_strong (N > 1)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="cfg2 / cfg3: write what the headline's last timed step computed (log_probs, h_V, h_E of rank 0; float32, "
                          "< 64 MB in all, a seeded row sample of what does not fit) as DIR/<name>.npy")
@@ -1229,6 +1256,8 @@ def main():
             assert out["n_gpus"] == world == args.gpus
             detail = args.detail_out or (os.path.join(ROOT, "gpurun_out", f"bench_detail_{args.workload}.json")
                                          if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else None)
+            if not (args.full or args.detail_out):
+                detail = None                           # a plain run writes no file beside --dump-outputs
             if detail:
                 try:
                     with open(detail, "w") as f:
@@ -1253,10 +1282,12 @@ def main():
 
     precision = args.precision or ("bf16" if args.workload == "cfg3" else "fp32")
     out, runner = encdec_bench(args, dev, rank, world, dist, args.workload, precision, args.steps, args.warmup,
-                               capture=bool(args.dump_outputs) and rank == 0)
+                               capture=bool(args.dump_outputs) and rank == 0, full=args.full)
     if args.dump_outputs and rank == 0:
         write_outputs(runner.outputs, args.dump_outputs)
         del runner.outputs
+    if not args.full:
+        return finish(out)
     ref_out = None
     traffic = None
     if rank == 0 and world == 1:

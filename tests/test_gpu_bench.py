@@ -1,5 +1,5 @@
 """bench.py's harness on the GPU box: the N > 1 path (self-spawned ranks, collation, one JSON line) exercised with two
-ranks sharing the box's single device over gloo, and the default line's contract keys."""
+ranks sharing the box's single device over gloo, the --full line's contract keys, and the plain run that carries the headline only."""
 import json
 import os
 import subprocess
@@ -27,7 +27,7 @@ def test_two_ranks_on_one_device(workload, scaling):
     """`bench.py --gpus 2` spawns its own two ranks (no launcher); both share device 0 and talk over gloo here, RCCL on a
     multi-GPU node.  cfg2: weak scaling, every rank its own complexes; cfg4: the split LPT-sharded over the ranks."""
     extra = ["--split-limit", "60", "--min-seconds", "0.3"] if workload == "cfg4" else []
-    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--no-cpu-baseline", "--no-gather",
+    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--full", "--no-cpu-baseline", "--no-gather",
                 "--no-secondary", "--no-pmc"] + extra, {"NAMP_BENCH_ONE_DEVICE": "1", "NAMP_BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["warmup"] == 1
     assert out["scaling"] == scaling and out["value"] > 0 and out["higher_is_better"] is True
@@ -53,9 +53,9 @@ def test_two_ranks_on_one_device(workload, scaling):
 
 
 def test_two_ranks_emit_both_scaling_points():
-    """`bench.py --gpus 2` (the driver's SCALE shape, no --no-secondary): ONE invocation yields the cfg2 weak-scaling value AND a
-    `cfg4_strong` sub-object — a timed region of passes over the LPT-sharded split with per-rank min / mean / max."""
-    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-gather", "--no-pmc", "--split-limit", "60",
+    """`bench.py --gpus 2 --full` (no --no-secondary): ONE invocation yields the cfg2 weak-scaling value AND a `cfg4_strong`
+    sub-object — a timed region of passes over the LPT-sharded split with per-rank min / mean / max."""
+    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-gather", "--no-pmc", "--split-limit", "60",
                 "--min-seconds", "0.3"], {"NAMP_BENCH_ONE_DEVICE": "1", "NAMP_BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     c4 = out["cfg4_strong"]
@@ -74,7 +74,7 @@ def test_eight_ranks_on_one_device():
     n_dev = torch.cuda.device_count()
     if n_dev < 8:
         pytest.skip(f"needs 8 GPUs (one rank per device), found {n_dev}")
-    out = _run(["--gpus", "8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-gather", "--no-secondary", "--no-pmc"],
+    out = _run(["--gpus", "8", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-gather", "--no-secondary", "--no-pmc"],
                {"OMP_NUM_THREADS": "2"}, timeout=1500)
     assert out["n_gpus"] == 8 and out["steps"] == 3 and out["scaling"] == "weak"
     col = out["collation"]
@@ -84,10 +84,10 @@ def test_eight_ranks_on_one_device():
 
 
 def test_default_line_contract():
-    """N = 1 default run (short): driver keys, exact-fp32 headline with its roofline on the EXECUTED flops vs the fp32 MFMA peak,
+    """N = 1 --full run (short): driver keys, exact-fp32 headline with its roofline on the EXECUTED flops vs the fp32 MFMA peak,
     live PMC traffic, the x3 object, parity with sequence recovery, the CPU baselines, the secondary workloads — in < 6 KB."""
     env = dict(os.environ)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2"], capture_output=True, text=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full"], capture_output=True, text=True,
                        env=env, timeout=1800, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -135,6 +135,20 @@ def test_default_line_contract():
         with open(os.path.join(ROOT, out["detail_file"])) as f:
             det = json.load(f)
         assert "per_kernel" in det and len(det["secondary"]) == 5
+
+
+def test_plain_run_carries_the_headline_only():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, the K timed steps and the result line — the
+    contract keys with the exact-fp32 headline, nothing that takes runs of its own (roofline, x3, CPU baselines, secondaries)."""
+    out = _run(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in out, k
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["n_gpus"] == 1
+    assert out["dtype"] == "f32" and out["unit"] == "residues/s" and out["higher_is_better"] is True
+    assert out["value"] > 0 and abs(out["value"] - 1000 / (out["ms_per_step"] * 1e-3)) < 0.01 * out["value"]
+    for k in ("roofline", "per_kernel", "collation", "gather", "features", "cpu_baseline", "parity", "x3", "x3_persistent_launch",
+              "secondary", "detail_file"):
+        assert k not in out, k
 
 
 def test_dump_outputs(tmp_path):

@@ -86,7 +86,7 @@ def main(fetch_db, write_db, commit, rnd, *extra):
     f, w = per_kernel(fetch_db, "FETCH_SIZE"), per_kernel(write_db, "WRITE_SIZE")
     out = {"_commit": commit, "_round": rnd,
            "_source": "tools/profile_round.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of "
-                      "`bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary`; bytes = 2 x FETCH_SIZE KB + WRITE_SIZE KB "
+                      "`bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary`; bytes = 2 x FETCH_SIZE KB + WRITE_SIZE KB "
                       "(FETCH_SIZE doubled per MI355X_MICROARCH.md)",
            "cfg2": {}, "cfg2_fp32": {}, "raw_KB": {}}
     for k in sorted(set(f) | set(w)):
@@ -103,7 +103,7 @@ def main(fetch_db, write_db, commit, rnd, *extra):
     for i in range(0, len(extra) - 2, 3):
         out["cfg5_" + extra[i + 2]] = cfg5_section(extra[i], extra[i + 1], extra[i + 2])
     if extra:
-        out["_cfg5_source"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE over `bench.py --workload cfg5 --precision <p> --steps 2 "
+        out["_cfg5_source"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE over `bench.py --full --workload cfg5 --precision <p> --steps 2 "
                                "--warmup 1`; per-dispatch averages per kernel; algorithmic = compulsory rows (tools/make_pmc_traffic.py:cfg5_algorithmic)")
     print(json.dumps(out, indent=1))
 

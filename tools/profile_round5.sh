@@ -7,22 +7,22 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cd /tmp
-B="python $R/bench.py --no-cpu-baseline --no-secondary --no-pmc"
+B="python $R/bench.py --full --no-cpu-baseline --no-secondary --no-pmc"
 db() { ls $1/*/*.db $1/*.db 2>/dev/null | head -1; }
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- $B --steps 50 --warmup 5 > $O/prof.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_f -o k -- $B --steps 10 --warmup 2 > $O/pmc_f.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_w -o k -- $B --steps 10 --warmup 2 > $O/pmc_w.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof3 -o cfg3 -- python $R/bench.py --workload cfg3 --steps 5 --warmup 2 --no-cpu-baseline --no-gather --no-pmc > $O/prof3.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof3 -o cfg3 -- python $R/bench.py --full --workload cfg3 --steps 5 --warmup 2 --no-cpu-baseline --no-gather --no-pmc > $O/prof3.log 2>&1
 for p in x3 bf16; do
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof5_$p -o train -- python $R/bench.py --workload cfg5 --precision $p --steps 5 --warmup 2 --no-cpu-baseline --no-pmc > $O/prof5_$p.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc5f_$p -o k -- python $R/bench.py --workload cfg5 --precision $p --steps 2 --warmup 1 --no-cpu-baseline --no-pmc > $O/pmc5f_$p.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc5w_$p -o k -- python $R/bench.py --workload cfg5 --precision $p --steps 2 --warmup 1 --no-cpu-baseline --no-pmc > $O/pmc5w_$p.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof5_$p -o train -- python $R/bench.py --full --workload cfg5 --precision $p --steps 5 --warmup 2 --no-cpu-baseline --no-pmc > $O/prof5_$p.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc5f_$p -o k -- python $R/bench.py --full --workload cfg5 --precision $p --steps 2 --warmup 1 --no-cpu-baseline --no-pmc > $O/pmc5f_$p.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc5w_$p -o k -- python $R/bench.py --full --workload cfg5 --precision $p --steps 2 --warmup 1 --no-cpu-baseline --no-pmc > $O/pmc5w_$p.log 2>&1
 done
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/proff -o feat -- python $R/tools/feat_time.py > $O/proff.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof4 -o cfg4 -- python $R/bench.py --workload cfg4 --steps 1 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-pmc > $O/bench_cfg4.json 2> $O/prof4.log
-timeout 600 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_INST_ANY SQ_WAIT_ANY -d $O/pmc_sq_bf16 -o k -- python $R/bench.py --workload cfg3 --steps 2 --warmup 1 --no-cpu-baseline --no-gather --no-pmc > $O/pmc_sq_bf16.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof4 -o cfg4 -- python $R/bench.py --full --workload cfg4 --steps 1 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-pmc > $O/bench_cfg4.json 2> $O/prof4.log
+timeout 600 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_INST_ANY SQ_WAIT_ANY -d $O/pmc_sq_bf16 -o k -- python $R/bench.py --full --workload cfg3 --steps 2 --warmup 1 --no-cpu-baseline --no-gather --no-pmc > $O/pmc_sq_bf16.log 2>&1
 cd $R
 python tools/rocpd_summary.py $(db $O/prof) > $O/bench_cfg2_kernel_stats.md
 python tools/rocpd_summary.py $(db $O/prof3) > $O/bench_cfg3_kernel_stats.md

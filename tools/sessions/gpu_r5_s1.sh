@@ -10,8 +10,8 @@ done
 cat gpurun_out/r5s1/region.jsonl
 # driver-style lines, alternating trees
 for i in 1 2 3; do
-  (cd $R && python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-pmc --no-gather 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('head', d['ms_per_step'], (d.get('x3') or {}).get('ms_per_step'))")
-  (cd $R/tools/_variants/r3tree && python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-pmc --no-gather 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('r3', d['ms_per_step'], (d.get('x3') or {}).get('ms_per_step'))")
+  (cd $R && python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-pmc --no-gather 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('head', d['ms_per_step'], (d.get('x3') or {}).get('ms_per_step'))")
+  (cd $R/tools/_variants/r3tree && python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-pmc --no-gather 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('r3', d['ms_per_step'], (d.get('x3') or {}).get('ms_per_step'))")
 done
 # same-box baselines of the other workloads (HEAD)
 timeout 600 python tools/train_time.py --steps 6 --precision bf16 2>&1 | tail -25 > gpurun_out/r5s1/train_bf16.txt

@@ -202,9 +202,7 @@ int ensure_attributes() {
 // The message kernels update their own residues in-launch (fused tail) while the batch is small enough
 // that this beats a separate 16-residue-per-workgroup node_update launch: every workgroup of the fused
 // form re-streams the 768 KiB of FFN + projection weights for <= 12 residues.
-#ifndef NAMP_FUSED_TAIL_MAX_RESIDUES
 #define NAMP_FUSED_TAIL_MAX_RESIDUES 2500   // tools/batch_sweep.py: 3000 / 4000 residues run 5 / 10 % faster unfused, 2000 run 5 % slower
-#endif
 
 struct EdgeGeom { int tpn, nwaves, npw, grid; };
 EdgeGeom edge_geom(int G, int K) {
@@ -383,8 +381,8 @@ int check_proj(const char* fn, const NampProj* proj, int nproj, const int32_t* S
 struct Out16Req { __bf16* p[8]; int n; bool honoured; };
 thread_local Out16Req* g_out16 = nullptr;
 // Set by encdec_bf16_storage around its residue-level launches: the bf16 throughput mode runs them as plain bf16 products (hi . hi of the
-// x3 images, fp32 accumulation) — the reference's AMP autocasts the whole model (na_run.py:216-218).  NAMP_BF16S_RESIDUE_X3=1 restores the
-// split-bf16 (fp32-equivalent) residue GEMMs of rounds 2-3 for A/B runs (measured: profiles/r03e, r04*).
+// x3 images, fp32 accumulation) — the reference's AMP autocasts the whole model (na_run.py:216-218).  Rounds 2-3 ran them as split-bf16
+// (fp32-equivalent) GEMMs (measured against this: profiles/r03e, r04*).
 thread_local bool g_residue_x1 = false;
 
 int launch_node_linear(const float* X, const int32_t* S, int G_out, int G_src, int N,
@@ -456,13 +454,9 @@ int launch_gather(const float* nodes, const float* nbrs, const int32_t* idx, flo
   const int NK = rows_per_table ? rows_per_table : N * K;
   if (((C1 | C2) & 3) == 0) {
     const long total = rows * ((C1 + C2) >> 2);
-#ifndef NAMP_GATHER_UNROLL
 #define NAMP_GATHER_UNROLL 2      // rows in flight per thread: 1 / 2 / 4 / 8 measure 4.69 / 4.72 / 4.12 / 3.81 TB/s at the cfg3 shape
-#endif
     long blocks = (total + 256L * NAMP_GATHER_UNROLL - 1) / (256L * NAMP_GATHER_UNROLL);
-#ifndef NAMP_GATHER_MAXBLK
 #define NAMP_GATHER_MAXBLK (256 * 16)
-#endif
     if (blocks > NAMP_GATHER_MAXBLK) blocks = NAMP_GATHER_MAXBLK;
     blocks = (blocks + 7) & ~7L;                       // a multiple of 8: one contiguous row range per XCD (gather_cat_kernel)
     hipLaunchKernelGGL(gather_cat_kernel<NAMP_GATHER_UNROLL>, dim3((unsigned)blocks), dim3(256), 0, s, nodes, nbrs, idx, out, rows,
@@ -883,9 +877,7 @@ static int node_update_auto(int64_t flags, const float* Win_ximg, const float* W
                             const float* h_V, const float* partial, const float* m3_img, const float* m3_ximg, const float* m3_b,
                             const int32_t* mask, float* h_V_out,
                             const NampProj* proj, int nproj, const int32_t* S, int G, int K, void* stream) {
-#ifndef NAMP_NODE_X3_MIN_RESIDUES
 #define NAMP_NODE_X3_MIN_RESIDUES 2500   // the whole unfused regime: 3-12 % per forward at 3,000-16,000 residues (tools/batch_sweep.py)
-#endif
   bool x3 = prec_of(flags) != PREC_F32 && Win_ximg && Wout_ximg && G >= NAMP_NODE_X3_MIN_RESIDUES && nproj <= 8 && (!m3_img || m3_ximg);
   for (int i = 0; x3 && i < nproj; ++i) x3 = proj_ximg && proj_ximg[i] != nullptr;
   if (!x3)
@@ -1509,32 +1501,11 @@ int namp_decoder_sample_walk(const NampModelW* w, const float* h_V_enc, const fl
   }
   if (e != hipSuccess) return fail(NAMP_ELAUNCH, "namp_decoder_sample_walk: hipMemsetAsync / hipMemcpyAsync: %s", hipGetErrorString(e));
   ProfScope prof_(NAMP_KIND_DEC_MESSAGE, s);
-  int g2 = (nwork + a.slots - 1) / a.slots;
-  if (const char* e_ = getenv("NAMP_WALK_GRID")) { const int v = atoi(e_); if (v >= 1 && v < g2) g2 = v; }      // (measurement switch)
+  const int g2 = (nwork + a.slots - 1) / a.slots;
   launch_sample(2, prec_of(w->dec[0].flags) == PREC_X3, nwaves, g2 < grid ? g2 : grid, s, a, work, work_n, nwork, level_off, sync);
   CHECK_LAUNCH();
   return NAMP_OK;
 }
-
-#ifdef NAMP_ABL_STAMPS
-extern "C" int namp_debug_stamps(long long* out16, int reset) {
-  long long z[16] = {0};
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(namp_stamp_acc), sizeof(z)) != hipSuccess) return -1;
-  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(namp_stamp_acc), z, sizeof(z)) != hipSuccess) return -1;
-  return 0;
-}
-#endif
-
-#ifdef NAMP_ABL_WSTAMPS
-// copies the per-wave event log of workgroup 0 out and clears it: counts[8], log[8][NAMP_WS_EVENTS][2]
-extern "C" int namp_debug_wstamps(int* counts8, long long* log, int reset) {
-  if (hipMemcpyFromSymbol(counts8, HIP_SYMBOL(namp_wstamp_n), 8 * sizeof(int)) != hipSuccess) return -1;
-  if (hipMemcpyFromSymbol(log, HIP_SYMBOL(namp_wstamp_log), sizeof(long long) * 8 * NAMP_WS_EVENTS * 2) != hipSuccess) return -1;
-  int z[8] = {0};
-  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(namp_wstamp_n), z, sizeof(z)) != hipSuccess) return -1;
-  return NAMP_WS_EVENTS;
-}
-#endif
 
 int namp_set_bf16p(int mask) { return g_bf16p.exchange(mask & 255); }
 
@@ -1714,8 +1685,7 @@ static int encdec_bf16_storage(const NampModelW* w, const float* V, const float*
   hipStream_t s = (hipStream_t)stream;
   int rc = ensure_attributes();
   if (rc) return rc;
-  static const bool residue_x3 = [] { const char* e = getenv("NAMP_BF16S_RESIDUE_X3"); return e && atoi(e) != 0; }();   // A/B switch
-  struct X1Scope { bool prev; X1Scope(bool on) : prev(g_residue_x1) { g_residue_x1 = on; } ~X1Scope() { g_residue_x1 = prev; } } x1scope_(!residue_x3);
+  struct X1Scope { bool prev; X1Scope() : prev(g_residue_x1) { g_residue_x1 = true; } ~X1Scope() { g_residue_x1 = prev; } } x1scope_;
   Carver c(ws, ws_bytes);
   float* hv[2] = {c.take((size_t)G * NAMP_HIDDEN), c.take((size_t)G * NAMP_HIDDEN)};
   float* P[6];
@@ -1756,8 +1726,7 @@ static int encdec_bf16_storage(const NampModelW* w, const float* V, const float*
     CHECK_LAUNCH();
     if (!rq.honoured) cvt({P[0], P[1]}, {T16[0], T16[1]});
   }
-  static const bool fuse_embed = [] { const char* e = getenv("NAMP_BF16S_SEPARATE_EMBED"); return !(e && atoi(e) != 0); }();   // A/B switch
-  const bool emb_fused = fuse_embed && w->We_simg != nullptr;
+  const bool emb_fused = w->We_simg != nullptr;
   if (!emb_fused) {
     EdgeArgs a = {};
     a.hE = E; a.hE16_out = h16; a.W1_img = w->We_bimg ? w->We_bimg : w->We_img; a.b1 = w->We_b; a.G = a.G_enc = G; a.N = N; a.K = K;

@@ -30,15 +30,6 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-#ifndef P32_NOFENCE
-#define P32_SB() __builtin_amdgcn_sched_barrier(0)
-#else
-#define P32_SB()
-#endif
-#ifndef P32_DIST
-#define P32_DIST 3                  // weight fragments are requested this many MFMA slots ahead
-#endif
-
 __device__ __forceinline__ float bf16_lo(const unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16_hi(const unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
@@ -49,17 +40,6 @@ __device__ __forceinline__ f4 bf8_quad(const bf8& p, const int h) {
 __device__ __forceinline__ void set_quad(bf8& p, const int h, const f4 v) {
   p[4 * h] = (__bf16)v.x; p[4 * h + 1] = (__bf16)v.y; p[4 * h + 2] = (__bf16)v.z; p[4 * h + 3] = (__bf16)v.w;
 }
-
-// -DP32_STAMPS: per-wave time line (s_memtime deltas between fixed points of a tile, summed over the wave's tiles in scalar registers, written
-// once at the end by the waves of workgroup 0; read back with namp_debug_p32_stamps).  Points: 0 top of the tile .. 1 rows awaited .. 2 requests
-// for this tile issued, next metadata .. 3/4/5/6 behind each quarter of the MFMA slots .. 7 last epilogue .. 8 LayerNorm / K-sum tail .. 9 stores issued
-#ifdef P32_STAMPS
-__device__ unsigned long long g_p32_stamps[4][8][12];
-#define P32_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-                          st_sum[i] += t_ - st_prev; st_prev = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define P32_STAMP(i)
-#endif
 
 // LDS: W1 | W2 | W3 or W_e (32 KiB each) | constants (2 KiB) | per wave: 32 row weights (128 B)
 #define BF16P_LDS (3 * NAMP_BIMG_BYTES + 2048 + 8 * 128)
@@ -75,7 +55,7 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16p_kernel(const EdgeArgs a) {
   constexpr int NL = EDGE ? 3 : EMB ? 3 : 2;               // layers of the chain (EMB: the embedding product in front)
   constexpr int NB = 4 * NL, NSLOT = 8 * NB;
   constexpr int L1 = EMB ? 1 : 0, L2 = L1 + 1, L3 = EDGE ? 2 : -1, LE = EMB ? 0 : -1;       // layer index of each product
-  constexpr int D = P32_DIST, RING = D + 1;
+  constexpr int D = 3, RING = D + 1;                   // weight fragments are requested D MFMA slots ahead
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -171,11 +151,7 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16p_kernel(const EdgeArgs a) {
     if constexpr (EMB) {
       raw_fetch(mt, 0); raw_pack(0); raw_fetch(mt, 1); raw_pack(1);             // (prologue only)
     } else {
-#ifdef P32_NOMEM
-      const bf8* src = (const bf8*)(a.hE16 + (mt.erow & 1023) * NAMP_H) + hk;
-#else
       const bf8* src = (const bf8*)(a.hE16 + mt.erow * NAMP_H) + hk;
-#endif
 #pragma unroll
       for (int s = 0; s < 8; ++s) xn[s] = src[2 * s];
     }
@@ -211,23 +187,14 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16p_kernel(const EdgeArgs a) {
     return o;
   };
   typedef float f2 __attribute__((ext_vector_type(2)));
-#ifdef P32_STAMPS
-  unsigned long long st_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_prev = __builtin_amdgcn_s_memtime();
-#endif
   for (; pair < npairs; pair += stride) {
     asm volatile("" ::: "memory");
-    P32_STAMP(0);
     const TileMeta me = cur;
     bf8 xb[8], a1[8], a2[8];
     if constexpr (!EMB) {
 #pragma unroll
       for (int s = 0; s < 8; ++s) xb[s] = xn[s];
     }
-#ifdef P32_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    st_sum[10] += 1;
-#endif
-    P32_STAMP(1);
     bf8 pj[8], pa[8];
     auto gather_fetch = [&]() {
       const bf8* src = (const bf8*)((me.pj_from1 ? a.Pj116 : a.Pj016) + me.pj_row * NAMP_H) + hk;
@@ -328,21 +295,15 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16p_kernel(const EdgeArgs a) {
     auto wfrag = [&](auto Gc) {
       constexpr int g = decltype(Gc)::value, b = g / 8, s = g % 8, li = b / 4, tn = b % 4;
       constexpr int slot = li == LE ? 2 : li == L1 ? 0 : li == L2 ? 1 : 2;
-#ifdef P32_NOLDSW
-      wf[g % RING] = xn[g % 8];
-#else
       wf[g % RING] = wimg[slot * (NAMP_BIMG_BYTES / 16) + (s * 4 + tn) * 64];
-#endif
     };
-    P32_STAMP(2);
     static_for<0, D>([&](auto Gc) { wfrag(Gc); });
     static_for<0, NSLOT>([&](auto Gc) {
       constexpr int g = decltype(Gc)::value, b = g / 8, s = g % 8, li = b / 4, tn = b % 4;
       constexpr bool FLIP = !EDGE && li == L2;
-      if constexpr (g > 0 && g % (NSLOT / 4) == 0) P32_STAMP(2 + g / (NSLOT / 4));
       if constexpr (g + D < NSLOT) wfrag(std::integral_constant<int, g + D>{});
       if constexpr (s == 5 && b + 1 < NB) init_issue(std::integral_constant<int, b + 1>{});
-      P32_SB();
+      __builtin_amdgcn_sched_barrier(0);
       {
         bf8 ab;
         if constexpr (li == LE) ab = xn[s];
@@ -355,15 +316,10 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16p_kernel(const EdgeArgs a) {
 #pragma unroll
           for (int v = 0; v < 16; ++v) c[v] = 0.f;
         }
-#ifdef P32_NOMFMA
-        asm volatile("" :: "v"(wf[g % RING]), "v"(ab));
-        A[b] = c;
-#else
         A[b] = FLIP ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab, wf[g % RING], c, 0, 0, 0)
                     : __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[g % RING], ab, c, 0, 0, 0);
-#endif
       }
-      P32_SB();
+      __builtin_amdgcn_sched_barrier(0);
       if constexpr (b >= 1 && s >= 1 && s <= 4) epilogue(std::integral_constant<int, b - 1>{}, std::integral_constant<int, s - 1>{});
       // the next pair's rows: behind the last use of this pair's rows as an operand (message modes) / behind layer 2 (edge update: their
       // 32 registers are free once a1 is dead)
@@ -390,13 +346,11 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16p_kernel(const EdgeArgs a) {
         const int node_h = hk ? nodeB : nodeA, kt_h = hk ? ktB : ktA;
         kdst = (hk == 0 || okB) ? a.partial + ((long)node_h * a.TPN + kt_h) * NAMP_H + r : g_bf16s32_dump + r;
       }
-      P32_SB();
+      __builtin_amdgcn_sched_barrier(0);
     });
     // the last block's epilogue has no MFMAs left to ride
-    P32_STAMP(6);
     static_for<0, 4>([&](auto Qc) { epilogue(std::integral_constant<int, NB - 1>{}, Qc); });
     if constexpr (EMB) raw_pack(1);
-    P32_STAMP(7);
     if constexpr (EDGE) {
       f16v* acc = &A[4 * L3];
       float sum = (sA.x + sA.y) + (sB.x + sB.y);
@@ -444,12 +398,7 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16p_kernel(const EdgeArgs a) {
           }
         }
       }
-      P32_STAMP(8);
-#ifdef P32_NOMEM
-      bf8* dst = (bf8*)(g_bf16s32_dump16 + m * NAMP_H) + hk;
-#else
       bf8* dst = (bf8*)(me.valid ? a.hE16_out + me.erow * NAMP_H : g_bf16s32_dump16 + m * NAMP_H) + hk;
-#endif
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
         const int tin = s >> 1, u = s & 1;
@@ -464,19 +413,7 @@ __global__ __launch_bounds__(512) void edge_mlp_bf16p_kernel(const EdgeArgs a) {
                   : (lane == 16 && okB) ? a.partial + (long)a.G * a.TPN * NAMP_H + (long)nodeB * a.TPN + ktB : g_bf16s32_dump + 128 + lane;
       *wdst = wsum;
     }
-    P32_STAMP(9);
     cur = nxt;
     par ^= 1;
   }
-#ifdef P32_STAMPS
-  if (blockIdx.x == 0 && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) g_p32_stamps[MODE + (EMB ? 3 : 0)][wave][i] = st_sum[i];
-  }
-#endif
 }
-#ifdef P32_STAMPS
-extern "C" int namp_debug_p32_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_p32_stamps), sizeof(g_p32_stamps), 0, hipMemcpyDeviceToHost);
-}
-#endif

@@ -67,18 +67,7 @@ __device__ __forceinline__ float gelu_erf(float x) {
   return fmaf(fabsf(h), fmaf(-2.0f, e, 1.0f), h);               // h + |h| (1 - 2 Phi(-|x|))
 }
 
-// Ablation switches for tools/kbench.py (never defined in the shipped build).
-//   NAMP_ABL_NOGELU   : GELU -> identity          NAMP_ABL_LAYERS=n : stop the edge MLP after layer n
-//   NAMP_ABL_NOPROLOG : edge kernel reads no per-row operands (constants instead)
-//   NAMP_ABL_NOGEMM   : 128x128 tile GEMMs -> acc += x      NAMP_ABL_X1 : split-bf16 GEMMs keep only the hi.hi product
-//   NAMP_ABL_NOSTORE  : fused edge update keeps its rows in registers only   NAMP_ABL_NOLN : LayerNorms -> identity
-//   NAMP_ABL_NOTABLE2 : fused launches skip the second (message) table gather
-//   NAMP_ABL_NOLDSW   : bf16 chain GEMMs take their weight fragment from registers (no ds_read)
-//   NAMP_ABL_NODMA    : no weight staging (LDS holds garbage)  NAMP_ABL_NOTAIL : fused residue tail -> plain store
 __device__ __forceinline__ f4 gelu4(f4 v) {
-#ifdef NAMP_ABL_NOGELU
-  return v;
-#endif
   // gelu_erf() on four values, written on vectors so that the Horner steps can be selected as packed fp32 (v_pk_fma_f32);
   // the transcendental stays per element.  Same operation order per element as gelu_erf(): bit-identical results.
   const f4 a = __builtin_elementwise_abs((f4){__builtin_amdgcn_fmed3f(v.x, -NAMP_GELU_LIM, NAMP_GELU_LIM),
@@ -143,54 +132,20 @@ typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 #define NAMP_GELU4_Q1 -6.1600986289e-02f
 #define NAMP_GELU4_Q0 3.9660173626e-01f
 __device__ __forceinline__ f4 gelu4_bf16mode(const f4 x) {
-#ifdef NAMP_ABL_NOGELU
-  return x;
-#endif
-#ifdef NAMP_ABL_GELU16_SCALAR
-  f4 o;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float c = __builtin_amdgcn_fmed3f(x[i], -4.f, 4.f), t = c * c;
-    float q = fmaf(2.2787273029e-08f, t, -1.5988982626e-06f);
-    q = fmaf(q, t, 4.7961328822e-05f); q = fmaf(q, t, -8.1407082443e-04f); q = fmaf(q, t, 8.7726502299e-03f);
-    q = fmaf(q, t, -6.4573666617e-02f); q = fmaf(q, t, 3.9788372746e-01f);
-    o[i] = x[i] * fmaf(c, q, 0.5f);
-  }
-  return o;
-#endif
   // Phi(x) = clamp01(1/2 + x Q(x^2)) with NO clamp of the argument: beyond the fit range the polynomial keeps x Q(x^2) >= 1/2 in magnitude
   // (checked on 1.2 M points up to |x| = 12; the leading coefficient is positive, so Q grows — to +inf on overflow — from there), and the
   // [0, 1] clamp is the output modifier of the last v_pk_fma_f32: one v_med3_f32 per value less than clamping x first (round 3).
   const f4 t = x * x;
-#ifndef NAMP_GELU16_DEG
-#define NAMP_GELU16_DEG 4
-#endif
-#if NAMP_GELU16_DEG == 6
-  // rounds 1-3: degree 6 in x^2, max |error| 1.9e-4
-  f4 q = (f4){2.2787273029e-08f, 2.2787273029e-08f, 2.2787273029e-08f, 2.2787273029e-08f};
-  q = q * t + -1.5988982626e-06f;
-  q = q * t + 4.7961328822e-05f;
-  q = q * t + -8.1407082443e-04f;
-  q = q * t + 8.7726502299e-03f;
-  q = q * t + -6.4573666617e-02f;
-  q = q * t + 3.9788372746e-01f;
-#elif NAMP_GELU16_DEG == 2
-  // degree 2 in x^2: max |error| 7.7e-3 (two bf16 ulps at |y| ~ 1) — measured only, not shipped
-  f4 q = (f4){2.2650967672e-03f, 2.2650967672e-03f, 2.2650967672e-03f, 2.2650967672e-03f};
-  q = q * t + -4.2712306742e-02f;
-  q = q * t + 3.7477252573e-01f;
-#else
   // round 4: degree 4 in x^2 (minimax over the real line, the [0, 1] clamp included; positive leading coefficient, x Q(x^2) >= 0.62 beyond
   // |x| = 4): max |error| 1.3e-3 — a third of the bf16 rounding step of the result at |y| >= 1 (2^-8 |y|) and below it for |y| > 0.33;
-  // near 0 the error is x^2 (Q - Q*), i.e. vanishes.  Two packed FMAs per value pair less than the degree-6 form.  The constants are the
-  // NAMP_GELU4_Q* macros above (shared with the training backward's dw_gelu_split4_bf16, namp_train_dw.h); tests/test_host_logic.py
+  // near 0 the error is x^2 (Q - Q*), i.e. vanishes.  Two packed FMAs per value pair less than the degree-6 form of rounds 1-3.  The constants
+  // are the NAMP_GELU4_Q* macros above (shared with the training backward's dw_gelu_split4_bf16, namp_train_dw.h); tests/test_host_logic.py
   // parses them: test_device_gelu_bf16_mode_polynomial.
   f4 q = (f4){NAMP_GELU4_Q4, NAMP_GELU4_Q4, NAMP_GELU4_Q4, NAMP_GELU4_Q4};
   q = q * t + NAMP_GELU4_Q3;
   q = q * t + NAMP_GELU4_Q2;
   q = q * t + NAMP_GELU4_Q1;
   q = q * t + NAMP_GELU4_Q0;
-#endif
   // (written as instructions: the compiler emits a separate `v_max_f32 ... clamp` per value instead of folding the clamp into the packed FMA)
   typedef float f2 __attribute__((ext_vector_type(2)));
   const f2 half = (f2){0.5f, 0.5f};
@@ -214,18 +169,9 @@ __device__ __forceinline__ void chain_gemm_bf16(f4 (&acc)[8], const f4 (&x)[8], 
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     const bf8 xb = pack_bf16<ACT>(x[2 * s], x[2 * s + 1]);
-#ifdef NAMP_ABL_NOGEMM
-    acc[s].x += (float)xb[0] + (float)xb[5]; acc[s + 4].y += (float)xb[2] + (float)xb[7];
-    acc[s].z += (float)xb[1] + (float)xb[4]; acc[s + 4].w += (float)xb[3] + (float)xb[6];
-    continue;
-#endif
 #pragma unroll
     for (int tn = 0; tn < 8; ++tn) {
-#ifdef NAMP_ABL_NOLDSW
-      bf8 wf = xb; wf[0] = (__bf16)(float)(s * 8 + tn);
-#else
       const bf8 wf = w[(s * 8 + tn) * 64];
-#endif
       if (FLIP) acc[tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xb, wf, acc[tn], 0, 0, 0);
       else      acc[tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xb, acc[tn], 0, 0, 0);
     }
@@ -245,9 +191,6 @@ __device__ __forceinline__ void chain_gemm_bf16(f4 (&acc)[8], const f4 (&x)[8], 
 // (tools/coexec_probe.hip), and packed fp32 operations beside MFMAs cost more than they save (measured -1.5 % per launch
 // for the scalar form here, +2 % for it in the fp32-MFMA kernels, which keep gelu4()).
 __device__ __forceinline__ f4 gelu4_scalar(const f4 v) {
-#ifdef NAMP_ABL_NOGELU
-  return v;
-#endif
   return (f4){gelu_erf(v.x), gelu_erf(v.y), gelu_erf(v.z), gelu_erf(v.w)};
 }
 
@@ -262,9 +205,6 @@ __device__ __forceinline__ void split_x3(const f4 a, const f4 b, bf8& hi, bf8& m
 }
 // acc += W . x for one fragment pair (hi, mid images of the same tile): the three split products
 __device__ __forceinline__ f4 mfma_x3(const bf8 wh, const bf8 wm, const bf8 hi, const bf8 mid, f4 acc) {
-#ifdef NAMP_ABL_X1
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, hi, acc, 0, 0, 0);
-#endif
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, mid, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, hi, acc, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, hi, acc, 0, 0, 0);
@@ -346,14 +286,6 @@ __device__ __forceinline__ void chain_gemm_x3(f4 (&acc)[8], const f4 (&x)[8], co
       bf8 wh[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) wh[q] = w[(s * 8 + 4 * h + q) * 64];
-#ifdef NAMP_ABL_X1
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (FLIP) acc[4 * h + q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, wh[q], acc[4 * h + q], 0, 0, 0);
-        else      acc[4 * h + q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[q], hi, acc[4 * h + q], 0, 0, 0);
-      }
-      continue;
-#endif
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         if (FLIP) acc[4 * h + q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mid, wh[q], acc[4 * h + q], 0, 0, 0);
@@ -435,11 +367,6 @@ __device__ __forceinline__ f4 gelu_prec(const f4 v) {
 // one 128 x 128 tile GEMM of the edge kernels out of a 64 KiB LDS slot: exact fp32 MFMA or the split-bf16 form
 template <bool X3, bool FLIP, bool ACT>
 __device__ __forceinline__ void gemm128(f4 (&acc)[8], const f4 (&x)[8], const f4* w) {
-#ifdef NAMP_ABL_NOGEMM
-#pragma unroll
-  for (int t = 0; t < 8; ++t) acc[t] += ACT ? gelu4(x[t]) : x[t];
-  return;
-#endif
   if constexpr (X3) chain_gemm_x3<FLIP, ACT>(acc, x, (const bf8*)w);
   else chain_gemm<8, 8, FLIP, ACT>(acc, x, w, 8);
 }
@@ -510,9 +437,6 @@ __device__ __forceinline__ void chain_gemm_global(f4 (&acc)[NTN], const f4 (&x)[
 // 64 lanes x 16 B).  The LDS image is the global image verbatim (lane-linear), which is all
 // global_load_lds can do.  Completion: s_waitcnt vmcnt(0) in every issuing wave + a barrier.
 __device__ __forceinline__ void dma_to_lds(char* lds_dst, const float* gsrc, int nchunks, int wave, int nwaves, int lane) {
-#ifdef NAMP_ABL_NODMA
-  return;
-#endif
   for (int c = wave; c < nchunks; c += nwaves) {
     const char* g = (const char*)gsrc + (size_t)c * 1024 + lane * 16;
     char* d = lds_dst + c * 1024;
@@ -528,9 +452,6 @@ __device__ __forceinline__ void dma_to_lds(char* lds_dst, const float* gsrc, int
 // Synchronous: returns with the wave's chunks written; the caller still needs a barrier before other waves read them.
 template <int NPER>
 __device__ __forceinline__ void copy_to_lds(char* lds_dst, const float* gsrc, int nchunks, int wave, int nwaves, int lane) {
-#ifdef NAMP_ABL_NODMA
-  return;
-#endif
   for (int c0 = wave * NPER; c0 < nchunks; c0 += nwaves * NPER) {
     f4 v[NPER];
 #pragma unroll
@@ -564,9 +485,6 @@ __device__ __forceinline__ float drop_factor(uint32_t row_key, int channel, uint
 // Workgroup b of a grid of n (dispatched to XCD b % 8) -> position of b in the order "all of XCD 0's workgroups, then XCD 1's, ...": a bijection
 // on [0, n) for any n.  Kernels that index their data with it give every XCD one contiguous range.
 __device__ __forceinline__ int xcd_block_index(const int b, const int n) {
-#ifdef NAMP_ABL_NOXCD
-  return b;
-#endif
   const int x = b & 7, slot = b >> 3, q = n >> 3, r = n & 7;
   return x * q + (x < r ? x : r) + slot;
 }
@@ -583,9 +501,6 @@ __device__ __forceinline__ float xg_sum(float v) {
 // (torch.nn.LayerNorm; reference model_utils.py:627-628,668-670).
 __device__ __forceinline__ void layernorm_row_T(f4 (&v)[8], const float* __restrict__ gamma,
                                                 const float* __restrict__ beta, int g) {
-#ifdef NAMP_ABL_NOLN
-  return;
-#endif
   float s = 0.f;
 #pragma unroll
   for (int t = 0; t < 8; ++t) s += (v[t].x + v[t].y) + (v[t].z + v[t].w);

@@ -180,56 +180,6 @@ static __global__ void gather_cat_scalar_kernel(const float* __restrict__ nodes,
 // channel tile tn) units over all waves.  Used by node_update_kernel (16 residues per workgroup) and
 // as the fused tail of the message kernels (the workgroup's own <= 12 residues).
 // ------------------------------------------------------------------------------------------
-#ifdef NAMP_ABL_STAMPS
-// phase attribution of the sampler step (tools/build_variants.sh stamps:-DNAMP_ABL_STAMPS): wall-clock ticks (100 MHz) of workgroup 0,
-// summed per phase over the whole launch; read back by namp_debug_stamps()
-__device__ long long namp_stamp_acc[16];
-__device__ long long namp_stamp_prev;
-#define NAMP_STAMP(slot)                                                                          \
-  do {                                                                                            \
-    __syncthreads();                                                                              \
-    if (blockIdx.x == 0 && threadIdx.x == 0) {                                                    \
-      const long long now_ = wall_clock64();                                                      \
-      namp_stamp_acc[slot] += now_ - namp_stamp_prev;                                             \
-      namp_stamp_prev = now_;                                                                     \
-    }                                                                                             \
-  } while (0)
-#define NAMP_STAMP_BEGIN()                                                                         \
-  do {                                                                                            \
-    __syncthreads();                                                                              \
-    if (blockIdx.x == 0 && threadIdx.x == 0) namp_stamp_prev = wall_clock64();                    \
-  } while (0)
-#elif defined(NAMP_ABL_WSTAMPS)
-// Per-WAVE event log of workgroup 0 (tools/build_variants.sh wstamps:-DNAMP_ABL_WSTAMPS; tools/sample_wstamps.py): lane 0 of every wave appends
-// (slot, s_memtime) — no barrier, one 16-byte store per event — so the phases' true durations AND the waits at the barriers between them can be
-// read off per wave.  (The barrier-per-stamp form above costs ~1 us per stamp and synchronises the waves: good for sums, not for a time line.)
-#define NAMP_WS_EVENTS 8192
-__device__ long long namp_wstamp_log[8][NAMP_WS_EVENTS][2];
-__device__ int namp_wstamp_n[8];                      // events logged by the LAST launch (written at its end)
-__shared__ int namp_ws_cur[8];                        // the running event count lives in LDS: a global counter would put a dependent load into every stamp
-#define NAMP_STAMP(slot)                                                                          \
-  do {                                                                                            \
-    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) < 8) {                    \
-      const int w_ = threadIdx.x >> 6;                                                            \
-      const int c_ = namp_ws_cur[w_];                                                             \
-      if ((unsigned)c_ < (unsigned)NAMP_WS_EVENTS) {                                              \
-        namp_wstamp_log[w_][c_][0] = (slot);                                                      \
-        namp_wstamp_log[w_][c_][1] = (long long)__builtin_amdgcn_s_memtime();                     \
-        namp_ws_cur[w_] = c_ + 1;                                                                 \
-      }                                                                                           \
-    }                                                                                             \
-  } while (0)
-#define NAMP_WSTAMP_INIT() do { if (threadIdx.x < 8) namp_ws_cur[threadIdx.x] = 0; __syncthreads(); } while (0)
-#define NAMP_WSTAMP_FINI() do { __syncthreads(); if (blockIdx.x == 0 && threadIdx.x < 8) namp_wstamp_n[threadIdx.x] = namp_ws_cur[threadIdx.x]; } while (0)
-#define NAMP_STAMP_BEGIN() do {} while (0)
-#else
-#define NAMP_STAMP(slot) do {} while (0)
-#define NAMP_STAMP_BEGIN() do {} while (0)
-#endif
-#ifndef NAMP_WSTAMP_INIT
-#define NAMP_WSTAMP_INIT() do {} while (0)
-#define NAMP_WSTAMP_FINI() do {} while (0)
-#endif
 struct ProjDesc {
   const float* img;    // 64 KiB image of the [128x128] block
   const float* bias;   // [128] or null
@@ -581,15 +531,6 @@ __device__ __forceinline__ void tail4_x(f4 (&xr)[NB][8], const float* xB, const 
 template <int NB>
 __device__ __forceinline__ void tail4_unit(f4 (&o)[NB], const f4 (&wf)[8], const f4 (&xr)[NB][8]) {
   f4 c0[NB], c1[NB];
-#ifdef NAMP_ABL_T4_NOMFMA
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    o[nb] = (f4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int S = 0; S < 8; ++S) o[nb] += wf[S] * xr[nb][S];
-  }
-  return;
-#endif
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) { c0[nb] = (f4){0.f, 0.f, 0.f, 0.f}; c1[nb] = (f4){0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
@@ -620,11 +561,6 @@ __device__ __forceinline__ void tail4_unit(f4 (&o)[NB], const f4 (&wf)[8], const
 #define TAIL4_AHEAD 3
 template <class FragFn>
 __device__ __forceinline__ void tail4_request1(f4 (&wf)[8], const int u, const int lane, FragFn frag) {
-#ifdef NAMP_ABL_T4_NOLOAD
-#pragma unroll
-  for (int tk = 0; tk < 8; ++tk) wf[tk] = (f4){1.f * u, 2.f * lane, 3.f, 4.f * tk};
-  return;
-#endif
 #pragma unroll
   for (int tk = 0; tk < 8; ++tk) wf[tk] = frag(u, tk)[lane];
 }
@@ -670,7 +606,6 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
   const auto win_frag = [&](const int u, const int tk) { return (const f4*)a.Win_img + (tk * 32 + u) * 64; };
   const auto wout_frag = [&](const int u, const int tk) { return (const f4*)a.Wout_img + ((8 * (u >> 3) + tk) * 8 + (u & 7)) * 64; };
 
-  NAMP_STAMP_BEGIN();
   f4 wa[AHEAD ? TAIL4_AHEAD : 1][8];
   float bin_a[TAIL4_AHEAD] = {0.f, 0.f, 0.f};
   if constexpr (AHEAD) {
@@ -712,14 +647,12 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
     for (int t = 0; t < 8; ++t) x[t] = *(const f4*)(hsrc + 16 * t) + *(const f4*)(oP + mr * NAMP_H + 16 * t + 4 * g);
   }
 
-  NAMP_STAMP(7);                       // hoisted layer 3 (when done here)
   layernorm_row_T(x, a.ln1_g, a.ln1_b, g);
   if (wave == 0 && m < R) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) *(f4*)(xB + (m >> 2) * 512 + t * 64 + g * 16 + (m & 3) * 4) = x[t];
   }
   __syncthreads();
-  NAMP_STAMP(8);                       // LayerNorm 1
   // ---- hidden = gelu(W_in x + b_in): 32 units; every lane holds a unit's sums after the kb reduction, lane group kb takes component kb
   {
     f4 xr[NB][8];
@@ -743,7 +676,6 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
     else tail_units<PF>(wave, 32, nwaves, lane, win_frag, body);
   }
   __syncthreads();
-  NAMP_STAMP(9);                       // W_in + GELU
   // ---- W_out: units (channel tile tn, hidden quarter q); partials summed in the LayerNorm2 pass
   {
     const auto body = [&](const int u, const f4 (&wf)[8]) {
@@ -770,7 +702,6 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
     else tail_units<PF>(wave, 32, nwaves, lane, wout_frag, body);
   }
   __syncthreads();
-  NAMP_STAMP(10);                      // W_out partials
   // ---- LayerNorm2 over channels: thread -> (row n = tid / 128, channel c = tid % 128), 128 * R threads
   const int n_ = tid >> 7, c_ = tid & 127;
   const bool ln_thr = tid < 128 * R;
@@ -805,7 +736,6 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
     yB[boff] = y;
     if (orw >= 0) st_out<SC1>(a.hV_out + (long)orw * NAMP_H + c_, y);
   }
-  NAMP_STAMP(11);                      // partial sums + LayerNorm 2 + h_V' out
   if (a.nproj == 0 && !a.head_w) return;
   __syncthreads();
   if (a.head_w) {
@@ -844,7 +774,6 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
                        tail4_unit<NB>(o, wf, xr);
                        proj_out(o, second ? a.p[1].bias : a.p[0].bias, second ? a.p[1].tok : a.p[0].tok, second ? a.p[1].out : a.p[0].out, v & 7);
                      });
-    NAMP_STAMP(12);
     return;
   }
 #pragma unroll
@@ -867,7 +796,6 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
       proj_out(o, pd.bias, pd.tok, pd.out, tn);
     }
   }
-  NAMP_STAMP(12);                      // output head + projections
 }
 
 // M3 = false: the caller has already applied the hoisted message layer 3 (x = h_V + message), whatever a.m3_img says
@@ -885,7 +813,6 @@ __device__ __forceinline__ void node_tail_rows(const NodeTail& a, f4 (&x)[8], co
   float* red = yT + 128 * R;          // [2][32]     LayerNorm2 cross-wave sums
   const int m = lane & 15, g = lane >> 4;
 
-  NAMP_STAMP_BEGIN();
   if (M3 && a.m3_img) {
     // hoisted message layer 3 (see NodeTail): x = K-sums of the layer-2 activations -> x = h_V + W3 . x + b3 * wsum
     if (wave == 0 && m < R) {
@@ -926,7 +853,6 @@ __device__ __forceinline__ void node_tail_rows(const NodeTail& a, f4 (&x)[8], co
     }
   }
 
-  NAMP_STAMP(7);
   layernorm_row_T(x, a.ln1_g, a.ln1_b, g);
   if (wave == 0 && m < R) {
 #pragma unroll
@@ -936,18 +862,9 @@ __device__ __forceinline__ void node_tail_rows(const NodeTail& a, f4 (&x)[8], co
     }
   }
   __syncthreads();
-  NAMP_STAMP(8);
   // ---- hidden = gelu(W_in x + b_in): 32 channel tiles dealt over the waves
-#ifdef NAMP_ABL_NOROT
-  const int rot = 0;
-#else
   const int rot = PF ? 0 : (int)((blockIdx.x >> 3) & 31);       // the workgroup's index within its XCD (see tail_units)
-#endif
-#ifdef NAMP_ABL_TAILPF
-  constexpr bool PFU = true;
-#else
   constexpr bool PFU = PF;
-#endif
   tail_units<PFU>(wave, 32, nwaves, lane,
                  [&](const int tn, const int tk) { return (const f4*)a.Win_img + (tk * 32 + tn) * 64; },
                  [&](const int tn, const f4 (&wf)[8]) {
@@ -964,7 +881,6 @@ __device__ __forceinline__ void node_tail_rows(const NodeTail& a, f4 (&x)[8], co
                    }
                  }, rot);
   __syncthreads();
-  NAMP_STAMP(9);
   // ---- W_out: units (channel tile tn, k-quarter kq); partials reduced in the LayerNorm2 pass
   tail_units<PFU>(wave, 32, nwaves, lane,
                  [&](const int u, const int tk) { return (const f4*)a.Wout_img + ((8 * (u >> 3) + tk) * 8 + (u & 7)) * 64; },
@@ -982,7 +898,6 @@ __device__ __forceinline__ void node_tail_rows(const NodeTail& a, f4 (&x)[8], co
                    }
                  }, rot);
   __syncthreads();
-  NAMP_STAMP(10);
   // ---- LayerNorm2 over channels: thread -> (residue n = tid / 128, channel c = tid % 128), 128*R threads
   const int n_ = tid >> 7, c_ = tid & 127;
   const bool ln_thr = tid < 128 * R;
@@ -1015,7 +930,6 @@ __device__ __forceinline__ void node_tail_rows(const NodeTail& a, f4 (&x)[8], co
     yT[c_ * R + n_] = y;
     if (orw >= 0) st_out<SC1>(a.hV_out + (long)orw * NAMP_H + c_, y);
   }
-  NAMP_STAMP(11);
   if (a.nproj == 0 && !a.head_w) return;
   __syncthreads();
   if (a.head_w) {
@@ -1088,7 +1002,6 @@ __device__ __forceinline__ void node_tail_rows(const NodeTail& a, f4 (&x)[8], co
       }
     }
   }
-  NAMP_STAMP(12);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1121,9 +1034,7 @@ __device__ __forceinline__ void node_tail_x3_rows(const NodeTail& a, f4 (&x)[8],
   const float* win_p = a.Win_img; const float* wout_p = a.Wout_img; const float* p0_p = a.p[0].img; const float* p1_p = a.p[1].img;
   const float* bin_p = a.b_in; const float* bout_p = a.b_out; const float* l1g = a.ln1_g; const float* l1b = a.ln1_b;
   const float* l2g = a.ln2_g; const float* l2b = a.ln2_b;
-  NAMP_STAMP(7);                       // (entry: images for the next layer copied, K-sums read)
   layernorm_row_T(x, l1g, l1b, g);
-  NAMP_STAMP(8);                       // LayerNorm 1
   bf8 xh[4], xm[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) split_x3(x[2 * s], x[2 * s + 1], xh[s], xm[s]);
@@ -1148,7 +1059,6 @@ __device__ __forceinline__ void node_tail_x3_rows(const NodeTail& a, f4 (&x)[8],
     for (int s = 0; s < 4; ++s) acc = mfma_x3(cur[2 * s], cur[2 * s + 1], xh[s], xm[s], acc);
     h[q] = gelu4_scalar(acc);
   }
-  NAMP_STAMP(9);                       // W_in + GELU
   // ---- W_out restricted to this wave's 64 hidden units: K-steps 2w, 2w+1 of the [128 x 512] image; partial rows to LDS
   const bf8* wo = (const bf8*)wout_p + lane;
   constexpr int WO_MID = 128 * 512 / 8;
@@ -1183,9 +1093,7 @@ __device__ __forceinline__ void node_tail_x3_rows(const NodeTail& a, f4 (&x)[8],
       }
     }
   }
-  NAMP_STAMP(22);                      // (W_out partials written; barrier wait follows)
   __syncthreads();
-  NAMP_STAMP(10);                      // W_out partials
   // ---- the eight partial products, reduce-scatter: wave w adds up channel tile w of the R rows (8 reads per lane instead of 64) and leaves the
   // sums in lds[0 .. 128 R) (same tile swizzle); then every wave picks up its rows' full sums
   static_assert(R <= 8, "the tile swizzle t ^ m needs m < 8");
@@ -1199,9 +1107,7 @@ __device__ __forceinline__ void node_tail_x3_rows(const NodeTail& a, f4 (&x)[8],
   // ---- y = LayerNorm2(x + W_out h + b_out) * mask, in the chain layout, by every wave
 #pragma unroll
   for (int t = 0; t < 8; ++t) x[t] = (x[t] + *(const f4*)(bout_p + 16 * t + 4 * g)) + *(const f4*)(lds + mr * 128 + 16 * (t ^ mr) + 4 * g);
-  NAMP_STAMP(13);                      // (partial sums read)
   layernorm_row_T(x, l2g, l2b, g);
-  NAMP_STAMP(14);                      // (LayerNorm 2)
   const int orw = (m < R) ? orow(m) : -1;
   {
     const float mk = (a.mask && orw >= 0) ? (float)a.mask[orw] : 1.0f;
@@ -1216,7 +1122,6 @@ __device__ __forceinline__ void node_tail_x3_rows(const NodeTail& a, f4 (&x)[8],
       if (orw >= 0) st_f4<SC1>(a.hV_out + (long)orw * NAMP_H + 16 * t + 4 * g, x[t]);
     }
   }
-  NAMP_STAMP(11);                      // partial sums + LayerNorm 2 + h_V' out
   // ---- projections of h_V' (<= 2 blocks: the next layer's Pa / Pv): unit v = 8 pi + tn -> wave v % 8
   if (a.nproj > 0) {
 #pragma unroll
@@ -1339,9 +1244,7 @@ enum { PREC_F32 = 0, PREC_BF16 = 1, PREC_X3 = 2 };
 // given, and the kernel's LDS is re-used stage after stage (the caller separates stages by a grid barrier).
 template <int MODE, int TAIL, int PREC, int PRE, int PERSIST, class Args>
 __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem) {
-#ifndef NAMP_ABL_NOL2PF
   f4 l2pf0 = (f4){0.f, 0.f, 0.f, 0.f}, l2pf1 = l2pf0;
-#endif
   constexpr bool BF16 = (PREC == PREC_BF16);
   constexpr bool X3 = (PREC == PREC_X3);
   static_assert(PRE == PRE_NONE || (!BF16 && TAIL != 0 && (MODE == MODE_ENC_MSG || MODE == MODE_DEC_MSG)), "PRE: fp32-class message + tail only");
@@ -1383,20 +1286,12 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
   f4 (&y)[8] = PERSIST ? ybuf : x;     // layer-2 pre-activations / residue-tail rows: x itself unless x must survive the stage
   f4 pjv[8];                       // gathered neighbour term, added after layer 1 (its latency hides under the MFMAs)
   float w_row = 0.f;
-#ifdef NAMP_ABL_NOPROLOG
-#pragma unroll
-  for (int t = 0; t < 8; ++t) { x[t] = (f4){0.1f * lane, 0.2f, 0.3f, 0.4f * t}; acc[t] = x[t]; pjv[t] = x[t]; }
-  w_row = valid ? 1.f : 0.f;
-  if (true) {
-  } else if (MODE == MODE_EMBED) {
-#else
   if (PERSIST != 2) {
     const float* src = a.hE + erow * NAMP_H + 4 * g;
 #pragma unroll
     for (int t = 0; t < 8; ++t) x[t] = *(const f4*)(src + 16 * t);
   }
   if (MODE == MODE_EMBED) {
-#endif
     // training (namp_edge_embed_ln): the rows are PRE-LayerNorm (norm_edges, na_model_utils.py:509) — normalised here, so that the
     // normalised rows never exist in memory (the backward launch and the weight-gradient contraction re-derive them from the same rows)
     if (a.ln_g) layernorm_row_T(x, a.ln_g, a.ln_b, g);
@@ -1489,11 +1384,7 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
 #pragma unroll
     for (int t = 0; t < 8; ++t) x[t] += acc[t];           // residual
     layernorm_row_T(x, cstf + 256, cstf + 384, g);        // x = updated h_E row: stored, and the message input
-#ifdef NAMP_ABL_NOSTORE
-    if (valid && a.G < 0) {
-#else
     if (valid && (PERSIST == 0 || a.hE_out != nullptr)) {
-#endif
       float* dst = a.hE_out + erow * NAMP_H + 4 * g;
 #pragma unroll
       for (int t = 0; t < 8; ++t) *(f4*)(dst + 16 * t) = x[t];
@@ -1517,14 +1408,6 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
       }
     }
     // message tables of this layer
-#ifdef NAMP_ABL_NOTABLE2
-    {
-#pragma unroll
-      for (int t = 0; t < 8; ++t) { acc[t] = x[t]; pjv[t] = x[t]; }
-      w_row = valid ? (1.0f / 30.0f) : 0.f;
-    }
-    if (false)
-#endif
     {
       const int j_loc = a.E_idx[erow];
       const float* pj;
@@ -1567,7 +1450,6 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
     if (PRE != PRE_NONE) wait_dma_and_sync();             // W2 (issued one GEMM ago) landed; buf0 (W1) is free
     else if (M3_LDS) __syncthreads();                     // every wave is done with buf0 (W1)
     if (M3_LDS) dma_to_lds(buf0, a.W3_img, 64, wave, nwaves, lane);   // for the per-residue layer 3 behind the K-sum
-#ifndef NAMP_ABL_NOL2PF
     if (TAIL == 4 || TAIL == 8) {
       // The residue tail's weights (W_in, W_out, the projections: 0.6-0.8 MB that every workgroup reads) are pulled into this XCD's L2 one
       // GEMM ahead, each workgroup asking for the 1/32 slice of its index within the XCD (blockIdx / 8: a speed choice only); the rows of
@@ -1584,7 +1466,6 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
       }
       l2pf0 = p0[lane]; l2pf1 = p1[lane];
     }
-#endif
 #pragma unroll
     for (int t = 0; t < 8; ++t) { const float b = a.b2[16 * t + m]; y[t] = (f4){b, b, b, b}; }
     gemm128<X3, true, true>(y, acc, w1);
@@ -1671,9 +1552,7 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
         if (g == 0) dpart[wave * NAMP_H + 16 * t + m] = s;
       }
       if (lane == 0) dws[wave] = wsum;
-#ifndef NAMP_ABL_NOL2PF
       asm volatile("" :: "v"(l2pf0), "v"(l2pf1));               // (the prefetch above has landed)
-#endif
       if (M3_LDS) wait_dma_and_sync();                          // all tiles summed; W3 landed in buf0
       else __syncthreads();                                     // all tiles summed; weight ring is free
       // tile rows = this workgroup's residues: row m -> residue row0 + m
@@ -1690,26 +1569,9 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
         for (int t = 0; t < 8; ++t) y[t] += *(const f4*)(dp + 16 * t);
         wsum_m += dws[mm * a.TPN + q];
       }
-#ifdef NAMP_ABL_NOTAIL
-      if (tvalid) {
-        float* dst = a.tail.hV_out + (long)trow * NAMP_H + 4 * g;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) *(f4*)(dst + 16 * t) = y[t];
-      }
-      return;
-#endif
-#ifdef NAMP_ABL_PAIRTAIL
-      // TIMING PROBE ONLY (wrong results): every other workgroup runs an 8-row tail (its rows + its neighbour's), the others none
-      if (blockIdx.x & 1) return;
-#endif
       if (TAIL == 4 || TAIL == 8) {
-#ifdef NAMP_ABL_PAIRTAIL
-        constexpr int R = 8;
-        const ConsecutiveRows orow = {row0, 2 * npw, a.G};
-#else
         constexpr int R = (TAIL == 4 || TAIL == 8) ? TAIL : 4;
         const ConsecutiveRows orow = {row0, npw, a.G};
-#endif
         if (M3_LDS) {
           // x = h_V + W3 . (K-sums) + b3 * wsum: wave w < 8 evaluates channel tile w of the (<= 8-row) tile, exchanged through
           // the K-sum area (8 rows x 128 floats <= 12 x 128)
@@ -1766,9 +1628,7 @@ __global__ __launch_bounds__(768) void edge_mlp_kernel(const EdgeArgs a) {
 #define NAMP_SYNC_GEN 16
 #define NAMP_SYNC_TIMEOUT 32
 #define NAMP_SYNC_DEFER 40          // [40..45] three 64-bit device pointers of the sampler's deferred group draw (dec_sample_kernel, MODE 2)
-#ifndef NAMP_SPIN_LIMIT
 #define NAMP_SPIN_LIMIT (1u << 22)  // polls (each followed by s_sleep): several seconds — a hang becomes a reported failure
-#endif
 
 typedef __attribute__((address_space(1))) unsigned int gu32;
 
@@ -1788,18 +1648,11 @@ __device__ __forceinline__ bool spin_until_ge(gu32* word, unsigned target, gu32*
 __device__ __forceinline__ void grid_barrier(unsigned* sync, const unsigned epoch, const int tid) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // every wave: its own (write-through) stores have completed
   __syncthreads();
-#ifdef NAMP_ABL_NOGRIDBARRIER
-  return;
-#endif
   if (tid == 0) {
     gu32* sy = (gu32*)sync;
     const int grp = blockIdx.x % NAMP_SYNC_GROUPS;
     const unsigned ngroups = gridDim.x < NAMP_SYNC_GROUPS ? gridDim.x : NAMP_SYNC_GROUPS;
     const unsigned in_group = (gridDim.x - grp + NAMP_SYNC_GROUPS - 1) / NAMP_SYNC_GROUPS;
-#ifdef NAMP_PERSIST_RELEASE_FENCE                                 // plain table stores + release fence instead of sc1 stores (A/B)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the write-back has completed before the arrival (G16 pitfall 12)
-#endif
     const unsigned old = __hip_atomic_fetch_add(sy + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (old + 1 == in_group * epoch) {                           // last arriver of the group: arrive on the top counter,
       __hip_atomic_fetch_add(sy + NAMP_SYNC_TOP, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2421,9 +2274,7 @@ static __global__ __launch_bounds__(64) void sample_levels_kernel(const int32_t*
 // 90 us at B = 1), and the host has to read the level histogram back before it can launch.  What later levels gather from other
 // workgroups — the next layer's Pv rows — is stored write-through (sc1); tokens travel through agent-scope atomics as before; no
 // workgroup ever reads a row before the level that wrote it (rank order), so no reader holds a stale line.
-#ifndef NAMP_SAMPLE_AHEAD
 #define NAMP_SAMPLE_AHEAD 1
-#endif
 // the sampler's three tile GEMMs: split-bf16 with the fragments requested ahead (chain_gemm_x3_ahead) in the 8-wave forms
 #define SGEMM(FLIP, ACT) sample_gemm<X3, MAXW == 8 && NAMP_SAMPLE_AHEAD, FLIP, ACT>
 template <bool X3, bool AHEAD, bool FLIP, bool ACT>
@@ -2451,7 +2302,6 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
   const f4* w0 = (const f4*)buf0 + lane;
   const f4* w1 = (const f4*)buf1 + lane;
   const SampleRows rows = {node_lds};
-  NAMP_WSTAMP_INIT();
   float tot = 0.f;                                  // running symmetry-group logit sum (head waves)
   // every token starts "not drawn" (-1): the reference's h_S is all-zero until a residue is assigned (:264)
   // (LEVEL: the host fills S_out with -1 before the first level)
@@ -2472,9 +2322,6 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
   __syncthreads();
   // One step: the workgroup's <= a.slots items starting at item0 (MODE 0: streams item0 .. at visit t_seq; else work-list entries
   // item0 .. < nitems).  `more`: another step follows in this launch (its first layer's images are requested under this step's last tail).
-#ifdef NAMP_ABL_STAMPS
-  if (blockIdx.x == 0 && threadIdx.x == 0) namp_stamp_prev = wall_clock64();
-#endif
   // MODE 2 with symmetry groups split over several work items (members that are not graph neighbours of each other run in parallel):
   // every member's logits go to zbuf [B_dec][N][vocab]; after the level's grid barrier one wave per group sums them in visit order — the
   // same fma chain as the running sum of the walk — and draws (close = (stream, last visit) per group sorted by level, close_off per level)
@@ -2531,7 +2378,6 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
   };
   auto step = [&](const int item0, const int nitems, const int t_seq, const bool more) __attribute__((always_inline)) {
     asm volatile("" ::: "memory");      // keep the step's (loop-invariant) vector loads inside the step, not in registers across steps
-    NAMP_STAMP(0);                      // (time since the previous stamp: barrier / launch-side)
     const int item = item0 + slot;                                // LEVEL: index into the work list; else: the stream
     const bool in_list = (slot < a.slots) && (item < nitems);
     const int wi = in_list ? item : item0;
@@ -2597,7 +2443,6 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
       }
       const float* b2p = L.b2; const float* b3p = L.b3;
       f4 x[8], acc[8];
-      NAMP_STAMP(2);                    // (the layer's argument block read)
       {
         // z1 = ctx * (W1e . h_E)[i,k] + Pa[i] + ctx * (Pv | Pfw)[j] (+ tok[S_j])
         const float* src = L.Z1 + erow * NAMP_H + 4 * g;
@@ -2614,7 +2459,6 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
           acc[q] = (z + pav) + pjv;
         }
       }
-      NAMP_STAMP(1);                    // index chain + row gather
       // A wave whose slot holds no residue (a level of B = 1 has ~2.5 of 4) skips the tile products — it would only take matrix-pipe
       // and issue time from the wave it shares a SIMD with — but keeps every barrier and its share of the image copies.
       if (wave_active) {
@@ -2622,7 +2466,6 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
         for (int q = 0; q < 8; ++q) x[q] = *(const f4*)(b2p + 16 * q + 4 * g);
         SGEMM(false, true)(x, acc, w1);
       }
-      NAMP_STAMP(3);                    // product 2 (W2 . gelu(z1))
       if (wave_active) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -2642,9 +2485,7 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
       } else if (lane < 32) {
         *(f4*)(dpart + wave * NAMP_H + 4 * lane) = (f4){0.f, 0.f, 0.f, 0.f};      // (read by the tail's padding rows: keep it finite)
       }
-      NAMP_STAMP(20);                   // (product 3 + K-sum done; the difference to the next stamp is this wave's barrier wait)
       __syncthreads();
-      NAMP_STAMP(4);                    // product 3 + K-sum
       // both ring slots are free: the next layer's W3 / W2 (the next step's first layer in the sequential walk) are copied in
       // ahead of the residue tail, whose scratch lives behind the ring
       if (l + 1 < a.n_layers) {
@@ -2654,7 +2495,6 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
         copy_to_lds<8>(buf0, a.l[0].W3_img, 64, wave, nwaves, lane);
         copy_to_lds<8>(buf1, a.l[0].W2_img, 64, wave, nwaves, lane);
       }
-      NAMP_STAMP(21);                   // (next images copied)
       // residue tail over the workgroup's <= 4 streams: tile row m -> stream slot m
       {
         const int nd = (m < NAMP_SAMPLE_SLOTS) ? node_lds[m] : -1;
@@ -2671,16 +2511,12 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
 #pragma unroll
           for (int q = 0; q < 8; ++q) x[q] += *(const f4*)(dp + 16 * (q ^ ms));
         }
-#ifndef NAMP_ABL_SAMPLE_NOTAIL
         // split-bf16 mode, 8-wave workgroups: the tail as one MFMA tile on x3 images (both walks: level == sequential bit for bit);
         // otherwise the VALU form on fp32 images (prefetching in the level kernel, whose 256 registers hold two units in flight)
         if constexpr (X3 && MAXW == 8) node_tail_x3_rows<NAMP_SAMPLE_SLOTS, SampleRows, MODE == 2>(L.tail, x, rows, tail_lds, tid, wave, lane);
         else node_tail_rows<NAMP_SAMPLE_SLOTS, SampleRows, MODE == 2, true, LEVEL && MAXW == 8>(L.tail, x, 0.f, rows, tail_lds, tid, wave, nwaves, lane);
-#endif
       }
-      NAMP_STAMP(23);                   // (tail done; barrier wait follows)
       __syncthreads();            // tail outputs (h^(l+1), next layer's Pa / Pv) visible to every wave; LDS reusable
-      NAMP_STAMP(5);                    // next images requested + residue tail
     }
 
     // ---- output head + draw, one wave per stream slot (wave n owns slot n for the whole walk, so the running
@@ -2727,9 +2563,7 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
         draw(bq, t, v_first, tot);
       }
     }
-    NAMP_STAMP(24);                     // (head + draw done; barrier wait follows)
     __syncthreads();              // S of this step is published before the next step's neighbours read it
-    NAMP_STAMP(6);                      // output head + draw
   };
 
   // LEVEL: members of the largest symmetry group among the workgroup's items item0 .. (1 without groups)
@@ -2790,7 +2624,6 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
         a.logp_out[e] = __builtin_nanf("");
     }
   }
-  NAMP_WSTAMP_FINI();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no LDS-DMA of a prefetched image is in flight when the workgroup's LDS is released
 }
 
@@ -3661,16 +3494,6 @@ static __device__ __forceinline__ void decoding_order_body(const OrderJob o, con
   }
 }
 
-#ifdef FEAT_STAMPS
-// -DFEAT_STAMPS (tools/feat_stamps.py): per workgroup of the last edge_features launch: s_memrealtime (100 MHz, one clock for the chip) at entry, behind the set-up, at the end; residue
-// block, part, chunks walked, HW_ID
-#define GETREG_IMMED(SZ, OFF, REG) (((SZ) << 11) | ((OFF) << 6) | (REG))
-__device__ unsigned long long g_feat_stamps[1024][8];
-extern "C" int namp_debug_feat_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_feat_stamps), sizeof(g_feat_stamps), 0, hipMemcpyDeviceToHost);
-}
-#endif
-
 // edge_features_kernel: RBF + positional features -> edge_embedding (5200 -> 128, no bias) -> LayerNorm
 // (model_utils.py:499-519, 577-585), optionally followed by W_e (model_utils.py:89).  Same tiling as
 // edge_mlp_kernel (one wave = 16 neighbours of one residue, activations in registers); the GEMM's 5200-long
@@ -3716,9 +3539,6 @@ __global__ __launch_bounds__(768) void edge_features_kernel(const FeatArgs a) {
   const int node_l = wave / a.TPN, kt = wave - node_l * a.TPN;
   if ((int)blockIdx.x < a.ord.B) { decoding_order_body(a.ord, blockIdx.x, smem); return; }      // (workgroup-uniform; first in dispatch order)
   const int bx0 = (int)blockIdx.x - a.ord.B, ngrid = (int)gridDim.x - a.ord.B;
-#ifdef FEAT_STAMPS
-  const unsigned long long st0 = __builtin_amdgcn_s_memrealtime();
-#endif
   int blk = bx0, part = 0, myparts = 1;
   if (a.nparts > 1) {
     // One complex, at most a round of the chip unsplit: the launch lasts as long as its longest workgroup — a block of residues that holds a
@@ -3805,10 +3625,6 @@ __global__ __launch_bounds__(768) void edge_features_kernel(const FeatArgs a) {
     need = mine;
   }
   __syncthreads();                                                  // votes consumed before the ring overwrites... (slot tail is not DMA'd, but keep order simple)
-#ifdef FEAT_STAMPS
-  const unsigned long long st1 = __builtin_amdgcn_s_memrealtime();
-  const int st_chunks = __popcll(need);
-#endif
   int slot = 0;
   if (need) dma_to_lds(smem, img1 + (long)__builtin_ctzll(need) * (FEAT_CHUNK_BYTES / 4), chunk_kb, wave, nwaves, lane);
   // ---- chunk 0: positional k-tile (weights: first 8 KiB of the image, read straight from L2), under the first chunk's DMA
@@ -3828,7 +3644,6 @@ __global__ __launch_bounds__(768) void edge_features_kernel(const FeatArgs a) {
 #pragma unroll
       for (int tn = 0; tn < 8; ++tn) acc[tn] = mfma4(w[tn * 64][r], xk[r], acc[tn]);
   }
-#ifndef FEAT_NOPIPE
   if constexpr (X3 != 0) {
     // Round 6 — split-bf16 / bf16 products: a step (K = 32: the RBFs of two atom pairs) as compact run-time loops over (b-group, step) instead
     // of nine unrolled copies with a branch per atom; the distance through the bare v_sqrt_f32 (1 ulp; sqrtf expands to ~13 more instructions
@@ -3850,11 +3665,7 @@ __global__ __launch_bounds__(768) void edge_features_kernel(const FeatArgs a) {
           const int bb = 6 * bg + sl;
           const float* xb = xj + (3 * bb) * 16;
           const float dx = xi0 - xb[0], dy = xi1 - xb[16], dz = xi2 - xb[32];
-#ifdef FEAT_PRECISE_SQRT
-          const float D = fminf(sqrtf(dx * dx + dy * dy + dz * dz + 1e-6f), 40.0f);
-#else
           const float D = fminf(__builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz + 1e-6f), 40.0f);
-#endif
           dbuf[sl * 16] = ((mj >> bb) & 1u) ? D : 40.0f;
         }
       }
@@ -3918,12 +3729,8 @@ __global__ __launch_bounds__(768) void edge_features_kernel(const FeatArgs a) {
         const uint32_t pres = wave_a ? ((mj_s >> (6 * bg)) & 63u) : 0u;
         uint32_t steps = ((pres & 3u) ? 1u : 0u) | ((pres & 12u) ? 2u : 0u) | ((pres & 48u) ? 4u : 0u);
         const bf8* wc = (const bf8*)(smem + slot * NAMP_IMG_BYTES) + lane;
-#ifndef FEAT_ABL_NOGEN
         if (steps) dist(xi0, xi1, xi2, bg, pres);                    // (in front of the barrier: under the chunk's DMA)
-#endif
-#ifndef FEAT_ABL_NOBARRIER
         wait_dma_and_sync();                                         // chunk c has landed; everyone is done with the previous one
-#endif
         {
           const unsigned long long rest = (c + 1 < 64) ? (need >> (c + 1)) : 0ull;
           if (rest) dma_to_lds(smem + (slot ^ 1) * NAMP_IMG_BYTES, img1 + (long)(c + 1 + __builtin_ctzll(rest)) * (FEAT_CHUNK_BYTES / 4),
@@ -3934,24 +3741,15 @@ __global__ __launch_bounds__(768) void edge_features_kernel(const FeatArgs a) {
         while (steps) {
           const int st = __builtin_ctz(steps);
           bf8 hi, mid;
-#ifdef FEAT_ABL_NOGEN
-          hi = (bf8){(__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f}; mid = hi;
-#else
           gen(st, pres, hi, mid);
-#endif
-#ifdef FEAT_ABL_NOMUL
-          acc[st & 7][0] += (float)hi[0] + (float)mid[3];
-#else
           __builtin_amdgcn_s_setprio(1);                             // the products ahead of the other waves' VALU work: -0.8 % (the same hint in
           mul(hi, mid, wc + st * 8 * 64);                            // chain_gemm_x3 cost the split-bf16 edge launches 4.7 %: profiles/r06g)
           __builtin_amdgcn_s_setprio(0);
-#endif
           steps &= steps - 1u;
         }
       }
     }
   } else
-#endif
 #pragma unroll 1
   for (int aa = 0; aa < 18; ++aa) {
     if (!((need >> (3 * aa)) & 7ull)) continue;                      // workgroup-uniform: no chunk of atom a is needed
@@ -4050,13 +3848,6 @@ __global__ __launch_bounds__(768) void edge_features_kernel(const FeatArgs a) {
       }
     }
   }
-#ifdef FEAT_STAMPS
-  if (tid == 0 && bx0 < 1024) {
-    unsigned long long* o = g_feat_stamps[bx0];
-    o[0] = st0; o[1] = st1; o[2] = __builtin_amdgcn_s_memrealtime(); o[3] = blk; o[4] = part | (myparts << 8); o[5] = st_chunks;
-    o[6] = __builtin_amdgcn_s_getreg(GETREG_IMMED(32 - 1, 0, 4)); o[7] = __builtin_amdgcn_s_getreg(GETREG_IMMED(4 - 1, 0, 20));
-  }
-#endif
   if (myparts > 1) {                                               // partial rows out; feat_finish_kernel does the rest
     if (valid) {
       float* dst = a.pbuf[part] + erow * NAMP_H + 4 * g;

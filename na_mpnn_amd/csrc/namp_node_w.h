@@ -28,10 +28,6 @@
 
 // acc[tn] += W[16tn .., :] . x  for one 128 x 128 block image in LDS (w = block + lane), x as the four K-step operands of the tile
 __device__ __forceinline__ void gemm16(f4 (&acc)[8], const bf8 (&xb)[4], const bf8* w) {
-#ifdef NW_NOGEMM
-  acc[0].x += (float)xb[0][0] + (float)w[0][0];
-  return;
-#endif
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     bf8 wf[8];
@@ -105,18 +101,12 @@ static __global__ __launch_bounds__(NODEW_THREADS, 2) void node_update_w_kernel(
   };
   f4 sreg[8];
   auto stage_load = [&](const int i) {
-#ifdef NW_NOSTAGE
-    return;
-#endif
     const char* b = block_base(i) + tid * 16;
     const long st = block_stride(i);
 #pragma unroll
     for (int k = 0; k < 4; ++k) { sreg[2 * k] = *(const f4*)(b + k * st); sreg[2 * k + 1] = *(const f4*)(b + k * st + 4096); }
   };
   auto stage_store = [&](const int i) {
-#ifdef NW_NOSTAGE
-    return;
-#endif
     char* d = smem + (i & 1) * NODEW_SLOT + tid * 16;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { *(f4*)(d + 8192 * k) = sreg[2 * k]; *(f4*)(d + 8192 * k + 4096) = sreg[2 * k + 1]; }
@@ -153,7 +143,6 @@ static __global__ __launch_bounds__(NODEW_THREADS, 2) void node_update_w_kernel(
 #pragma unroll
       for (int c = 0; c < 8; ++c) hv[c] = *(const f4*)(src + 16 * c);
     }
-#ifndef NW_NOIN
     for (int p0 = 0; p0 < a.TPN; p0 += 3) {
       f4 v[3][8];
       float wv[3];
@@ -166,11 +155,9 @@ static __global__ __launch_bounds__(NODEW_THREADS, 2) void node_update_w_kernel(
         wv[q] = a.partial[(long)a.G * a.TPN * NAMP_H + (long)rr * a.TPN + p];
       }
       if (p0 == 0) {
-#ifndef NW_NOSTAGE
         char* d0 = smem + tid * 16;
 #pragma unroll
         for (int k = 0; k < 4; ++k) { *(f4*)(d0 + 8192 * k) = sreg2[2 * k]; *(f4*)(d0 + 8192 * k + 4096) = sreg2[2 * k + 1]; }
-#endif
         stage_store(1);
         stage_load(2);
       }
@@ -183,9 +170,6 @@ static __global__ __launch_bounds__(NODEW_THREADS, 2) void node_update_w_kernel(
         }
       }
     }
-#else
-    stage_store(0); stage_store(1); stage_load(2);
-#endif
     bf8 xb[4], xm[X3 ? 4 : 1];
     split_rows<X3>(xb, (bf8(&)[4])xm, x);
     __syncthreads();                                             // ring entries 0, 1 in LDS
@@ -213,11 +197,7 @@ static __global__ __launch_bounds__(NODEW_THREADS, 2) void node_update_w_kernel(
         for (int c = 0; c < 8; ++c) hacc[c] = *(const f4*)(t.b_in + 128 * h + 16 * c + 4 * g);
         product(hacc, xb, (bf8(&)[4])xm, 2 * h + 1, advance, slot);
 #pragma unroll
-#ifndef NW_NOGELU
         for (int c = 0; c < 8; ++c) hacc[c] = gelu4(hacc[c]);
-#else
-        for (int c = 0; c < 8; ++c) hacc[c] *= 0.5f;
-#endif
         split_rows<X3>(hb, (bf8(&)[4])hm, hacc);
       }
       product(oacc, hb, (bf8(&)[4])hm, 2 * h + 2, advance, slot);

@@ -36,9 +36,6 @@ __device__ __forceinline__ void gelu_val_grad(float x, float& val, float& grad) 
 
 // in: pre-activations z; out: z <- gelu'(z), returns gelu(z) — one exp / rcp pair serves both
 __device__ __forceinline__ f4 gelu_split4(f4& z) {
-#ifdef DW_EXP_NOGELU
-  { const f4 v_ = z; z = z * 0.5f; return v_; }
-#endif
   float v0, v1, v2, v3, d0, d1, d2, d3;
   gelu_val_grad(z.x, v0, d0); gelu_val_grad(z.y, v1, d1); gelu_val_grad(z.z, v2, d2); gelu_val_grad(z.w, v3, d3);
   z = (f4){d0, d1, d2, d3};
@@ -62,7 +59,6 @@ template <bool BF> __device__ __forceinline__ f4 ld_row4(const float* base, cons
 // piece index 4t + g, so a lane's own pieces are 32 bytes apart and a store instruction moves 16 x 32 bytes.  v_permlane16_swap_b32 (gfx950: the odd
 // 16-lane rows of one register against the even rows of another) hands lane group g the piece of g ^ 1: even groups then store pieces (4t + g, 4t + g + 1),
 // odd ones (4(t+1) + g - 1, 4(t+1) + g) — four 16-byte stores per lane and tile instead of eight 8-byte ones.
-#ifndef NAMP_ABL_NOPAIRST
 __device__ __forceinline__ void st_tile_bf16(float* base, const long row_off, const f4 (&v)[8], const int g) {
   __bf16* dst = (__bf16*)base + row_off;
   typedef int i4v __attribute__((ext_vector_type(4)));
@@ -78,12 +74,6 @@ __device__ __forceinline__ void st_tile_bf16(float* base, const long row_off, co
     *(i4v*)(dst + col) = o;
   }
 }
-#else
-__device__ __forceinline__ void st_tile_bf16(float* base, const long row_off, const f4 (&v)[8], const int g) {
-#pragma unroll
-  for (int t = 0; t < 8; ++t) st_row4<true>(base, row_off + 4 * g + 16 * t, v[t]);
-}
-#endif
 
 enum { BWD_ENC_MSG = 0, BWD_DEC_MSG = 1, BWD_ROWS = 2, BWD_EDGE_LN = 3 };
 
@@ -897,9 +887,7 @@ static __global__ __launch_bounds__(256) void feat_wgrad_kernel(const float* __r
 // the in-order memory counter behind each), and a step's eight g_pre fragments are read once with each live block's eight products behind one branch.
 // cfg5: 3.43 -> 3.18 ms (split-bf16), 3.03 -> 2.77 ms (bf16) per step.  Measured and NOT kept: (iii) in the split-bf16 instantiation (4.1-6.3 ms: the
 // compiler serialises differently and loses a wave per SIMD); four blocks per wave — twice the products per staged tile — at half the occupancy (6.8 ms).
-#ifndef FEATW_NBW
 #define FEATW_NBW 2
-#endif
 #define FEATW_WG_BLOCKS (4 * FEATW_NBW)
 #define FEATW_GRID_X ((FEATW_BLOCKS + FEATW_WG_BLOCKS - 1) / FEATW_WG_BLOCKS)
 
@@ -1154,9 +1142,7 @@ __global__ __launch_bounds__(256) void feat_wgrad_x3_kernel(const float* __restr
                                                             long g16_plane = 0) {
   feat_wgrad_x3_body<MID, PK, S16>(X18, M18, E_idx, E_pos, g_pre, pres, E, edges_per_chunk, L, K, dW_part, g16, g16_plane);
 }
-#ifndef FEATW_T16_WAVES
 #define FEATW_T16_WAVES 3
-#endif
 // The mixed-precision launch on bf16 operand tiles at three workgroups per CU (156 registers; at four — 128 registers — it spills 47 and runs 2.5 ms):
 // the waves of the other workgroups cover the per-tile round trips (coordinates, LDS, two barriers) that are what is left of a tile visit once the
 // staging is four copies.
@@ -1454,12 +1440,8 @@ struct TailTrainArgs {
   int G;
 };
 
-#ifndef FFN_LD
 #define FFN_LD 132             // padded row stride (floats) of the LDS tiles (as in namp_kernels.h)
-#endif
-#ifndef TAIL_T
 #define TAIL_T 3             // 48 rows per pass over the 1 MB of FFN images a workgroup pulls from L2 (2: 0.89 ms per cfg5 step in the six fwd + bwd launches; 3: 0.81; 4 spills)
-#endif
 #define TAIL_LDS (((2 * TAIL_T * 16) + 8 * 16) * FFN_LD * 4)
 
 // per-wave GEMM "A": out[q][4 tiles of this wave's 64 hidden units] = W (512 x 128 image) . rows of tile q (from LDS, fp32)

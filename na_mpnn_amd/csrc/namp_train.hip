@@ -165,9 +165,6 @@ int namp_train_edge_bwd_dw(int mode, const float* h_E, const int32_t* E_idx, con
   a.G = B * N; a.N = N; a.K = K; a.E = (long)a.G * K;
   a.acc_hE = (x3 & 4) ? 1 : 0;
   a.g_hE_in = g_hE_in;
-#ifdef DW_EXP_STAMPS
-  { const char* e = getenv("NAMP_DW_STAMPS"); a.S3 = e ? (float*)strtoull(e, nullptr, 0) : nullptr; }   // device address of the stamp buffer (tools/dw_time.py)
-#endif
   REQUIRE(!a.acc_hE || g_hE_in != nullptr, "namp_train_edge_bwd_dw: the accumulate flag needs g_hE_in");
   a.gpa_tiles = (x3 & 8) ? 1 : 0;
   REQUIRE(!a.gpa_tiles || (K % 16) == 0, "namp_train_edge_bwd_dw: per-tile g_Pa sums need K %% 16 == 0 (K=%d)", K);

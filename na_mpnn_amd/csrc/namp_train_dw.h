@@ -48,17 +48,12 @@ __device__ __forceinline__ void dw_lds_barrier() { asm volatile("s_waitcnt lgkmc
 // plane at `base`: S[ch][16 wave + m] = bf16(v); X3: the plane behind it takes bf16 of the remainder.  Row chunk c (8 rows = 16 bytes)
 // of channel ch sits at chunk position c ^ ((ch >> 1) & 7): with 128-byte channel rows a quarter-wave of fragment reads (16 channels, one
 // chunk) then covers all 64 banks exactly once (tests/test_layout_sim.py).
-// Ablation switches for tools/dw_time.py (never defined in the shipped build): DW_EXP_NOSTAGE / NOCONTRACT / NOGEMM / NOGELU / NOSTORE / NOLOAD
-// drop the staging writes, the contraction, the chain products, the GELU evaluations, the row stores, the per-round row loads.
 // Split-bf16 (X3: two planes per value), round 5: rows m and m ^ 1 of a channel are neighbours in the plane (2 bytes each) and live in neighbouring
 // lanes: the even lane of a pair takes components 0, 1 of BOTH rows, the odd lane components 2, 3 (two DPP quad_perm [1,0,3,2] moves each way), so
 // that a value pair goes out as one v_cvt_pk_bf16_f32 + ds_write_b32 — half the LDS write instructions: -4 % on the ring kernels (4.54 -> 4.35 ms
 // per three cfg5 launches).  The one-plane bf16 form keeps single values: paired, it measured the same and cost edge_bwd_dw16_kernel its last registers.
 template <bool X3>
 __device__ __forceinline__ void dw_stage(char* base, const f4 (&v)[8], const int wave, const int m, const int g) {
-#ifdef DW_EXP_NOSTAGE
-  return;
-#endif
   const int chunkv = 2 * wave + (m >> 3);
   if constexpr (!X3) {
 #pragma unroll
@@ -117,9 +112,6 @@ __device__ __forceinline__ float dw_row_sum_to_lane15(float v) {
 template <bool X3, bool BIAS>
 __device__ __forceinline__ void dw_contract(f4 (&acc)[4][4], f4 (&accb)[2], const char* SG, const char* SA, const int wo, const int wc,
                                             const int n, const int g) {
-#ifdef DW_EXP_NOCONTRACT
-  return;
-#endif
   const int fsw = (n >> 1) & 7;
   const char* gb = SG + (64 * wo + n) * DW_ROWB;
   const char* ab = SA + (64 * wc + n) * DW_ROWB;
@@ -454,11 +446,6 @@ __global__ __launch_bounds__(64 * DW_WAVES) void edge_bwd_dw_kernel(const EdgeBw
 // MFMAs of step s issue (two fragment sets in flight).  One wave per SIMD has nobody to cover an LDS round trip: the compiler's own
 // schedule (read, wait, MFMA — nearly one for one) made this launch 13 us per 64-row round where its MFMAs need 1.3.
 __device__ __forceinline__ void dw_gemm16_ahead(f4 (&acc)[8], const f4 (&x)[8], const bf8* w) {
-#ifdef DW_EXP_NOGEMM
-#pragma unroll
-  for (int t = 0; t < 8; ++t) acc[t] += x[t];
-  return;
-#endif
   // half-steps of four channel tiles: the four fragments of half-step i + 1 are requested before the MFMAs of half-step i issue
   // (two sets of four in flight: 32 registers — a full step ahead, 64, spills next to the launch's prefetched row streams)
   bf8 wf[2][4];
@@ -519,9 +506,6 @@ __device__ __forceinline__ void dw_contract16_ahead(f4 (&acc)[4][4], f4 (&accb)[
 // instead of the 17 of gelu_val_grad's Abramowitz-Stegun form (two transcendentals there, one here).
 // in: pre-activations z; out: z <- gelu'(z), returns gelu(z)
 __device__ __forceinline__ f4 dw_gelu_split4_bf16(f4& z) {
-#ifdef DW_EXP_NOGELU
-  { const f4 v_ = z; z = z * 0.5f; return v_; }
-#endif
   const f4 x = z;
   const f4 t = x * x;
   f4 q = (f4){NAMP_GELU4_Q4, NAMP_GELU4_Q4, NAMP_GELU4_Q4, NAMP_GELU4_Q4};       // the constants of gelu4_bf16mode (namp_device.h)
@@ -540,9 +524,6 @@ __device__ __forceinline__ f4 dw_gelu_split4_bf16(f4& z) {
 
 // dw_stage<false> from a tile kept as packed bf16 pairs: h[2t + (r >> 1)][r & 1] = bf16(v[t][r])
 __device__ __forceinline__ void dw_stage_packed(char* base, const bf2 (&h)[16], const int wave, const int m, const int g) {
-#ifdef DW_EXP_NOSTAGE
-  return;
-#endif
   const int chunkv = 2 * wave + (m >> 3);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -651,16 +632,8 @@ __global__ __launch_bounds__(64 * DW_WAVES) void edge_bwd_dw16_kernel(const Edge
   int idx_n1 = a.E_idx[row_of(round + gridDim.x < aa.nrounds ? round + gridDim.x : round)];
   __syncthreads();                                                   // the images are in place
 
-#ifdef DW_EXP_STAMPS
-  // phase stamps (s_memtime) of workgroup 0 into the otherwise unused S3 pointer: [round][wave][32] (tools/dw_time.py --stamps)
-  int stamp_round = 0;
-#define DW_STAMP(i) do { if (blockIdx.x == 0 && lane == 0 && stamp_round < 8 && a.S3) ((long long*)a.S3)[(stamp_round * DW_WAVES + wave) * 32 + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define DW_STAMP(i) do { } while (0)
-#endif
   for (; round < aa.nrounds; round += gridDim.x) {
     const Meta me = cur;
-    DW_STAMP(0);
     const long round_n = round + gridDim.x;
     const bool more = round_n < aa.nrounds;
     // ---- z1 = W1b . h_E + (Pa + Pj).  h_E is kept as packed bf16 (16 registers) for the second contraction instead of being read again.
@@ -676,24 +649,12 @@ __global__ __launch_bounds__(64 * DW_WAVES) void edge_bwd_dw16_kernel(const Edge
     pend2(pn, rn);                                                   // rank / mask of the next round's rows: consumed behind g1
     const long round_n2 = round_n + gridDim.x;
     idx_n1 = a.E_idx[row_of(round_n2 < aa.nrounds ? round_n2 : round)];
-#ifndef DW_EXP_NOLOAD
 #pragma unroll
     for (int t = 0; t < 8; ++t) A[t] = *(const f4*)(a.b2 + 16 * t + 4 * g);      // (L1: 512 bytes every lane re-reads)
-#else
-#pragma unroll
-    for (int t = 0; t < 8; ++t) A[t] = x[t];
-#endif
-    DW_STAMP(1);
     dw_gemm16_ahead(z1, x, w1);
-    DW_STAMP(2);
     // dL/d(K-sum) rows of the tile's residues (L1 / L2): requested here, consumed behind the second product
-#ifndef DW_EXP_NOLOAD
 #pragma unroll
     for (int t = 0; t < 8; ++t) gr[t] = *(const f4*)(a.g_node + (long)me.node * NAMP_H + 4 * g + 16 * t);
-#else
-#pragma unroll
-    for (int t = 0; t < 8; ++t) gr[t] = x[t];
-#endif
     // x <- a1; gelu'(z1) is kept as packed bf16 (16 registers; it multiplies a bf16-grade gradient): z1 is free for the next round's Pa rows
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
@@ -701,43 +662,32 @@ __global__ __launch_bounds__(64 * DW_WAVES) void edge_bwd_dw16_kernel(const Edge
       d16[2 * t] = (bf2){(__bf16)z1[t].x, (__bf16)z1[t].y};
       d16[2 * t + 1] = (bf2){(__bf16)z1[t].z, (__bf16)z1[t].w};
     }
-    DW_STAMP(3);
     // ---- z2 = W2 . a1 + b2;  g2 = w_ik * dL/d(K-sum) * gelu'(z2)
     dw_gemm16_ahead(A, x, w2);
-    DW_STAMP(4);
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       (void)dw_gelu_split4_bf16(A[t]);                                       // A <- gelu'(z2)
       gr[t] = gr[t] * me.w_row * A[t];
     }
-    DW_STAMP(5);
     // ---- contraction 1: dW2 += G2^T A1, db2 += sum G2
     dw_lds_barrier();                                                // the previous round's second contraction has been read out
-    DW_STAMP(6);
     dw_stage<false>(SG, gr, wave, m, g);
     dw_stage<false>(SA, x, wave, m, g);
-    DW_STAMP(7);
-#ifndef DW_EXP_NOLOAD
     {                                                                // the next round's h_E rows: two products and two contractions to land
       const float* src = a.hE + row_of(rn) * NAMP_H + 4 * g;
 #pragma unroll
       for (int t = 0; t < 8; ++t) x[t] = *(const f4*)(src + 16 * t);
     }
-#endif
     dw_lds_barrier();
-    DW_STAMP(8);
     dw_contract<false, true>(dW2, db2, SG, SA, wo, wc, m, g);
-    DW_STAMP(9);
     // ---- g1 = (W2^T g2) * gelu'(z1)
 #pragma unroll
     for (int t = 0; t < 8; ++t) A[t] = (f4){0.f, 0.f, 0.f, 0.f};
     dw_gemm16_ahead(A, gr, w2t);
-    DW_STAMP(10);
 #pragma unroll
     for (int t = 0; t < 8; ++t)
       gr[t] = A[t] * (f4){(float)d16[2 * t][0], (float)d16[2 * t][1], (float)d16[2 * t + 1][0], (float)d16[2 * t + 1][1]};
     cur = pend3(pn, rn);
-#ifndef DW_EXP_NOLOAD
     {                                                                // the next round's table rows (L2): Pa -> z1, Pj -> A
       const float* pa = a.Pa + (long)cur.node * NAMP_H + 4 * g;
       const float* pj = (cur.from1 ? a.Pj1 : a.Pj0) + (long)cur.j * NAMP_H + 4 * g;
@@ -748,20 +698,11 @@ __global__ __launch_bounds__(64 * DW_WAVES) void edge_bwd_dw16_kernel(const Edge
 #pragma unroll
       for (int t = 0; t < 8; ++t) P[t] = ACC ? *(const f4*)(a.g_hE_in + me.e * NAMP_H + 4 * g + 16 * t) : (f4){0.f, 0.f, 0.f, 0.f};
     }
-#else
-#pragma unroll
-    for (int t = 0; t < 8; ++t) P[t] = gr[t];
-#endif
-    DW_STAMP(11);
     // ---- contraction 2: dW1b += G1^T h_E
     dw_lds_barrier();                                                // contraction 1 has been read out
-    DW_STAMP(12);
     dw_stage<false>(SG, gr, wave, m, g);
     dw_stage_packed(SA, h16, wave, m, g);
-    DW_STAMP(13);
     dw_lds_barrier();
-    DW_STAMP(14);
-#ifndef DW_EXP_NOSTORE
     const long e_st = (round * DW_WAVES + wave) * 16 + m;           // unclamped: rows past E go to the buffers' padding
     st_tile_bf16(a.G1, e_st * NAMP_H, gr, g);
     if constexpr (GPA == 1) {
@@ -785,25 +726,15 @@ __global__ __launch_bounds__(64 * DW_WAVES) void edge_bwd_dw16_kernel(const Edge
         unsafeAtomicAdd(d + 16 * t + 2, gr[t].z * vz); unsafeAtomicAdd(d + 16 * t + 3, gr[t].w * vz);
       }
     }
-#endif
-    DW_STAMP(15);
     f4 nob[2];
     dw_contract<false, false>(dW1, nob, SG, SA, wo, wc, m, g);
-    DW_STAMP(16);
     // ---- dL/dh_E = W1b^T g1 + the other consumer's rows (P)
     dw_gemm16_ahead(P, gr, w1t);
-    DW_STAMP(17);
-#ifndef DW_EXP_NOSTORE
     {
       float* d = a.g_hE + ((round * DW_WAVES + wave) * 16 + m) * NAMP_H + 4 * g;
 #pragma unroll
       for (int t = 0; t < 8; ++t) *(f4*)(d + 16 * t) = P[t];
     }
-#endif
-    DW_STAMP(18);
-#ifdef DW_EXP_STAMPS
-    ++stamp_round;
-#endif
   }
   float* o2 = aa.dW_part + (long)blockIdx.x * 2 * NAMP_H * NAMP_H;
   float* o1 = o2 + NAMP_H * NAMP_H;

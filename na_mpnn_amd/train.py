@@ -42,8 +42,6 @@ DW_ONCHIP = _os.environ.get("NAMP_TRAIN_DW", "1") != "0"
 # The edge update's backward in the same form (mixed precision): two persistent launches cut at g2 = dL/dz2, all three weight gradients and the
 # LayerNorm sums on chip (csrc/namp_train_eu.h; round 5).  NAMP_TRAIN_DW_EDGE=0 restores the round-3 launch + its three row contractions.
 DW_ONCHIP_EDGE = _os.environ.get("NAMP_TRAIN_DW_EDGE", "1") != "0"
-# norm_edges + W_e as one forward / one backward launch without the normalised rows in memory (split-bf16 / mixed precision; 0 = the round-4 pair)
-EMBED_LN_FUSED = _os.environ.get("NAMP_TRAIN_EMBED_LN", "1") != "0"
 G16_SPLIT = _os.environ.get("NAMP_TRAIN_G16_SPLIT", "0") == "1"      # bf16 operand tiles of dL/dy in the split-bf16 mode too (measured: a loss)
 # split-bf16 edge-update backward (fp32 row tensors): complexes per batch are walked in this many slices at most (1 = the whole batch at once)
 EDGE_UPDATE_SLICES = max(1, int(_os.environ.get("NAMP_TRAIN_EU_SLICES", "2")))
@@ -1049,7 +1047,7 @@ def _forward_train(model, fd, decoding_randn):
     B, N, K = E_idx.shape
     V = _ln(_TableRows.apply(fp.node_embedding.weight.t(), fd["R_polymer_type"].long()), fp.norm_nodes)   # one-hot @ W^T
     h_V = _lin(V, (model.W_v.weight, model.W_v.bias))[0]
-    if X3 and EMBED_LN_FUSED:
+    if X3:          # norm_edges + W_e as one forward / one backward launch, without the normalised rows in memory
         h_E = _EdgeEmbedTail.apply(y, fp.norm_edges.weight, fp.norm_edges.bias, model.W_e.weight, model.W_e.bias)
     else:
         h_E = _EdgeLinear.apply(_RowLayerNorm.apply(y, fp.norm_edges.weight, fp.norm_edges.bias), model.W_e.weight, model.W_e.bias)

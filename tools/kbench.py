@@ -3,7 +3,7 @@
 
     NAMP_LIB_PATH=/path/to/variant.so python tools/kbench.py [--reps 200] [--B 1]
 
-Used with ablation builds (see NAMP_ABL_* in csrc/namp_device.h) to attribute kernel time.
+Run once per build to compare two of them kernel by kernel.
 """
 import argparse
 import os

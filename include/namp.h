@@ -678,6 +678,25 @@ int namp_decoder_sample_walk(const NampModelW* w, const float* h_V_enc, const fl
                              float temperature, uint64_t special_tokens, int32_t* S_out, float* probs_out, float* logp_out,
                              void* ws, size_t ws_bytes, int B_dec, int B_enc, int N, int K, void* stream);
 
+/* ---- leave-one-out conditional log-probs ---------------------------------------------------------
+ * log p(s_i | X, S_-i) for EVERY residue i in one call, after encode(): row i of the parallel decoder (model_utils.py:391-421)
+ * run with the decoding order of score() (model_utils.py:388-389) in which residue i is taken out and appended at the end,
+ * rank_i[j] = rank[j] - (rank[j] > rank[i]), rank_i[i] = N - 1, the true S teacher-forced everywhere.  The same numbers as N
+ * streams of namp_decoder_fwd, but only the dependency cone of every stream is evaluated (DecLayer, model_utils.py:636-657, on a grid
+ * of ITEMS): layer 1 at the residues that lose i from their decoded neighbours (one item per directed edge, slot (m, k) with
+ * E_idx[m, k] = i), layer 2 at the neighbours of i that those reach (slot (i, kq)), and the three layers of i itself — about
+ * K + 3 layer evaluations per residue whatever N is, behind ONE ordinary decoder pass over the base order (two layers of it).
+ * Three decoder layers, split-bf16 or exact fp32 evaluation (NAMP_EINVAL otherwise: run the N streams through namp_decoder_fwd).
+ *   S / mask / rank  [B, N] int32 (rank = inverse of score()'s decoding order)        log_probs [B, N, vocab]
+ *   counts           int32 [2] (device): the numbers of active layer-1 / layer-2 items of the call
+ *   ws               namp_loo_workspace_bytes(B, N, K, n_dec) bytes: 5 item-row tensors [B*N*K][128] + 2 index tables [B*N*K][K]
+ *                    + residue-sized tables — O(B*N*K*128), never O(N^2); 0 for an unsupported n_dec.
+ * Separate launches on `stream` (no grid barrier, no atomics: two calls give identical bits). */
+size_t namp_loo_workspace_bytes(int B, int N, int K, int n_dec);
+int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx, const int32_t* S,
+                     const int32_t* mask, const int32_t* rank, float* log_probs, int32_t* counts, void* ws, size_t ws_bytes,
+                     int B, int N, int K, void* stream);
+
 /* ---- measurement hook (bench.py) ------------------------------------------------------------
  * When enabled (thread-local), every kernel launch made through this ABI is bracketed by HIP
  * events on the launch stream; namp_profile_collect() waits for them and returns the summed

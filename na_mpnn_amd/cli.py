@@ -58,6 +58,8 @@ def build_parser():
     a("--output_pdbs", type=int, default=1, help="1 - write backbones/<name>_<id>.pdb with the designed residue names")
     a("--output_sequences", type=int, default=1)
     a("--output_specificity", type=int, default=0)
+    a("--conditional_probs_only", type=int, default=0, help="1 - no sampling: write conditional_probs/<name>.npz with "
+      "log p(s_i | structure, all other residues) for every residue (ProteinMPNN.conditional_probs)")
     a("--load_residues_with_missing_atoms", type=int, default=0)
     a("--mode", type=str, default=None)
     a("--device", type=str, default="cuda:0")
@@ -152,7 +154,11 @@ def main(argv=None):
     omit_AA = torch.tensor([float(c in omit_list) for c in alphabet], device=device)
 
     base = args.out_folder if args.out_folder.endswith("/") else args.out_folder + "/"
-    os.makedirs(base + "seqs", exist_ok=True)
+    if args.conditional_probs_only:
+        os.makedirs(base + "conditional_probs", exist_ok=True)
+        args.output_pdbs = args.output_sequences = args.output_specificity = 0
+    else:
+        os.makedirs(base + "seqs", exist_ok=True)
     if args.output_pdbs:
         os.makedirs(base + "backbones", exist_ok=True)
     if args.output_specificity:
@@ -212,6 +218,15 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
                    "symmetry_residues": sym_res, "symmetry_weights": sym_w})
         if pair_bias_AA is not None:
             fd["pair_bias"] = make_pair_bias(fd["chain_labels"][0], fd["R_idx"][0], pair_bias_AA)
+        if args.conditional_probs_only:
+            # one deterministic leave-one-out profile instead of draws: the decoding order's noise is the only random input
+            fd["randn"] = torch.randn(1, L, device=device)
+            out = model.conditional_probs(fd)
+            np.savez(os.path.join(base, "conditional_probs", name + ".npz"),
+                     log_probs=out["log_probs"][0].cpu().numpy(), S=P["S"].astype(np.int64), mask=P["mask"],
+                     chain_mask=chain_mask, chain_labels=P["chain_labels"], decoding_order=out["decoding_order"].cpu().numpy(),
+                     encoded_residues=encoded)
+            return
         S_l, lp_l, sp_l, loss_l, lpr_l = [], [], [], [], []
         cmask = (fd["mask"] * fd["chain_mask"]).float()
         forced = np.load(args.forced_draws_npz) if args.forced_draws_npz else None

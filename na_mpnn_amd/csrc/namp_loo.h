@@ -1,0 +1,267 @@
+// Leave-one-out conditional log-probs (namp_decoder_loo, include/namp.h): log p(s_i | X, S_-i) for EVERY residue i of a complex —
+// row i of the parallel decoder (model_utils.py:391-421) run with the decoding order of score() in which i is moved to the end.
+//
+// Stream i differs from the base stream (the plain score() order) only inside a small dependency cone around i:
+//   phase 1  layer-1 outputs of the residues m that used to see i as decoded (i in N(m), rank[i] < rank[m], mask[m] = 1): one edge of m
+//            flips from backward to forward.  Item = the directed edge, slot (m, k) with E_idx[m, k] = i: an [L, K] grid of items;
+//   phase 2  layer-2 outputs of i's own neighbours q = E_idx[i, kq], slot (i, kq), where a phase-1 output feeds them;
+//   own      residue i itself, layers 1..3 with every neighbour backward (the self edge stays forward), then W_out + log_softmax.
+// loo_prepare_kernel / loo_edges_kernel turn (E_idx, rank, mask) into per-item INDEX tables — which residue's h_E rows, which centre
+// state and, per edge, which table row (base backward / base forward / an override row written by an earlier phase) — and
+// dec_items_kernel is the DecLayer message MLP + K-sum + residue tail (model_utils.py:636-657) over a grid of such items: the body of
+// edge_mlp_kernel<MODE_DEC_MSG> with the rank comparison replaced by indirection.  Every item owns its output rows (no atomics, two
+// runs are bit-identical); phases are separate launches (nothing waits on the device).
+#pragma once
+#include "namp_kernels.h"
+
+// table row code of the index tables: bits 28-29 = table (edges: 0 base backward Pbw, 1 forward Pfw, 2 override; centres: 0 base,
+// 1 override), bits 0-27 = row
+#define LOO_ROW_BITS 28
+#define LOO_ROW_MASK ((1 << LOO_ROW_BITS) - 1)
+#define LOO_FW (1 << LOO_ROW_BITS)
+#define LOO_OV (2 << LOO_ROW_BITS)
+#define LOO_CEN_OV (1 << LOO_ROW_BITS)
+
+struct LooPrepArgs {
+  const int32_t* E_idx;   // [G][K] neighbour ids, local to the complex
+  const int32_t* rank;    // [G]
+  const int32_t* mask;    // [G]
+  const int32_t* S;       // [G]
+  int32_t* rev;           // [R] edge (a, k) -> b: position of a in E_idx[b], or -1
+  int32_t* act1;          // [R] phase-1 item (m, k) is active
+  int32_t* act2;          // [R] phase-2 item (i, kq) is active
+  int32_t* ctr1;          // [R] centre residue of a phase-1 item (also its centre-state code: base row m)
+  int32_t* ctr2;          // [R] centre residue q of a phase-2 item
+  int32_t* cen2;          // [R] its centre-state code
+  int32_t* msk1; int32_t* S1; int32_t* msk2; int32_t* S2;   // [R] mask / token of the items' centres
+  int32_t* eo1; int32_t* eo2; int32_t* eo3;                  // [R] = [G][K] edge codes of residue i's own layers 1..3
+  int32_t* idG; int32_t* ovG;                                // [G] centre codes of the own items: base row g / override row g
+  int32_t* esrc1; int32_t* esrc2;                            // [R][K] edge codes of the phase-1 / phase-2 items
+  int G, N, K;
+};
+
+__device__ __forceinline__ int loo_clamp(const int v, const int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+// one thread per slot r = (g, k): reverse-edge index, phase-1 flag, the phase-1 items' centres
+static __global__ __launch_bounds__(256) void loo_prepare_kernel(const LooPrepArgs a) {
+  const long R = (long)a.G * a.K;
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  const int g = (int)(r / a.K), k = (int)(r - (long)g * a.K);
+  const int b0 = (g / a.N) * a.N, m_loc = g - b0;
+  const int i_loc = loo_clamp(a.E_idx[r], a.N), i = b0 + i_loc;
+  int p = -1;
+  for (int q = a.K - 1; q >= 0; --q)
+    if (a.E_idx[(long)i * a.K + q] == m_loc) p = q;
+  a.rev[r] = p;
+  a.act1[r] = (i_loc != m_loc && a.rank[i] < a.rank[g] && a.mask[g] != 0) ? 1 : 0;
+  a.ctr1[r] = g; a.msk1[r] = a.mask[g]; a.S1[r] = a.S[g];
+  if (k == 0) { a.idG[g] = g; a.ovG[g] = LOO_CEN_OV | g; }
+}
+
+// one wave per slot r: the edge codes of the phase-1 item (m, k) and of the phase-2 item (i, kq) that share the slot, the phase-2
+// flag and centre, and the edge codes of the own layers (after loo_prepare_kernel: reads rev / act1 of other slots)
+static __global__ __launch_bounds__(256) void loo_edges_kernel(const LooPrepArgs a) {
+  const long R = (long)a.G * a.K;
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;                                       // (wave-uniform)
+  const int g = (int)(r / a.K);
+  const int b0 = (g / a.N) * a.N, c_loc = g - b0;           // g = the slot's residue: m of the phase-1 item, i of the phase-2 item
+  const int n_loc = loo_clamp(a.E_idx[r], a.N), n = b0 + n_loc;   // its k-th neighbour: i of the phase-1 item, q of the phase-2 item
+  const int rk_g = a.rank[g], rk_n = a.rank[n];
+  const int pr = a.rev[r];                                  // position of g in E_idx[n]
+  const bool cen_ov = pr >= 0 && a.act1[(long)n * a.K + (pr >= 0 ? pr : 0)] != 0;   // n in A1(g): its layer-1 state is overridden in stream g
+  bool any = false;
+  for (int e = lane; e < a.K; e += 64) {
+    // phase 1, item (m = g, i = n): edge e of m; the edge to i is forward now
+    const int j_loc = loo_clamp(a.E_idx[(long)g * a.K + e], a.N), j = b0 + j_loc;
+    a.esrc1[r * a.K + e] = (j_loc == n_loc || !(a.rank[j] < rk_g)) ? (LOO_FW | j) : j;
+    // phase 2, item (i = g, q = n): edge e of q
+    const int m_loc = loo_clamp(a.E_idx[(long)n * a.K + e], a.N), mm = b0 + m_loc;
+    int code = LOO_FW | mm;
+    if (m_loc != c_loc && a.rank[mm] < rk_n) {
+      code = mm;
+      int p = -1;
+      for (int q = a.K - 1; q >= 0; --q)
+        if (a.E_idx[(long)mm * a.K + q] == c_loc) p = q;
+      if (p >= 0 && a.act1[(long)mm * a.K + p] != 0) { code = LOO_OV | (int)((long)mm * a.K + p); any = true; }
+    }
+    a.esrc2[r * a.K + e] = code;
+  }
+  const bool on2 = n_loc != c_loc && a.mask[n] != 0 && (cen_ov || __any(any));
+  if (lane == 0) {
+    a.act2[r] = on2 ? 1 : 0;
+    a.ctr2[r] = n; a.msk2[r] = a.mask[n]; a.S2[r] = a.S[n];
+    a.cen2[r] = cen_ov ? (LOO_CEN_OV | (int)((long)n * a.K + pr)) : n;
+    // residue i = g itself: every neighbour backward, the self edge forward
+    const bool self = n_loc == c_loc;
+    a.eo1[r] = self ? (LOO_FW | g) : n;
+    a.eo2[r] = self ? (LOO_FW | g) : cen_ov ? (LOO_OV | (int)((long)n * a.K + pr)) : n;
+    a.eo3[r] = self ? (LOO_FW | g) : on2 ? (LOO_OV | (int)r) : n;
+  }
+}
+
+// counts[0] / counts[1] = active phase-1 / phase-2 items (one workgroup; integer sums: the order does not matter)
+static __global__ __launch_bounds__(1024) void loo_count_kernel(const int32_t* __restrict__ act1, const int32_t* __restrict__ act2,
+                                                                 int32_t* __restrict__ counts, const long R) {
+  __shared__ int s1[16], s2[16];
+  int c1 = 0, c2 = 0;
+  for (long r = threadIdx.x; r < R; r += 1024) { c1 += act1[r]; c2 += act2[r]; }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { c1 += __shfl_xor(c1, o); c2 += __shfl_xor(c2, o); }
+  if ((threadIdx.x & 63) == 0) { s1[threadIdx.x >> 6] = c1; s2[threadIdx.x >> 6] = c2; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t1 = 0, t2 = 0;
+    for (int w = 0; w < 16; ++w) { t1 += s1[w]; t2 += s2[w]; }
+    counts[0] = t1; counts[1] = t2;
+  }
+}
+
+struct LooItemArgs {
+  const float* hE;             // [G*K][128] encoder edge rows
+  const int32_t* act;          // [R] item flags (null: every item is active)
+  const int32_t* ctr;          // [R] residue whose h_E row block the item reads
+  const int32_t* cen;          // [R] centre code: table 0 -> Pa0 / hV0, table 1 -> Pa1 / hV1
+  const int32_t* esrc;         // [R][K] edge codes: table 0 -> T0, 1 -> T1, 2 -> T2
+  const float* Pa0; const float* Pa1;     // W1a . (centre state) + b1
+  const float* hV0; const float* hV1;     // centre state (the layer's input)
+  const float* T0; const float* T1; const float* T2;   // base Pbw, Pfw, override Pbw rows of this layer
+  const float* W1_img; const float* W2_img; const float* b2;   // per-edge images in the launch's precision
+  const float* m3_img; const float* m3_b;                       // fp32 image of W3 (hoisted behind the K-sum), b3
+  NodeTail tail;               // mask / S / outputs indexed by item row; hV and m3_img are not used (see cen, m3_img above)
+  int R, K, TPN;
+};
+
+// 2 weight images | per-wave K-sums [12][128] + weight sums [16] | per-item K-sums [16][128] + weight sums [16] | active list [16] + count
+#define LOO_ITEMS_LDS (2 * NAMP_IMG_BYTES + 12 * NAMP_H * 4 + 64 + 16 * NAMP_H * 4 + 64 + 128)
+static_assert(NODE_TAIL_LDS <= 2 * NAMP_IMG_BYTES, "the residue tail re-uses the weight ring");
+
+// Workgroup = 16 consecutive item rows (one 16-row tile of the residue tail), 12 waves.  The active items of the tile run the message
+// MLP in rounds of 12 / TPN items (one 16-edge tile per wave, W1 / W2 resident in LDS across rounds); their K-sums meet in LDS and ONE
+// residue tail (node_tail, the 16-row MFMA form) finishes the tile.  Rows of inactive items are written too (a zero message: never read).
+template <int PREC>
+__global__ __launch_bounds__(768) void dec_items_kernel(const LooItemArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr bool X3 = (PREC == PREC_X3);
+  char* buf0 = smem;
+  char* buf1 = smem + NAMP_IMG_BYTES;
+  float* dpart = (float*)(smem + 2 * NAMP_IMG_BYTES);       // [12][128] per-wave tile sums of a round
+  float* dws = dpart + 12 * NAMP_H;                          // [16]
+  float* ksum = dws + 16;                                    // [16][128] per-item K-sums, by tile row
+  float* kws = ksum + 16 * NAMP_H;                           // [16]
+  int* list = (int*)(kws + 16);                              // [16] tile rows of the active items, [16] = their number
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nwaves = blockDim.x >> 6;
+  const int m = lane & 15, g = lane >> 4;
+  const int bid = xcd_block_index(blockIdx.x, gridDim.x);
+  const int row0 = bid * 16;
+
+  if (wave == 0) {
+    const int r = row0 + m;
+    const int rc = r < a.R ? r : row0;
+    const bool on = lane < 16 && r < a.R && (a.act == nullptr || a.act[rc] != 0);
+    const unsigned long long bal = __ballot(on);
+    if (on) list[__popcll(bal & ((1ull << lane) - 1ull))] = lane;
+    if (lane == 0) list[16] = __popcll(bal);
+  }
+  for (int i = tid; i < 16 * NAMP_H + 16; i += (int)blockDim.x) ksum[i] = 0.f;
+  __syncthreads();
+  const int nact = list[16];
+  if (nact == 0) return;                                     // (uniform)
+
+  const int npw = nwaves / a.TPN;                            // items per round
+  const int node_l = wave / a.TPN, kt = wave - node_l * a.TPN;
+  const f4* w0 = (const f4*)buf0 + lane;
+  const f4* w1 = (const f4*)buf1 + lane;
+  f4 x[8], acc[8], pjv[8];
+  bool first = true;
+  for (int base = 0; base < nact; base += npw) {
+    const int idx = base + node_l;
+    const bool wact = node_l < npw && idx < nact;
+    const int trow = list[wact ? idx : 0];
+    const int row = row0 + trow;
+    const int k = 16 * kt + m;
+    const bool valid = wact && k < a.K;
+    const int kc = valid ? k : 0;
+    {
+      const float* src = a.hE + ((long)a.ctr[row] * a.K + kc) * NAMP_H + 4 * g;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) x[t] = *(const f4*)(src + 16 * t);
+      const int cc = a.cen[row];
+      const float* pa = ((cc >> LOO_ROW_BITS) ? a.Pa1 : a.Pa0) + (long)(cc & LOO_ROW_MASK) * NAMP_H + 4 * g;
+      const int ec = a.esrc[(long)row * a.K + kc];
+      const int et = ec >> LOO_ROW_BITS;
+      const float* pj = (et == 0 ? a.T0 : et == 1 ? a.T1 : a.T2) + (long)(ec & LOO_ROW_MASK) * NAMP_H + 4 * g;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) { acc[t] = *(const f4*)(pa + 16 * t); pjv[t] = *(const f4*)(pj + 16 * t); }
+    }
+    const float w_row = valid ? (1.0f / 30.0f) : 0.f;
+    if (first) {
+      // weight staging behind the first round's operand loads (the vector-memory counter retires in order)
+      dma_to_lds(buf0, a.W1_img, 64, wave, nwaves, lane);
+      dma_to_lds(buf1, a.W2_img, 64, wave, nwaves, lane);
+      wait_dma_and_sync();
+      first = false;
+    }
+    // layer 1 (T): Pa + W1e . h_E + table row; layer 2 (F): lane (m, g) gets rows 4g..4g+3 of channel 16t + m
+    gemm128<X3, false, false>(acc, x, w0);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc[t] += pjv[t];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) { const float b = a.b2[16 * t + m]; x[t] = (f4){b, b, b, b}; }
+    gemm128<X3, true, true>(x, acc, w1);
+    // K-sum of the layer-2 activations over the tile's 16 edges (layer 3 follows per item)
+    float wr[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wr[r] = __shfl(w_row, 4 * g + r);
+    float wsum = w_row;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) wsum += __shfl_xor(wsum, o);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const f4 v = gelu_prec<PREC>(x[t]);
+      float s = (v.x * wr[0] + v.y * wr[1]) + (v.z * wr[2] + v.w * wr[3]);
+      s = xg_sum(s);
+      if (g == 0) dpart[wave * NAMP_H + 16 * t + m] = s;
+    }
+    if (lane == 0) dws[wave] = wsum;
+    __syncthreads();
+    // the round's items: tile sums -> the item's row (fixed order: two runs agree bit for bit)
+    for (int u = tid; u < npw * NAMP_H; u += (int)blockDim.x) {
+      const int il = u >> 7, ch = u & 127;
+      if (base + il < nact) {
+        float s = 0.f, ws = 0.f;
+        for (int q = 0; q < a.TPN; ++q) { s += dpart[(il * a.TPN + q) * NAMP_H + ch]; ws += dws[il * a.TPN + q]; }
+        const int tr = list[base + il];
+        ksum[tr * NAMP_H + ch] = s;
+        if (ch == 0) kws[tr] = ws;
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- residue tail over the tile: x = centre state + W3 . K-sum + b3 * weight sum, then node_tail (LN1, FFN, LN2, mask, projections, head)
+#pragma unroll
+  for (int t = 0; t < 8; ++t) x[t] = *(const f4*)(ksum + m * NAMP_H + 16 * t + 4 * g);
+  const float wsum_m = kws[m];
+  float* ys = (float*)smem + 16 * FFN_LD;
+  if (wave < 8) {
+    f4 o[1] = {*(const f4*)(a.m3_b + 16 * wave + 4 * g) * wsum_m};
+    chain_gemm_global<8, 1, false>(o, x, (const f4*)a.m3_img + wave * 64 + lane, 8);
+    *(f4*)(ys + m * FFN_LD + 16 * wave + 4 * g) = o[0];
+  }
+  __syncthreads();
+  {
+    const int r = row0 + m;
+    const int cc = a.cen[r < a.R ? r : row0];
+    const float* hsrc = ((cc >> LOO_ROW_BITS) ? a.hV1 : a.hV0) + (long)(cc & LOO_ROW_MASK) * NAMP_H + 4 * g;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) x[t] = *(const f4*)(hsrc + 16 * t) + *(const f4*)(ys + m * FFN_LD + 16 * t + 4 * g);
+  }
+  const int nrows = a.R - row0 < 16 ? a.R - row0 : 16;
+  node_tail<false>(a.tail, x, 0.f, row0, nrows, a.R, (float*)smem, tid, wave, nwaves, lane);
+}

@@ -1,0 +1,208 @@
+// Translation unit of the leave-one-out decoder (namp_loo.h): namp_loo_workspace_bytes / namp_decoder_loo of include/namp.h.
+// Host code only validates, carves the caller's workspace and enqueues launches on the caller's stream.  The base stream's
+// per-layer states and tables come from the library's own building blocks (namp_node_linear, namp_dec_message_update, ...).
+#include "../../include/namp.h"
+#include "namp_loo.h"
+
+#include <cstdio>
+#include <mutex>
+
+__attribute__((visibility("hidden"))) int namp_internal_fail(int code, const char* msg);
+
+namespace {
+
+int lfail(int code, const char* fmt, long a = 0, long b = 0, long c = 0) {
+  char buf[256];
+  snprintf(buf, sizeof(buf), fmt, a, b, c);
+  return namp_internal_fail(code, buf);
+}
+
+std::once_flag g_loo_once;
+hipError_t g_loo_err = hipSuccess;
+void set_loo_attrs() {
+  auto set = [](const void* f) {
+    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LOO_ITEMS_LDS);
+    if (e != hipSuccess) g_loo_err = e;
+  };
+  set((const void*)dec_items_kernel<PREC_F32>);
+  set((const void*)dec_items_kernel<PREC_X3>);
+}
+
+// the call's buffers, carved in one fixed order (base == nullptr: sizes only)
+struct LooBuffers {
+  float *Pa1, *Pbw1, *Pfw[3], *h1, *Pa2, *Pbw2, *h2, *Pa3, *Pbw3, *h1o, *Pa2o, *h2o, *Pa3o, *h3o, *partial;
+  float *h1O, *Pa2O, *Pbw2O, *h2O, *Pbw3O;
+  int32_t *rev, *act1, *act2, *ctr1, *ctr2, *cen2, *msk1, *S1, *msk2, *S2, *eo1, *eo2, *eo3, *idG, *ovG, *esrc1, *esrc2;
+  size_t bytes;
+};
+
+LooBuffers loo_carve(void* base, long G, int K) {
+  LooBuffers b;
+  size_t off = 0;
+  auto take = [&](size_t elems) {
+    void* p = base ? (void*)((char*)base + off) : nullptr;
+    off += (elems * 4 + 255) & ~size_t(255);
+    return p;
+  };
+  const size_t g128 = (size_t)G * NAMP_HIDDEN, R = (size_t)G * K, r128 = R * NAMP_HIDDEN, tpn = (K + 15) / 16;
+  float** gs[] = {&b.Pa1, &b.Pbw1, &b.Pfw[0], &b.Pfw[1], &b.Pfw[2], &b.h1, &b.Pa2, &b.Pbw2, &b.h2, &b.Pa3, &b.Pbw3,
+                  &b.h1o, &b.Pa2o, &b.h2o, &b.Pa3o, &b.h3o};
+  for (float** p : gs) *p = (float*)take(g128);
+  b.partial = (float*)take((size_t)G * tpn * (NAMP_HIDDEN + 1) + 3);
+  float** rs[] = {&b.h1O, &b.Pa2O, &b.Pbw2O, &b.h2O, &b.Pbw3O};
+  for (float** p : rs) *p = (float*)take(r128);
+  int32_t** ri[] = {&b.rev, &b.act1, &b.act2, &b.ctr1, &b.ctr2, &b.cen2, &b.msk1, &b.S1, &b.msk2, &b.S2, &b.eo1, &b.eo2, &b.eo3};
+  for (int32_t** p : ri) *p = (int32_t*)take(R);
+  b.idG = (int32_t*)take((size_t)G); b.ovG = (int32_t*)take((size_t)G);
+  b.esrc1 = (int32_t*)take(R * K); b.esrc2 = (int32_t*)take(R * K);
+  b.bytes = off;
+  return b;
+}
+
+int loo_dims(long B, long N, long K) {
+  if (B < 1 || N < 1 || K < 1 || K > NAMP_MAX_K || K > N) return lfail(NAMP_EINVAL, "namp_decoder_loo: bad dims B=%ld N=%ld K=%ld", B, N, K);
+  if (B * N * K >= (1L << LOO_ROW_BITS)) return lfail(NAMP_EINVAL, "namp_decoder_loo: B*N*K=%ld exceeds 2^28 item rows", B * N * K);
+  return NAMP_OK;
+}
+
+int launch_items(LooItemArgs a, int prec, hipStream_t s) {
+  a.TPN = (a.K + 15) / 16;
+  a.tail.m3_img = nullptr; a.tail.m3_b = nullptr; a.tail.hV = nullptr;
+  const int grid = (a.R + 15) / 16;
+  if (prec == PREC_X3) hipLaunchKernelGGL(dec_items_kernel<PREC_X3>, dim3(grid), dim3(768), LOO_ITEMS_LDS, s, a);
+  else hipLaunchKernelGGL(dec_items_kernel<PREC_F32>, dim3(grid), dim3(768), LOO_ITEMS_LDS, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+  return NAMP_OK;
+}
+
+void loo_tail(NodeTail& t, const NampDecLayerW* D, const int32_t* mask, const int32_t* S, float* hV_out) {
+  t = NodeTail{};
+  t.mask = mask; t.S = S; t.hV_out = hV_out;
+  t.ln1_g = D->ln1_g; t.ln1_b = D->ln1_b; t.Win_img = D->Win_img; t.b_in = D->b_in; t.Wout_img = D->Wout_img; t.b_out = D->b_out;
+  t.ln2_g = D->ln2_g; t.ln2_b = D->ln2_b;
+}
+
+void loo_proj(NodeTail& t, const float* img, const float* bias, const float* tok, float* out) {
+  ProjDesc& p = t.p[t.nproj++];
+  p.img = img; p.bias = bias; p.tok = tok; p.out = out;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t namp_loo_workspace_bytes(int B, int N, int K, int n_dec) {
+  if (B < 1 || N < 1 || K < 1 || K > NAMP_MAX_K || n_dec != 3) return 0;
+  return loo_carve(nullptr, (long)B * N, K).bytes;
+}
+
+int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx, const int32_t* S,
+                     const int32_t* mask, const int32_t* rank, float* log_probs, int32_t* counts, void* ws, size_t ws_bytes,
+                     int B, int N, int K, void* stream) {
+  if (!w || !h_V_enc || !h_E || !E_idx || !S || !mask || !rank || !log_probs || !counts || !ws)
+    return lfail(NAMP_EINVAL, "namp_decoder_loo: null pointer argument");
+  if ((((uintptr_t)h_V_enc | (uintptr_t)h_E | (uintptr_t)ws | (uintptr_t)log_probs) & 15u) != 0)
+    return lfail(NAMP_EINVAL, "namp_decoder_loo: h_V_enc / h_E / log_probs / ws must be 16-byte aligned");
+  if (w->n_dec != 3) return lfail(NAMP_EINVAL, "namp_decoder_loo: the cone kernels walk three decoder layers (n_dec=%ld): use the L-stream form", w->n_dec);
+  if (w->vocab < 1 || w->vocab > 64) return lfail(NAMP_EINVAL, "namp_decoder_loo: vocab=%ld out of range", w->vocab);
+  int rc = loo_dims(B, N, K);
+  if (rc) return rc;
+  int prec = PREC_F32;
+  for (int l = 0; l < 3; ++l) {
+    const NampDecLayerW* D = &w->dec[l];
+    if (D->flags & NAMP_FLAG_BF16) return lfail(NAMP_EINVAL, "namp_decoder_loo: split-bf16 and exact fp32 evaluation only (layer %ld is bf16)", l);
+    const int p = (D->flags & NAMP_FLAG_X3) ? PREC_X3 : PREC_F32;
+    if (l && p != prec) return lfail(NAMP_EINVAL, "namp_decoder_loo: the decoder layers must share one precision");
+    prec = p;
+    const void* need[] = {D->W1a_img, D->W1e_img, D->W1v_img, D->b1, D->tok, D->W2_img, D->b2, D->W3_img, D->b3, D->Win_img, D->b_in,
+                          D->Wout_img, D->b_out, D->ln1_g, D->ln1_b, D->ln2_g, D->ln2_b, p == PREC_X3 ? D->W1e_ximg : D->W1e_img,
+                          p == PREC_X3 ? D->W2_ximg : D->W2_img};
+    for (const void* q : need)
+      if (!q || ((uintptr_t)q & 15u)) return lfail(NAMP_EINVAL, "namp_decoder_loo: decoder layer %ld lacks a weight image (or it is misaligned)", l);
+  }
+  if (!w->Wout_w || !w->Wout_b) return lfail(NAMP_EINVAL, "namp_decoder_loo: null output head");
+  const long G = (long)B * N, R = G * K;
+  LooBuffers b = loo_carve(ws, G, K);
+  if (b.bytes > ws_bytes) return lfail(NAMP_EWORKSPACE, "namp_decoder_loo: workspace too small (%ld bytes, %ld needed)", (long)ws_bytes, (long)b.bytes);
+  std::call_once(g_loo_once, set_loo_attrs);
+  if (g_loo_err != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(g_loo_err));
+  hipStream_t s = (hipStream_t)stream;
+  const NampDecLayerW *D0 = &w->dec[0], *D1 = &w->dec[1], *D2 = &w->dec[2];
+
+  // ---- index tables (they depend on the graph, the order and the mask only)
+  LooPrepArgs pa = {};
+  pa.E_idx = E_idx; pa.rank = rank; pa.mask = mask; pa.S = S;
+  pa.rev = b.rev; pa.act1 = b.act1; pa.act2 = b.act2; pa.ctr1 = b.ctr1; pa.ctr2 = b.ctr2; pa.cen2 = b.cen2;
+  pa.msk1 = b.msk1; pa.S1 = b.S1; pa.msk2 = b.msk2; pa.S2 = b.S2; pa.eo1 = b.eo1; pa.eo2 = b.eo2; pa.eo3 = b.eo3;
+  pa.idG = b.idG; pa.ovG = b.ovG; pa.esrc1 = b.esrc1; pa.esrc2 = b.esrc2;
+  pa.G = (int)G; pa.N = N; pa.K = K;
+  hipLaunchKernelGGL(loo_prepare_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
+  hipLaunchKernelGGL(loo_edges_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
+  hipLaunchKernelGGL(loo_count_kernel, dim3(1), dim3(1024), 0, s, b.act1, b.act2, counts, R);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+
+  // ---- base stream (the order of score()): tables of every layer, states and tables behind layers 1 and 2
+  NampProj pf[5] = {{D0->W1v_img, nullptr, nullptr, b.Pfw[0]}, {D1->W1v_img, nullptr, nullptr, b.Pfw[1]}, {D2->W1v_img, nullptr, nullptr, b.Pfw[2]},
+                    {D0->W1a_img, D0->b1, nullptr, b.Pa1}, {D0->W1v_img, nullptr, D0->tok, b.Pbw1}};
+  if ((rc = namp_node_linear(h_V_enc, S, B, B, N, pf, 5, nullptr, stream))) return rc;
+  const bool fused = G <= namp_fused_tail_max_residues();
+  for (int l = 0; l < 2; ++l) {
+    const NampDecLayerW *D = &w->dec[l], *Dn = &w->dec[l + 1];
+    const float* hin = l ? b.h1 : h_V_enc;
+    float* out = l ? b.h2 : b.h1;
+    const float *Pa = l ? b.Pa2 : b.Pa1, *Pbw = l ? b.Pbw2 : b.Pbw1;
+    NampProj pn[2] = {{Dn->W1a_img, Dn->b1, nullptr, l ? b.Pa3 : b.Pa2}, {Dn->W1v_img, nullptr, Dn->tok, l ? b.Pbw3 : b.Pbw2}};
+    if (fused) {
+      if ((rc = namp_dec_message_update(D, h_E, E_idx, rank, Pa, Pbw, b.Pfw[l], hin, mask, out, pn, 2, S, nullptr, nullptr, nullptr, nullptr,
+                                        w->vocab, B, B, N, K, stream)))
+        return rc;
+    } else {
+      if ((rc = namp_dec_message(D, h_E, E_idx, rank, Pa, Pbw, b.Pfw[l], b.partial, B, B, N, K, stream))) return rc;
+      if ((rc = namp_node_update(D->ln1_g, D->ln1_b, D->Win_img, D->b_in, D->Wout_img, D->b_out, D->ln2_g, D->ln2_b, hin, b.partial,
+                                 D->W3_img, D->b3, mask, out, pn, 2, S, (int)G, K, stream)))
+        return rc;
+    }
+  }
+
+  // ---- the cone
+  auto items = [&](const NampDecLayerW* D, long rows, const int32_t* act, const int32_t* ctr, const int32_t* cen, const int32_t* esrc,
+                   const float* Pa0, const float* Pa1, const float* hV0, const float* hV1, const float* T0, const float* T1,
+                   const float* T2) {
+    LooItemArgs a = {};
+    a.hE = h_E; a.act = act; a.ctr = ctr; a.cen = cen; a.esrc = esrc; a.Pa0 = Pa0; a.Pa1 = Pa1; a.hV0 = hV0; a.hV1 = hV1;
+    a.T0 = T0; a.T1 = T1; a.T2 = T2;
+    a.W1_img = prec == PREC_X3 ? D->W1e_ximg : D->W1e_img; a.W2_img = prec == PREC_X3 ? D->W2_ximg : D->W2_img; a.b2 = D->b2;
+    a.m3_img = D->W3_img; a.m3_b = D->b3;
+    a.R = (int)rows; a.K = K;
+    return a;
+  };
+  // phase 1: layer 1 at the residues that lose i from their decoded neighbours (tables of layer 2 for phase 2 and the own layer 2)
+  LooItemArgs a = items(D0, R, b.act1, b.ctr1, b.ctr1, b.esrc1, b.Pa1, b.Pa1, h_V_enc, h_V_enc, b.Pbw1, b.Pfw[0], b.Pbw1);
+  loo_tail(a.tail, D0, b.msk1, b.S1, b.h1O);
+  loo_proj(a.tail, D1->W1a_img, D1->b1, nullptr, b.Pa2O);
+  loo_proj(a.tail, D1->W1v_img, nullptr, D1->tok, b.Pbw2O);
+  if ((rc = launch_items(a, prec, s))) return rc;
+  // own layer 1 (the encoder states are every stream's layer-1 input: no override)
+  a = items(D0, G, nullptr, b.idG, b.idG, b.eo1, b.Pa1, b.Pa1, h_V_enc, h_V_enc, b.Pbw1, b.Pfw[0], b.Pbw1);
+  loo_tail(a.tail, D0, mask, S, b.h1o);
+  loo_proj(a.tail, D1->W1a_img, D1->b1, nullptr, b.Pa2o);
+  if ((rc = launch_items(a, prec, s))) return rc;
+  // phase 2: layer 2 at i's neighbours that a phase-1 output reaches (table of layer 3 for the own layer 3)
+  a = items(D1, R, b.act2, b.ctr2, b.cen2, b.esrc2, b.Pa2, b.Pa2O, b.h1, b.h1O, b.Pbw2, b.Pfw[1], b.Pbw2O);
+  loo_tail(a.tail, D1, b.msk2, b.S2, b.h2O);
+  loo_proj(a.tail, D2->W1v_img, nullptr, D2->tok, b.Pbw3O);
+  if ((rc = launch_items(a, prec, s))) return rc;
+  // own layers 2 and 3, the output head behind the last
+  a = items(D1, G, nullptr, b.idG, b.ovG, b.eo2, b.Pa2, b.Pa2o, b.h1, b.h1o, b.Pbw2, b.Pfw[1], b.Pbw2O);
+  loo_tail(a.tail, D1, mask, S, b.h2o);
+  loo_proj(a.tail, D2->W1a_img, D2->b1, nullptr, b.Pa3o);
+  if ((rc = launch_items(a, prec, s))) return rc;
+  a = items(D2, G, nullptr, b.idG, b.ovG, b.eo3, b.Pa3, b.Pa3o, b.h2, b.h2o, b.Pbw3, b.Pfw[2], b.Pbw3O);
+  loo_tail(a.tail, D2, mask, S, b.h3o);
+  a.tail.head_w = w->Wout_w; a.tail.head_b = w->Wout_b; a.tail.log_probs = log_probs; a.tail.logits = nullptr; a.tail.vocab = w->vocab;
+  return launch_items(a, prec, s);
+}
+
+}  // extern "C"

@@ -179,6 +179,19 @@ def pair_bias_dependencies(pair_bias, max_deps=64):
     return torch.where(cols < L, cols, torch.full((), -1, device=dev)).to(torch.int32).contiguous(), n_dep
 
 
+def leave_one_out_ranks(rank, start=0, stop=None):
+    """Decoding ranks of the leave-one-out streams of conditional_probs(): stream i is the order of `rank` [B, L] (the inverse of a
+    decoding order) with residue i taken out and appended at the end — rank_i[j] = rank[j] - (rank[j] > rank[i]) for j != i,
+    rank_i[i] = L - 1.  Returns [B, stop - start, L] (streams start .. stop-1; all L by default) in rank's dtype; works on CPU tensors."""
+    B, L = rank.shape
+    stop = L if stop is None else stop
+    i = torch.arange(start, stop, device=rank.device)
+    ri = rank[:, start:stop, None]
+    out = rank[:, None, :] - (rank[:, None, :] > ri).to(rank.dtype)
+    out[:, i - start, i] = L - 1
+    return out
+
+
 class _DecodingOrder:
     """The decoding order of ONE score / forward / sample call: order int64, order32 / rank int32 [B', L].  With the HIP sort
     (namp_decoding_order) the three tensors are allocated but not yet written while `pending`: the call's featuriser launch takes the
@@ -589,6 +602,62 @@ class ProteinMPNN(nn.Module):
         m = rep(mask)
         zeros = torch.zeros_like(m, dtype=torch.int32)
         return {"log_probs": self.decode_graph(h_V, h_E, E_idx, zeros, m, zeros)}
+
+    # streams of the L-stream form of conditional_probs() per decoder call: chunk * L stays within the 64 x 1000 tokens of the B = 64 batches
+    loo_dense_tokens = 65536
+
+    @torch.no_grad()
+    def conditional_probs(self, feature_dict, method="auto"):
+        """Leave-one-out conditionals of every residue in one call: out["log_probs"][b, i, :] = log p(s_i | X, S_-i), row i of score()'s
+        parallel decoder (model_utils.py:391-421) run with score()'s decoding order (:388-389) in which residue i is moved to the end,
+        the true S teacher-forced everywhere (leave_one_out_ranks).  Returns {"S", "log_probs" [B, L, vocab], "decoding_order"};
+        `batch_size` is ignored (nothing is random once `randn` is given).  Rows of masked residues are what the reference computes
+        for them (a zero context).
+        method: "dense" — L streams through the ordinary decoder (namp_decoder_fwd), chunked over streams; "cone" — only the dependency
+        cone of every stream (namp_decoder_loo: about K + 3 layer evaluations per residue instead of 3 L), for three decoder layers in
+        the split-bf16 ("x3") and exact fp32 evaluations; it also returns "cone_items", the int32 [2] device tensor of active layer-1 /
+        layer-2 items; "auto" — the cone where it is implemented, the dense form otherwise (another number of decoder layers, the
+        bf16 throughput mode)."""
+        if method not in ("auto", "dense", "cone"):
+            raise ValueError(f"method must be 'auto', 'dense' or 'cone'; got {method!r}")
+        S_true, mask = feature_dict["S"], feature_dict["mask"]
+        B, L = S_true.shape
+        cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        if method == "cone" and not cone_ok:
+            raise NotImplementedError("conditional_probs(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
+                                      "use method='dense'")
+        o = self._decoding_order(mask, feature_dict["chain_mask"], feature_dict["randn"])
+        h_V, h_E, E_idx = self.encode(feature_dict, order=o)
+        self._check_tokens(S_true)
+        o.wait()
+        rank = o.rank[:B]
+        out = {"S": S_true, "decoding_order": o.order[0]}
+        if method == "cone" or (method == "auto" and cone_ok):
+            W = self._weights()
+            Lb = hip.lib()
+            K = E_idx.shape[-1]
+            dev = h_V.device
+            E32, S32, m32, r32 = _i32(E_idx), self._as(S_true, "i32"), self._as(mask, "i32"), _i32(rank)
+            ws = torch.empty(Lb.namp_loo_workspace_bytes(B, L, K, len(self.decoder_layers)), dtype=torch.uint8, device=dev)
+            counts = torch.empty(2, dtype=torch.int32, device=dev)
+            log_probs = torch.empty(B, L, self.num_letters, device=dev)
+            hip.check(Lb.namp_decoder_loo(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
+                                          r32.data_ptr(), log_probs.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), B, L, K,
+                                          hip.current_stream()), "decoder_loo")
+            out.update(log_probs=log_probs, cone_items=counts)
+            return out
+        log_probs = torch.empty(B, L, self.num_letters, device=h_V.device)
+        chunk = max(1, self.loo_dense_tokens // L)
+        for b in range(B):
+            for i0 in range(0, L, chunk):
+                i1 = min(L, i0 + chunk)
+                n = i1 - i0
+                ranks = leave_one_out_ranks(rank[b:b + 1], i0, i1)[0]
+                lp = self.decode_graph(h_V[b:b + 1], h_E[b:b + 1], E_idx[b:b + 1], S_true[b:b + 1].expand(n, L), mask[b:b + 1].expand(n, L), ranks)
+                ar = torch.arange(n, device=lp.device)
+                log_probs[b, i0:i1] = lp[ar, i0 + ar]
+        out["log_probs"] = log_probs
+        return out
 
     def forward(self, feature_dict, decoding_randn=None):
         """Training-copy surface (na_model_utils.py:589-646): feature_dict -> (log_probs, probs).

@@ -678,6 +678,26 @@ int namp_decoder_sample_walk(const NampModelW* w, const float* h_V_enc, const fl
                              float temperature, uint64_t special_tokens, int32_t* S_out, float* probs_out, float* logp_out,
                              void* ws, size_t ws_bytes, int B_dec, int B_enc, int N, int K, void* stream);
 
+/* ---- tied states: the plan of one sequence sampled over M backbone states of the same molecule -------------------
+ * M states of N residues, encoded as a batch, are ONE symmetric design on the block-diagonal flattened graph of M * N residues:
+ * residue n of state m is flat residue m * N + n, its neighbours are E_idx[m][n][:] + m * N, and the M copies of a residue form a
+ * symmetry group with the state weights.  No member of a group is a graph neighbour of another, so every visit is a work item of its
+ * own and every group draws deferred (namp_decoder_sample_walk's close lists).  This call writes, in ONE launch and without reading
+ * anything back, every array namp_decoder_sample_walk(B_enc = 1, N = M * N) takes for that problem:
+ *   E_idx [M][N][K], order0 / rank0 [N] (the one decoding order of every stream and its inverse), weights [M] float
+ *   E_flat [M * N][K]; order / rank / group_first / group_last [B_dec][M * N] (visit t * M + m = residue order0[t] of state m);
+ *   sym_w [M * N]; work_n [B_dec * M * N] (all 1); level [N] by step: 1 + the highest level among the earlier-decoded neighbours of
+ *   all M members; work [B_dec * M * N][2] and close [B_dec * N][2] sorted by level (stream-major inside a level, then by step);
+ *   level_off / close_off [M * N + 2]; n_levels[0] = number of levels.
+ * One workgroup walks the N steps (the M * K look-ups of a step over the lanes of one wave, levels in LDS, the neighbours of a step
+ * requested two steps ahead) and counting-sorts the lists; the other workgroups write the flattened arrays.  Plain stores only:
+ * two calls give identical arrays.
+ * N <= 8192, M * N <= 16000, K <= NAMP_MAX_K. */
+int namp_states_plan(const int32_t* E_idx, const int32_t* order0, const int32_t* rank0, const float* weights,
+                     int32_t* E_flat, int32_t* order, int32_t* rank, int32_t* group_first, int32_t* group_last, float* sym_w,
+                     int32_t* work_n, int32_t* level, int32_t* work, int32_t* level_off, int32_t* n_levels,
+                     int32_t* close, int32_t* close_off, int B_dec, int M, int N, int K, void* stream);
+
 /* ---- leave-one-out conditional log-probs ---------------------------------------------------------
  * log p(s_i | X, S_-i) for EVERY residue i in one call, after encode(): row i of the parallel decoder (model_utils.py:391-421)
  * run with the decoding order of score() (model_utils.py:388-389) in which residue i is taken out and appended at the end,

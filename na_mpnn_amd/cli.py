@@ -50,6 +50,9 @@ def build_parser():
     a("--pair_bias_AA", type=str, default="", help="pair bias for sequence neighbours, e.g. 'KK:-10.0,KE:-10.0'")
     a("--symmetry_residues", type=str, default="", help="tied residues, e.g. 'A12,A13,A14|C2,C3'")
     a("--symmetry_weights", type=str, default="", help="weights matching --symmetry_residues, e.g. '1.0,1.0,1.0|-1.0,2.0'")
+    a("--multi_state", type=int, default=0, help="1 - the MODELs of --pdb_path are states of one molecule: ONE sequence is designed "
+      "to fit all of them (ProteinMPNN.sample with state_weights)")
+    a("--state_weights", type=str, default="", help="weights of the states in model order, e.g. '0.5,0.3,0.2' (default: 1/M each)")
     a("--na_shared_tokens", type=int, default=1)
     a("--parse_na_only", type=int, default=0)
     a("--design_na_only", type=int, default=0)
@@ -187,9 +190,20 @@ def main(argv=None):
 
 def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bias_AA, omit_AA, int_to_str, dna_to_rna, rti, base,
             pair_bias_AA=None):
-    P = pdbio.parse_pdb(pdb, chains=list(args.parse_these_chains_only) or None, parse_na_only=bool(args.parse_na_only),
-                        na_shared_tokens=bool(args.na_shared_tokens),
-                        load_residues_with_missing_atoms=bool(args.load_residues_with_missing_atoms))
+    parse = pdbio.parse_states if args.multi_state else pdbio.parse_pdb
+    P = parse(pdb, chains=list(args.parse_these_chains_only) or None, parse_na_only=bool(args.parse_na_only),
+              na_shared_tokens=bool(args.na_shared_tokens),
+              load_residues_with_missing_atoms=bool(args.load_residues_with_missing_atoms))
+    state_w = None
+    if args.multi_state:
+        if args.conditional_probs_only:
+            raise ValueError("--conditional_probs_only scores one structure: it does not go with --multi_state")
+        X_states, X_m_states = P["X"], P["X_m"]
+        P = dict(P, X=X_states[0], X_m=X_m_states[0])       # everything per residue (and the backbones written) comes from state 1
+        M = X_states.shape[0]
+        state_w = [float(v) for v in args.state_weights.split(",")] if args.state_weights else [1.0 / M] * M
+        if len(state_w) != M:
+            raise ValueError(f"--state_weights lists {len(state_w)} weights for the {M} models of {pdb}")
     L = len(P["S"])
     encoded = [f"{c}{r}{ic}" for c, r, ic in zip(P["chain_letters"], P["R_idx"].tolist(), P["icodes"])]
     encoded_dict = dict(zip(encoded, range(L)))
@@ -216,6 +230,12 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
         fd.update({"batch_size": args.batch_size, "temperature": args.temperature,
                    "bias": (-1e8 * omit_AA[None, None, :] + bias_AA).repeat(1, L, 1),
                    "symmetry_residues": sym_res, "symmetry_weights": sym_w})
+        if state_w is not None:
+            fd["X"] = torch.as_tensor(X_states, dtype=torch.float32, device=device)
+            fd["X_m"] = torch.as_tensor(X_m_states, dtype=torch.int32, device=device)
+            fd["state_weights"] = state_w
+            wn = torch.tensor(state_w, device=device)
+            wn = wn / wn.sum() if float(wn.sum()) != 0 else torch.full_like(wn, 1.0 / len(state_w))
         if pair_bias_AA is not None:
             fd["pair_bias"] = make_pair_bias(fd["chain_labels"][0], fd["R_idx"][0], pair_bias_AA)
         if args.conditional_probs_only:
@@ -239,7 +259,10 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
                 fd["S_forced"] = torch.from_numpy(forced["S_forced"][rows]).to(device)
             out = model.sample(fd)
             onehot = torch.nn.functional.one_hot(out["S"], 33)
-            lpr = -(onehot * out["log_probs"]).sum(-1)                                   # get_score, data_utils.py:36-52
+            if state_w is None:
+                lpr = -(onehot * out["log_probs"]).sum(-1)                               # get_score, data_utils.py:36-52
+            else:                                       # log_probs [bs, M, L, V]: the weight-averaged per-state log-prob of the drawn tokens
+                lpr = (-(onehot[:, None] * out["log_probs"]).sum(-1) * wn[None, :, None]).sum(1)
             lpr_l.append(lpr)
             loss_l.append((lpr * cmask).sum(-1) / (cmask.sum(-1) + 1e-8))
             S_l.append(out["S"]); lp_l.append(out["log_probs"]); sp_l.append(out["sampling_probs"])

@@ -704,6 +704,8 @@ class ProteinMPNN(nn.Module):
 
     def _sample(self, fd, walk, uniform=None):
         """sample() with the persistent level walk on or off (`walk`) and the uniforms of the draws given (None: torch.rand)."""
+        if fd.get("state_weights") is not None:
+            return self._sample_states(fd, walk, uniform)
         bs = fd["batch_size"]
         S_true, mask, bias = fd["S"], fd["mask"], fd["bias"]
         sym = fd.get("symmetry_residues", [[]])
@@ -850,6 +852,162 @@ class ProteinMPNN(nn.Module):
             warnings.warn(f"persistent level walk timed out (code {code:#x}); re-running with per-level launches")
             return self._sample(fd, walk=False, uniform=uniform)
         return out
+
+    # ---------------------------------------------------------------------------------------
+    # tied states: one sequence over M backbone states of the same molecule
+    # ---------------------------------------------------------------------------------------
+    # build the plan of the flattened problem in one HIP launch (namp_states_plan); False: the host route through symmetry_visits,
+    # namp_sample_levels_dep and level_work_lists (same results; also what `symmetry_residues` with states and walk=False take)
+    sample_states_device_plan = True
+    _STATE_SHARED = ("S", "mask", "chain_mask", "R_idx", "chain_labels", "protein_mask", "dna_mask", "rna_mask", "R_polymer_type")
+
+    def _states_arguments(self, fd):
+        """The checks of the tied-states path (they need no device) -> (state weights as floats, M, L, batch_size, symmetric)."""
+        w = fd["state_weights"]
+        w = [float(v) for v in (w.detach().reshape(-1).tolist() if torch.is_tensor(w) else list(w))]
+        M, bs = len(w), int(fd["batch_size"])
+        X, X_m = fd["X"], fd["X_m"]
+        if M < 1 or X.dim() != 4 or X.shape[0] != M or X.shape[-1] != 3:
+            raise ValueError(f"state_weights has {M} entries: X must be [{M}, L, atoms, 3]; got {tuple(X.shape)}")
+        L = X.shape[1]
+        if tuple(X_m.shape) != tuple(X.shape[:3]):
+            raise ValueError(f"X_m must be {tuple(X.shape[:3])} with states; got {tuple(X_m.shape)}")
+        for k in self._STATE_SHARED:
+            if tuple(fd[k].shape) != (1, L):
+                raise ValueError(f"'{k}' is shared by the states and must be [1, {L}]; got {tuple(fd[k].shape)}")
+        bias = fd["bias"]
+        if bias.dim() != 3 or bias.shape[0] != 1 or bias.shape[1] not in (1, L) or bias.shape[2] != self.num_letters:
+            raise ValueError(f"bias must be [1, {L}, {self.num_letters}] with states; got {tuple(bias.shape)}")
+        if tuple(fd["randn"].shape) != (bs, L):
+            raise ValueError(f"randn must be [batch_size, L] = [{bs}, {L}] with states (row 0 orders every sample); got {tuple(fd['randn'].shape)}")
+        if fd.get("S_forced") is not None and tuple(fd["S_forced"].shape) != (bs, L):
+            raise ValueError(f"S_forced must be [{bs}, {L}] with states; got {tuple(fd['S_forced'].shape)}")
+        if "pair_bias" in fd:
+            raise NotImplementedError("pair_bias is not supported together with state_weights")
+        if M * L > 16000:
+            raise ValueError(f"states x residues = {M * L} exceeds the level lists' limit of 16000")
+        sym = fd.get("symmetry_residues", [[]])
+        return w, M, L, bs, not (len(sym) == 1 and len(sym[0]) == 0)
+
+    def _sample_states(self, fd, walk, uniform=None):
+        """sample() of ONE sequence tied across M backbone states (feature_dict["state_weights"], X [M, L, A, 3]): at every step of the one
+        decoding order each state runs what a plain sample() stream on that state would run given the tokens drawn so far, one token is
+        drawn from softmax((sum_m w_m logits_m + bias_i) / T) and written to all states.  The states are encoded as a batch and decoded as
+        a symmetric design on the block-diagonal flattened graph of M * L residues (flat residue m * L + i, neighbours E_idx[m] + m * L,
+        groups {i, L + i, ...} with the state weights): the decoder sees the graph through E_idx only.  Returns S [bs, L], sampling_probs
+        [bs, L, V], log_probs [bs, M, L, V], decoding_order [bs, L], uniform [bs, L] (by step), levels, work_items."""
+        w, M, L, bs, symmetric = self._states_arguments(fd)
+        S_true, mask = fd["S"], fd["mask"]
+        dev, N, Vn = S_true.device, M * L, self.num_letters
+        _require_device(fd["X"], "X")
+        self._check_tokens(S_true)
+        if fd.get("S_forced") is not None:
+            self._check_tokens(fd["S_forced"], "S_forced")
+        o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1])           # row 0: the one order of every sample (model_utils.py:220)
+        fd_enc = dict(fd)
+        for k in self._STATE_SHARED:
+            fd_enc[k] = fd[k].expand(M, L)
+        V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
+        K = E_idx.shape[-1]
+        Lb = hip.lib()
+        i32e = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        walk = bool(walk and self.sample_level_parallel and Lb.namp_decoder_sample_walk_grid(bs, N, K) > 0)
+        close = close_off = zbuf = None
+        device_plan = (self.sample_states_device_plan and walk and self.sample_split_groups and not symmetric and o.order32 is not None
+                       and L <= 8192)
+        if device_plan:
+            # one launch writes the flattened neighbour lists, the visit plan of every stream, the levels and the level-sorted lists.  It
+            # needs the neighbour lists and the decoding order only: enqueued on the side stream behind the featuriser launch, beside
+            # the encoder launches (its walk over the L steps is serial), as the plain branch does with its levels
+            o.wait()                                                                   # (the sort, if the featuriser launch did not take it)
+            sizes = (N * K, N, bs * N, L, bs * N, bs * N, bs * N, bs * N, 2 * bs * N, N + 2, 1, 2 * bs * L, N + 2)
+            offs = np.concatenate(([0], np.cumsum([(n + 3) & ~3 for n in sizes]))).tolist()      # (16-byte aligned pieces of ONE allocation)
+            buf = i32e(offs[-1])
+            (E_f, sym_w, work_n, level, order_f, rank_f, group_first, group_last, work, level_off, n_levels, close,
+             close_off) = (buf[o_:o_ + n] for o_, n in zip(offs, sizes))
+            sym_w = sym_w.view(torch.float32)
+            wt = torch.tensor(w, dtype=torch.float32).to(dev)
+            main_, side_ = torch.cuda.current_stream(dev), self._side_stream(dev)
+            ev_ = torch.cuda.Event(); ev_.record(main_)                                # the neighbour lists and the order are out
+        h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
+        if device_plan:                                                                # (enqueued behind the encoder's launches: they are running by now)
+            side_.wait_event(ev_)
+            hip.check(Lb.namp_states_plan(E_idx.data_ptr(), o.order32.data_ptr(), o.rank.data_ptr(), wt.data_ptr(), E_f.data_ptr(),
+                                          order_f.data_ptr(), rank_f.data_ptr(), group_first.data_ptr(), group_last.data_ptr(),
+                                          sym_w.data_ptr(), work_n.data_ptr(), level.data_ptr(), work.data_ptr(), level_off.data_ptr(),
+                                          n_levels.data_ptr(), close.data_ptr(), close_off.data_ptr(), bs, M, L, K, side_.cuda_stream),
+                      "states_plan")
+            o.event = torch.cuda.Event(); o.event.record(side_)                        # o.wait() orders the decoder behind the plan
+            for t_ in (E_idx, o.order32, o.rank, wt, buf):                             # (not recycled before the side stream is done)
+                t_.record_stream(side_)
+        o.wait()
+        if device_plan:
+            nwork, levels, step_of = bs * N, n_levels[0], None
+        else:
+            groups = [[int(i) + m * L for m in range(M) for i in g] for g in fd["symmetry_residues"]] if symmetric else []
+            weights = [[w[m] * float(ws) for m in range(M) for ws in gw] for gw in fd["symmetry_weights"]] if symmetric else []
+            tied = {int(i) for g in (fd["symmetry_residues"] if symmetric else []) for i in g}
+            for i in range(L):
+                if i not in tied:
+                    groups.append([i + m * L for m in range(M)]); weights.append(list(w))
+            visits, gf, gl, wl = symmetry_visits(groups, weights, o.order[0].tolist(), N)
+            order_f = torch.tensor(visits, dtype=torch.int32, device=dev).repeat(bs, 1)
+            group_first = torch.tensor(gf, dtype=torch.int32, device=dev).repeat(bs, 1).contiguous()
+            group_last = torch.tensor(gl, dtype=torch.int32, device=dev).repeat(bs, 1).contiguous()
+            sym_w = torch.tensor(wl, dtype=torch.float32).to(dev)
+            rank_f = _i32(self.ranks_of(order_f.long()))
+            step_of = torch.tensor(np.cumsum([int(v == f) for v, f in enumerate(gf)]) - 1, device=dev)     # visit -> its group's step
+            E_f = _i32(E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).view(N, K)
+            level = i32e(bs, N)
+            hip.check(Lb.namp_sample_levels_dep(E_f.data_ptr(), order_f.data_ptr(), rank_f.data_ptr(), None, 0, group_first.data_ptr(),
+                                                group_last.data_ptr(), level.data_ptr(), bs, 1, N, K, hip.current_stream()), "sample_levels")
+            sel, flat, work_n, close, close_off = level_work_lists(level, group_first, group_last, order_f[0], E_f.long(),
+                                                                   split=bool(walk and self.sample_split_groups))
+            nwork = int(sel.numel())
+            work = torch.stack((sel // N, sel % N), 1).to(torch.int32).contiguous()
+            hist = torch.zeros(N + 1, dtype=torch.int64, device=dev).scatter_add_(0, flat, torch.ones_like(flat))
+            level_off = torch.cat((hist.new_zeros(1), hist.cumsum(0))).to(torch.int32).contiguous()
+            levels = (hist > 0).sum()
+        if uniform is None:
+            uniform = torch.rand(bs, L, device=dev)
+        # the walk reads a group's uniform at its LAST visit; `uniform` is by step (group)
+        u_f = (uniform.repeat_interleave(M, dim=1) if step_of is None else uniform[:, step_of]).contiguous()
+        special = 0
+        for name in ("UNK", "DX", "RX", "MAS", "PAD"):                        # model_utils.py:199-203
+            special |= 1 << int(self.restype_to_int[name])
+        W = self._weights()
+        flat_i32 = lambda t: _i32(t.repeat(1, M))
+        m_f, cm_f, S_f = flat_i32(mask), flat_i32(mask * fd["chain_mask"]), flat_i32(S_true)
+        md_f = m_f if bs == 1 else m_f.repeat(bs, 1)
+        bias_f = fd["bias"].float().expand(1, L, Vn).repeat(1, M, 1).contiguous()
+        forced = flat_i32(fd["S_forced"]) if fd.get("S_forced") is not None else None
+        S_out, probs = i32e(bs, N), torch.empty(bs, N, Vn, device=dev)
+        logp = torch.empty_like(probs)
+        if close is not None:
+            zbuf = torch.empty(bs, N, Vn, device=dev)
+        ws_bytes = Lb.namp_sample_workspace_bytes_n(1, bs, N, K, len(self.decoder_layers))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+        common = (W.model(), h_V.data_ptr(), h_E.data_ptr(), E_f.data_ptr(), m_f.data_ptr(), md_f.data_ptr(), cm_f.data_ptr(),
+                  S_f.data_ptr(), bias_f.data_ptr(), order_f.data_ptr(), rank_f.data_ptr(), u_f.data_ptr(), hip.ptr(forced),
+                  group_first.data_ptr(), group_last.data_ptr(), sym_w.data_ptr(), None)
+        tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
+                bs, 1, N, K, hip.current_stream())
+        if not walk:
+            counts = torch.bincount(flat).cpu().tolist()                       # per-level launches: one host sync
+            hip.check(Lb.namp_decoder_sample_levels(*common, work.data_ptr(), work_n.data_ptr(), (C.c_int32 * len(counts))(*counts),
+                                                    len(counts), *tail), "decoder_sample_levels")
+            levels = len(counts)
+        else:
+            hip.check(Lb.namp_decoder_sample_walk(*common, work.data_ptr(), work_n.data_ptr(), nwork, level_off.data_ptr(), hip.ptr(close),
+                                                  hip.ptr(close_off), hip.ptr(zbuf), *tail), "decoder_sample_walk")
+            self._walk_sync = ws[ws_bytes - 4096:][:256].view(torch.int32).clone()
+            code = self.sample_walk_status() if self.sample_check_walk else 0
+            if code != 0:
+                warnings.warn(f"persistent level walk timed out (code {code:#x}); re-running with per-level launches")
+                return self._sample_states(fd, walk=False, uniform=uniform)
+        return {"S": S_out[:, :L].long(), "sampling_probs": probs[:, :L], "log_probs": logp.view(bs, M, L, Vn),
+                "decoding_order": o.order[0].expand(bs, L), "uniform": uniform, "levels": levels, "work_items": nwork}
 
     def sample_walk_status(self):
         """Barrier state of the last persistent level walk (synchronises): 0 = every grid barrier completed; otherwise the code of the barrier

@@ -3,7 +3,8 @@
 Restates the semantics of the reference's prody-based ``parse_PDB`` + ``featurize``
 (/root/reference/inference/data_utils.py:84-439) without prody (absent from this image):
 
-* atoms with occupancy > 0, altloc blank or 'A', first MODEL only;
+* atoms with occupancy > 0, altloc blank or 'A', first MODEL only (another one through ``model=``; ``parse_states`` stacks the
+  MODELs of an ensemble — the states of a multi-state design — after checking that they list the same residues);
 * residues are keyed chain / resnum / insertion-code and ordered by the first appearance of their
   reference atom (CA for amino acids, C1' for nucleotides; data_utils.py:258-276);
 * the 16 backbone atoms in the order N, CA, C, O, OP1, OP2, P, O5', C5', C4', O4', C3', O3', C2', O2', C1';
@@ -47,14 +48,22 @@ class Atom:
         self.resnum, self.icode, self.xyz, self.occ, self.bfac, self.element = resnum, icode, xyz, occ, bfac, element
 
 
-def _pdb_atoms(path):
-    """ATOM / HETATM records of the first MODEL of a PDB file (prody parsePDB: model 1, HETATM included)."""
+def _pdb_atoms(path, model=None):
+    """ATOM / HETATM records of the first MODEL of a PDB file (prody parsePDB: model 1, HETATM included), or of MODEL `model` (its
+    serial number; a file without MODEL records is model 1)."""
+    cur = 1
     with open(path) as fh:
         for line in fh:
             rec = line[:6]
+            if rec == "MODEL ":
+                cur = _model_serial(line, cur)
+                continue
             if rec == "ENDMDL":
-                break
-            if rec not in ("ATOM  ", "HETATM"):
+                if model is None or cur == model:
+                    break
+                cur = None                                    # between two models
+                continue
+            if rec not in ("ATOM  ", "HETATM") or (model is not None and cur != model):
                 continue
             try:
                 occ = float(line[54:60]) if line[54:60].strip() else 1.0
@@ -66,6 +75,11 @@ def _pdb_atoms(path):
                 continue
             yield Atom(rec == "HETATM", serial, line[12:16].strip(), line[16].strip(), line[17:20].strip(), line[21],
                        resnum, line[26].strip(), xyz, occ, bfac, line[76:78].strip() if len(line) >= 78 else "")
+
+
+def _model_serial(line, cur):
+    f = line[6:].split()
+    return int(f[0]) if f and f[0].lstrip("-").isdigit() else (cur or 0) + 1
 
 
 def _split_cif_row(line):
@@ -88,9 +102,8 @@ def _split_cif_row(line):
     return out
 
 
-def _mmcif_atoms(path):
-    """The `_atom_site` loop of an mmCIF file, first model, with the author (auth_*) identifiers PDB files carry —
-    chain = auth_asym_id, residue number = auth_seq_id, insertion code = pdbx_PDB_ins_code."""
+def _mmcif_site(path):
+    """(column names, rows) of the `_atom_site` loop of an mmCIF file."""
     cols, rows, in_loop, in_site = [], [], False, False
     with open(path) as fh:
         for raw in fh:
@@ -118,6 +131,13 @@ def _mmcif_atoms(path):
                 in_loop = False
     if not cols:
         raise ValueError(f"{path}: no _atom_site loop found")
+    return cols, rows
+
+
+def _mmcif_atoms(path, model=None):
+    """The `_atom_site` loop of an mmCIF file, first model (or the one whose pdbx_PDB_model_num is `model`), with the author (auth_*)
+    identifiers PDB files carry — chain = auth_asym_id, residue number = auth_seq_id, insertion code = pdbx_PDB_ins_code."""
+    cols, rows = _mmcif_site(path)
     ix = {c: i for i, c in enumerate(cols)}
     need = ("Cartn_x", "Cartn_y", "Cartn_z")
     if any(c not in ix for c in need):
@@ -128,11 +148,15 @@ def _mmcif_atoms(path):
     for row in rows:
         if len(row) < len(cols):
             continue
-        model = get(row, "pdbx_PDB_model_num", default="1")
-        if first_model is None:
-            first_model = model
-        if model != first_model:
-            break
+        row_model = get(row, "pdbx_PDB_model_num", default="1")
+        if model is not None:
+            if row_model != str(model):
+                continue
+        else:
+            if first_model is None:
+                first_model = row_model
+            if row_model != first_model:
+                break
         try:
             xyz = (float(row[ix["Cartn_x"]]), float(row[ix["Cartn_y"]]), float(row[ix["Cartn_z"]]))
             resnum = int(get(row, "auth_seq_id", "label_seq_id", "0"))
@@ -146,16 +170,41 @@ def _mmcif_atoms(path):
                    resnum, nul(get(row, "pdbx_PDB_ins_code")), xyz, occ, bfac, nul(get(row, "type_symbol")))
 
 
-def read_atoms(path, chains=None, normalize_legacy_names=False, chain_order=None, ca_residues=None):
+def model_ids(path):
+    """The model numbers of a structure file in file order: the serials of the MODEL records of a PDB file, the distinct
+    pdbx_PDB_model_num values of an mmCIF file; [1] for a file without either."""
+    if str(path).lower().endswith((".cif", ".mmcif")):
+        cols, rows = _mmcif_site(path)
+        if "pdbx_PDB_model_num" not in cols:
+            return [1]
+        i, ids = cols.index("pdbx_PDB_model_num"), []
+        for row in rows:
+            if len(row) >= len(cols) and row[i].lstrip("-").isdigit() and int(row[i]) not in ids:
+                ids.append(int(row[i]))
+        return ids or [1]
+    ids, cur = [], 0
+    with open(path) as fh:
+        for line in fh:
+            if line[:6] == "MODEL ":
+                cur = _model_serial(line, cur)
+                ids.append(cur)
+    return ids or [1]
+
+
+def read_atoms(path, chains=None, normalize_legacy_names=False, chain_order=None, ca_residues=None, model=None):
     """Coordinate records the reference's parse_PDB keeps before any polymer logic (data_utils.py:232-238): first model,
     altloc blank or 'A' (prody's default), occupancy > 0, optionally only the given chains.  `.cif` / `.mmcif` files go
     through the mmCIF reader.  normalize_legacy_names maps pre-remediation nucleic atom names (O1P, O2P, C1*, ...) to the
     current ones; the reference (prody) does not, so it is off by default.  chain_order (a list) receives the chain ids in
     order of first appearance over EVERY parsed record — before the occupancy / chain filters, hetero atoms and waters
     included: that is the numbering prody's getChindices() reports (data_utils.py:303).  ca_residues (a set) receives the
-    (chain, number, insertion code) keys of the residues that have an atom named CA, likewise over every parsed record."""
+    (chain, number, insertion code) keys of the residues that have an atom named CA, likewise over every parsed record.
+    model: the model to read (see model_ids) instead of the first one."""
     low = str(path).lower()
-    src = _mmcif_atoms(path) if low.endswith((".cif", ".mmcif")) else _pdb_atoms(path)
+    if model is not None and int(model) not in model_ids(path):
+        raise ValueError(f"{path}: no model {model} (the file has {model_ids(path)})")
+    model = None if model is None else int(model)
+    src = _mmcif_atoms(path, model) if low.endswith((".cif", ".mmcif")) else _pdb_atoms(path, model)
     chains = set(chains) if chains else None
     records = [a for a in src if a.altloc in ("", "A")]
     for a in records:                                   # properties of the WHOLE parsed structure, like prody's flags / hierarchy
@@ -172,10 +221,38 @@ def read_atoms(path, chains=None, normalize_legacy_names=False, chain_order=None
 
 
 def parse_pdb(path, chains=None, parse_na_only=False, na_shared_tokens=True, load_residues_with_missing_atoms=False,
-              normalize_legacy_names=False):
+              normalize_legacy_names=False, model=None):
     """parse_PDB of the reference (data_utils.py:84-405) for PDB and mmCIF files -> dict of numpy arrays (no batch
     dimension) + 'chain_letters', 'icodes', 'na_chain_letters', and the atom records the backbone writer needs
-    ('backbone_atoms': protein N/CA/C/O and the 12 nucleic backbone atoms; 'other_atoms': neither polymer nor water)."""
+    ('backbone_atoms': protein N/CA/C/O and the 12 nucleic backbone atoms; 'other_atoms': neither polymer nor water).
+    model: the model to parse (see model_ids); None = the first one."""
+    return _parse(path, chains, parse_na_only, na_shared_tokens, load_residues_with_missing_atoms, normalize_legacy_names, model)[0]
+
+
+def parse_states(path, chains=None, parse_na_only=False, na_shared_tokens=True, load_residues_with_missing_atoms=False,
+                 normalize_legacy_names=False):
+    """Every model of a structure file as the states of ONE molecule (an NMR ensemble, the folds of a riboswitch): the first
+    model's parse_pdb dict with 'X' [M, L, 16, 3] and 'X_m' [M, L, 16] stacked over the models, and 'model_ids'.  Raises ValueError
+    unless all models give the same residues — chain, number, insertion code, residue name and `mask`."""
+    ids = model_ids(path)
+    parsed = [_parse(path, chains, parse_na_only, na_shared_tokens, load_residues_with_missing_atoms, normalize_legacy_names, i) for i in ids]
+    key = lambda P, names: (P["chain_letters"], P["R_idx"].tolist(), P["icodes"], names, P["mask"].tolist())
+    first = key(*parsed[0])
+    for i, pn in zip(ids[1:], parsed[1:]):
+        other = key(*pn)
+        if other != first:
+            what = [n for n, a, b in zip(("chains", "residue numbers", "insertion codes", "residue names", "mask"), first, other) if a != b]
+            raise ValueError(f"{path}: model {i} does not list the same residues as model {ids[0]} ({', '.join(what)} differ): "
+                             "the states of a multi-state design must be conformations of one molecule")
+    out = dict(parsed[0][0])
+    out["X"] = np.stack([P["X"] for P, _ in parsed])
+    out["X_m"] = np.stack([P["X_m"] for P, _ in parsed])
+    out["model_ids"] = ids
+    return out
+
+
+def _parse(path, chains, parse_na_only, na_shared_tokens, load_residues_with_missing_atoms, normalize_legacy_names, model):
+    """parse_pdb's work -> (its dict, the residue names)."""
     atom_index = {a: i for i, a in enumerate(spec.ATOM_TYPES)}
     rti = spec.restype_to_int(na_shared_tokens)
     residues, order = {}, []        # key -> {"resname", "kind", "atoms": {name: xyz}}
@@ -183,7 +260,7 @@ def parse_pdb(path, chains=None, parse_na_only=False, na_shared_tokens=True, loa
     backbone_atoms, other_atoms = [], []
     bb_names = {"protein": set(PROTEIN_BB), "nucleic": set(RNA_BB)}
     ca_residues = set()
-    for at in read_atoms(path, chains, normalize_legacy_names, chain_order, ca_residues):
+    for at in read_atoms(path, chains, normalize_legacy_names, chain_order, ca_residues, model):
         name, resname, chain = at.name, at.resname, at.chain
         # prody's `protein` flag: a qualifying residue name AND an atom named CA in the residue (manual, Atom Flags)
         kind = "protein" if (resname in PROTEIN_NAMES and (chain, at.resnum, at.icode) in ca_residues) else \
@@ -242,7 +319,7 @@ def parse_pdb(path, chains=None, parse_na_only=False, na_shared_tokens=True, loa
         "chain_letters": chain_letters, "icodes": [k[2] for k in order],
         "na_chain_letters": [c for i, c in enumerate(chain_letters) if dna_mask[i] or rna_mask[i]],
         "backbone_atoms": backbone_atoms, "other_atoms": other_atoms,
-    }
+    }, resnames
 
 
 def renumber(R_idx):

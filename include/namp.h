@@ -678,6 +678,16 @@ int namp_decoder_sample_walk(const NampModelW* w, const float* h_V_enc, const fl
                              float temperature, uint64_t special_tokens, int32_t* S_out, float* probs_out, float* logp_out,
                              void* ws, size_t ws_bytes, int B_dec, int B_enc, int N, int K, void* stream);
 
+/* ---- mapped groups (base-paired design) --------------------------------------------------------------------------
+ * Attaches token maps to the calling thread's NEXT namp_decoder_sample / _levels / _walk call (that call takes them and clears them,
+ * whether it succeeds or not; null detaches).  tok_maps: ONE device array of int32, alive until that call's work is done —
+ * [n_maps][64] permutations of the vocabulary that are their own inverse and fix every special token, identity beyond vocab, and
+ * directly behind them [B_enc][N] the index of the map P_i of residue i, in [0, n_maps).  Member j of a symmetry group then contributes w_j * logits_j[P_j[a]] to the group's
+ * sum for group token a, the closing member's bias row is read as bias_c[P_c[a]], member j receives the token P_j[a] of the drawn a
+ * and the probability row probs_j[P_j[a]] = p[a]; a fixed or forced member passes P_j[its token] on as the group token.  All-identity
+ * maps give the bits of a call without maps.  Not together with pair_bias (NAMP_EINVAL from the sampler call). */
+int namp_sample_token_maps(const int32_t* tok_maps, int n_maps);
+
 /* ---- tied states: the plan of one sequence sampled over M backbone states of the same molecule -------------------
  * M states of N residues, encoded as a batch, are ONE symmetric design on the block-diagonal flattened graph of M * N residues:
  * residue n of state m is flat residue m * N + n, its neighbours are E_idx[m][n][:] + m * N, and the M copies of a residue form a
@@ -697,6 +707,21 @@ int namp_states_plan(const int32_t* E_idx, const int32_t* order0, const int32_t*
                      int32_t* E_flat, int32_t* order, int32_t* rank, int32_t* group_first, int32_t* group_last, float* sym_w,
                      int32_t* work_n, int32_t* level, int32_t* work, int32_t* level_off, int32_t* n_levels,
                      int32_t* close, int32_t* close_off, int B_dec, int M, int N, int K, void* stream);
+
+/* ---- base-paired design: the plan of a design whose symmetry groups are all pairs ---------------------------------
+ * One complex (B_enc = 1), every stream in the ONE decoding order order0 / rank0 [N] (stream 0's and its inverse).  partner int32 [N]
+ * (-1: unpaired, else the paired residue; partner[partner[i]] = i), first int32 [N] (1: the residue is listed first in its pair).
+ * namp_pairs_plan writes, without reading anything back, what symmetry-tied sampling takes: order / rank / group_first / group_last
+ * [B_dec][N] — a residue reached first in order0 emits its pair in listed order, as two consecutive visits of one group.
+ * namp_pairs_work_lists then turns level [N] by visit (row 0 of namp_sample_levels_dep with those groups) into the lists of
+ * namp_decoder_sample_walk with every pair kept as ONE work item: work [<= B_dec * N][2] = (stream, first visit) sorted by level —
+ * stream-major inside a level, then by visit: a stable sort —, work_n the visits per item, level_off [N + 2], n_levels[0] the number
+ * of non-empty levels.  The number of items is B_dec * (N - pairs).  One workgroup each, plain stores: two calls give identical arrays.
+ * N <= 8192. */
+int namp_pairs_plan(const int32_t* partner, const int32_t* first, const int32_t* order0, const int32_t* rank0, int32_t* order,
+                    int32_t* rank, int32_t* group_first, int32_t* group_last, int B_dec, int N, void* stream);
+int namp_pairs_work_lists(const int32_t* level, const int32_t* group_first, int32_t* work, int32_t* work_n, int32_t* level_off,
+                          int32_t* n_levels, int B_dec, int N, void* stream);
 
 /* ---- leave-one-out conditional log-probs ---------------------------------------------------------
  * log p(s_i | X, S_-i) for EVERY residue i in one call, after encode(): row i of the parallel decoder (model_utils.py:391-421)

@@ -53,6 +53,9 @@ def build_parser():
     a("--multi_state", type=int, default=0, help="1 - the MODELs of --pdb_path are states of one molecule: ONE sequence is designed "
       "to fit all of them (ProteinMPNN.sample with state_weights)")
     a("--state_weights", type=str, default="", help="weights of the states in model order, e.g. '0.5,0.3,0.2' (default: 1/M each)")
+    a("--paired_residues", type=str, default="", help="base pairs, e.g. 'A5:B20,A6:B19' (residues named as in --fixed_residues): the "
+      "second residue of a pair receives the Watson-Crick complement of the first (canonical pairs only; a fixed residue decides)")
+    a("--paired_strands", type=str, default="", help="chains paired antiparallel over their full lengths, e.g. 'A:B' or 'A:B,C:D'")
     a("--na_shared_tokens", type=int, default=1)
     a("--parse_na_only", type=int, default=0)
     a("--design_na_only", type=int, default=0)
@@ -110,6 +113,34 @@ def make_pair_bias(chain_labels, R_idx, pair_bias_AA):
     out[0, i, :, i + 1, :] = pair_bias_AA
     out[0, i + 1, :, i, :] = pair_bias_AA.t()
     return out
+
+
+def parse_pairs(paired_residues, paired_strands, encoded, chain_letters):
+    """--paired_residues 'A5:B20,A6:B19' and --paired_strands 'A:B' as a list of residue-index pairs.  `encoded`: the residue names
+    (chain letter + number + insertion code, as --fixed_residues takes them), `chain_letters`: the chain of every residue.  Two paired
+    strands pair antiparallel: residue k of the first chain with residue n - 1 - k of the second."""
+    index = dict(zip(encoded, range(len(encoded))))
+    pairs = []
+    for item in filter(None, (t.strip() for t in paired_residues.split(","))):
+        names = item.split(":")
+        if len(names) != 2:
+            raise ValueError(f"--paired_residues: '{item}' is not of the form RES:RES")
+        for nm in names:
+            if nm not in index:
+                raise ValueError(f"--paired_residues: no residue '{nm}' in the structure")
+        pairs.append((index[names[0]], index[names[1]]))
+    for item in filter(None, (t.strip() for t in paired_strands.split(","))):
+        names = item.split(":")
+        if len(names) != 2 or names[0] == names[1]:
+            raise ValueError(f"--paired_strands: '{item}' is not of the form CHAIN:CHAIN with two different chains")
+        a, b = ([i for i, c in enumerate(chain_letters) if c == nm] for nm in names)
+        if not a or not b:
+            raise ValueError(f"--paired_strands: '{item}' names a chain that is not in the structure")
+        if len(a) != len(b):
+            raise ValueError(f"--paired_strands: chains {names[0]} and {names[1]} have {len(a)} and {len(b)} residues; "
+                             "paired strands must have equal lengths")
+        pairs += list(zip(a, reversed(b)))
+    return pairs
 
 
 def main(argv=None):
@@ -225,8 +256,14 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
     else:
         sym_res, sym_w = [[]], [[]]
 
+    pairs = parse_pairs(args.paired_residues, args.paired_strands, encoded, list(P["chain_letters"]))
+    if pairs and args.conditional_probs_only:
+        raise ValueError("--conditional_probs_only scores a given sequence: it does not go with --paired_residues / --paired_strands")
+
     with torch.no_grad():
         fd = pdbio.to_feature_dict(P, chain_mask, device)
+        if pairs:
+            fd["paired_residues"] = pairs
         fd.update({"batch_size": args.batch_size, "temperature": args.temperature,
                    "bias": (-1e8 * omit_AA[None, None, :] + bias_AA).repeat(1, L, 1),
                    "symmetry_residues": sym_res, "symmetry_weights": sym_w})

@@ -1240,6 +1240,16 @@ static size_t sample_ws_bytes(int B_enc, int B_dec, int N, int K, int n_dec) {
 size_t namp_sample_workspace_bytes_n(int B_enc, int B_dec, int N, int K, int n_dec) { return sample_ws_bytes(B_enc, B_dec, N, K, n_dec); }
 size_t namp_sample_workspace_bytes(int B_enc, int B_dec, int N, int K) { return sample_ws_bytes(B_enc, B_dec, N, K, NAMP_MAX_LAYERS); }
 
+// the token maps of the calling thread's NEXT sampler call (namp_sample_token_maps): taken, and cleared, by sample_prepare
+static thread_local const int32_t* g_tok_maps = nullptr;
+static thread_local int g_n_maps = 0;
+
+int namp_sample_token_maps(const int32_t* tok_maps, int n_maps) {
+  REQUIRE(tok_maps == nullptr || (n_maps >= 1 && n_maps <= 4096), "namp_sample_token_maps: n_maps=%d", n_maps);
+  g_tok_maps = tok_maps; g_n_maps = tok_maps ? n_maps : 0;
+  return NAMP_OK;
+}
+
 static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
                           const int32_t* mask, const int32_t* mask_dec, const int32_t* chain_mask, const int32_t* S_true, const float* bias,
                           const int32_t* order, const int32_t* rank, const float* uniform, const int32_t* S_forced,
@@ -1248,7 +1258,10 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
                           float temperature, uint64_t special_tokens, int32_t* S_out, float* probs_out, float* logp_out,
                           void* ws, size_t ws_bytes, int B_dec, int B_enc, int N, int K, void* stream,
                           SampleArgs* a_out, int* nwaves_out) {
+  const int32_t* tok_maps = g_tok_maps; const int n_maps = g_n_maps;
+  g_tok_maps = nullptr; g_n_maps = 0;                            // (one call only, whatever becomes of it)
   REQUIRE(w != nullptr, "namp_decoder_sample: null weights");
+  REQUIRE(tok_maps == nullptr || pair_bias == nullptr, "namp_decoder_sample: token maps and pair_bias do not go together");
   REQUIRE((group_first == nullptr) == (group_last == nullptr), "namp_decoder_sample: group_first and group_last go together");
   REQUIRE(w->n_dec >= 1 && w->n_dec <= NAMP_MAX_LAYERS, "namp_decoder_sample: supports 1..%d decoder layers (got %d)", NAMP_MAX_LAYERS, w->n_dec);
   REQUIRE(w->vocab >= 1 && w->vocab <= 64, "namp_decoder_sample: vocab=%d must be in [1,64]", w->vocab);
@@ -1300,7 +1313,7 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
   SampleArgs a = {};
   a.hE = h_E; a.E_idx = E_idx; a.mask_true = mask; a.chain_mask = chain_mask; a.S_true = S_true; a.bias = bias; a.order = order; a.rank = rank;
   a.uniform = uniform; a.S_forced = S_forced; a.group_first = group_first; a.group_last = group_last;
-  a.sym_w = sym_weights; a.pair_bias = pair_bias; a.head_wT = head_wT; a.head_b = w->Wout_b; a.S_out = S_out;
+  a.sym_w = sym_weights; a.pair_bias = pair_bias; a.tok_maps = tok_maps; a.n_maps = n_maps; a.head_wT = head_wT; a.head_b = w->Wout_b; a.S_out = S_out;
   a.probs_out = probs_out; a.logp_out = logp_out; a.special = special_tokens; a.inv_T = 1.0f / temperature;
   a.B_dec = B_dec; a.B_enc = B_enc; a.N = N; a.K = K; a.TPN = (K + 15) / 16; a.n_layers = w->n_dec; a.vocab = w->vocab;
   // 8 waves per workgroup (256 VGPRs per lane: no scratch) serve 8 / TPN streams; K > 128 falls back to the 12-wave form

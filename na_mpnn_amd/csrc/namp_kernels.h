@@ -2115,6 +2115,10 @@ __device__ __forceinline__ float wv_dpp(const float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
 __device__ __forceinline__ float wv_lane(const float v, const int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
+// v of lane `src` (0..63, any lane pattern): ds_bpermute_b32 goes through the LDS crossbar, not through memory
+__device__ __forceinline__ float wv_fetch(const float v, const int src) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v)));
+}
 __device__ __forceinline__ float wave_sum64(float v) {
   v += wv_dpp<0xB1>(v); v += wv_dpp<0x4E>(v); v += wv_dpp<0x141>(v); v += wv_dpp<0x140>(v);      // quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
   return (wv_lane(v, 0) + wv_lane(v, 16)) + (wv_lane(v, 32) + wv_lane(v, 48));
@@ -2157,6 +2161,9 @@ struct SampleArgs {
   const int32_t* group_last;   // optional [B_dec][N]: 1 if visit v closes its group                       (null: always)
   const float* sym_w;          // optional [G_enc]: weight of a residue's logits in its group's sum        (null: 1)
   const float* pair_bias;      // optional [G_enc][vocab][N][vocab] (model_utils.py:116,170-172)
+  // mapped groups (base-paired design): member j of a group speaks the group's token a as P_j[a] — P_j an involution of the vocabulary
+  const int32_t* tok_maps;     // optional [n_maps][64]: the token maps, identity beyond vocab, and behind them [G_enc]: the map of a residue
+                               //          (null: every map is the identity)
   const float* head_wT; const float* head_b;   // head_wT [128][64]: W_out transposed, token t of channel c at c * 64 + t (zero beyond vocab): coalesced reads
   int32_t* S_out;              // [B_dec][N]   (also the running sequence read back for decoded neighbours)
   float* probs_out;            // [B_dec][N][vocab]
@@ -2164,9 +2171,10 @@ struct SampleArgs {
   unsigned long long special;  // bit t set -> token t can never be drawn
   float inv_T;
   int B_dec, B_enc, N, K, TPN, n_layers, vocab, slots;
-  SampleLayer l[NAMP_MAX_LAYERS];      // 8 x 480 B: with the scalars and the launch's own arguments 4,072 of the 4,096 kernel-argument bytes
+  int n_maps;                  // (in the padding in front of l: the struct grows by the one pointer only)
+  SampleLayer l[NAMP_MAX_LAYERS];      // 8 x 480 B: with the scalars and the launch's own 40 argument bytes 4,088 of the 4,096 kernel-argument bytes
 };
-static_assert(sizeof(SampleArgs) + 32 <= 4096, "SampleArgs + the sampler launch's scalar arguments must fit the kernel-argument segment");
+static_assert(sizeof(SampleArgs) + 40 <= 4096, "SampleArgs + the sampler launch's scalar arguments must fit the kernel-argument segment");
 
 struct SampleRows {             // tile row n -> residue of stream (b0 + n) at this step, or -1
   const int* node_lds;
@@ -2336,7 +2344,10 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     const int iq = a.order[(long)bq * a.N + t];
     const int ne = (bq % a.B_enc) * a.N + iq;
     const long vis = (long)bq * a.N + t;
-    float add = (lane < a.vocab) ? a.bias[(long)ne * a.vocab + lane] : 0.f;
+    // (mapped groups: group token `lane` is the closing member's token P_c[lane], so its bias row is read through its map)
+    const int32_t* map_idx = a.tok_maps + a.n_maps * 64;             // (read only where tok_maps is set)
+    const int bl = a.tok_maps ? a.tok_maps[map_idx[ne] * 64 + lane] : lane;
+    float add = (lane < a.vocab) ? a.bias[(long)ne * a.vocab + bl] : 0.f;
     if (a.pair_bias && lane < a.vocab) {
       const float* pb = a.pair_bias + ((long)ne * a.vocab + lane) * a.N * a.vocab;
       float acc_pb = 0.f;
@@ -2369,8 +2380,18 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
       const int im = a.order[(long)bq * a.N + v];
       const int nem = (bq % a.B_enc) * a.N + im;
       const long ndm = (long)bq * a.N + im;
-      if (a.S_forced) S_t = a.S_forced[ndm];
       const int cm = a.chain_mask[nem];
+      if (a.tok_maps) {
+        // S_t stays the GROUP token: a forced or fixed member passes on P^-1[its token] (= P[..]: the maps are involutions), every
+        // member holds P[S_t] and its probability row is the drawn distribution in its own alphabet
+        const int32_t* pm = a.tok_maps + map_idx[nem] * 64;
+        if (a.S_forced) S_t = pm[a.S_forced[ndm]];
+        if (!cm) S_t = pm[a.S_true[nem]];
+        if (lane < a.vocab) a.probs_out[ndm * a.vocab + pm[lane]] = cm ? p : 0.f;
+        if (lane == 0) __hip_atomic_store(a.S_out + ndm, pm[S_t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        continue;
+      }
+      if (a.S_forced) S_t = a.S_forced[ndm];
       if (!cm) S_t = a.S_true[nem];
       if (lane < a.vocab) a.probs_out[ndm * a.vocab + lane] = cm ? p : 0.f;
       if (lane == 0) __hip_atomic_store(a.S_out + ndm, S_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2556,7 +2577,8 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
         const long vis = (long)bq * a.N + t;
         const int v_first = a.group_first ? a.group_first[vis] : t;
         const float wsym = a.sym_w ? a.sym_w[ne] : 1.0f;
-        const float zz = (lane < a.vocab) ? z : 0.f;
+        float zz = (lane < a.vocab) ? z : 0.f;
+        if (a.tok_maps) zz = wv_fetch(zz, a.tok_maps[a.tok_maps[a.n_maps * 64 + ne] * 64 + lane]);      // the member's logit of group token `lane`
         tot = (v_first == t) ? wsym * zz : fmaf(wsym, zz, tot);
         const bool closes = a.group_last ? (a.group_last[vis] != 0) : true;
         if (!closes) continue;
@@ -2609,7 +2631,8 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
           float tt = 0.f;
           for (int v = vf; v <= tl; ++v) {
             const int im = a.order[(long)bq * a.N + v];
-            const float zv = (lane < a.vocab) ? __hip_atomic_load(zbuf + ((long)bq * a.N + im) * a.vocab + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+            float zv = (lane < a.vocab) ? __hip_atomic_load(zbuf + ((long)bq * a.N + im) * a.vocab + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+            if (a.tok_maps) zv = wv_fetch(zv, a.tok_maps[a.tok_maps[a.n_maps * 64 + (bq % a.B_enc) * a.N + im] * 64 + lane]);
             const float wsym = a.sym_w ? a.sym_w[(bq % a.B_enc) * a.N + im] : 1.0f;
             tt = (v == vf) ? wsym * zv : fmaf(wsym, zv, tt);
           }

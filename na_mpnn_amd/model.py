@@ -155,6 +155,91 @@ def symmetry_visits(groups, weights, order0, L):
     return visits, gf, gl, w
 
 
+def mapped_groups(L, restype_to_int, pairs=None, pair_weights=None, polymer=None, fixed=None, groups=None, weights=None, maps=None):
+    """Groups of mapped symmetry-tied sampling — base pairs (feature_dict["paired_residues"]) and explicit token maps
+    (feature_dict["symmetry_token_maps"]) — as plain lists; needs no device.
+
+    Member j of a mapped group carries a token map P_j, an involution of the vocabulary that fixes the special tokens: for the group's
+    token a the member receives P_j[a], and the group's logit sum reads its logits through P_j.  pairs [(i, j), ...] ties residue j to
+    the Watson-Crick complement of residue i (spec.WC_SAME for two residues of one polymer type, spec.WC_CROSS for DNA with RNA;
+    polymer [L]: 1 DNA, 2 RNA, anything else is refused); pair_weights (w_i, w_j) or one such tuple per pair, default (1, 1).  A member
+    that is fixed (fixed [L] true) is listed first, so that its partner receives the complement of its token.  groups / weights / maps:
+    symmetry_residues, symmetry_weights and symmetry_token_maps (per group None or a list with None or a [vocab] map per member).  A
+    pair whose members sit in symmetry groups joins the two groups: the members of i's group first, the weights of each side multiplied
+    by the pair's weight of that side, the maps of j's side composed with the pair's map.
+    Returns (groups, weights, maps, pair_list): lists parallel to each other, every map a list of vocab ids; pair_list = the pairs as
+    (first listed, second listed, w_first, w_second, kind) when the pairs are ALL there is (else None).  ValueError on a residue in two
+    pairs, paired with itself, outside [0, L) or not a nucleic acid, and on a map that is not an involution or moves a special token."""
+    V = len(spec.RESTYPES)
+    ident = list(range(V))
+    out, group_of = [], {}                                   # out: [members, weights, maps] or None once merged away
+    plain = groups is None or (len(groups) == 1 and len(groups[0]) == 0)
+    if maps is not None and (plain or len(maps) != len(groups)):
+        raise ValueError("symmetry_token_maps must be parallel to symmetry_residues")
+    if not plain:
+        for gi, g in enumerate(groups):
+            gm = maps[gi] if maps is not None else None
+            if gm is not None and len(gm) != len(g):
+                raise ValueError(f"symmetry_token_maps[{gi}] has {len(gm)} entries for the {len(g)} residues of its group")
+            ms = []
+            for k, r in enumerate(g):
+                if not 0 <= int(r) < L:
+                    raise ValueError(f"symmetry_residues: residue {int(r)} is outside [0, {L})")
+                m = None if gm is None else gm[k]
+                if m is not None:
+                    m = m.tolist() if hasattr(m, "tolist") else list(m)
+                    m = spec.check_token_map(restype_to_int, m, f"symmetry_token_maps[{gi}][{k}]")
+                ms.append(ident if m is None else m)
+                group_of.setdefault(int(r), gi)
+            out.append([[int(r) for r in g], [float(v) for v in weights[gi]], ms])
+    pair_list = [] if plain else None
+    paired = set()
+    for n, pr in enumerate(pairs or []):
+        i, j = int(pr[0]), int(pr[1])
+        pw = (1.0, 1.0) if pair_weights is None else pair_weights
+        if len(pw) and hasattr(pw[0], "__len__"):
+            pw = pw[n]
+        wi, wj = float(pw[0]), float(pw[1])
+        for r in (i, j):
+            if not 0 <= r < L:
+                raise ValueError(f"paired_residues: residue {r} is outside [0, {L})")
+        if i == j:
+            raise ValueError(f"paired_residues: residue {i} is paired with itself")
+        for r in (i, j):
+            if r in paired:
+                raise ValueError(f"paired_residues: residue {r} is in two pairs")
+            if polymer is not None and int(polymer[r]) not in (1, 2):
+                raise ValueError(f"paired_residues: residue {r} is not a nucleic acid (protein residues cannot be base-paired)")
+        paired.update((i, j))
+        if fixed is not None and bool(fixed[j]) and not bool(fixed[i]):
+            i, j, wi, wj = j, i, wj, wi
+        kind = "same" if polymer is None or int(polymer[i]) == int(polymer[j]) else "cross"
+        P = spec.token_map(restype_to_int, kind)
+        if pair_list is not None:
+            pair_list.append((i, j, wi, wj, kind))
+        for r in (i, j):
+            if r not in group_of:
+                group_of[r] = len(out)
+                out.append([[r], [1.0], [ident]])
+        gi, gj = group_of[i], group_of[j]
+        if gi == gj:
+            raise ValueError(f"paired_residues: residues {i} and {j} are already tied to each other by symmetry_residues")
+        A, Bm = out[gi], out[gj]
+        Pi, Pj = A[2][A[0].index(i)], Bm[2][Bm[0].index(j)]
+        A[1] = [w * wi for w in A[1]]
+        for r, w, Pk in zip(*Bm):
+            if group_of.get(r) != gj:                      # (listed in an earlier group as well: it belongs to that one)
+                continue
+            A[0].append(r); A[1].append(w * wj); A[2].append([Pk[Pj[P[Pi[a]]]] for a in ident])
+            group_of[r] = gi
+        out[gj] = None
+    out = [g for g in out if g is not None]
+    for g in out:
+        for r, m in zip(g[0], g[2]):
+            spec.check_token_map(restype_to_int, m, f"the token map of residue {r}")
+    return [g[0] for g in out], [g[1] for g in out], [g[2] for g in out], pair_list
+
+
 def pair_bias_dependencies(pair_bias, max_deps=64):
     """Extra dependencies of the sampler's levels from pair_bias [B, L, A, L, A] (model_utils.py:116,169-172): the bias of residue i
     reads the token of every residue j whose block pair_bias[:, i, :, j, :] is not all zero — the sequence neighbours for run.py's
@@ -347,6 +432,59 @@ class ProteinMPNN(nn.Module):
             raise IndexError(f"na_mpnn_amd: token ids in '{what}' must lie in [0, {self.vocab}); got [{int(lo)}, {int(hi)}]")
         if cached:
             self._tokens_ok[what] = (weakref.ref(S), S._version)
+
+    def _host_list(self, t, what):
+        """`t` (a small per-residue tensor of the feature_dict) as a Python list, read back ONCE per tensor object and version (see
+        _check_tokens): the plan of a base-paired design needs the polymer types and the fixed residues on the host."""
+        cached = torch.is_tensor(t) and not t.is_inference()
+        slot = self._tokens_ok.get(("host", what))
+        if cached and slot is not None and slot[0]() is t and slot[1] == t._version:
+            return slot[2]
+        out = t.detach().reshape(-1).tolist() if torch.is_tensor(t) else list(np.asarray(t).reshape(-1))
+        if cached:
+            self._tokens_ok[("host", what)] = (weakref.ref(t), t._version, out)
+        return out
+
+    def _mapped_arguments(self, fd, B, L):
+        """Base pairs / token maps of a sample() call (feature_dict["paired_residues"], "paired_weights", "symmetry_token_maps") ->
+        (groups, weights, the token maps as n_maps lists of 64 ids (map 0: the identity), the map index of every residue as a list of L,
+        pair_list or None), see mapped_groups(); None without them."""
+        pairs, maps = fd.get("paired_residues"), fd.get("symmetry_token_maps")
+        if (pairs is None or len(pairs) == 0) and maps is None:
+            return None
+        if self.restype_to_int is None:
+            raise ValueError("paired_residues / symmetry_token_maps need the model's restype_to_int")
+        if B != 1:
+            raise ValueError("paired_residues / symmetry_token_maps expect one input complex (B == 1)")
+        if "pair_bias" in fd:
+            raise ValueError("pair_bias is not supported together with paired_residues / symmetry_token_maps")
+        polymer = fixed = None
+        if pairs is not None and len(pairs):
+            dna, rna = self._host_list(fd["dna_mask"], "dna_mask"), self._host_list(fd["rna_mask"], "rna_mask")
+            polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
+            m, cm = self._host_list(fd["mask"], "mask"), self._host_list(fd["chain_mask"], "chain_mask")
+            fixed = [not (a and b) for a, b in zip(m, cm)]                       # (a masked residue keeps its token as a fixed one does)
+        groups, weights, gmaps, pair_list = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, fixed,
+                                                          fd.get("symmetry_residues"), fd.get("symmetry_weights"), maps)
+        table, index = [list(range(64))], {tuple(range(self.num_letters)): 0}
+        idx = [None] * L
+        for g, ms in zip(groups, gmaps):
+            for r, m in zip(g, ms):
+                if idx[r] is not None:                                            # (listed in an earlier group: it belongs to that one)
+                    continue
+                k = index.get(tuple(m))
+                if k is None:
+                    k = index[tuple(m)] = len(table)
+                    table.append(list(m) + list(range(len(m), 64)))
+                idx[r] = k
+        if not groups:
+            groups, weights = [[]], [[]]
+        return groups, weights, table, [k or 0 for k in idx], pair_list
+
+    @staticmethod
+    def _token_map_array(table, idx, device):
+        """What namp_sample_token_maps takes: ONE int32 array, the maps [n_maps][64] and behind them the map index of every residue."""
+        return torch.tensor([t for m in table for t in m] + list(idx), dtype=torch.int32).to(device)
 
     def _as(self, t, kind):
         """`t` in the dtype / layout the kernels read ("i32": int32, "f32": float32; contiguous), converted ONCE per tensor object: a
@@ -702,16 +840,23 @@ class ProteinMPNN(nn.Module):
         CDF instead of torch.multinomial; ``feature_dict["S_forced"]`` (optional, [batch,L]) teacher-forces."""
         return self._sample(feature_dict, self.sample_level_walk)
 
-    def _sample(self, fd, walk, uniform=None):
-        """sample() with the persistent level walk on or off (`walk`) and the uniforms of the draws given (None: torch.rand)."""
+    def _sample(self, fd, walk, uniform=None, plan_out=None):
+        """sample() with the persistent level walk on or off (`walk`) and the uniforms of the draws given (None: torch.rand).
+        plan_out: a dict that receives the plan arrays of a symmetry-tied call (tests compare the routes array for array)."""
         if fd.get("state_weights") is not None:
             return self._sample_states(fd, walk, uniform)
         bs = fd["batch_size"]
         S_true, mask, bias = fd["S"], fd["mask"], fd["bias"]
-        sym = fd.get("symmetry_residues", [[]])
-        symmetric = not (len(sym) == 1 and len(sym[0]) == 0)
+        sym, sym_weights = fd.get("symmetry_residues", [[]]), fd.get("symmetry_weights", [[]])
         B, L = S_true.shape
         dev = S_true.device
+        tok_maps = pair_list = None
+        n_maps = 0
+        mapped = self._mapped_arguments(fd, B, L)                                 # base pairs / token maps: mapped symmetry groups
+        if mapped is not None:
+            sym, sym_weights, table, idx, pair_list = mapped
+            tok_maps, n_maps = self._token_map_array(table, idx, dev), len(table)
+        symmetric = not (len(sym) == 1 and len(sym[0]) == 0)
         self._check_tokens(S_true)
         if fd.get("S_forced") is not None:
             self._check_tokens(fd["S_forced"], "S_forced")
@@ -743,14 +888,28 @@ class ProteinMPNN(nn.Module):
             for t_ in (E_idx, o.order32, rank, level, work, level_off, n_levels):    # (not recycled before the side stream is done)
                 t_.record_stream(side_)
             early = (level, work, level_off, n_levels)
+        # Base pairs only: the visit plan, the levels and the work lists are built on the device, beside the encoder, with nothing read back
+        plan = None
+        if (pair_list and self.sample_pairs_device_plan and self.sample_level_parallel and walk and o.order32 is not None
+                and order.shape[0] == B_dec and L <= 8192 and E_idx.dtype == torch.int32 and E_idx.is_contiguous()
+                and hip.lib().namp_decoder_sample_walk_grid(B_dec, L, K) > 0):
+            o.wait()                                                                 # (the sort, if the featuriser launch did not take it)
+            # The plan's buffers are allocated HERE, in front of the event: the side stream writes them behind `ev_` only, and a block the
+            # allocator hands out later could still be a temporary of the encoder launches enqueued below.
+            plan = self._pairs_plan_buffers(pair_list, B_dec, L, dev)
+            ev_ = torch.cuda.Event(); ev_.record(torch.cuda.current_stream(dev))     # the neighbour lists, the order and the uploads are out
         h_V, h_E = self.encode_graph(V, None, E_idx, mask, h_E_embedded=h_E)
+        if plan is not None:                                                         # (enqueued behind the encoder's launches: they are running by now)
+            self._pairs_plan_launch(plan, o, E_idx, ev_, B_dec, L, K)
         o.wait()
         chain_mask = mask * fd["chain_mask"]
         group_first = group_last = sym_w = None
-        if symmetric:
+        if plan is not None:
+            order, rank, group_first, group_last, sym_w = (plan[k] for k in ("order", "rank", "group_first", "group_last", "sym_w"))
+        elif symmetric:
             if B != 1:
                 raise ValueError("symmetry-tied sampling expects one input complex (B == 1)")
-            visits, gf, gl, wl = symmetry_visits(sym, fd["symmetry_weights"], order[0].tolist(), L)
+            visits, gf, gl, wl = symmetry_visits(sym, sym_weights, order[0].tolist(), L)
             order = torch.tensor(visits, device=dev).unsqueeze(0).repeat(B_dec, 1)
             group_first = torch.tensor(gf, dtype=torch.int32, device=dev).repeat(B_dec, 1).contiguous()
             group_last = torch.tensor(gl, dtype=torch.int32, device=dev).repeat(B_dec, 1).contiguous()
@@ -778,6 +937,8 @@ class ProteinMPNN(nn.Module):
         E32, cm32, St32 = _i32(E_idx), _i32(chain_mask), self._as(S_true, "i32")
         m32 = self._as(mask, "i32")
         md32, o32, r32 = (m32 if mask_dec is mask else _i32(mask_dec)), (o.order32 if early is not None else _i32(order)), _i32(rank)
+        if plan is not None:
+            order = order.long()                                               # (decoding_order of the result: int64 as on every route)
         bias_f = bias.float().expand(B, L, self.num_letters).contiguous()
         forced = _i32(fd["S_forced"]) if fd.get("S_forced") is not None else None
         h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
@@ -791,8 +952,13 @@ class ProteinMPNN(nn.Module):
                   hip.ptr(group_first), hip.ptr(group_last), hip.ptr(sym_w), hip.ptr(pair_bias))
         tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
                 B_dec, B, L, K, hip.current_stream())
+
+        def attach():       # the token maps go to the NEXT sampler call of this thread (namp_sample_token_maps)
+            if tok_maps is not None:
+                hip.check(Lb.namp_sample_token_maps(tok_maps.data_ptr(), n_maps), "sample_token_maps")
         out = {"S": None, "sampling_probs": probs, "log_probs": logp, "decoding_order": order, "uniform": uniform}   # (S: after the launch)
         if not (self.sample_level_parallel and deps is not None):
+            attach()
             hip.check(Lb.namp_decoder_sample(*common, *tail), "decoder_sample")
             # (no host sync needed: temporaries are stream-ordered allocations, see _featurize_hip)
             out["S"] = S_out.long()
@@ -803,6 +969,8 @@ class ProteinMPNN(nn.Module):
         dep_idx, n_dep = deps
         if early is not None:
             level = early[0]
+        elif plan is not None:
+            level = plan["level"]
         else:
             level = torch.empty(B_dec, L, dtype=torch.int32, device=dev)
             hip.check(Lb.namp_sample_levels_dep(E32.data_ptr(), o32.data_ptr(), r32.data_ptr(), hip.ptr(dep_idx), n_dep,
@@ -822,6 +990,8 @@ class ProteinMPNN(nn.Module):
                 n_levels = torch.empty(1, dtype=torch.int32, device=dev)
                 hip.check(Lb.namp_sample_work_lists(level.data_ptr(), work.data_ptr(), level_off.data_ptr(), n_levels.data_ptr(), B_dec, L,
                                                     hip.current_stream()), "sample_work_lists")
+        elif plan is not None:
+            work, work_n, level_off, n_levels, nwork = (plan[k] for k in ("work", "work_n", "level_off", "n_levels", "nwork"))
         else:
             sel, flat, work_n, close, close_off = level_work_lists(level, group_first, group_last, order[0], E_idx[0].long(),
                                                                    split=bool(symmetric and walk and self.sample_split_groups))
@@ -832,6 +1002,7 @@ class ProteinMPNN(nn.Module):
             if not walk:
                 counts = torch.bincount(flat).cpu().tolist()                   # per-level launches: the one host sync of the sampler
                 counts_c = (C.c_int32 * len(counts))(*counts)
+                attach()
                 hip.check(Lb.namp_decoder_sample_levels(*common, work.data_ptr(), hip.ptr(work_n), counts_c, len(counts), *tail),
                           "decoder_sample_levels")
                 out.update(S=S_out.long(), levels=len(counts))
@@ -839,7 +1010,12 @@ class ProteinMPNN(nn.Module):
             # the level histogram stays on the device (levels < L, so L + 2 offsets; everything behind the last level equals nwork)
             hist = torch.zeros(L + 1, dtype=torch.int64, device=dev).scatter_add_(0, flat, torch.ones_like(flat))
             level_off = torch.cat((hist.new_zeros(1), hist.cumsum(0))).to(torch.int32).contiguous()
+        if plan_out is not None and symmetric:
+            plan_out.update(order=o32, rank=r32, group_first=group_first, group_last=group_last, sym_w=sym_w, map_idx=tok_maps,
+                            work=work[:nwork], work_n=work_n[:nwork], level_off=level_off,
+                            n_levels=n_levels[0] if hist is None else (hist > 0).sum())
         # one persistent launch walking the levels: nothing is read back, the call returns with the whole design enqueued
+        attach()
         hip.check(Lb.namp_decoder_sample_walk(*common, work.data_ptr(), hip.ptr(work_n), nwork, level_off.data_ptr(), hip.ptr(close),
                                               hip.ptr(close_off), hip.ptr(zbuf), *tail), "decoder_sample_walk")
         # the 64 barrier words, copied out of the per-call workspace (a view would keep the whole workspace alive on the model)
@@ -852,6 +1028,49 @@ class ProteinMPNN(nn.Module):
             warnings.warn(f"persistent level walk timed out (code {code:#x}); re-running with per-level launches")
             return self._sample(fd, walk=False, uniform=uniform)
         return out
+
+    # build the plan of a design whose groups are all base pairs on the device (namp_pairs_plan, namp_sample_levels_dep,
+    # namp_pairs_work_lists: nothing is read back); False: the host route through symmetry_visits and level_work_lists (same results; also
+    # what symmetry_residues or states beside the pairs and walk=False take)
+    sample_pairs_device_plan = True
+
+    def _pairs_plan_buffers(self, pair_list, B_dec, L, dev):
+        """The arrays of the plan of a base-paired design (every group a pair, one complex): the host's part uploaded (partner, listed-first
+        flag, weights), the device's part allocated — ONE allocation: visit order, rank, group_first / group_last, levels, work lists."""
+        partner, first, w = [-1] * L, [0] * L, [1.0] * L
+        for i, j, wi, wj, _ in pair_list:
+            partner[i], partner[j], first[i], w[i], w[j] = j, i, 1, wi, wj
+        pf = torch.tensor([partner, first], dtype=torch.int32).to(dev)
+        sym_w = torch.tensor(w, dtype=torch.float32).to(dev)
+        n = B_dec * L
+        sizes = (n, n, n, n, n, 2 * n, n, L + 2, 1)
+        offs = np.concatenate(([0], np.cumsum([(q + 3) & ~3 for q in sizes]))).tolist()          # (16-byte aligned pieces of ONE allocation)
+        buf = torch.empty(offs[-1], dtype=torch.int32, device=dev)
+        order, rank, group_first, group_last, level, work, work_n, level_off, n_levels = (buf[a:a + q] for a, q in zip(offs, sizes))
+        v2 = lambda t: t.view(B_dec, L)
+        return {"order": v2(order), "rank": v2(rank), "group_first": v2(group_first), "group_last": v2(group_last), "sym_w": sym_w,
+                "level": v2(level), "work": work.view(n, 2), "work_n": work_n, "level_off": level_off, "n_levels": n_levels,
+                "nwork": B_dec * (L - len(pair_list)), "pf": pf, "buf": buf}
+
+    def _pairs_plan_launch(self, plan, o, E_idx, ev, B_dec, L, K):
+        """Enqueues the plan on the side stream behind `ev`: the visit order of every stream (namp_pairs_plan), the levels of the groups
+        (namp_sample_levels_dep) and the level-sorted work lists with the pairs kept as whole items (namp_pairs_work_lists).  Sets o.event."""
+        Lb = hip.lib()
+        pf, buf = plan["pf"], plan["buf"]
+        order, rank, group_first, group_last, level, work, work_n, level_off, n_levels = (
+            plan[k] for k in ("order", "rank", "group_first", "group_last", "level", "work", "work_n", "level_off", "n_levels"))
+        side = self._side_stream(E_idx.device)
+        side.wait_event(ev)
+        s_ = side.cuda_stream
+        hip.check(Lb.namp_pairs_plan(pf[0].data_ptr(), pf[1].data_ptr(), o.order32.data_ptr(), o.rank.data_ptr(), order.data_ptr(),
+                                     rank.data_ptr(), group_first.data_ptr(), group_last.data_ptr(), B_dec, L, s_), "pairs_plan")
+        hip.check(Lb.namp_sample_levels_dep(E_idx.data_ptr(), order.data_ptr(), rank.data_ptr(), None, 0, group_first.data_ptr(),
+                                            group_last.data_ptr(), level.data_ptr(), B_dec, 1, L, K, s_), "sample_levels")
+        hip.check(Lb.namp_pairs_work_lists(level.data_ptr(), group_first.data_ptr(), work.data_ptr(), work_n.data_ptr(),
+                                           level_off.data_ptr(), n_levels.data_ptr(), B_dec, L, s_), "pairs_work_lists")
+        o.event = torch.cuda.Event(); o.event.record(side)                         # o.wait() orders the decoder behind the plan
+        for t_ in (E_idx, o.order32, o.rank, pf, buf):                             # (not recycled before the side stream is done)
+            t_.record_stream(side)
 
     # ---------------------------------------------------------------------------------------
     # tied states: one sequence over M backbone states of the same molecule
@@ -897,6 +1116,13 @@ class ProteinMPNN(nn.Module):
         groups {i, L + i, ...} with the state weights): the decoder sees the graph through E_idx only.  Returns S [bs, L], sampling_probs
         [bs, L, V], log_probs [bs, M, L, V], decoding_order [bs, L], uniform [bs, L] (by step), levels, work_items."""
         w, M, L, bs, symmetric = self._states_arguments(fd)
+        sym_groups, sym_weights = fd.get("symmetry_residues", [[]]), fd.get("symmetry_weights", [[]])
+        tok_maps, n_maps = None, 0
+        mapped = self._mapped_arguments(fd, 1, L)                                   # base pairs beside the states: the host route
+        if mapped is not None:
+            sym_groups, sym_weights, table, idx, _ = mapped
+            symmetric = not (len(sym_groups) == 1 and len(sym_groups[0]) == 0)
+            tok_maps, n_maps = self._token_map_array(table, idx * M, fd["S"].device), len(table)   # flat residue m * L + i speaks as residue i does
         S_true, mask = fd["S"], fd["mask"]
         dev, N, Vn = S_true.device, M * L, self.num_letters
         _require_device(fd["X"], "X")
@@ -944,9 +1170,9 @@ class ProteinMPNN(nn.Module):
         if device_plan:
             nwork, levels, step_of = bs * N, n_levels[0], None
         else:
-            groups = [[int(i) + m * L for m in range(M) for i in g] for g in fd["symmetry_residues"]] if symmetric else []
-            weights = [[w[m] * float(ws) for m in range(M) for ws in gw] for gw in fd["symmetry_weights"]] if symmetric else []
-            tied = {int(i) for g in (fd["symmetry_residues"] if symmetric else []) for i in g}
+            groups = [[int(i) + m * L for m in range(M) for i in g] for g in sym_groups] if symmetric else []
+            weights = [[w[m] * float(ws) for m in range(M) for ws in gw] for gw in sym_weights] if symmetric else []
+            tied = {int(i) for g in (sym_groups if symmetric else []) for i in g}
             for i in range(L):
                 if i not in tied:
                     groups.append([i + m * L for m in range(M)]); weights.append(list(w))
@@ -993,6 +1219,8 @@ class ProteinMPNN(nn.Module):
                   group_first.data_ptr(), group_last.data_ptr(), sym_w.data_ptr(), None)
         tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
                 bs, 1, N, K, hip.current_stream())
+        if tok_maps is not None:                    # the token maps go to the NEXT sampler call of this thread (namp_sample_token_maps)
+            hip.check(Lb.namp_sample_token_maps(tok_maps.data_ptr(), n_maps), "sample_token_maps")
         if not walk:
             counts = torch.bincount(flat).cpu().tolist()                       # per-level launches: one host sync
             hip.check(Lb.namp_decoder_sample_levels(*common, work.data_ptr(), work_n.data_ptr(), (C.c_int32 * len(counts))(*counts),

@@ -59,6 +59,39 @@ def na_canonical_base_pair_ints(restype_to_int):
     return [(restype_to_int[a], restype_to_int[b]) for a, b in NA_CANONICAL_BASE_PAIRS]
 
 
+# Token maps of base-paired design (ProteinMPNN.sample with feature_dict["paired_residues"]): the partner of a residue receives the
+# Watson-Crick complement of its token.  WC_SAME pairs two residues of one polymer type; WC_CROSS pairs a DNA residue with an RNA
+# residue.  Only the canonical pairs are expressed (no G-U wobble).  Every other residue type maps to itself.
+WC_SAME = {"DA": "DT", "DT": "DA", "DC": "DG", "DG": "DC", "A": "U", "U": "A", "C": "G", "G": "C"}
+WC_CROSS = {"DA": "U", "U": "DA", "DT": "A", "A": "DT", "DC": "G", "G": "DC", "DG": "C", "C": "DG"}
+SPECIAL_RESTYPES = ("UNK", "DX", "RX", "MAS", "PAD")
+
+
+def token_map(restype_to_int, kind):
+    """The token map `kind` ("same" / WC_SAME or "cross" / WC_CROSS) as a list over the vocabulary: entry t is the token paired with
+    token t.  An involution that fixes the amino acids and the special tokens; under the shared DNA/RNA tokens both kinds coincide."""
+    names = {"same": WC_SAME, "cross": WC_CROSS}[kind] if isinstance(kind, str) else kind
+    out = list(range(len(RESTYPES)))
+    for a, b in names.items():
+        out[restype_to_int[a]] = restype_to_int[b]
+    return out
+
+
+def check_token_map(restype_to_int, tmap, what="token map"):
+    """ValueError unless `tmap` is a permutation of the vocabulary that is its own inverse and fixes every special token."""
+    tmap = [int(t) for t in tmap]
+    n = len(RESTYPES)
+    if len(tmap) != n or any(not 0 <= t < n for t in tmap):
+        raise ValueError(f"{what}: expected {n} token ids in [0, {n}); got {tmap}")
+    for t, u in enumerate(tmap):
+        if tmap[u] != t:
+            raise ValueError(f"{what} is not an involution: token {t} -> {u} -> {tmap[u]}")
+    for name in SPECIAL_RESTYPES:
+        if tmap[restype_to_int[name]] != restype_to_int[name]:
+            raise ValueError(f"{what} moves the special token {name}")
+    return tmap
+
+
 def state_dict_spec(num_encoder_layers: int = 3, num_decoder_layers: int = 3,
                     hidden: int = H, vocab: int = VOCAB, num_letters: int = VOCAB):
     """Ordered {key: shape} of the reference ``ProteinMPNN.state_dict()``.

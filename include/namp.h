@@ -688,6 +688,25 @@ int namp_decoder_sample_walk(const NampModelW* w, const float* h_V_enc, const fl
  * maps give the bits of a call without maps.  Not together with pair_bias (NAMP_EINVAL from the sampler call). */
 int namp_sample_token_maps(const int32_t* tok_maps, int n_maps);
 
+/* Class tables: the generalisation of the token maps in which a group draws a PAIR CLASS instead of a token (base pairs with G-U
+ * wobble: "G pairs with C or U" is no map).  Attached to the calling thread's next sampler call and cleared by it exactly as the
+ * token maps are, and in their place.  tables: ONE device array, alive until that call's work is done —
+ *   int32 [n_tables][64]   C_k[c]: the token of a member with table k under class c, -1: the member has no token for class c;
+ *                          on the classes c < vocab a table is a token map (its own inverse, special tokens on their own lanes),
+ *                          every class >= n_classes is -1;
+ *   int32 [B_enc][N]       the table of every residue, in [0, n_tables);
+ *   float [n_tables][64]   the bias of class c in a group whose closing (last listed) member has table k.
+ * n_classes in [vocab, 64].  All members of a group must have tokens for the same classes: the classes of a group are read from its
+ * closing member's table.  With total[c] = sum_j w_j * logits_j[C_j[c]] +
+ * bias_close[C_close[c]] + class_bias[c] over those classes, p = softmax(total / T) with the classes whose closing token is special
+ * removed and renormalised.  A fixed or forced member keeps its token and restricts the classes to those under which it holds that
+ * token (in visit order; a restriction that would leave no class with p > 0 is skipped); one class is drawn from p over what is left,
+ * renormalised, by the inverse CDF in ascending class index; a free member receives C_j[class].  The probability row of a designable
+ * member is the marginal of the unrestricted p, probs_j[t] = sum of p[c] over the classes with C_j[c] == t in ascending c; a fixed
+ * member's row is zero.  Tables that are maps below vocab with every further class biased to zero mass draw the bits of
+ * namp_sample_token_maps with free members.  Not together with pair_bias (NAMP_EINVAL from the sampler call). */
+int namp_sample_class_tables(const int32_t* tables, int n_tables, int n_classes);
+
 /* ---- tied states: the plan of one sequence sampled over M backbone states of the same molecule -------------------
  * M states of N residues, encoded as a batch, are ONE symmetric design on the block-diagonal flattened graph of M * N residues:
  * residue n of state m is flat residue m * N + n, its neighbours are E_idx[m][n][:] + m * N, and the M copies of a residue form a

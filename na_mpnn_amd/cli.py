@@ -54,8 +54,13 @@ def build_parser():
       "to fit all of them (ProteinMPNN.sample with state_weights)")
     a("--state_weights", type=str, default="", help="weights of the states in model order, e.g. '0.5,0.3,0.2' (default: 1/M each)")
     a("--paired_residues", type=str, default="", help="base pairs, e.g. 'A5:B20,A6:B19' (residues named as in --fixed_residues): the "
-      "second residue of a pair receives the Watson-Crick complement of the first (canonical pairs only; a fixed residue decides)")
+      "second residue of a pair receives the Watson-Crick complement of the first (canonical pairs; G-U as well with --paired_wobble 1; "
+      "a fixed residue decides)")
     a("--paired_strands", type=str, default="", help="chains paired antiparallel over their full lengths, e.g. 'A:B' or 'A:B,C:D'")
+    a("--paired_wobble", type=int, default=0, help="1 - a pair with an RNA residue may also be the G-U wobble pair (G with U, or with T "
+      "of a DNA partner), as the model weighs it against the canonical pairs")
+    a("--paired_wobble_bias", type=float, default=None, help="added to the logit sums of the two wobble classes of every pair before "
+      "the temperature (default 0; negative: fewer G-U pairs); needs --paired_wobble 1")
     a("--na_shared_tokens", type=int, default=1)
     a("--parse_na_only", type=int, default=0)
     a("--design_na_only", type=int, default=0)
@@ -141,6 +146,19 @@ def parse_pairs(paired_residues, paired_strands, encoded, chain_letters):
                              "paired strands must have equal lengths")
         pairs += list(zip(a, reversed(b)))
     return pairs
+
+
+def wobble_arguments(args, have_pairs):
+    """--paired_wobble / --paired_wobble_bias as the feature_dict keys of ProteinMPNN.sample ({} without wobble)."""
+    if args.paired_wobble not in (0, 1):
+        raise ValueError(f"--paired_wobble is 0 or 1; got {args.paired_wobble}")
+    if (args.paired_wobble or args.paired_wobble_bias is not None) and not have_pairs:
+        raise ValueError("--paired_wobble / --paired_wobble_bias need --paired_residues or --paired_strands")
+    if args.paired_wobble_bias is not None and not args.paired_wobble:
+        raise ValueError("--paired_wobble_bias needs --paired_wobble 1")
+    if not args.paired_wobble:
+        return {}
+    return {"paired_wobble": True, "paired_wobble_bias": float(args.paired_wobble_bias or 0.0)}
 
 
 def main(argv=None):
@@ -257,6 +275,7 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
         sym_res, sym_w = [[]], [[]]
 
     pairs = parse_pairs(args.paired_residues, args.paired_strands, encoded, list(P["chain_letters"]))
+    wobble = wobble_arguments(args, bool(pairs))
     if pairs and args.conditional_probs_only:
         raise ValueError("--conditional_probs_only scores a given sequence: it does not go with --paired_residues / --paired_strands")
 
@@ -264,6 +283,7 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
         fd = pdbio.to_feature_dict(P, chain_mask, device)
         if pairs:
             fd["paired_residues"] = pairs
+            fd.update(wobble)
         fd.update({"batch_size": args.batch_size, "temperature": args.temperature,
                    "bias": (-1e8 * omit_AA[None, None, :] + bias_AA).repeat(1, L, 1),
                    "symmetry_residues": sym_res, "symmetry_weights": sym_w})

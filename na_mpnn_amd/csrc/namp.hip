@@ -1250,6 +1250,13 @@ int namp_sample_token_maps(const int32_t* tok_maps, int n_maps) {
   return NAMP_OK;
 }
 
+int namp_sample_class_tables(const int32_t* tables, int n_tables, int n_classes) {
+  REQUIRE(tables == nullptr || (n_tables >= 1 && n_tables <= 4096), "namp_sample_class_tables: n_tables=%d", n_tables);
+  REQUIRE(tables == nullptr || (n_classes >= 1 && n_classes <= 64), "namp_sample_class_tables: n_classes=%d must be in [1,64]", n_classes);
+  g_tok_maps = tables; g_n_maps = tables ? (n_tables | (n_classes << 16)) : 0;       // (the class count rides in the upper half of the n_maps word)
+  return NAMP_OK;
+}
+
 static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
                           const int32_t* mask, const int32_t* mask_dec, const int32_t* chain_mask, const int32_t* S_true, const float* bias,
                           const int32_t* order, const int32_t* rank, const float* uniform, const int32_t* S_forced,
@@ -1261,10 +1268,12 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
   const int32_t* tok_maps = g_tok_maps; const int n_maps = g_n_maps;
   g_tok_maps = nullptr; g_n_maps = 0;                            // (one call only, whatever becomes of it)
   REQUIRE(w != nullptr, "namp_decoder_sample: null weights");
-  REQUIRE(tok_maps == nullptr || pair_bias == nullptr, "namp_decoder_sample: token maps and pair_bias do not go together");
+  REQUIRE(tok_maps == nullptr || pair_bias == nullptr, "namp_decoder_sample: token maps / class tables and pair_bias do not go together");
   REQUIRE((group_first == nullptr) == (group_last == nullptr), "namp_decoder_sample: group_first and group_last go together");
   REQUIRE(w->n_dec >= 1 && w->n_dec <= NAMP_MAX_LAYERS, "namp_decoder_sample: supports 1..%d decoder layers (got %d)", NAMP_MAX_LAYERS, w->n_dec);
   REQUIRE(w->vocab >= 1 && w->vocab <= 64, "namp_decoder_sample: vocab=%d must be in [1,64]", w->vocab);
+  REQUIRE((n_maps >> 16) == 0 || (n_maps >> 16) >= w->vocab, "namp_decoder_sample: %d pair classes are fewer than the vocabulary's %d tokens",
+          n_maps >> 16, w->vocab);
   REQUIRE_PTR(h_V_enc); REQUIRE_PTR(h_E); REQUIRE_PTR(ws);
   if (!E_idx || !mask || !chain_mask || !S_true || !bias || !order || !rank || !uniform || !S_out || !probs_out || !logp_out)
     return fail(NAMP_EINVAL, "namp_decoder_sample: null pointer argument");
@@ -1313,7 +1322,7 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
   SampleArgs a = {};
   a.hE = h_E; a.E_idx = E_idx; a.mask_true = mask; a.chain_mask = chain_mask; a.S_true = S_true; a.bias = bias; a.order = order; a.rank = rank;
   a.uniform = uniform; a.S_forced = S_forced; a.group_first = group_first; a.group_last = group_last;
-  a.sym_w = sym_weights; a.pair_bias = pair_bias; a.tok_maps = tok_maps; a.n_maps = n_maps; a.head_wT = head_wT; a.head_b = w->Wout_b; a.S_out = S_out;
+  a.sym_w = sym_weights; a.pair_bias = pair_bias; a.tok_maps = tok_maps; a.n_maps = n_maps & 0xffff; a.n_classes = n_maps >> 16; a.head_wT = head_wT; a.head_b = w->Wout_b; a.S_out = S_out;
   a.probs_out = probs_out; a.logp_out = logp_out; a.special = special_tokens; a.inv_T = 1.0f / temperature;
   a.B_dec = B_dec; a.B_enc = B_enc; a.N = N; a.K = K; a.TPN = (K + 15) / 16; a.n_layers = w->n_dec; a.vocab = w->vocab;
   // 8 waves per workgroup (256 VGPRs per lane: no scratch) serve 8 / TPN streams; K > 128 falls back to the 12-wave form

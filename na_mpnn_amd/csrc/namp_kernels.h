@@ -2119,6 +2119,9 @@ __device__ __forceinline__ float wv_lane(const float v, const int l) { return __
 __device__ __forceinline__ float wv_fetch(const float v, const int src) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v)));
 }
+// a wave-uniform value made opaque at this point: what is derived from it is computed here, not hoisted and kept in scalar registers across the
+// sampler's layers (the kernel's scalar registers are full: every further one is spilled to a lane of a vector register)
+__device__ __forceinline__ int scalar_here(int v) { asm volatile("" : "+s"(v)); return v; }
 __device__ __forceinline__ float wave_sum64(float v) {
   v += wv_dpp<0xB1>(v); v += wv_dpp<0x4E>(v); v += wv_dpp<0x141>(v); v += wv_dpp<0x140>(v);      // quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
   return (wv_lane(v, 0) + wv_lane(v, 16)) + (wv_lane(v, 32) + wv_lane(v, 48));
@@ -2171,8 +2174,13 @@ struct SampleArgs {
   unsigned long long special;  // bit t set -> token t can never be drawn
   float inv_T;
   int B_dec, B_enc, N, K, TPN, n_layers, vocab, slots;
+  int n_classes;               // 0, or the class count of CLASS TABLES (base pairs with G-U wobble): tok_maps then holds [n_maps][64] tables C (C[c]: the
+                               // member's token under pair class c, -1: no such class), [G_enc] the table of a residue, and behind them [n_maps][64]
+                               // float: the bias of class c in a group whose closing member has that table.  (A word of its own, not bits of n_maps:
+                               // the fetch in `step` reads a.n_maps as the parent does.  With the 4 bytes of padding behind it the struct and the
+                               // launch's own 40 argument bytes fill the 4,096 bytes exactly.)
   int n_maps;                  // (in the padding in front of l: the struct grows by the one pointer only)
-  SampleLayer l[NAMP_MAX_LAYERS];      // 8 x 480 B: with the scalars and the launch's own 40 argument bytes 4,088 of the 4,096 kernel-argument bytes
+  SampleLayer l[NAMP_MAX_LAYERS];      // 8 x 480 B: with the scalars and the launch's own 40 argument bytes all 4,096 kernel-argument bytes
 };
 static_assert(sizeof(SampleArgs) + 40 <= 4096, "SampleArgs + the sampler launch's scalar arguments must fit the kernel-argument segment");
 
@@ -2344,6 +2352,68 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     const int iq = a.order[(long)bq * a.N + t];
     const int ne = (bq % a.B_enc) * a.N + iq;
     const long vis = (long)bq * a.N + t;
+    const int nm = scalar_here(a.n_maps) | (scalar_here(a.n_classes) << 16);      // (both counts in one scalar register: n_maps <= 4096)
+    if (nm >> 16) {
+      // Class tables: the group draws a PAIR CLASS c = lane, member j holds C_j[c].  Lanes < vocab are the group tokens of the maps (the
+      // tables are involutions there), the lanes from vocab on are further classes (G-U wobble) that several classes may share a token with.
+      const int n_cls = nm >> 16;
+      const int32_t* tab_idx = a.tok_maps + (nm & 0xffff) * 64;
+      const float* cls_bias = (const float*)(tab_idx + a.B_enc * a.N);
+      const int e0 = (bq % a.B_enc) * a.N;
+      const int kc = tab_idx[ne];
+      const int ce = a.tok_maps[kc * 64 + lane];
+      const int bl = ce < 0 ? 0 : ce;                                  // the closing member's token of class `lane` (clamped: loads stay unconditional)
+      const float add = a.bias[(long)ne * a.vocab + bl] + cls_bias[kc * 64 + lane];
+      const float u = a.uniform[vis];
+      // the classes of a group are those of its closing member's table: every member of a group has a token for the same classes (the
+      // host builds the tables so), and the sum of any other class — some lane's logit, see the fetch in `step` — is never looked at
+      const bool ok = lane < n_cls && ce >= 0;
+      const float zt = ok ? (total + add) * a.inv_T : -INFINITY;
+      const float mt = wave_max64(zt);
+      float p = ok ? expf(zt - mt) : 0.f;
+      p = p / wave_sum64(p);
+      if ((a.special >> bl) & 1ull) p = 0.f;
+      p = p / wave_sum64(p);
+      // a pinned member (fixed, or forced) does not overwrite a running token: it RESTRICTS the classes to those under which it holds its
+      // token, in visit order; a restriction that would leave no class is skipped
+      const unsigned long long any = __ballot(p > 0.f);
+      unsigned long long keep = any;
+      for (int v = v_first; v <= t; ++v) {
+        const int im = a.order[(long)bq * a.N + v];
+        const int cm = a.chain_mask[e0 + im];
+        int tk = -2;                                                   // (no table entry is -2: a free member restricts nothing)
+        if (a.S_forced) tk = a.S_forced[(long)bq * a.N + im];
+        if (!cm) tk = a.S_true[e0 + im];
+        const unsigned long long r = keep & __ballot(a.tok_maps[tab_idx[e0 + im] * 64 + lane] == tk);
+        if (r) keep = r;
+      }
+      float pr = ((keep >> lane) & 1ull) ? p : 0.f;
+      if (keep != any) pr = pr / wave_sum64(pr);
+      const float cdf = wave_scan64(pr, lane);
+      const unsigned long long hit = __ballot(pr > 0.f && cdf > u);
+      const int cls = hit ? (int)__builtin_ctzll(hit) : (keep ? 63 - (int)__builtin_clzll(keep) : 0);
+      for (int v = v_first; v <= t; ++v) {
+        const int im = a.order[(long)bq * a.N + v];
+        const int nem = e0 + im;
+        const long ndm = (long)bq * a.N + im;
+        const int cm = a.chain_mask[nem];
+        const int32_t* pm = a.tok_maps + tab_idx[nem] * 64;
+        const int cv = pm[lane];
+        int tok = pm[cls];
+        if (a.S_forced) tok = a.S_forced[ndm];
+        if (!cm) tok = a.S_true[nem];
+        // the member's row: the marginal of the unrestricted p in its own alphabet — lane = token; the one class below vocab that gives
+        // it (the table is an involution there), then the further classes in ascending order: no two lanes write one address
+        float row = wv_fetch(p, (lane < a.vocab && cv >= 0) ? cv : 0);
+        for (int c = a.vocab; c < n_cls; ++c) {
+          const float pc = wv_lane(p, c);
+          if (lane == __builtin_amdgcn_readlane(cv, c)) row += pc;
+        }
+        if (lane < a.vocab) a.probs_out[ndm * a.vocab + lane] = cm ? row : 0.f;
+        if (lane == 0) __hip_atomic_store(a.S_out + ndm, tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      return;
+    }
     // (mapped groups: group token `lane` is the closing member's token P_c[lane], so its bias row is read through its map)
     const int32_t* map_idx = a.tok_maps + a.n_maps * 64;             // (read only where tok_maps is set)
     const int bl = a.tok_maps ? a.tok_maps[map_idx[ne] * 64 + lane] : lane;
@@ -2578,6 +2648,8 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
         const int v_first = a.group_first ? a.group_first[vis] : t;
         const float wsym = a.sym_w ? a.sym_w[ne] : 1.0f;
         float zz = (lane < a.vocab) ? z : 0.f;
+        // (class tables: an entry -1 — a class the member has no token for — selects lane 63, ds_bpermute_b32 taking bits 7:2 of its byte address;
+        //  no memory is touched, and the draw never looks at the sum of such a class.  Masking the entry here cost the <1, false, 12> form 8 bytes of scratch.)
         if (a.tok_maps) zz = wv_fetch(zz, a.tok_maps[a.tok_maps[a.n_maps * 64 + ne] * 64 + lane]);      // the member's logit of group token `lane`
         tot = (v_first == t) ? wsym * zz : fmaf(wsym, zz, tot);
         const bool closes = a.group_last ? (a.group_last[vis] != 0) : true;

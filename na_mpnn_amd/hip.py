@@ -208,6 +208,7 @@ _PROTOTYPES = {
     "namp_decoder_fwd": (i32, [C.POINTER(NampModelW), c_fp, c_fp, c_ip, c_ip, c_ip, c_ip, c_fp, c_fp, c_fp,
                                vp, sz, i32, i32, i32, i32, vp]),
     "namp_sample_token_maps": (i32, [c_ip, i32]),
+    "namp_sample_class_tables": (i32, [c_ip, i32, i32]),
     "namp_pairs_plan": (i32, [c_ip] * 8 + [i32, i32, vp]),
     "namp_pairs_work_lists": (i32, [c_ip] * 6 + [i32, i32, vp]),
     "namp_states_plan": (i32, [c_ip, c_ip, c_ip, c_fp] + [c_ip] * 5 + [c_fp] + [c_ip] * 7 + [i32, i32, i32, i32, vp]),

@@ -155,7 +155,8 @@ def symmetry_visits(groups, weights, order0, L):
     return visits, gf, gl, w
 
 
-def mapped_groups(L, restype_to_int, pairs=None, pair_weights=None, polymer=None, fixed=None, groups=None, weights=None, maps=None):
+def mapped_groups(L, restype_to_int, pairs=None, pair_weights=None, polymer=None, fixed=None, groups=None, weights=None, maps=None,
+                  wobble=None, wobble_bias=None):
     """Groups of mapped symmetry-tied sampling — base pairs (feature_dict["paired_residues"]) and explicit token maps
     (feature_dict["symmetry_token_maps"]) — as plain lists; needs no device.
 
@@ -169,7 +170,14 @@ def mapped_groups(L, restype_to_int, pairs=None, pair_weights=None, polymer=None
     by the pair's weight of that side, the maps of j's side composed with the pair's map.
     Returns (groups, weights, maps, pair_list): lists parallel to each other, every map a list of vocab ids; pair_list = the pairs as
     (first listed, second listed, w_first, w_second, kind) when the pairs are ALL there is (else None).  ValueError on a residue in two
-    pairs, paired with itself, outside [0, L) or not a nucleic acid, and on a map that is not an involution or moves a special token."""
+    pairs, paired with itself, outside [0, L) or not a nucleic acid, and on a map that is not an involution or moves a special token.
+
+    wobble (None: as above; a bool, or one per pair): the call speaks in PAIR CLASSES (spec.class_table) — a pair that asks for wobble
+    and has an RNA member may also hold G-U / U-G (classes spec.CLASS_GU / CLASS_UG: the first listed member's G with the second's U / T,
+    and the reverse), with wobble_bias (a float, or one per pair; default 0) added to the totals of those two classes.  Returns
+    (groups, weights, tables, pair_list, class_bias) then: per member a table of spec.N_CLASS_LANES ids (-1: no such class; a pair
+    without wobble and every other group: its map, -1 beyond the vocabulary), per group the N_CLASS_LANES biases of its classes.
+    ValueError on a wobble pair with a member in a symmetry_residues group (tables that are no maps do not compose)."""
     V = len(spec.RESTYPES)
     ident = list(range(V))
     out, group_of = [], {}                                   # out: [members, weights, maps] or None once merged away
@@ -194,6 +202,8 @@ def mapped_groups(L, restype_to_int, pairs=None, pair_weights=None, polymer=None
             out.append([[int(r) for r in g], [float(v) for v in weights[gi]], ms])
     pair_list = [] if plain else None
     paired = set()
+    per_pair = lambda v, n, default: default if v is None else (v[n] if hasattr(v, "__len__") else v)
+    wobbling = {}                                            # (first listed, second listed) -> (kind of spec.PAIR_KINDS, bias)
     for n, pr in enumerate(pairs or []):
         i, j = int(pr[0]), int(pr[1])
         pw = (1.0, 1.0) if pair_weights is None else pair_weights
@@ -217,6 +227,16 @@ def mapped_groups(L, restype_to_int, pairs=None, pair_weights=None, polymer=None
         P = spec.token_map(restype_to_int, kind)
         if pair_list is not None:
             pair_list.append((i, j, wi, wj, kind))
+        if wobble is not None and bool(per_pair(wobble, n, False)):
+            if polymer is None:
+                raise ValueError("paired_wobble needs the polymer type of the paired residues")
+            for r in (i, j):
+                if r in group_of:
+                    raise ValueError(f"paired_wobble: residue {r} of the wobble pair ({i}, {j}) sits in a symmetry_residues group; "
+                                     "wobble pairs do not join symmetry groups")
+            names = {1: "dna", 2: "rna"}
+            if 2 in (int(polymer[i]), int(polymer[j])):                         # (a DNA-DNA pair never wobbles)
+                wobbling[(i, j)] = (f"{names[int(polymer[i])]}-{names[int(polymer[j])]}", float(per_pair(wobble_bias, n, 0.0)))
         for r in (i, j):
             if r not in group_of:
                 group_of[r] = len(out)
@@ -237,7 +257,32 @@ def mapped_groups(L, restype_to_int, pairs=None, pair_weights=None, polymer=None
     for g in out:
         for r, m in zip(g[0], g[2]):
             spec.check_token_map(restype_to_int, m, f"the token map of residue {r}")
-    return [g[0] for g in out], [g[1] for g in out], [g[2] for g in out], pair_list
+    if wobble is None:
+        return [g[0] for g in out], [g[1] for g in out], [g[2] for g in out], pair_list
+    # (a design has a few distinct tables for hundreds of pairs: each is built and checked once, and shared)
+    tables, class_bias, made, biases = [], [], {}, {}
+
+    def table(key, make, r):
+        t = made.get(key)
+        if t is None:
+            t = spec.check_class_table(restype_to_int, make(), f"the class table of residue {r}")
+            t = made[key] = (t, tuple(c >= 0 for c in t))
+        return t
+    for g in out:
+        kind, b = wobbling.get(tuple(g[0]), (None, 0.0))
+        if kind is None:
+            ts = [table(tuple(m), lambda m=m: list(m) + [-1] * (spec.N_CLASS_LANES - V), r) for r, m in zip(g[0], g[2])]
+        else:
+            ts = [table((kind, first), lambda first=first: spec.class_table(restype_to_int, kind, True, first), r)
+                  for r, first in zip(g[0], (True, False))]
+        if any(t[1] is not ts[0][1] and t[1] != ts[0][1] for t in ts):          # (the sampler reads a group's classes from its closing member)
+            raise ValueError(f"the members of group {g[0]} do not have tokens for the same pair classes")
+        if b not in biases:
+            biases[b] = [0.0] * spec.N_CLASS_LANES
+            if kind is not None:
+                biases[b][spec.CLASS_GU] = biases[b][spec.CLASS_UG] = b
+        tables.append([t[0] for t in ts]); class_bias.append(biases[b])       # (b is 0 for a group that is no wobble pair)
+    return [g[0] for g in out], [g[1] for g in out], tables, pair_list, class_bias
 
 
 def pair_bias_dependencies(pair_bias, max_deps=64):
@@ -448,8 +493,21 @@ class ProteinMPNN(nn.Module):
     def _mapped_arguments(self, fd, B, L):
         """Base pairs / token maps of a sample() call (feature_dict["paired_residues"], "paired_weights", "symmetry_token_maps") ->
         (groups, weights, the token maps as n_maps lists of 64 ids (map 0: the identity), the map index of every residue as a list of L,
-        pair_list or None), see mapped_groups(); None without them."""
+        pair_list or None, None), see mapped_groups(); None without them.  With feature_dict["paired_wobble"] (a bool, or one per pair;
+        "paired_wobble_bias": a float, or one per pair) true for some pair the maps are class tables (table 0: the identity below the
+        vocabulary, -1 beyond) and the last entry holds the 64 class biases of every table: tables are told apart by (table, bias)."""
         pairs, maps = fd.get("paired_residues"), fd.get("symmetry_token_maps")
+        wobble, wobble_bias = fd.get("paired_wobble"), fd.get("paired_wobble_bias")
+        to_list = lambda v: v.detach().reshape(-1).tolist() if torch.is_tensor(v) else (list(v) if hasattr(v, "__len__") else v)
+        wobble, wobble_bias = to_list(wobble), to_list(wobble_bias)
+        n_pairs = 0 if pairs is None else len(pairs)
+        for v, what in ((wobble, "paired_wobble"), (wobble_bias, "paired_wobble_bias")):
+            if isinstance(v, list) and len(v) != n_pairs:
+                raise ValueError(f"{what} has {len(v)} entries for {n_pairs} pairs")
+        if not (any(wobble) if isinstance(wobble, list) else bool(wobble)):
+            wobble = None                                                        # no pair asks for wobble: the token maps, as without the key
+        elif n_pairs == 0:
+            raise ValueError("paired_wobble needs paired_residues")
         if (pairs is None or len(pairs) == 0) and maps is None:
             return None
         if self.restype_to_int is None:
@@ -464,27 +522,54 @@ class ProteinMPNN(nn.Module):
             polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
             m, cm = self._host_list(fd["mask"], "mask"), self._host_list(fd["chain_mask"], "chain_mask")
             fixed = [not (a and b) for a, b in zip(m, cm)]                       # (a masked residue keeps its token as a fixed one does)
-        groups, weights, gmaps, pair_list = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, fixed,
-                                                          fd.get("symmetry_residues"), fd.get("symmetry_weights"), maps)
-        table, index = [list(range(64))], {tuple(range(self.num_letters)): 0}
-        idx = [None] * L
-        for g, ms in zip(groups, gmaps):
+        groups, weights, gmaps, pair_list, *gbias = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, fixed,
+                                                                  fd.get("symmetry_residues"), fd.get("symmetry_weights"), maps,
+                                                                  wobble, wobble_bias)
+        idx, seen = [None] * L, {}
+        if wobble is None:
+            table, index, bias = [list(range(64))], {tuple(range(self.num_letters)): 0}, None
+            gbias = [None] * len(groups)
+        else:
+            V = len(spec.RESTYPES)
+            table, bias = [list(range(V)) + [-1] * (spec.N_CLASS_LANES - V)], [[0.0] * spec.N_CLASS_LANES]
+            index, gbias = {(tuple(table[0]), tuple(bias[0])): 0}, gbias[0]
+        for g, ms, gb in zip(groups, gmaps, gbias):
             for r, m in zip(g, ms):
                 if idx[r] is not None:                                            # (listed in an earlier group: it belongs to that one)
                     continue
-                k = index.get(tuple(m))
+                k = seen.get((id(m), id(gb)))                                   # (shared list objects: hundreds of pairs, a few tables)
+                if k is not None:
+                    idx[r] = k
+                    continue
+                key = tuple(m) if gb is None else (tuple(m), tuple(gb))
+                k = index.get(key)
+                seen[(id(m), id(gb))] = len(table) if k is None else k
                 if k is None:
-                    k = index[tuple(m)] = len(table)
+                    k = index[key] = len(table)
                     table.append(list(m) + list(range(len(m), 64)))
+                    if gb is not None:
+                        bias.append(list(gb))
                 idx[r] = k
         if not groups:
             groups, weights = [[]], [[]]
-        return groups, weights, table, [k or 0 for k in idx], pair_list
+        return groups, weights, table, [k or 0 for k in idx], pair_list, bias
 
     @staticmethod
-    def _token_map_array(table, idx, device):
-        """What namp_sample_token_maps takes: ONE int32 array, the maps [n_maps][64] and behind them the map index of every residue."""
-        return torch.tensor([t for m in table for t in m] + list(idx), dtype=torch.int32).to(device)
+    def _token_map_array(table, idx, device, bias=None):
+        """What namp_sample_token_maps takes: ONE int32 array, the maps [n_maps][64] and behind them the map index of every residue; with
+        `bias` what namp_sample_class_tables takes: behind those the class biases [n_maps][64] as float32 (their bits, in the one array)."""
+        ints = torch.tensor([t for m in table for t in m] + list(idx), dtype=torch.int32)
+        if bias is not None:
+            ints = torch.cat((ints, torch.tensor([b for row in bias for b in row], dtype=torch.float32).view(torch.int32)))
+        return ints.to(device)
+
+    def _attach_maps(self, tok_maps, n_maps, classes):
+        """The token maps (class tables: `classes`) go to the NEXT sampler call of this thread."""
+        Lb = hip.lib()
+        if tok_maps is not None and classes:
+            hip.check(Lb.namp_sample_class_tables(tok_maps.data_ptr(), n_maps, spec.N_CLASSES), "sample_class_tables")
+        elif tok_maps is not None:
+            hip.check(Lb.namp_sample_token_maps(tok_maps.data_ptr(), n_maps), "sample_token_maps")
 
     def _as(self, t, kind):
         """`t` in the dtype / layout the kernels read ("i32": int32, "f32": float32; contiguous), converted ONCE per tensor object: a
@@ -850,12 +935,12 @@ class ProteinMPNN(nn.Module):
         sym, sym_weights = fd.get("symmetry_residues", [[]]), fd.get("symmetry_weights", [[]])
         B, L = S_true.shape
         dev = S_true.device
-        tok_maps = pair_list = None
+        tok_maps = pair_list = cls_bias = None
         n_maps = 0
         mapped = self._mapped_arguments(fd, B, L)                                 # base pairs / token maps: mapped symmetry groups
         if mapped is not None:
-            sym, sym_weights, table, idx, pair_list = mapped
-            tok_maps, n_maps = self._token_map_array(table, idx, dev), len(table)
+            sym, sym_weights, table, idx, pair_list, cls_bias = mapped
+            tok_maps, n_maps = self._token_map_array(table, idx, dev, cls_bias), len(table)
         symmetric = not (len(sym) == 1 and len(sym[0]) == 0)
         self._check_tokens(S_true)
         if fd.get("S_forced") is not None:
@@ -953,9 +1038,8 @@ class ProteinMPNN(nn.Module):
         tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
                 B_dec, B, L, K, hip.current_stream())
 
-        def attach():       # the token maps go to the NEXT sampler call of this thread (namp_sample_token_maps)
-            if tok_maps is not None:
-                hip.check(Lb.namp_sample_token_maps(tok_maps.data_ptr(), n_maps), "sample_token_maps")
+        def attach():       # the token maps go to the NEXT sampler call of this thread (namp_sample_token_maps / namp_sample_class_tables)
+            self._attach_maps(tok_maps, n_maps, cls_bias is not None)
         out = {"S": None, "sampling_probs": probs, "log_probs": logp, "decoding_order": order, "uniform": uniform}   # (S: after the launch)
         if not (self.sample_level_parallel and deps is not None):
             attach()
@@ -1117,12 +1201,12 @@ class ProteinMPNN(nn.Module):
         [bs, L, V], log_probs [bs, M, L, V], decoding_order [bs, L], uniform [bs, L] (by step), levels, work_items."""
         w, M, L, bs, symmetric = self._states_arguments(fd)
         sym_groups, sym_weights = fd.get("symmetry_residues", [[]]), fd.get("symmetry_weights", [[]])
-        tok_maps, n_maps = None, 0
+        tok_maps, n_maps, cls_bias = None, 0, None
         mapped = self._mapped_arguments(fd, 1, L)                                   # base pairs beside the states: the host route
         if mapped is not None:
-            sym_groups, sym_weights, table, idx, _ = mapped
+            sym_groups, sym_weights, table, idx, _, cls_bias = mapped
             symmetric = not (len(sym_groups) == 1 and len(sym_groups[0]) == 0)
-            tok_maps, n_maps = self._token_map_array(table, idx * M, fd["S"].device), len(table)   # flat residue m * L + i speaks as residue i does
+            tok_maps, n_maps = self._token_map_array(table, idx * M, fd["S"].device, cls_bias), len(table)   # flat residue m * L + i speaks as residue i does
         S_true, mask = fd["S"], fd["mask"]
         dev, N, Vn = S_true.device, M * L, self.num_letters
         _require_device(fd["X"], "X")
@@ -1219,8 +1303,7 @@ class ProteinMPNN(nn.Module):
                   group_first.data_ptr(), group_last.data_ptr(), sym_w.data_ptr(), None)
         tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
                 bs, 1, N, K, hip.current_stream())
-        if tok_maps is not None:                    # the token maps go to the NEXT sampler call of this thread (namp_sample_token_maps)
-            hip.check(Lb.namp_sample_token_maps(tok_maps.data_ptr(), n_maps), "sample_token_maps")
+        self._attach_maps(tok_maps, n_maps, cls_bias is not None)
         if not walk:
             counts = torch.bincount(flat).cpu().tolist()                       # per-level launches: one host sync
             hip.check(Lb.namp_decoder_sample_levels(*common, work.data_ptr(), work_n.data_ptr(), (C.c_int32 * len(counts))(*counts),

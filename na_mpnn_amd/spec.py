@@ -61,7 +61,8 @@ def na_canonical_base_pair_ints(restype_to_int):
 
 # Token maps of base-paired design (ProteinMPNN.sample with feature_dict["paired_residues"]): the partner of a residue receives the
 # Watson-Crick complement of its token.  WC_SAME pairs two residues of one polymer type; WC_CROSS pairs a DNA residue with an RNA
-# residue.  Only the canonical pairs are expressed (no G-U wobble).  Every other residue type maps to itself.
+# residue.  A map expresses the canonical pairs only; the G-U wobble pair is expressed by the class tables below.  Every other residue
+# type maps to itself.
 WC_SAME = {"DA": "DT", "DT": "DA", "DC": "DG", "DG": "DC", "A": "U", "U": "A", "C": "G", "G": "C"}
 WC_CROSS = {"DA": "U", "U": "DA", "DT": "A", "A": "DT", "DC": "G", "G": "DC", "DG": "C", "C": "DG"}
 SPECIAL_RESTYPES = ("UNK", "DX", "RX", "MAS", "PAD")
@@ -90,6 +91,57 @@ def check_token_map(restype_to_int, tmap, what="token map"):
         if tmap[restype_to_int[name]] != restype_to_int[name]:
             raise ValueError(f"{what} moves the special token {name}")
     return tmap
+
+
+# Pair classes of base-paired design with G-U wobble ("G pairs with C or U" is no map of the vocabulary): a pair draws one of N_CLASSES
+# classes and each member reads its token from a class table.  Class a < VOCAB: the first-listed member holds token a, the second its
+# Watson-Crick complement (the token maps above).  CLASS_GU: the first member holds its G, the second its U / T; CLASS_UG: the first its
+# U / T, the second its G — "its" base by the member's own polymer type (WOBBLE_G / WOBBLE_U).  A pair has the two wobble classes only
+# if wobble was asked for on it and at least one member is RNA.
+N_CLASS_LANES = 64
+CLASS_GU, CLASS_UG = VOCAB, VOCAB + 1
+N_CLASSES = VOCAB + 2
+WOBBLE_G = {"dna": "DG", "rna": "G"}
+WOBBLE_U = {"dna": "DT", "rna": "U"}
+PAIR_KINDS = ("dna-dna", "dna-rna", "rna-dna", "rna-rna")          # polymer type of the first-listed member - of the second
+
+
+def class_table(restype_to_int, kind, wobble, first):
+    """The class table of one member of a base pair as a list of N_CLASS_LANES token ids: entry c is the member's token under pair class
+    c, -1 where the pair has no such class.  kind: the polymer types of the two members in listed order, one of PAIR_KINDS ("same" /
+    "cross" are accepted for a pair without wobble); first: the first-listed member (the identity on the classes below VOCAB) or the
+    second (the Watson-Crick map of the kind).  The wobble classes are filled only with `wobble` and an RNA member in the pair."""
+    if kind in ("same", "cross"):
+        if wobble:
+            raise ValueError(f"class_table: kind '{kind}' does not say which member is RNA; name it as one of {PAIR_KINDS}")
+        wc = kind
+    elif kind in PAIR_KINDS:
+        wc = "same" if kind in ("dna-dna", "rna-rna") else "cross"
+    else:
+        raise ValueError(f"class_table: unknown kind '{kind}'")
+    out = (list(range(len(RESTYPES))) if first else token_map(restype_to_int, wc)) + [-1] * (N_CLASS_LANES - len(RESTYPES))
+    if wobble and kind != "dna-dna":
+        own = kind.split("-")[0 if first else 1]
+        g, u = restype_to_int[WOBBLE_G[own]], restype_to_int[WOBBLE_U[own]]
+        out[CLASS_GU], out[CLASS_UG] = (g, u) if first else (u, g)
+    return out
+
+
+def check_class_table(restype_to_int, table, what="class table"):
+    """ValueError unless `table` has N_CLASS_LANES entries in [-1, vocab), is a token map (check_token_map) on the classes below the
+    vocabulary's size, is -1 from N_CLASSES on and holds a special token on no other lane than that token's own."""
+    table = [int(t) for t in table]
+    n = len(RESTYPES)
+    if len(table) != N_CLASS_LANES or any(not -1 <= t < n for t in table):
+        raise ValueError(f"{what}: expected {N_CLASS_LANES} entries in [-1, {n}); got {table}")
+    check_token_map(restype_to_int, table[:n], what)
+    special = {restype_to_int[name]: name for name in SPECIAL_RESTYPES}
+    for c in range(n, N_CLASS_LANES):
+        if table[c] in special:
+            raise ValueError(f"{what} moves the special token {special[table[c]]} to class {c}")
+        if c >= N_CLASSES and table[c] != -1:
+            raise ValueError(f"{what}: class {c} is beyond the {N_CLASSES} pair classes and must be -1")
+    return table
 
 
 def state_dict_spec(num_encoder_layers: int = 3, num_decoder_layers: int = 3,

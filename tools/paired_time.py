@@ -5,6 +5,9 @@ plain sample() — the floor, and the parent build's code.  Synthetic backbones 
 in split-bf16; they are alternated in one process, synchronised, and reported as medians with their [min, max] spread after warm-up.
 
     python tools/paired_time.py [--reps 7] [--sizes 300x20x32x1,0x150x48x8]     (protein residues x strand length x K x batch_size)
+
+--wobble: the same shapes with an RNA duplex, the paired call (device plan) with paired_wobble on — the class tables of the sampler,
+G-U pairs allowed — alternated with the same call with wobble off (the token maps: canonical pairs only).
 """
 import os, sys, time
 import numpy as np, torch
@@ -26,10 +29,10 @@ def model(k):
     m.load_state_dict({k_: torch.from_numpy(v) for k_, v in w.items()}); return m.to(dev).eval()
 
 
-def inputs(n_prot, n_strand, bs):
-    """A protein of n_prot residues (none for 0) with a DNA duplex of 2 x n_strand residues, the strands paired antiparallel."""
+def inputs(n_prot, n_strand, bs, rna=False):
+    """A protein of n_prot residues (none for 0) with a DNA (rna: RNA) duplex of 2 x n_strand residues, the strands paired antiparallel."""
     L = n_prot + 2 * n_strand
-    cx = synth.make_complex(seed=3, n=L, n_chains=1, frac_protein=n_prot / L, frac_dna=2 * n_strand / L)
+    cx = synth.make_complex(seed=3, n=L, n_chains=1, frac_protein=n_prot / L, frac_dna=0.0 if rna else 2 * n_strand / L)
     cx["chain_labels"] = np.searchsorted([n_prot, n_prot + n_strand] if n_prot else [n_strand], np.arange(L), side="right").astype(np.int32)
     for c in range(int(cx["chain_labels"].max()) + 1):
         sel = cx["chain_labels"] == c
@@ -46,10 +49,39 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
+def time_wobble(m, n_prot, n_strand, K, bs, reps):
+    """Wobble on against wobble off on an RNA duplex: medians of `reps` alternated synchronised calls, with what was drawn."""
+    _, paired, pairs = inputs(n_prot, n_strand, bs, rna=True)
+    calls = {"wobble on": lambda: m.sample(dict(paired, paired_wobble=True)), "wobble off": lambda: m.sample(paired)}
+    torch.manual_seed(1); a = calls["wobble on"]()
+    rti = spec.restype_to_int()
+    i, j = (torch.tensor(v, device=dev) for v in zip(*pairs))
+    comp = torch.tensor(spec.token_map(rti, "same"), device=dev)
+    Si, Sj = a["S"][:, i], a["S"][:, j]
+    canonical = Sj == comp[Si]
+    gu = ((Si == rti["G"]) & (Sj == rti["U"])) | ((Si == rti["U"]) & (Sj == rti["G"]))
+    for f in calls.values():
+        f(); f()
+    t = {name: [] for name in calls}
+    for _ in range(reps):
+        for name, f in calls.items():
+            t[name].append(timed(f))
+    med = {name: float(np.median(v)) for name, v in t.items()}
+    txt = "  ".join(f"{name} {med[name]:.2f} ms [{min(v):.2f}, {max(v):.2f}]" for name, v in t.items())
+    spread = max(max(v) - min(v) for v in t.values())
+    print(f"protein={n_prot} RNA duplex=2x{n_strand} K={K} batch_size={bs}: {txt}  (on - off {med['wobble on'] - med['wobble off']:+.2f} ms, "
+          f"larger min-max spread of the two {spread:.2f} ms; {int(a['levels'])} levels, {a['work_items']} work items; pairs drawn with "
+          f"wobble on: {int(canonical.sum())} canonical, {int(gu.sum())} G-U, {int((~canonical & ~gu).sum())} other; {reps} calls each, "
+          f"from coordinates)", flush=True)
+
+
 reps = int(arg("--reps", "7"))
 for size in arg("--sizes", "300x20x32x1,0x150x48x8").split(","):
     n_prot, n_strand, K, bs = map(int, size.split("x"))
     m = model(K)
+    if "--wobble" in sys.argv:
+        time_wobble(m, n_prot, n_strand, K, bs, reps)
+        continue
     plain, paired, pairs = inputs(n_prot, n_strand, bs)
 
     def route(device_plan):

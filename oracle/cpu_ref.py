@@ -136,7 +136,7 @@ def rbf_all_pairs(X18, E_idx, M18, num_rbf=16):
     Xg = gather_nodes(X18.reshape(b, l, -1), E_idx)
     Xg = Xg.reshape(list(Xg.shape[:-1]) + list(X18.shape[-2:]))
     D = torch.sqrt(torch.sum((X18[:, :, None, :, None, :] - Xg[:, :, :, None, :, :]) ** 2, -1) + 1e-6)
-    mu = torch.linspace(2., 22., num_rbf).view(1, 1, 1, 1, 1, -1)
+    mu = torch.linspace(2., 22., num_rbf, dtype=D.dtype).view(1, 1, 1, 1, 1, -1)
     sigma = (22. - 2.) / num_rbf
     R = torch.exp(-((torch.unsqueeze(D, -1) - mu) / sigma) ** 2)
     Mg = gather_nodes(M18, E_idx)
@@ -147,7 +147,8 @@ def rbf_all_pairs(X18, E_idx, M18, num_rbf=16):
 def positional(w, offset, same_chain, max_rel=32):
     """PositionalEncodings.forward (model_utils.py:613-617)."""
     d = torch.clip(offset + max_rel, 0, 2 * max_rel) * same_chain + (1 - same_chain) * (2 * max_rel + 1)
-    return _lin(w, "features.embeddings.linear", F.one_hot(d, 2 * max_rel + 2).float())
+    lin_w = w["features.embeddings.linear.weight"]
+    return _lin(w, "features.embeddings.linear", F.one_hot(d, 2 * max_rel + 2).to(lin_w.dtype))
 
 
 def features(w, fd, top_k, na_ref_atom="C1'"):
@@ -173,7 +174,8 @@ def features(w, fd, top_k, na_ref_atom="C1'"):
     same = gather_edges(((chain[:, :, None] - chain[:, None, :]) == 0).long()[:, :, :, None], E_idx)[:, :, :, 0]
     E = torch.cat((positional(w, offset.long(), same), R), -1)
     E = _ln(w, "features.norm_edges", _lin(w, "features.edge_embedding", E))
-    V = F.one_hot(fd["R_polymer_type"], num_classes=w["features.node_embedding.weight"].shape[1]).float()
+    emb_w = w["features.node_embedding.weight"]
+    V = F.one_hot(fd["R_polymer_type"], num_classes=emb_w.shape[1]).to(emb_w.dtype)
     V = _ln(w, "features.norm_nodes", _lin(w, "features.node_embedding", V))
     return V, E, E_idx
 
@@ -376,8 +378,8 @@ def sample(w, fd, top_k, special=SPECIAL_TOKENS, S_forced=None):
     chain_mask, mask, bias = chain_mask.repeat(bs, 1), mask.repeat(bs, 1), bias.repeat(bs, 1, 1)
     if pair_bias is not None:
         pair_bias = pair_bias.repeat(bs, 1, 1, 1, 1)
-    all_probs = torch.zeros((bs, L, nl))
-    all_logp = torch.zeros((bs, L, nl))
+    all_probs = torch.zeros((bs, L, nl), dtype=h_V.dtype)
+    all_logp = torch.zeros((bs, L, nl), dtype=h_V.dtype)
     h_S = torch.zeros_like(h_V)
     S = (nl - 1) * torch.ones((bs, L), dtype=torch.int64)
     nd = n_layers(w, "decoder")
@@ -414,8 +416,8 @@ def sample(w, fd, top_k, special=SPECIAL_TOKENS, S_forced=None):
         else:
             S_t = g1(S_forced)
         # the reference scatters probabilities with an index of nl-1 columns (model_utils.py:211)
-        all_probs.scatter_(1, t[:, None, None].repeat(1, 1, nl - 1), (cm_t[:, None, None] * probs[:, None, :]).float())
-        all_logp.scatter_(1, t[:, None, None].repeat(1, 1, nl), (cm_t[:, None, None] * logp[:, None, :]).float())
+        all_probs.scatter_(1, t[:, None, None].repeat(1, 1, nl - 1), (cm_t[:, None, None] * probs[:, None, :]).to(all_probs.dtype))
+        all_logp.scatter_(1, t[:, None, None].repeat(1, 1, nl), (cm_t[:, None, None] * logp[:, None, :]).to(all_logp.dtype))
         S_t = (S_t * cm_t + g1(S_true) * (1.0 - cm_t)).long()
         h_S.scatter_(1, t[:, None, None].repeat(1, 1, H), F.embedding(S_t, w["W_s.weight"])[:, None, :])
         S.scatter_(1, t[:, None], S_t[:, None])
@@ -453,8 +455,8 @@ def sample_symmetric(w, fd, top_k, special=SPECIAL_TOKENS, S_forced=None):
     pair_bias = fd.get("pair_bias")
     if pair_bias is not None:
         pair_bias = rep(pair_bias)
-    all_probs = torch.zeros((bs, L, nl))
-    all_logp = torch.zeros((bs, L, nl))
+    all_probs = torch.zeros((bs, L, nl), dtype=h_V.dtype)
+    all_logp = torch.zeros((bs, L, nl), dtype=h_V.dtype)
     h_S = torch.zeros_like(h_V)
     S = (nl - 1) * torch.ones((bs, L), dtype=torch.int64)
     nd = n_layers(w, "decoder")
@@ -472,7 +474,7 @@ def sample_symmetric(w, fd, top_k, special=SPECIAL_TOKENS, S_forced=None):
                 stack[l + 1][:, t:t + 1, :] = dec_layer(w, f"decoder_layers.{l}.", stack[l][:, t:t + 1], h_ESV_t,
                                                         mask_V=mask_t[:, None])
             logits = _lin(w, "W_out", stack[-1][:, t])
-            all_logp[:, t] = (cm_t[:, None] * F.log_softmax(logits, dim=-1)).float()
+            all_logp[:, t] = (cm_t[:, None] * F.log_softmax(logits, dim=-1)).to(all_logp.dtype)
             total = total + sym_w[t] * logits
             if pair_bias is not None:      # model_utils.py:273-276: the row of member t with the running S; the LAST member's is used (:300)
                 pb = torch.gather(pair_bias[:, t], -1, S[:, None, :, None].repeat(1, nl, 1, 1))[:, :, :, 0].sum(-1)
@@ -483,7 +485,7 @@ def sample_symmetric(w, fd, top_k, special=SPECIAL_TOKENS, S_forced=None):
         S_t = torch.multinomial(probs, 1)[:, 0] if S_forced is None else None
         for t in t_list:
             cm_t = chain_mask[:, t]
-            all_probs[:, t] = (cm_t[:, None] * probs).float()
+            all_probs[:, t] = (cm_t[:, None] * probs).to(all_probs.dtype)
             if S_forced is not None:
                 S_t = S_forced[:, t]
             S_t = (S_t * cm_t + S_true[:, t] * (1.0 - cm_t)).long()
@@ -499,6 +501,13 @@ def encdec_from_graph(w, V, E, E_idx, S, mask, chain_mask, randn):
     """The BASELINE metric scope: (V,E,E_idx,...) -> log_probs."""
     h_V, h_E = encode_from_graph(w, V, E, E_idx, mask)
     return score_from_encoded(w, h_V, h_E, E_idx, S, mask, chain_mask, randn)
+
+
+def to_dtype(d, dtype):
+    """A copy of a weight mapping or feature_dict with its floating tensors in `dtype` (torch.float64: the same op sequence
+    evaluated in double precision).  "randn" keeps its dtype: the decoding order is defined by its fp32 products."""
+    return {k: (v.to(dtype) if isinstance(v, torch.Tensor) and v.is_floating_point() and k != "randn" else v)
+            for k, v in d.items()}
 
 
 def to_torch(d):

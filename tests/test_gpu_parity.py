@@ -730,8 +730,19 @@ def test_logits_head_matches_torch(L, dev, G, V, want_logits):
     """namp_logits_log_softmax — the small-batch kernel (one token per lane) and, from 4,096 residues, logits_mfma_kernel (16-row tiles on the
     exact-fp32 matrix pipe, W_out as a fragment image built in LDS, the tile's [16][V] block written through LDS) — against torch in fp64:
     log-probs and logits within 2e-5, rows normalised; G not a multiple of 16 and a vocabulary of 21 (V * rows not a multiple of 4) included."""
+    _logits_head_case(L, dev, G, V, want_logits, 1.0)
+
+
+@pytest.mark.parametrize("G,V,want_logits", [(4100, 33, True), (100, 21, True)])
+def test_logits_head_matches_torch_scaled(L, dev, G, V, want_logits):
+    """The same with the rows x 20 (logits of +-100 and more: exp() of an unshifted logit would overflow), both kernels.  Bar: 2e-5, or
+    4 x the deviation of torch's own fp32 CPU evaluation from fp64 on the same inputs where that is larger."""
+    _logits_head_case(L, dev, G, V, want_logits, 20.0)
+
+
+def _logits_head_case(L, dev, G, V, want_logits, scale):
     g = torch.Generator().manual_seed(G + V)
-    h = torch.randn(G, 128, generator=g).to(dev)
+    h = (scale * torch.randn(G, 128, generator=g)).to(dev)
     W = (torch.randn(V, 128, generator=g) * 0.2).to(dev).contiguous()
     b = (torch.randn(V, generator=g) * 0.1).to(dev)
     lp = torch.full((G, V), float("nan"), device=dev)
@@ -740,10 +751,19 @@ def test_logits_head_matches_torch(L, dev, G, V, want_logits):
     torch.cuda.synchronize()
     z = h.double() @ W.double().t() + b.double()
     ref = torch.log_softmax(z, -1)
+    bar_lp = bar_lg = 2e-5
+    if scale != 1.0:
+        assert float(z.abs().max()) > 100.0
+        zc = h.cpu() @ W.cpu().t() + b.cpu()
+        dev_lp = float((torch.log_softmax(zc, -1).double() - ref.cpu()).abs().max())
+        dev_lg = float((zc.double() - z.cpu()).abs().max())
+        bar_lp, bar_lg = max(bar_lp, 4 * dev_lp), max(bar_lg, 4 * dev_lg)
+        print(f"log-probs: error {float((lp.double() - ref).abs().max()):.2e}, bar {bar_lp:.2e} (torch fp32 on the CPU: {dev_lp:.2e}); "
+              f"logits bar {bar_lg:.2e} (torch fp32 on the CPU: {dev_lg:.2e})")
     assert torch.isfinite(lp).all()
-    assert float((lp.double() - ref).abs().max()) < 2e-5
+    assert float((lp.double() - ref).abs().max()) < bar_lp
     if want_logits:
-        assert float((lg.double() - z).abs().max()) < 2e-5
+        assert float((lg.double() - z).abs().max()) < bar_lg
     assert float((torch.logsumexp(lp.double(), -1)).abs().max()) < 1e-5
 
 

@@ -31,9 +31,28 @@ def make_model(weights_np, k, dropout=0.0):
 @pytest.mark.parametrize("mode,B,N,K", [(0, 2, 37, 20), (1, 2, 37, 20), (2, 1, 50, 48), (0, 1, 64, 48), (1, 3, 21, 16)])
 def test_edge_mlp_backward_matches_autograd(mode, B, N, K):
     """namp_train_edge_fwd / _bwd / _wgrad vs fp64 autograd of z3 = W3 gelu(W2 gelu(W1b h_E + Pa_i + Pj_j) + b2) + b3."""
+    _edge_mlp_backward_case(mode, B, N, K, 1.0)
+
+
+def scaled_bar(bar, fp32_dev, name, err):
+    """Bar of a scaled kernel-level case: the unit-scale bar, or 4 x the deviation of the same torch fp32 CPU operation from fp64 on the
+    same inputs where that is larger (the factor covers a different but fixed summation order and MFMA accumulation)."""
+    bar = max(bar, 4.0 * fp32_dev)
+    print(f"{name}: error {err:.2e}, bar {bar:.2e} (torch fp32 on the CPU: {fp32_dev:.2e})")
+    return bar
+
+
+@pytest.mark.parametrize("mode,B,N,K", [(0, 2, 37, 20), (1, 2, 37, 20), (2, 1, 50, 48)])
+def test_edge_mlp_backward_matches_autograd_scaled(mode, B, N, K, monkeypatch):
+    """The same with h_E, Pa and Pj x 4: z1 reaches about +-35, far into both saturated branches of GELU and of its derivative."""
+    monkeypatch.setattr(train, "X3", 1)                      # split-bf16 products, whatever an earlier test's forward_train left
+    _edge_mlp_backward_case(mode, B, N, K, 4.0)
+
+
+def _edge_mlp_backward_case(mode, B, N, K, scale):
     g = torch.Generator(device="cpu").manual_seed(100 * mode + K)
     rn = lambda *s, sc=1.0: (sc * torch.randn(*s, generator=g)).to(DEV)
-    h_E, Pa, Pj0, Pj1 = rn(B, N, K, 128), rn(B, N, 128), rn(B, N, 128), rn(B, N, 128)
+    h_E, Pa, Pj0, Pj1 = rn(B, N, K, 128, sc=scale), rn(B, N, 128, sc=scale), rn(B, N, 128, sc=scale), rn(B, N, 128, sc=scale)
     W1 = rn(128, 384, sc=0.08)
     W2, W3, b2, b3 = rn(128, 128, sc=0.1), rn(128, 128, sc=0.1), rn(128, sc=0.1), rn(128, sc=0.1)
     E_idx = torch.stack([torch.stack([torch.randperm(N, generator=g)[:K] for _ in range(N)]) for _ in range(B)]).to(DEV)
@@ -43,17 +62,19 @@ def test_edge_mlp_backward_matches_autograd(mode, B, N, K):
     leaves = [h_E, Pa, Pj0, Pj1, W1, W2, b2, W3, b3]
 
     def dense(hE, pa, pj0, pj1, w1, w2, bb2, w3, bb3):
-        bidx = torch.arange(B, device=DEV)[:, None, None]
+        dv = hE.device
+        bidx = torch.arange(B, device=dv)[:, None, None]
+        idx, msk, rnk = E_idx.to(dv), mask.to(dv), rank.to(dv)
         if mode == 1:
-            bw = (rank[bidx, E_idx] < rank[:, :, None]).unsqueeze(-1)
-            pj = torch.where(bw, pj0[bidx, E_idx], pj1[bidx, E_idx])
+            bw = (rnk[bidx, idx] < rnk[:, :, None]).unsqueeze(-1)
+            pj = torch.where(bw, pj0[bidx, idx], pj1[bidx, idx])
         else:
-            pj = pj0[bidx, E_idx]
+            pj = pj0[bidx, idx]
         z1 = hE @ w1[:, 128:256].t() + pa[:, :, None] + pj
         z3 = F.gelu(F.gelu(z1) @ w2.t() + bb2) @ w3.t() + bb3
         if mode == 2:
             return z3
-        wgt = (mask[:, :, None] & mask[bidx, E_idx]).to(z3.dtype) if mode == 0 else torch.ones_like(z3[..., 0])
+        wgt = (msk[:, :, None] & msk[bidx, idx]).to(z3.dtype) if mode == 0 else torch.ones_like(z3[..., 0])
         return (wgt.unsqueeze(-1) * z3).sum(2) / 30.0
 
     with torch.enable_grad():
@@ -73,13 +94,26 @@ def test_edge_mlp_backward_matches_autograd(mode, B, N, K):
             ((out * R).sum() + (h_pass * R2).sum()).backward()
         else:
             (out * R).sum().backward()
-    assert rel(out, ref_out) < 2e-5
     names = ["h_E", "Pa", "Pj0", "Pj1", "W1", "W2", "b2", "W3", "b3"]
+    bar_out, bar_grad = 2e-5, {name: 5e-5 for name in names}
+    if scale != 1.0:
+        assert float(ref_in[0].detach().abs().max()) > 3.0 * scale
+        with torch.enable_grad():
+            cpu_in = [t.cpu().requires_grad_(True) for t in leaves]
+            cpu_out = dense(*cpu_in)
+            ((cpu_out * R.cpu()).sum() + ((cpu_in[0] * R2.cpu()).sum() if mode != 2 else 0.0)).backward()
+        bar_out = scaled_bar(bar_out, rel(cpu_out, ref_out), "out", rel(out, ref_out))
+        for name, a, c, b in zip(names, ours_in, cpu_in, ref_in):
+            if c.grad is not None and a.grad is not None:
+                bar_grad[name] = scaled_bar(bar_grad[name], rel(c.grad, b.grad), "d" + name, rel(a.grad, b.grad))
+    assert torch.isfinite(out).all()
+    assert rel(out, ref_out) < bar_out
     for name, a, b in zip(names, ours_in, ref_in):
         if name == "Pj1" and mode != 1:
             continue
         assert a.grad is not None, name
-        assert rel(a.grad, b.grad) < 5e-5, (name, rel(a.grad, b.grad))
+        assert torch.isfinite(a.grad).all(), name
+        assert rel(a.grad, b.grad) < bar_grad[name], (name, rel(a.grad, b.grad))
 
 
 # (one case per precision: these compare two HIP paths; the fp64 comparison of test_on_chip_backward_matches_fp64_autograd supersedes them)
@@ -621,8 +655,18 @@ def test_feature_weight_gradient(weights_np):
 @pytest.mark.parametrize("rows", [1, 7, 64, 1000, 70001])
 def test_row_layernorm_matches_torch(rows):
     """ln_rows_fwd / ln_rows_bwd (norm_edges on the edge embedding) against torch.nn.functional.layer_norm in fp64."""
+    _row_layernorm_case(rows, 0.5)
+
+
+@pytest.mark.parametrize("rows", [7, 1000])
+def test_row_layernorm_matches_torch_large_mean(rows):
+    """The same on x = 3 randn + 300: rows whose mean is a hundred times their spread (a one-pass variance loses (mean / std)^2 digits)."""
+    _row_layernorm_case(rows, 300.0)
+
+
+def _row_layernorm_case(rows, mean):
     torch.manual_seed(rows)
-    x = (torch.randn(rows, 128, device=DEV) * 3 + 0.5).requires_grad_()
+    x = (torch.randn(rows, 128, device=DEV) * 3 + mean).requires_grad_()
     w = (torch.randn(128, device=DEV) * 0.5 + 1).requires_grad_()
     b = torch.randn(128, device=DEV).requires_grad_()
     gout = torch.randn(rows, 128, device=DEV)
@@ -633,8 +677,18 @@ def test_row_layernorm_matches_torch(rows):
     with torch.enable_grad():
         yr = torch.nn.functional.layer_norm(xr, (128,), wr, br, 1e-5)
         yr.backward(gout.double())
-    assert rel(y, yr) < 2e-6
-    assert rel(x.grad, xr.grad) < 2e-5 and rel(w.grad, wr.grad) < 2e-5 and rel(b.grad, br.grad) < 2e-5
+    got, ref = (y, x.grad, w.grad, b.grad), (yr, xr.grad, wr.grad, br.grad)
+    bars = [2e-6, 2e-5, 2e-5, 2e-5]
+    if mean != 0.5:
+        xc, wc, bc = (t.detach().cpu().requires_grad_() for t in (x, w, b))
+        with torch.enable_grad():
+            yc = torch.nn.functional.layer_norm(xc, (128,), wc, bc, 1e-5)
+            yc.backward(gout.cpu())
+        bars = [scaled_bar(bar, rel(c, r), name, rel(a, r))
+                for bar, name, a, c, r in zip(bars, ("y", "dx", "dw", "db"), got, (yc, xc.grad, wc.grad, bc.grad), ref)]
+    for a, r, bar in zip(got, ref, bars):
+        assert torch.isfinite(a).all()
+        assert rel(a, r) < bar
 
 
 def _g7_on_device():
@@ -907,10 +961,20 @@ def test_node_tail_matches_autograd(G, p, monkeypatch):
     """_NodeTail (residue tail of EncLayer / DecLayer in training: LayerNorm1, FFN, LayerNorm2, mask, both dropouts — one HIP
     launch each way) against fp64 autograd of the same expression.  With p > 0 the kernels' hash dropout masks are read back
     through two probe calls (they depend on seed, row and channel only) and handed to the reference."""
+    _node_tail_case(G, p, 1.0, monkeypatch)
+
+
+@pytest.mark.parametrize("G,p", [(37, 0.0), (300, 0.2)])
+def test_node_tail_matches_autograd_scaled(G, p, monkeypatch):
+    """The same with h_V and dh x 4."""
+    _node_tail_case(G, p, 4.0, monkeypatch)
+
+
+def _node_tail_case(G, p, scale, monkeypatch):
     monkeypatch.setattr(train, "X3", 1)                      # split-bf16 products, whatever an earlier test's forward_train left
     gen = torch.Generator(device="cpu").manual_seed(1000 + G)
     rn = lambda *s, sc=1.0: (sc * torch.randn(*s, generator=gen)).to(DEV)
-    h_V, dh, R = rn(G, 128), rn(G, 128, sc=0.5), rn(G, 128)
+    h_V, dh, R = rn(G, 128, sc=scale), rn(G, 128, sc=0.5 * scale), rn(G, 128)
     mask = (torch.rand(G, generator=gen) > 0.2).to(DEV)
     ln1_w, ln1_b, ln2_w, ln2_b = 1 + rn(128, sc=0.1), rn(128, sc=0.1), 1 + rn(128, sc=0.1), rn(128, sc=0.1)
     W_in, b_in, W_out, b_out = rn(512, 128, sc=0.08), rn(512, sc=0.1), rn(128, 512, sc=0.05), rn(128, sc=0.1)
@@ -941,9 +1005,10 @@ def test_node_tail_matches_autograd(G, p, monkeypatch):
     leaves = [h_V, dh, ln1_w, ln1_b, W_in, b_in, W_out, b_out, ln2_w, ln2_b]
 
     def dense(hV, d, l1w, l1b, Wi, bi, Wo, bo, l2w, l2b):
-        x1_ = F.layer_norm(hV + m1 * d, (128,), l1w, l1b, 1e-5)
+        k1, k2, mk = (t.to(device=hV.device, dtype=hV.dtype) for t in (m1, m2, mask))
+        x1_ = F.layer_norm(hV + k1 * d, (128,), l1w, l1b, 1e-5)
         f = F.linear(F.gelu(F.linear(x1_, Wi, bi)), Wo, bo)
-        return mask.double().unsqueeze(-1) * F.layer_norm(x1_ + m2 * f, (128,), l2w, l2b, 1e-5)
+        return mk.unsqueeze(-1) * F.layer_norm(x1_ + k2 * f, (128,), l2w, l2b, 1e-5)
 
     with torch.enable_grad():
         ref_in = [t.double().requires_grad_(True) for t in leaves]
@@ -953,11 +1018,21 @@ def test_node_tail_matches_autograd(G, p, monkeypatch):
         hV_, d_, l1w_, l1b_, Wi_, bi_, Wo_, bo_, l2w_, l2b_ = ours_in
         out = train._NodeTail.apply(hV_, d_, mask32, l1w_, l1b_, Wi_, bi_, Wo_, bo_, l2w_, l2b_, p, s1, s2)
         (out * R).sum().backward()
-    assert rel(out, ref_out) < 2e-5, rel(out, ref_out)
     names = ["h_V", "dh", "ln1_w", "ln1_b", "W_in", "b_in", "W_out", "b_out", "ln2_w", "ln2_b"]
+    bar_out, bar_grad = 2e-5, {name: 1e-4 for name in names}
+    if scale != 1.0:
+        with torch.enable_grad():
+            cpu_in = [t.cpu().requires_grad_(True) for t in leaves]
+            cpu_out = dense(*cpu_in)
+            (cpu_out * R.cpu()).sum().backward()
+        bar_out = scaled_bar(bar_out, rel(cpu_out, ref_out), "out", rel(out, ref_out))
+        for name, a_, c_, b_ in zip(names, ours_in, cpu_in, ref_in):
+            bar_grad[name] = scaled_bar(bar_grad[name], rel(c_.grad, b_.grad), "d" + name, rel(a_.grad, b_.grad))
+    assert torch.isfinite(out).all()
+    assert rel(out, ref_out) < bar_out, rel(out, ref_out)
     for name, a_, b_ in zip(names, ours_in, ref_in):
         assert a_.grad is not None, name
-        assert rel(a_.grad, b_.grad) < 1e-4, (name, rel(a_.grad, b_.grad))
+        assert rel(a_.grad, b_.grad) < bar_grad[name], (name, rel(a_.grad, b_.grad))
 
 
 @pytest.mark.parametrize("ppm", [False, True])

@@ -2590,7 +2590,10 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
       {
         const int nd = (m < NAMP_SAMPLE_SLOTS) ? node_lds[m] : -1;
         const int ms = nd >= 0 ? m : 0;
-        const int ndc = nd >= 0 ? nd : node_lds[0];
+        // (padding rows repeat slot 0's residue; slot 0 idles while a later slot still runs the second member of its group — a single
+        //  in front of a pair —, then they repeat this wave's own residue: -1 would read the row in front of the table)
+        const int nd0 = node_lds[0];
+        const int ndc = nd >= 0 ? nd : (nd0 >= 0 ? nd0 : node);
         // h^(l) of the residue: layer 0 reads the (stream-shared) encoder output
         long hrow = ndc;
         if (l == 0) { const int bq = ndc / a.N; hrow = (long)(bq % a.B_enc) * a.N + (ndc - bq * a.N); }

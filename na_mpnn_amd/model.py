@@ -522,6 +522,13 @@ class ProteinMPNN(nn.Module):
             polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
             m, cm = self._host_list(fd["mask"], "mask"), self._host_list(fd["chain_mask"], "chain_mask")
             fixed = [not (a and b) for a, b in zip(m, cm)]                       # (a masked residue keeps its token as a fixed one does)
+            # A residue the parser masks (a 5' nucleotide without its phosphate) comes without a polymer flag.  It is fixed, so all the
+            # map does is hand the complement of its token to its partner: the partner's polymer type stands in for its own.
+            for pr in pairs:
+                for r, q in ((int(pr[0]), int(pr[1])), (int(pr[1]), int(pr[0]))):
+                    if 0 <= r < L and 0 <= q < L and not m[r] and polymer[r] == 0 and polymer[q] in (1, 2) \
+                            and not self._host_list(fd["protein_mask"], "protein_mask")[r]:
+                        polymer[r] = polymer[q]
         groups, weights, gmaps, pair_list, *gbias = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, fixed,
                                                                   fd.get("symmetry_residues"), fd.get("symmetry_weights"), maps,
                                                                   wobble, wobble_bias)

@@ -761,6 +761,31 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
                      const int32_t* mask, const int32_t* rank, float* log_probs, int32_t* counts, void* ws, size_t ws_bytes,
                      int B, int N, int K, void* stream);
 
+/* ---- pair conditionals: leave-PAIR-out scoring of base pairs, riding on namp_decoder_loo ------------------------------------
+ * Residues i, j tied as a base pair (LISTED order) share one stream: the order of score() with both taken out and appended as
+ * ..., i, j, the true S teacher-forced, and the token embedding of i hidden (only j could read it) — what the tied branch of the
+ * sampler (model_utils.py:219-326) computes when the pair is decoded last.  With z_i, z_j the two members' head rows there,
+ *     total[a] = w_i z_i[P_i[a]] + w_j z_j[P_j[a]],   lp = log_softmax(total),   row_m[P_m[a]] = lp[a]   for m in (i, j)
+ * (P: the members' token maps, involutions of the vocabulary) and both rows of log_probs hold the pair's conditional, each in its
+ * member's alphabet.  Rows of unpaired residues are bit-identical to a call without pairs; counts still reports the active items.
+ * No entry point takes a pointer: the tables travel in a caller-filled INPUT SECTION of `ws`,
+ *     namp_loo_pairs_offset(B, N, K, n_dec)   byte offset of the section in ws (256-byte aligned; = namp_loo_workspace_bytes)
+ *     int32 words, G = B * N:  partner[G]  local index of the partner in its complex, -1 for none
+ *                              first[G]    1 on the listed-first member of a pair
+ *                              map_idx[G]  index of the residue's token map
+ *                              weight[G]   w of the residue (float bits)
+ *                              maps[n_maps][64]
+ * and namp_loo_pairs(n_maps), 1 <= n_maps <= 64 (NAMP_EINVAL otherwise), attaches them to the calling thread's NEXT
+ * namp_decoder_loo call, which then requires ws_bytes >= namp_loo_pairs_workspace_bytes(B, N, K, n_dec, n_maps) (the carve of
+ * namp_loo_workspace_bytes, the section, [G] tables and two [2 G][128] row tables behind it; 0 where namp_loo_workspace_bytes is 0 or
+ * n_maps is out of range) and clears the attachment whether it succeeds or not.  The section is device data and is validated on
+ * the device: a member whose partner index is out of range or itself, whose partner does not name it back, or whose pair has a
+ * masked member (mask == 0) is treated as unpaired — both residues get their ordinary leave-one-out rows; map indices and map
+ * entries are clamped.  Without an attachment namp_decoder_loo is unchanged, bit for bit. */
+size_t namp_loo_pairs_workspace_bytes(int B, int N, int K, int n_dec, int n_maps);
+size_t namp_loo_pairs_offset(int B, int N, int K, int n_dec);
+int namp_loo_pairs(int n_maps);
+
 /* ---- measurement hook (bench.py) ------------------------------------------------------------
  * When enabled (thread-local), every kernel launch made through this ABI is bracketed by HIP
  * events on the launch stream; namp_profile_collect() waits for them and returns the summed

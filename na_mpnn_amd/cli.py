@@ -70,7 +70,8 @@ def build_parser():
     a("--output_sequences", type=int, default=1)
     a("--output_specificity", type=int, default=0)
     a("--conditional_probs_only", type=int, default=0, help="1 - no sampling: write conditional_probs/<name>.npz with "
-      "log p(s_i | structure, all other residues) for every residue (ProteinMPNN.conditional_probs)")
+      "log p(s_i | structure, all other residues) for every residue (ProteinMPNN.conditional_probs); with --paired_residues / "
+      "--paired_strands the rows of a pair hold the pair's conditional, log p(pair | structure, everything else), and `pairs` is added")
     a("--load_residues_with_missing_atoms", type=int, default=0)
     a("--mode", type=str, default=None)
     a("--device", type=str, default="cuda:0")
@@ -276,8 +277,8 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
 
     pairs = parse_pairs(args.paired_residues, args.paired_strands, encoded, list(P["chain_letters"]))
     wobble = wobble_arguments(args, bool(pairs))
-    if pairs and args.conditional_probs_only:
-        raise ValueError("--conditional_probs_only scores a given sequence: it does not go with --paired_residues / --paired_strands")
+    if pairs and args.conditional_probs_only and wobble:
+        raise ValueError("--conditional_probs_only scores base pairs by their Watson-Crick maps: it does not go with --paired_wobble")
 
     with torch.no_grad():
         fd = pdbio.to_feature_dict(P, chain_mask, device)
@@ -299,10 +300,13 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
             # one deterministic leave-one-out profile instead of draws: the decoding order's noise is the only random input
             fd["randn"] = torch.randn(1, L, device=device)
             out = model.conditional_probs(fd)
+            # with --paired_residues / --paired_strands the rows of paired residues hold the PAIR's conditional (each in its member's
+            # alphabet) and `pairs` [n, 2] lists the pairs that were tied; without pair flags the file keeps its keys
+            extra = {"pairs": out["pairs"].cpu().numpy()} if pairs else {}
             np.savez(os.path.join(base, "conditional_probs", name + ".npz"),
                      log_probs=out["log_probs"][0].cpu().numpy(), S=P["S"].astype(np.int64), mask=P["mask"],
                      chain_mask=chain_mask, chain_labels=P["chain_labels"], decoding_order=out["decoding_order"].cpu().numpy(),
-                     encoded_residues=encoded)
+                     encoded_residues=encoded, **extra)
             return
         S_l, lp_l, sp_l, loss_l, lpr_l = [], [], [], [], []
         cmask = (fd["mask"] * fd["chain_mask"]).float()

@@ -11,6 +11,16 @@
 // dec_items_kernel is the DecLayer message MLP + K-sum + residue tail (model_utils.py:636-657) over a grid of such items: the body of
 // edge_mlp_kernel<MODE_DEC_MSG> with the rank comparison replaced by indirection.  Every item owns its output rows (no atomics, two
 // runs are bit-identical); phases are separate launches (nothing waits on the device).
+//
+// Pair conditionals (namp_loo_pairs): residues i, j tied as a base pair share ONE stream, the order of score() with
+// both taken out and appended as ..., i, j (LISTED order), in which i's token is hidden.  Stream membership follows from the slot: a
+// slot whose neighbour (phase 1) or owner (phase 2, own) is a pair member belongs to that pair's stream, edges to BOTH members are
+// forward there, and a residue that used to see both members as decoded has two phase-1 slots that compute the same rows (each item
+// still owns its rows; readers take the listed-first member's slot if it is active).  j reads i as a backward neighbour WITHOUT its
+// token: layer 1 from Pfw[0][i], layers 2 / 3 from rows G + i of that layer's forward table, which hold W1v . (i's own-layer state):
+// with pairs the forward tables of layers 2 and 3 have 2 G rows and the own launches project the second half (dec_items_kernel
+// itself is unchanged).
+// loo_combine_kernel then sums the two members' head rows through their token maps and writes both rows.
 #pragma once
 #include "namp_kernels.h"
 
@@ -27,6 +37,8 @@ struct LooPrepArgs {
   const int32_t* rank;    // [G]
   const int32_t* mask;    // [G]
   const int32_t* S;       // [G]
+  const int32_t* pp;      // [G] validated pair partner (global residue index) or -1, from loo_pairs_kernel (PAIRS launches only)
+  const int32_t* lead;    // [G] 1 on the listed-first member of a valid pair
   int32_t* rev;           // [R] edge (a, k) -> b: position of a in E_idx[b], or -1
   int32_t* act1;          // [R] phase-1 item (m, k) is active
   int32_t* act2;          // [R] phase-2 item (i, kq) is active
@@ -42,7 +54,25 @@ struct LooPrepArgs {
 
 __device__ __forceinline__ int loo_clamp(const int v, const int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
+// The partner table is caller-supplied device data: one thread per residue validates it.  A member counts as unpaired when its
+// partner index is out of range or itself, when the partner does not name it back, or when either of the two is masked.
+static __global__ __launch_bounds__(256) void loo_pairs_kernel(const int32_t* __restrict__ partner, const int32_t* __restrict__ first,
+                                                                const int32_t* __restrict__ mask, int32_t* __restrict__ pp,
+                                                                int32_t* __restrict__ lead, const int G, const int N) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= G) return;
+  const int b0 = (g / N) * N, g_loc = g - b0;
+  const int p_loc = partner[g];
+  const int p = b0 + loo_clamp(p_loc, N);
+  const bool ok = p_loc >= 0 && p_loc < N && p_loc != g_loc && partner[p] == g_loc && mask[g] != 0 && mask[p] != 0;
+  const bool fg = first[g] != 0, fp = first[p] != 0;
+  pp[g] = ok ? p : -1;
+  lead[g] = (ok && (fg != fp ? fg : g < p)) ? 1 : 0;       // (flags that do not tell the two apart: the lower index leads)
+}
+
 // one thread per slot r = (g, k): reverse-edge index, phase-1 flag, the phase-1 items' centres
+// (PAIRS = false is the code of a call without pairs: no table of partners is read)
+template <bool PAIRS>
 static __global__ __launch_bounds__(256) void loo_prepare_kernel(const LooPrepArgs a) {
   const long R = (long)a.G * a.K;
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
@@ -54,13 +84,15 @@ static __global__ __launch_bounds__(256) void loo_prepare_kernel(const LooPrepAr
   for (int q = a.K - 1; q >= 0; --q)
     if (a.E_idx[(long)i * a.K + q] == m_loc) p = q;
   a.rev[r] = p;
-  a.act1[r] = (i_loc != m_loc && a.rank[i] < a.rank[g] && a.mask[g] != 0) ? 1 : 0;
+  const int pi = PAIRS ? a.pp[i] : -1;                      // m is not an item of its own pair's stream
+  a.act1[r] = (i_loc != m_loc && pi != g && a.rank[i] < a.rank[g] && a.mask[g] != 0) ? 1 : 0;
   a.ctr1[r] = g; a.msk1[r] = a.mask[g]; a.S1[r] = a.S[g];
   if (k == 0) { a.idG[g] = g; a.ovG[g] = LOO_CEN_OV | g; }
 }
 
 // one wave per slot r: the edge codes of the phase-1 item (m, k) and of the phase-2 item (i, kq) that share the slot, the phase-2
 // flag and centre, and the edge codes of the own layers (after loo_prepare_kernel: reads rev / act1 of other slots)
+template <bool PAIRS>
 static __global__ __launch_bounds__(256) void loo_edges_kernel(const LooPrepArgs a) {
   const long R = (long)a.G * a.K;
   const int lane = threadIdx.x & 63;
@@ -70,35 +102,58 @@ static __global__ __launch_bounds__(256) void loo_edges_kernel(const LooPrepArgs
   const int b0 = (g / a.N) * a.N, c_loc = g - b0;           // g = the slot's residue: m of the phase-1 item, i of the phase-2 item
   const int n_loc = loo_clamp(a.E_idx[r], a.N), n = b0 + n_loc;   // its k-th neighbour: i of the phase-1 item, q of the phase-2 item
   const int rk_g = a.rank[g], rk_n = a.rank[n];
-  const int pr = a.rev[r];                                  // position of g in E_idx[n]
-  const bool cen_ov = pr >= 0 && a.act1[(long)n * a.K + (pr >= 0 ? pr : 0)] != 0;   // n in A1(g): its layer-1 state is overridden in stream g
+  // pairs: the stream of the phase-1 item is that of n's pair, the stream of the phase-2 item and of the own layers that of g's pair
+  const int pg = PAIRS ? a.pp[g] : -1, pn = PAIRS ? a.pp[n] : -1;
+  const bool g_leads = !PAIRS || pg < 0 || a.lead[g] != 0;
+  const int f_loc = g_leads ? c_loc : pg - b0;              // the listed-first member of g's stream, and the other one (-1: none)
+  const int s_loc = pg < 0 ? -1 : (g_leads ? pg - b0 : c_loc);
+  // n's layer-1 override in stream g: the slot of n that names the listed-first member if it is active, else the other member's
+  int pf = a.rev[r], ps = -1;                               // positions of g / of its partner in E_idx[n]
+  if (PAIRS && pg >= 0) {                                   // (wave-uniform)
+    for (int q = a.K - 1; q >= 0; --q)
+      if (a.E_idx[(long)n * a.K + q] == pg - b0) ps = q;
+    if (!g_leads) { const int t = pf; pf = ps; ps = t; }
+  }
+  int ovn = -1;
+  if (PAIRS && ps >= 0 && a.act1[(long)n * a.K + ps] != 0) ovn = (int)((long)n * a.K + ps);
+  if (pf >= 0 && a.act1[(long)n * a.K + (pf >= 0 ? pf : 0)] != 0) ovn = (int)((long)n * a.K + pf);
+  const bool cen_ov = ovn >= 0;                             // n's layer-1 state is overridden in stream g
   bool any = false;
   for (int e = lane; e < a.K; e += 64) {
-    // phase 1, item (m = g, i = n): edge e of m; the edge to i is forward now
+    // phase 1, item (m = g, i = n): edge e of m; the edges to i and to i's partner are forward now
     const int j_loc = loo_clamp(a.E_idx[(long)g * a.K + e], a.N), j = b0 + j_loc;
-    a.esrc1[r * a.K + e] = (j_loc == n_loc || !(a.rank[j] < rk_g)) ? (LOO_FW | j) : j;
+    a.esrc1[r * a.K + e] = (j_loc == n_loc || j == pn || !(a.rank[j] < rk_g)) ? (LOO_FW | j) : j;
     // phase 2, item (i = g, q = n): edge e of q
     const int m_loc = loo_clamp(a.E_idx[(long)n * a.K + e], a.N), mm = b0 + m_loc;
     int code = LOO_FW | mm;
-    if (m_loc != c_loc && a.rank[mm] < rk_n) {
+    if (m_loc != c_loc && mm != pg && a.rank[mm] < rk_n) {
       code = mm;
-      int p = -1;
-      for (int q = a.K - 1; q >= 0; --q)
-        if (a.E_idx[(long)mm * a.K + q] == c_loc) p = q;
-      if (p >= 0 && a.act1[(long)mm * a.K + p] != 0) { code = LOO_OV | (int)((long)mm * a.K + p); any = true; }
+      int p1 = -1, p2 = -1;
+      for (int q = a.K - 1; q >= 0; --q) {
+        const int v = a.E_idx[(long)mm * a.K + q];
+        if (v == f_loc) p1 = q;
+        if (PAIRS && v == s_loc) p2 = q;
+      }
+      int ov = -1;
+      if (PAIRS && s_loc >= 0 && p2 >= 0 && a.act1[(long)mm * a.K + p2] != 0) ov = (int)((long)mm * a.K + p2);
+      if (p1 >= 0 && a.act1[(long)mm * a.K + p1] != 0) ov = (int)((long)mm * a.K + p1);
+      if (ov >= 0) { code = LOO_OV | ov; any = true; }
     }
     a.esrc2[r * a.K + e] = code;
   }
-  const bool on2 = n_loc != c_loc && a.mask[n] != 0 && (cen_ov || __any(any));
+  const bool part = PAIRS && pg >= 0 && n == pg;                     // the slot's neighbour is g's partner: no item, and its own edge codes
+  const bool on2 = n_loc != c_loc && !part && a.mask[n] != 0 && (cen_ov || __any(any));
   if (lane == 0) {
     a.act2[r] = on2 ? 1 : 0;
     a.ctr2[r] = n; a.msk2[r] = a.mask[n]; a.S2[r] = a.S[n];
-    a.cen2[r] = cen_ov ? (LOO_CEN_OV | (int)((long)n * a.K + pr)) : n;
-    // residue i = g itself: every neighbour backward, the self edge forward
+    a.cen2[r] = cen_ov ? (LOO_CEN_OV | ovn) : n;
+    // residue i = g itself: every neighbour backward, the self edge forward.  In a pair the listed-first member sees its partner
+    // forward; the other sees the first backward but without its token: Pfw[0] in layer 1, rows G + n of the forward tables in layers 2, 3
     const bool self = n_loc == c_loc;
-    a.eo1[r] = self ? (LOO_FW | g) : n;
-    a.eo2[r] = self ? (LOO_FW | g) : cen_ov ? (LOO_OV | (int)((long)n * a.K + pr)) : n;
-    a.eo3[r] = self ? (LOO_FW | g) : on2 ? (LOO_OV | (int)r) : n;
+    const int pc = LOO_FW | (g_leads ? n : a.G + n);
+    a.eo1[r] = (self || part) ? (LOO_FW | n) : n;
+    a.eo2[r] = self ? (LOO_FW | g) : part ? pc : cen_ov ? (LOO_OV | ovn) : n;
+    a.eo3[r] = self ? (LOO_FW | g) : part ? pc : on2 ? (LOO_OV | (int)r) : n;
   }
 }
 
@@ -116,6 +171,39 @@ static __global__ __launch_bounds__(1024) void loo_count_kernel(const int32_t* _
     int t1 = 0, t2 = 0;
     for (int w = 0; w < 16; ++w) { t1 += s1[w]; t2 += s2[w]; }
     counts[0] = t1; counts[1] = t2;
+  }
+}
+
+// The input section of a call with pairs (include/namp.h): int32 words partner[G], first[G], map_idx[G], weight[G] (float bits),
+// maps[n_maps][64].
+// One wave per residue; the listed-first member g of a valid pair forms total[a] = w_g z_g[P_g[a]] + w_p z_p[P_p[a]] from the two
+// head rows (log-softmax rows: they differ from the logits by one constant per member, which cancels; members in listed order, the
+// fma chain of dec_sample_kernel), lp = log_softmax(total), and writes row_m[b] = lp[P_m[b]] for both members (the maps are
+// involutions, so this gather IS row_m[P_m[a]] = lp[a]; it stays a plain in-bounds store per lane whatever the maps hold).
+static __global__ __launch_bounds__(256) void loo_combine_kernel(float* __restrict__ log_probs, const int32_t* __restrict__ pp,
+                                                                  const int32_t* __restrict__ lead, const int32_t* __restrict__ map_idx,
+                                                                  const float* __restrict__ weight, const int32_t* __restrict__ maps,
+                                                                  const int n_maps, const int vocab, const int G) {
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= G || lead[g] == 0) return;                        // (wave-uniform)
+  const int p = loo_clamp(pp[g], G);
+  const int a = lane < vocab ? lane : 0;
+  const int Pg = loo_clamp(maps[loo_clamp(map_idx[g], n_maps) * 64 + a], vocab);
+  const int Pp = loo_clamp(maps[loo_clamp(map_idx[p], n_maps) * 64 + a], vocab);
+  const float zg = log_probs[(long)g * vocab + Pg], zp = log_probs[(long)p * vocab + Pp];
+  const float tot = lane < vocab ? fmaf(weight[p], zp, weight[g] * zg) : -INFINITY;
+  float mx = tot;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  float e = (lane < vocab) ? expf(tot - mx) : 0.f;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) e += __shfl_xor(e, o);
+  const float lp = (tot - mx) - logf(e);
+  const float rg = __shfl(lp, Pg), rp = __shfl(lp, Pp);
+  if (lane < vocab) {
+    log_probs[(long)g * vocab + lane] = rg;
+    log_probs[(long)p * vocab + lane] = rp;
   }
 }
 

@@ -1,4 +1,5 @@
-// Translation unit of the leave-one-out decoder (namp_loo.h): namp_loo_workspace_bytes / namp_decoder_loo of include/namp.h.
+// Translation unit of the leave-one-out decoder (namp_loo.h): namp_loo_workspace_bytes / namp_decoder_loo of include/namp.h, and the
+// pair conditionals riding on it (namp_loo_pairs_workspace_bytes / namp_loo_pairs_offset / namp_loo_pairs).
 // Host code only validates, carves the caller's workspace and enqueues launches on the caller's stream.  The base stream's
 // per-layer states and tables come from the library's own building blocks (namp_node_linear, namp_dec_message_update, ...).
 #include "../../include/namp.h"
@@ -34,9 +35,15 @@ struct LooBuffers {
   float *h1O, *Pa2O, *Pbw2O, *h2O, *Pbw3O;
   int32_t *rev, *act1, *act2, *ctr1, *ctr2, *cen2, *msk1, *S1, *msk2, *S2, *eo1, *eo2, *eo3, *idG, *ovG, *esrc1, *esrc2;
   size_t bytes;
+  // with pairs, behind everything above (so that a call without pairs carves exactly what it always did):
+  int32_t *pin;            // the caller-filled input section: partner[G], first[G], map_idx[G], weight[G], maps[n_maps][64]
+  int32_t *pp, *lead;      // [G] validated partner / listed-first flag (loo_pairs_kernel)
+  float *PfwQ[2];          // [2 G][128] the forward tables of layers 2 / 3 with pairs: rows G.. = W1v . (own layer-1 / layer-2 state), no
+                           // token — what a pair's second member reads for the first
+  size_t pin_off, pair_bytes;
 };
 
-LooBuffers loo_carve(void* base, long G, int K) {
+LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0) {
   LooBuffers b;
   size_t off = 0;
   auto take = [&](size_t elems) {
@@ -56,6 +63,11 @@ LooBuffers loo_carve(void* base, long G, int K) {
   b.idG = (int32_t*)take((size_t)G); b.ovG = (int32_t*)take((size_t)G);
   b.esrc1 = (int32_t*)take(R * K); b.esrc2 = (int32_t*)take(R * K);
   b.bytes = off;
+  b.pin_off = off;
+  b.pin = (int32_t*)take((size_t)4 * G + (size_t)64 * n_maps);
+  b.pp = (int32_t*)take((size_t)G); b.lead = (int32_t*)take((size_t)G);
+  b.PfwQ[0] = (float*)take(2 * g128); b.PfwQ[1] = (float*)take(2 * g128);
+  b.pair_bytes = off;
   return b;
 }
 
@@ -88,9 +100,26 @@ void loo_proj(NodeTail& t, const float* img, const float* bias, const float* tok
   p.img = img; p.bias = bias; p.tok = tok; p.out = out;
 }
 
+// the pair tables of the calling thread's NEXT namp_decoder_loo call (namp_loo_pairs): taken, and cleared, by that call
+thread_local int g_loo_pairs = 0;
+
 }  // namespace
 
 extern "C" {
+
+size_t namp_loo_pairs_workspace_bytes(int B, int N, int K, int n_dec, int n_maps) {
+  if (namp_loo_workspace_bytes(B, N, K, n_dec) == 0 || n_maps < 1 || n_maps > 64) return 0;
+  return loo_carve(nullptr, (long)B * N, K, n_maps).pair_bytes;
+}
+
+size_t namp_loo_pairs_offset(int B, int N, int K, int n_dec) { return namp_loo_workspace_bytes(B, N, K, n_dec); }
+
+int namp_loo_pairs(int n_maps) {
+  g_loo_pairs = 0;
+  if (n_maps < 1 || n_maps > 64) return lfail(NAMP_EINVAL, "namp_loo_pairs: n_maps=%ld must be in [1, 64]", n_maps);
+  g_loo_pairs = n_maps;
+  return NAMP_OK;
+}
 
 size_t namp_loo_workspace_bytes(int B, int N, int K, int n_dec) {
   if (B < 1 || N < 1 || K < 1 || K > NAMP_MAX_K || n_dec != 3) return 0;
@@ -100,8 +129,11 @@ size_t namp_loo_workspace_bytes(int B, int N, int K, int n_dec) {
 int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx, const int32_t* S,
                      const int32_t* mask, const int32_t* rank, float* log_probs, int32_t* counts, void* ws, size_t ws_bytes,
                      int B, int N, int K, void* stream) {
+  const int n_maps = g_loo_pairs;
+  g_loo_pairs = 0;                                               // (one call only, whatever becomes of it)
   if (!w || !h_V_enc || !h_E || !E_idx || !S || !mask || !rank || !log_probs || !counts || !ws)
-    return lfail(NAMP_EINVAL, "namp_decoder_loo: null pointer argument");
+    return lfail(NAMP_EINVAL, n_maps ? "namp_decoder_loo: null pointer argument (pair tables were attached)"
+                                     : "namp_decoder_loo: null pointer argument");
   if ((((uintptr_t)h_V_enc | (uintptr_t)h_E | (uintptr_t)ws | (uintptr_t)log_probs) & 15u) != 0)
     return lfail(NAMP_EINVAL, "namp_decoder_loo: h_V_enc / h_E / log_probs / ws must be 16-byte aligned");
   if (w->n_dec != 3) return lfail(NAMP_EINVAL, "namp_decoder_loo: the cone kernels walk three decoder layers (n_dec=%ld): use the L-stream form", w->n_dec);
@@ -123,8 +155,10 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   }
   if (!w->Wout_w || !w->Wout_b) return lfail(NAMP_EINVAL, "namp_decoder_loo: null output head");
   const long G = (long)B * N, R = G * K;
-  LooBuffers b = loo_carve(ws, G, K);
-  if (b.bytes > ws_bytes) return lfail(NAMP_EWORKSPACE, "namp_decoder_loo: workspace too small (%ld bytes, %ld needed)", (long)ws_bytes, (long)b.bytes);
+  LooBuffers b = loo_carve(ws, G, K, n_maps);
+  if (n_maps && 2 * G >= (1L << LOO_ROW_BITS)) return lfail(NAMP_EINVAL, "namp_decoder_loo: 2*B*N=%ld exceeds 2^28 table rows", 2 * G);
+  const size_t need = n_maps ? b.pair_bytes : b.bytes;
+  if (need > ws_bytes) return lfail(NAMP_EWORKSPACE, "namp_decoder_loo: workspace too small (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
   std::call_once(g_loo_once, set_loo_attrs);
   if (g_loo_err != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(g_loo_err));
   hipStream_t s = (hipStream_t)stream;
@@ -137,8 +171,20 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   pa.msk1 = b.msk1; pa.S1 = b.S1; pa.msk2 = b.msk2; pa.S2 = b.S2; pa.eo1 = b.eo1; pa.eo2 = b.eo2; pa.eo3 = b.eo3;
   pa.idG = b.idG; pa.ovG = b.ovG; pa.esrc1 = b.esrc1; pa.esrc2 = b.esrc2;
   pa.G = (int)G; pa.N = N; pa.K = K;
-  hipLaunchKernelGGL(loo_prepare_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
-  hipLaunchKernelGGL(loo_edges_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
+  const int32_t *p_first = b.pin + G, *p_map = b.pin + 2 * G, *p_maps = b.pin + 4 * G;
+  const float* p_weight = (const float*)(b.pin + 3 * G);
+  if (n_maps) {
+    hipLaunchKernelGGL(loo_pairs_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, b.pin, p_first, mask, b.pp, b.lead, (int)G, N);
+    pa.pp = b.pp; pa.lead = b.lead;
+    b.Pfw[1] = b.PfwQ[0]; b.Pfw[2] = b.PfwQ[1];                   // (the same rows 0 .. G-1 at another address)
+  }
+  if (n_maps) {
+    hipLaunchKernelGGL(loo_prepare_kernel<true>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
+    hipLaunchKernelGGL(loo_edges_kernel<true>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
+  } else {
+    hipLaunchKernelGGL(loo_prepare_kernel<false>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
+    hipLaunchKernelGGL(loo_edges_kernel<false>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
+  }
   hipLaunchKernelGGL(loo_count_kernel, dim3(1), dim3(1024), 0, s, b.act1, b.act2, counts, R);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
@@ -188,6 +234,7 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   a = items(D0, G, nullptr, b.idG, b.idG, b.eo1, b.Pa1, b.Pa1, h_V_enc, h_V_enc, b.Pbw1, b.Pfw[0], b.Pbw1);
   loo_tail(a.tail, D0, mask, S, b.h1o);
   loo_proj(a.tail, D1->W1a_img, D1->b1, nullptr, b.Pa2o);
+  if (n_maps) loo_proj(a.tail, D1->W1v_img, nullptr, nullptr, b.PfwQ[0] + G * NAMP_HIDDEN);      // what the second member of a pair reads for the first, layer 2
   if ((rc = launch_items(a, prec, s))) return rc;
   // phase 2: layer 2 at i's neighbours that a phase-1 output reaches (table of layer 3 for the own layer 3)
   a = items(D1, R, b.act2, b.ctr2, b.cen2, b.esrc2, b.Pa2, b.Pa2O, b.h1, b.h1O, b.Pbw2, b.Pfw[1], b.Pbw2O);
@@ -198,11 +245,18 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   a = items(D1, G, nullptr, b.idG, b.ovG, b.eo2, b.Pa2, b.Pa2o, b.h1, b.h1o, b.Pbw2, b.Pfw[1], b.Pbw2O);
   loo_tail(a.tail, D1, mask, S, b.h2o);
   loo_proj(a.tail, D2->W1a_img, D2->b1, nullptr, b.Pa3o);
+  if (n_maps) loo_proj(a.tail, D2->W1v_img, nullptr, nullptr, b.PfwQ[1] + G * NAMP_HIDDEN);      // ... layer 3
   if ((rc = launch_items(a, prec, s))) return rc;
   a = items(D2, G, nullptr, b.idG, b.ovG, b.eo3, b.Pa3, b.Pa3o, b.h2, b.h2o, b.Pbw3, b.Pfw[2], b.Pbw3O);
   loo_tail(a.tail, D2, mask, S, b.h3o);
   a.tail.head_w = w->Wout_w; a.tail.head_b = w->Wout_b; a.tail.log_probs = log_probs; a.tail.logits = nullptr; a.tail.vocab = w->vocab;
-  return launch_items(a, prec, s);
+  if ((rc = launch_items(a, prec, s)) || !n_maps) return rc;
+  // pairs: the two members' rows -> the pair's conditional, through their token maps
+  hipLaunchKernelGGL(loo_combine_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.lead, p_map, p_weight, p_maps,
+                     n_maps, (int)w->vocab, (int)G);
+  e = hipGetLastError();
+  if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+  return NAMP_OK;
 }
 
 }  // extern "C"

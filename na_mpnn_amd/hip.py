@@ -214,6 +214,9 @@ _PROTOTYPES = {
     "namp_states_plan": (i32, [c_ip, c_ip, c_ip, c_fp] + [c_ip] * 5 + [c_fp] + [c_ip] * 7 + [i32, i32, i32, i32, vp]),
     "namp_loo_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "namp_decoder_loo": (i32, [C.POINTER(NampModelW), c_fp, c_fp, c_ip, c_ip, c_ip, c_ip, c_fp, c_ip, vp, sz, i32, i32, i32, vp]),
+    "namp_loo_pairs_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "namp_loo_pairs_offset": (sz, [i32, i32, i32, i32]),
+    "namp_loo_pairs": (i32, [i32]),
 }
 
 KERNEL_KINDS = ["gather", "node_linear", "edge_embed", "enc_message", "enc_edge_update", "node_update",

@@ -847,34 +847,67 @@ class ProteinMPNN(nn.Module):
         cone of every stream (namp_decoder_loo: about K + 3 layer evaluations per residue instead of 3 L), for three decoder layers in
         the split-bf16 ("x3") and exact fp32 evaluations; it also returns "cone_items", the int32 [2] device tensor of active layer-1 /
         layer-2 items; "auto" — the cone where it is implemented, the dense form otherwise (another number of decoder layers, the
-        bf16 throughput mode)."""
+        bf16 throughput mode).
+        Pair conditionals.  With feature_dict["paired_residues"] [(i, j), ...] (optional "paired_weights" as in sample()) the rows of
+        a pair's two residues hold the PAIR's conditional instead, the exact distribution paired sample() would draw the pair from if
+        it were decoded last with everything else teacher-forced: the stream is score()'s order with i and j taken out and appended
+        as ..., i, j (listed order; chain_mask does not reorder members), i's token hidden, and with z_i, z_j the members' logits
+        there total[a] = w_i z_i[P_i[a]] + w_j z_j[P_j[a]], lp = log_softmax(total), row_m[P_m[a]] = lp[a] (P: the Watson-Crick maps
+        of mapped_groups; T = 1, no bias, special tokens kept).  A pair with a masked member is dropped: both residues keep their
+        leave-one-out rows.  Also returned: "pairs" int64 [n, 2], the pairs actually tied in listed order, and "pair_log_probs"
+        [n, vocab], the rows of their listed-first members.  The cone evaluates all pairs in the one call (namp_loo_pairs); "dense",
+        and "auto" where the cone does not apply, is the SLOW route: the unpaired rows through the L streams, and ONE teacher-forced
+        design call of the sampler per pair (the pair decoded last), whose two log_probs rows are combined as above.
+        paired_wobble (pair classes are the follow-up), pairs together with symmetry_residues or state_weights: NotImplementedError;
+        pairs with more than one input complex: ValueError."""
         if method not in ("auto", "dense", "cone"):
             raise ValueError(f"method must be 'auto', 'dense' or 'cone'; got {method!r}")
         S_true, mask = feature_dict["S"], feature_dict["mask"]
         B, L = S_true.shape
+        paired = self._pair_conditional_arguments(feature_dict, B, L)
         cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
         if method == "cone" and not cone_ok:
             raise NotImplementedError("conditional_probs(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
                                       "use method='dense'")
+        use_cone = method == "cone" or (method == "auto" and cone_ok)
+        ws = None
+        if paired is not None and S_true.is_cuda:
+            # The pair tables go up BEFORE the encoder is enqueued (a host-to-device copy waits for the stream): with the cone into the
+            # input section of the call's workspace — ONE copy —, and the list of tied pairs for the result.
+            Lb, n_dec, K = hip.lib(), len(self.decoder_layers), int(min(self.k_neighbors, L))
+            for key in ("section", "pairs"):               # (page-locked once, with the cached tables: the copies below do not stall the host)
+                if not paired[key].is_pinned():
+                    paired[key] = paired[key].pin_memory()
+            if use_cone:
+                section, n_maps = paired["section"], paired["n_maps"]
+                ws = torch.empty(Lb.namp_loo_pairs_workspace_bytes(B, L, K, n_dec, n_maps), dtype=torch.uint8, device=S_true.device)
+                off = Lb.namp_loo_pairs_offset(B, L, K, n_dec)
+                ws[off:off + 4 * section.numel()].view(torch.int32).copy_(section, non_blocking=True)
+            pairs_dev = paired["pairs"].to(S_true.device, non_blocking=True)
         o = self._decoding_order(mask, feature_dict["chain_mask"], feature_dict["randn"])
         h_V, h_E, E_idx = self.encode(feature_dict, order=o)
         self._check_tokens(S_true)
         o.wait()
         rank = o.rank[:B]
         out = {"S": S_true, "decoding_order": o.order[0]}
-        if method == "cone" or (method == "auto" and cone_ok):
+        if use_cone:
             W = self._weights()
             Lb = hip.lib()
             K = E_idx.shape[-1]
             dev = h_V.device
             E32, S32, m32, r32 = _i32(E_idx), self._as(S_true, "i32"), self._as(mask, "i32"), _i32(rank)
-            ws = torch.empty(Lb.namp_loo_workspace_bytes(B, L, K, len(self.decoder_layers)), dtype=torch.uint8, device=dev)
+            if paired is None:
+                ws = torch.empty(Lb.namp_loo_workspace_bytes(B, L, K, len(self.decoder_layers)), dtype=torch.uint8, device=dev)
+            else:
+                hip.check(Lb.namp_loo_pairs(paired["n_maps"]), "loo_pairs")      # the NEXT namp_decoder_loo call reads the section
             counts = torch.empty(2, dtype=torch.int32, device=dev)
             log_probs = torch.empty(B, L, self.num_letters, device=dev)
             hip.check(Lb.namp_decoder_loo(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
                                           r32.data_ptr(), log_probs.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), B, L, K,
                                           hip.current_stream()), "decoder_loo")
             out.update(log_probs=log_probs, cone_items=counts)
+            if paired is not None:
+                out.update(pairs=pairs_dev, pair_log_probs=log_probs[0, pairs_dev[:, 0]])
             return out
         log_probs = torch.empty(B, L, self.num_letters, device=h_V.device)
         chunk = max(1, self.loo_dense_tokens // L)
@@ -887,7 +920,101 @@ class ProteinMPNN(nn.Module):
                 ar = torch.arange(n, device=lp.device)
                 log_probs[b, i0:i1] = lp[ar, i0 + ar]
         out["log_probs"] = log_probs
+        if paired is not None:
+            self._pair_conditionals_by_sampling(feature_dict, o.order[0], paired, log_probs)
+            out.update(pairs=pairs_dev, pair_log_probs=log_probs[0, pairs_dev[:, 0]])
         return out
+
+    def _pair_conditional_arguments(self, fd, B, L):
+        """The base pairs of a conditional_probs() call -> None without pairs, else {"tied": [(i, j, w_i, w_j, P_i, P_j)] the pairs the
+        device ties (both members unmasked), "pairs": int64 [n, 2] of those, "section": the int32 input section of the workspace
+        (include/namp.h: partner, first, map_idx, weight bits, maps), "n_maps"}."""
+        pairs = fd.get("paired_residues")
+        if pairs is None or len(pairs) == 0:
+            return None
+        wobble = fd.get("paired_wobble")
+        if wobble is not None:
+            wobble = wobble.detach().reshape(-1).tolist() if torch.is_tensor(wobble) else wobble
+            if any(wobble) if hasattr(wobble, "__len__") else bool(wobble):
+                raise NotImplementedError("conditional_probs: paired_wobble is not supported; pair classes (DESIGN.md 5.8) are the follow-up")
+        sym = fd.get("symmetry_residues")
+        if sym is not None and not (len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0)):
+            raise NotImplementedError("conditional_probs: paired_residues together with symmetry_residues is not supported")
+        if fd.get("state_weights") is not None:
+            raise NotImplementedError("conditional_probs: paired_residues together with state_weights is not supported")
+        if B != 1:
+            raise ValueError("paired_residues expect one input complex (B == 1)")
+        if self.restype_to_int is None:
+            raise ValueError("paired_residues need the model's restype_to_int")
+        dna, rna = self._host_list(fd["dna_mask"], "dna_mask"), self._host_list(fd["rna_mask"], "rna_mask")
+        m = self._host_list(fd["mask"], "mask")
+        # the tables of the last call are kept: a resident feature_dict is scored many times (the host lists above are the SAME objects
+        # while their tensors are unchanged; pairs and weights are compared by value)
+        pw = fd.get("paired_weights")
+        pw = pw.tolist() if hasattr(pw, "tolist") else pw
+        key = ([(int(a), int(b)) for a, b in pairs], pw, fd.get("symmetry_token_maps") is None)
+        last = getattr(self, "_pair_tables", None)
+        if last is not None and key[2] and last[0] == key and all(x is y for x, y in zip(last[1], (dna, rna, m))):
+            return last[2]
+        polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
+        for pr in pairs:                                  # (a masked residue may come without a polymer flag: its partner's stands in, as in sample())
+            for r, q in ((int(pr[0]), int(pr[1])), (int(pr[1]), int(pr[0]))):
+                if 0 <= r < L and 0 <= q < L and not m[r] and polymer[r] == 0 and polymer[q] in (1, 2) \
+                        and not self._host_list(fd["protein_mask"], "protein_mask")[r]:
+                    polymer[r] = polymer[q]
+        groups, weights, gmaps, _ = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, None,
+                                                  None, None, fd.get("symmetry_token_maps"))
+        partner, first, midx, w = [-1] * L, [0] * L, [0] * L, [1.0] * L
+        table, index = [list(range(64))], {tuple(range(64)): 0}
+        tied = []
+        for g, gw, gm in zip(groups, weights, gmaps):
+            (i, j), Ps = g, [list(P) + list(range(len(P), 64)) for P in gm]
+            partner[i], partner[j], first[i] = j, i, 1
+            for r, wr, P in zip(g, gw, Ps):
+                k = index.get(tuple(P))
+                if k is None:
+                    k = index[tuple(P)] = len(table)
+                    table.append(P)
+                midx[r], w[r] = k, wr
+            if m[i] and m[j]:                             # the device's rule: a pair with a masked member is not tied
+                tied.append((i, j, gw[0], gw[1], gm[0], gm[1]))
+        section = torch.cat((torch.tensor(partner + first + midx, dtype=torch.int32), torch.tensor(w, dtype=torch.float32).view(torch.int32),
+                             torch.tensor([t for P in table for t in P], dtype=torch.int32)))
+        out = {"tied": tied, "pairs": torch.tensor([(t[0], t[1]) for t in tied], dtype=torch.int64).reshape(-1, 2),
+               "section": section, "n_maps": len(table)}
+        self._pair_tables = (key, (dna, rna, m), out)
+        return out
+
+    def _pair_conditionals_by_sampling(self, fd, order0, paired, log_probs):
+        """The slow route of the pair conditionals: per tied pair ONE teacher-forced design call — chain_mask all ones, a randn whose
+        sort is score()'s order with the pair moved to the end as ..., i, j, T = 1, zero bias — whose two log_probs rows are combined
+        into the pair's rows of log_probs [1, L, vocab] (in place)."""
+        S_true, mask = fd["S"], fd["mask"]
+        L = S_true.shape[1]
+        dev = log_probs.device
+        keep = {k: v for k, v in fd.items() if k not in ("paired_residues", "paired_weights", "paired_wobble", "paired_wobble_bias",
+                                                          "symmetry_residues", "symmetry_weights", "symmetry_token_maps", "pair_bias",
+                                                          "S_forced")}
+        ones = torch.ones_like(fd["chain_mask"])
+        bias = torch.zeros(1, L, self.num_letters, device=dev)
+        pos = torch.arange(1, L + 1, dtype=torch.float32, device=dev)
+        for i, j, wi, wj, Pi, Pj in paired["tied"]:
+            rest = order0[(order0 != i) & (order0 != j)]
+            order = torch.cat((rest, torch.tensor([i, j], device=dev)))
+            randn = torch.empty(L, device=dev)
+            randn[order] = pos
+            randn = torch.where(mask[0] != 0, randn, randn * 1e4)          # (a masked residue's sort key is 1e-4 |randn|: its place again)
+            one = dict(keep, chain_mask=ones, randn=randn[None], batch_size=1, temperature=1.0, bias=bias, S_forced=S_true,
+                       paired_residues=[(i, j)], paired_weights=(wi, wj))
+            got = self._sample(one, self.sample_level_walk)
+            if not torch.equal(got["decoding_order"][0], order):
+                raise RuntimeError(f"conditional_probs: the design call of pair ({i}, {j}) did not decode it last")
+            lp = got["log_probs"][0]
+            Pi_t, Pj_t = torch.tensor(Pi, device=dev), torch.tensor(Pj, device=dev)
+            total = wi * lp[i][Pi_t] + wj * lp[j][Pj_t]
+            row = torch.log_softmax(total, -1)
+            log_probs[0, i, Pi_t] = row
+            log_probs[0, j, Pj_t] = row
 
     def forward(self, feature_dict, decoding_randn=None):
         """Training-copy surface (na_model_utils.py:589-646): feature_dict -> (log_probs, probs).

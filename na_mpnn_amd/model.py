@@ -446,8 +446,13 @@ class ProteinMPNN(nn.Module):
             z = self._zeros[key] = torch.zeros(key[0], dtype=torch.int32, device=key[1])
         return z, z
 
+    def _weights_signature(self):
+        """What the packed weight images are valid for: the storage address and version counter of every parameter.  A HIP launch that
+        writes a parameter through its raw pointer must bump the counter (train.mark_written) to be seen here."""
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
     def _weights(self):
-        sig = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        sig = self._weights_signature()
         if self._packed is None or sig != self._packed_sig:
             dev = self.W_v.weight.device
             _require_device(self.W_v.weight, "model parameters")

@@ -1177,6 +1177,13 @@ class NoamOpt:
         self.optimizer.zero_grad()
 
 
+def mark_written(tensors):
+    """Bump the version counter of every tensor a HIP launch has written through its raw pointer.  Such a write is invisible to torch:
+    `tensor._version` stays where it was, and everything keyed on (data_ptr, _version) — ProteinMPNN._weights' packed images, its V cache,
+    _PackPlan's per-step versions — would go on serving what it derived from the OLD values.  Host-only: no launch, no synchronisation."""
+    torch.autograd.graph.increment_version(tensors)
+
+
 class FusedAdam(torch.optim.Adam):
     """torch.optim.Adam whose step — optionally preceded by torch.nn.utils.clip_grad_norm_ (`clip_norm`, na_run.py:233-236) — runs as
     ONE multi-tensor HIP launch over all parameter tensors (namp_train_adam_step; three launches with clipping) instead of the
@@ -1184,7 +1191,11 @@ class FusedAdam(torch.optim.Adam):
     reference's checkpoint format (na_run.py:342) and loads into a plain torch.optim.Adam.  Plain Adam only (no amsgrad / weight decay
     / maximize), fp32 parameters on one HIP device; anything else falls back to torch's step.  The step count is read from the state's `step`
     tensors once per set of tensors and counted on the host afterwards: REPLACE those tensors to change it (as load_state_dict does) — an
-    in-place edit of state["step"] is not seen until they are replaced."""
+    in-place edit of state["step"] is not seen until they are replaced.
+    WARNING: the fused launch writes the parameters through raw pointers, which leaves their version counters unchanged, and the inference
+    paths of ProteinMPNN (score, eval-mode forward / valid_step, sample, conditional_probs, unconditional_probs, encode, featurize) repack
+    their weights only when a counter moves: after a fused step they run on the weights packed BEFORE it.  Call
+    `mark_written(model.parameters())` after the step(s) and before any inference call ("Call histories")."""
 
     clip_norm = 0.0            # > 0: clip the global gradient norm to this value inside the step
     last_grad_norm = None      # device tensor [2]: (gradient norm, clip coefficient) of the last clipped step
@@ -1270,7 +1281,8 @@ class FusedAdam(torch.optim.Adam):
 
 
 def get_std_opt(parameters, d_model, step):
-    """na_model_utils.py:682-686 (Adam lr 0, betas (0.9, 0.98), eps 1e-9 under the Noam schedule) on the multi-tensor HIP step."""
+    """na_model_utils.py:682-686 (Adam lr 0, betas (0.9, 0.98), eps 1e-9 under the Noam schedule) on the multi-tensor HIP step.
+    Before inference on a model trained with it, call `mark_written(model.parameters())`: see the warning in FusedAdam."""
     return NoamOpt(d_model, 2, 4000, FusedAdam(parameters, lr=0, betas=(0.9, 0.98), eps=1e-9), step)
 
 

@@ -150,6 +150,32 @@ def test_conversion_caches_take_inference_tensors():
     assert not m._conv and not m._tokens_ok and m._v_cache is None
 
 
+def test_raw_pointer_writes_need_mark_written():
+    """The premise and the cure of the fused optimiser's repack.  A write through a raw pointer (what namp_train_adam_step does to the
+    parameters; here ctypes.memset on host memory) leaves `_version` alone, so the V cache returns the OLD V and the signature
+    `_weights()` compares is unchanged; after train.mark_written on the written tensors both see the change."""
+    import ctypes
+    from na_mpnn_amd import train
+    m = ProteinMPNN(num_letters=33, vocab=33, k_neighbors=8, atom_dict=spec.atom_dict(), restype_to_int=spec.restype_to_int(),
+                    polytype_to_int=spec.polytype_to_int())
+    rp = torch.tensor([[0, 1, 2, 5]])
+    w = m.features.norm_nodes.weight
+    with torch.no_grad():
+        V0 = m._node_features({"R_polymer_type": rp})
+        sig0, v0 = m._weights_signature(), w._version
+        ctypes.memset(w.data_ptr(), 0, 4 * w.numel())                             # a raw write: every gain becomes 0.0
+        assert float(w.abs().max()) == 0.0 and w._version == v0                  # the memory changed, the counter did not
+        assert m._node_features({"R_polymer_type": rp}) is V0                    # the premise: the stale V is served
+        assert m._weights_signature() == sig0
+        train.mark_written([w])
+        assert w._version == v0 + 1
+        V1 = m._node_features({"R_polymer_type": rp})
+        assert V1 is not V0 and not torch.equal(V1, V0)
+        assert torch.equal(V1, m.features.norm_nodes.bias.detach().expand_as(V1))   # gain 0: V is the bias
+        sig1 = m._weights_signature()
+        assert sig1 != sig0 and [a == b for a, b in zip(sig0, sig1)].count(False) == 1
+
+
 def test_symmetry_visits():
     """Symmetry-tied visit plan: groups are visited in the order stream 0 reaches their first member, members in listed order; a
     residue listed in several groups belongs to the first one; groups that cover a residue twice raise."""

@@ -786,6 +786,36 @@ size_t namp_loo_pairs_workspace_bytes(int B, int N, int K, int n_dec, int n_maps
 size_t namp_loo_pairs_offset(int B, int N, int K, int n_dec);
 int namp_loo_pairs(int n_maps);
 
+/* ---- group conditionals: leave-GROUP-out scoring of tied residue groups, riding on namp_decoder_loo ------------------------
+ * A tied group (m_1, ..., m_n) in LISTED order, 2 <= n <= NAMP_LOO_GROUP_MAX — the copies of a residue in a homo-oligomer, one
+ * residue across backbone states on the block-diagonal flattened graph, base pairs joined with either — shares one stream: the
+ * order of score() with every member taken out and appended as ..., m_1, ..., m_n, the true S teacher-forced, the token embedding
+ * of EVERY member hidden (member t reads an earlier-listed member that is its graph neighbour backward, through its decoder states
+ * but without its token; later-listed members and itself forward).  With z_t the members' head rows there,
+ *     total[a] = sum_t w_t z_t[P_t[a]]  (listed order),   lp = log_softmax(total),   row_{m_t}[P_t[a]] = lp[a]
+ * and every member's row of log_probs holds the group's conditional in its own alphabet.  For n = 2 these are the pair path's bits.
+ * The tables travel in the INPUT SECTION of `ws`, at the place and with the layout of the pair section:
+ *     namp_loo_groups_offset(B, N, K, n_dec)  byte offset of the section in ws (256-byte aligned; = namp_loo_workspace_bytes)
+ *     int32 words, G = B * N:  next[G]     local index of the member listed AFTER this one in its complex (the last member names
+ *                                          the first: a cycle); anything outside [0, N), or the residue itself: ungrouped
+ *                              first[G]    1 on the listed-first member of a group
+ *                              map_idx[G]  index of the residue's token map
+ *                              weight[G]   w of the residue (float bits)
+ *                              maps[n_maps][64]
+ * namp_loo_groups(n_maps), 1 <= n_maps <= 64 (NAMP_EINVAL otherwise), attaches them to the calling thread's NEXT namp_decoder_loo
+ * call (replacing a pair attachment, as namp_loo_pairs replaces this one), which then requires
+ * ws_bytes >= namp_loo_groups_workspace_bytes(B, N, K, n_dec, n_maps) (the carve of namp_loo_pairs_workspace_bytes and one int32
+ * table [G * K] behind it) and clears the attachment whether it succeeds or not.
+ * The section is validated on the device, one walk of at most NAMP_LOO_GROUP_MAX steps per residue: a residue is grouped only if
+ * the walk returns to it, every successor on the way lies in [0, N), exactly one member of the cycle carries `first` and no member
+ * is masked.  Everything else — a self-loop, a tail that leads into a cycle, two `first` flags, a longer cycle, a masked member —
+ * is ungrouped and gets its ordinary leave-one-out row; map indices and map entries are clamped. */
+#define NAMP_LOO_GROUP_MAX 16   /* 8 backbone states of one base pair */
+size_t namp_loo_groups_workspace_bytes(int B, int N, int K, int n_dec, int n_maps);
+size_t namp_loo_groups_offset(int B, int N, int K, int n_dec);
+int namp_loo_groups(int n_maps);
+int namp_loo_group_max(void);   /* NAMP_LOO_GROUP_MAX of the built library */
+
 /* ---- measurement hook (bench.py) ------------------------------------------------------------
  * When enabled (thread-local), every kernel launch made through this ABI is bracketed by HIP
  * events on the launch stream; namp_profile_collect() waits for them and returns the summed

@@ -72,6 +72,10 @@ def build_parser():
     a("--conditional_probs_only", type=int, default=0, help="1 - no sampling: write conditional_probs/<name>.npz with "
       "log p(s_i | structure, all other residues) for every residue (ProteinMPNN.conditional_probs); with --paired_residues / "
       "--paired_strands the rows of a pair hold the pair's conditional, log p(pair | structure, everything else), and `pairs` is added")
+    a("--conditional_tied", type=int, default=0, help="1 - with --conditional_probs_only 1: honour every tie of the design call — "
+      "--symmetry_residues / --symmetry_weights, --multi_state 1 with --state_weights, and base pairs joined with either "
+      "(ProteinMPNN.conditional_probs(tied=True)): the rows of a tied group hold the GROUP's conditional, and `groups` (padded with -1; "
+      "flat indices state * L + residue with --multi_state) and `group_log_probs` are added")
     a("--load_residues_with_missing_atoms", type=int, default=0)
     a("--mode", type=str, default=None)
     a("--device", type=str, default="cuda:0")
@@ -207,6 +211,8 @@ def main(argv=None):
     omit_AA = torch.tensor([float(c in omit_list) for c in alphabet], device=device)
 
     base = args.out_folder if args.out_folder.endswith("/") else args.out_folder + "/"
+    if args.conditional_tied and not args.conditional_probs_only:
+        raise ValueError("--conditional_tied 1 goes with --conditional_probs_only 1")
     if args.conditional_probs_only:
         os.makedirs(base + "conditional_probs", exist_ok=True)
         args.output_pdbs = args.output_sequences = args.output_specificity = 0
@@ -246,8 +252,8 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
               load_residues_with_missing_atoms=bool(args.load_residues_with_missing_atoms))
     state_w = None
     if args.multi_state:
-        if args.conditional_probs_only:
-            raise ValueError("--conditional_probs_only scores one structure: it does not go with --multi_state")
+        if args.conditional_probs_only and not args.conditional_tied:
+            raise ValueError("--conditional_probs_only scores one structure: it does not go with --multi_state (without --conditional_tied 1)")
         X_states, X_m_states = P["X"], P["X_m"]
         P = dict(P, X=X_states[0], X_m=X_m_states[0])       # everything per residue (and the backbones written) comes from state 1
         M = X_states.shape[0]
@@ -299,10 +305,13 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
         if args.conditional_probs_only:
             # one deterministic leave-one-out profile instead of draws: the decoding order's noise is the only random input
             fd["randn"] = torch.randn(1, L, device=device)
-            out = model.conditional_probs(fd)
+            out = model.conditional_probs(fd, tied=bool(args.conditional_tied))
             # with --paired_residues / --paired_strands the rows of paired residues hold the PAIR's conditional (each in its member's
             # alphabet) and `pairs` [n, 2] lists the pairs that were tied; without pair flags the file keeps its keys
-            extra = {"pairs": out["pairs"].cpu().numpy()} if pairs else {}
+            # with --conditional_tied 1 the rows of every tied group hold the GROUP's conditional; `groups` / `group_log_probs` name them
+            extra = {"pairs": out["pairs"].cpu().numpy()} if pairs and "pairs" in out else {}
+            if "groups" in out:
+                extra.update(groups=out["groups"].cpu().numpy(), group_log_probs=out["group_log_probs"].cpu().numpy())
             np.savez(os.path.join(base, "conditional_probs", name + ".npz"),
                      log_probs=out["log_probs"][0].cpu().numpy(), S=P["S"].astype(np.int64), mask=P["mask"],
                      chain_mask=chain_mask, chain_labels=P["chain_labels"], decoding_order=out["decoding_order"].cpu().numpy(),

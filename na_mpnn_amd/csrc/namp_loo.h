@@ -21,6 +21,14 @@
 // with pairs the forward tables of layers 2 and 3 have 2 G rows and the own launches project the second half (dec_items_kernel
 // itself is unchanged).
 // loo_combine_kernel then sums the two members' head rows through their token maps and writes both rows.
+//
+// Group conditionals (namp_loo_groups): a tied group (m_1, ..., m_n), n <= NAMP_LOO_GROUP_MAX, in LISTED order shares
+// one stream, the order of score() with all members taken out and appended as ..., m_1, ..., m_n, every member's token hidden.  The
+// third instantiation of the table kernels (LOO_TIE_GROUPS): loo_groups_kernel turns the caller's successor cycle into (leader,
+// listed position) per residue; a slot belongs to the stream of its neighbour's (phase 1) or owner's (phase 2, own) group, edges to ANY
+// member are forward there, readers take the active phase-1 slot that names the earliest-listed member, member t reads an
+// earlier-listed member that is its neighbour without its token (Pfw[0], rows G + n in layers 2 / 3) and a later-listed one forward;
+// loo_group_combine_kernel loops over the members.  For n = 2 every table entry, and so every bit, is the pair path's.
 #pragma once
 #include "namp_kernels.h"
 
@@ -37,8 +45,9 @@ struct LooPrepArgs {
   const int32_t* rank;    // [G]
   const int32_t* mask;    // [G]
   const int32_t* S;       // [G]
-  const int32_t* pp;      // [G] validated pair partner (global residue index) or -1, from loo_pairs_kernel (PAIRS launches only)
-  const int32_t* lead;    // [G] 1 on the listed-first member of a valid pair
+  const int32_t* pp;      // [G] validated pair partner (global residue index) or -1, from loo_pairs_kernel (PAIRS launches only);
+                          //     GROUPS launches: the leader (listed-first member, global index) of the residue's valid group or -1
+  const int32_t* lead;    // [G] 1 on the listed-first member of a valid pair; GROUPS launches: the residue's listed position (0: ungrouped)
   int32_t* rev;           // [R] edge (a, k) -> b: position of a in E_idx[b], or -1
   int32_t* act1;          // [R] phase-1 item (m, k) is active
   int32_t* act2;          // [R] phase-2 item (i, kq) is active
@@ -49,6 +58,7 @@ struct LooPrepArgs {
   int32_t* eo1; int32_t* eo2; int32_t* eo3;                  // [R] = [G][K] edge codes of residue i's own layers 1..3
   int32_t* idG; int32_t* ovG;                                // [G] centre codes of the own items: base row g / override row g
   int32_t* esrc1; int32_t* esrc2;                            // [R][K] edge codes of the phase-1 / phase-2 items
+  int32_t* gkey;          // [R] GROUPS launches: stream << 4 | listed position of the member an ACTIVE phase-1 slot names, else -1
   int G, N, K;
 };
 
@@ -70,10 +80,54 @@ static __global__ __launch_bounds__(256) void loo_pairs_kernel(const int32_t* __
   lead[g] = (ok && (fg != fp ? fg : g < p)) ? 1 : 0;       // (flags that do not tell the two apart: the lower index leads)
 }
 
+// Groups: the caller's table is a successor cycle in LISTED order (next[g] = local index of the member listed after g, the last
+// names the first) with first[g] = 1 on the listed-first member.  One thread per residue walks its cycle, at most NAMP_LOO_GROUP_MAX
+// steps.  g is grouped only if the walk returns to it, every successor on the way is inside [0, N), exactly one member carries
+// `first` and no member is masked; a self-loop, a tail that leads into a cycle, a longer cycle: ungrouped.  Every member of a cycle
+// walks the same members and reaches the same verdict.  gl[g] = the leader (global index) or -1, gpos[g] = g's listed position.
+static __global__ __launch_bounds__(256) void loo_groups_kernel(const int32_t* __restrict__ next, const int32_t* __restrict__ first,
+                                                                 const int32_t* __restrict__ mask, int32_t* __restrict__ gl,
+                                                                 int32_t* __restrict__ gpos, const int G, const int N) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= G) return;
+  const int b0 = (g / N) * N;
+  int cur = g, n = 0, firsts = 0, at = 0, leader = g;
+  bool ok = true, closed = false;
+  for (int t = 0; t < NAMP_LOO_GROUP_MAX; ++t) {
+    const int nx = next[cur];
+    ok = ok && nx >= 0 && nx < N && mask[cur] != 0;
+    if (first[cur] != 0) { ++firsts; at = t; leader = cur; }
+    ++n;
+    cur = b0 + loo_clamp(nx, N);
+    if (cur == g) { closed = true; break; }
+  }
+  ok = ok && closed && n >= 2 && firsts == 1;
+  gl[g] = ok ? leader : -1;
+  gpos[g] = ok ? (at == 0 ? 0 : n - at) : 0;                 // (the leader sits `at` steps behind g on the cycle)
+}
+
+#define LOO_TIE_NONE 0
+#define LOO_TIE_PAIRS 1
+#define LOO_TIE_GROUPS 2
+
+// groups: the active phase-1 slot of residue x (global) that names the earliest-listed member of stream `sid` (the leader of a
+// group, or the residue of a stream of one), or -1: one pass over the keys loo_prepare_kernel left.  Duplicate slots are bounded by
+// the group size.
+__device__ __forceinline__ int loo_group_override(const LooPrepArgs& a, const int x, const int sid) {
+  int ov = -1, best = NAMP_LOO_GROUP_MAX;
+  for (int q = a.K - 1; q >= 0; --q) {
+    const long sl = (long)x * a.K + q;
+    const int key = a.gkey[sl];
+    if (key >= 0 && (key >> 4) == sid && (key & 15) <= best) { best = key & 15; ov = (int)sl; }
+  }
+  return ov;
+}
+
 // one thread per slot r = (g, k): reverse-edge index, phase-1 flag, the phase-1 items' centres
-// (PAIRS = false is the code of a call without pairs: no table of partners is read)
-template <bool PAIRS>
+// (TIE = LOO_TIE_NONE is the code of a call without pairs: no table of partners is read)
+template <int TIE>
 static __global__ __launch_bounds__(256) void loo_prepare_kernel(const LooPrepArgs a) {
+  constexpr bool PAIRS = TIE == LOO_TIE_PAIRS, GROUPS = TIE == LOO_TIE_GROUPS;
   const long R = (long)a.G * a.K;
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= R) return;
@@ -85,15 +139,20 @@ static __global__ __launch_bounds__(256) void loo_prepare_kernel(const LooPrepAr
     if (a.E_idx[(long)i * a.K + q] == m_loc) p = q;
   a.rev[r] = p;
   const int pi = PAIRS ? a.pp[i] : -1;                      // m is not an item of its own pair's stream
-  a.act1[r] = (i_loc != m_loc && pi != g && a.rank[i] < a.rank[g] && a.mask[g] != 0) ? 1 : 0;
+  const int li = GROUPS ? a.pp[i] : -1;                     // ... nor of its own group's
+  const bool same = GROUPS && li >= 0 && li == a.pp[g];
+  const bool on1 = i_loc != m_loc && pi != g && !same && a.rank[i] < a.rank[g] && a.mask[g] != 0;
+  a.act1[r] = on1 ? 1 : 0;
+  if (GROUPS) a.gkey[r] = on1 ? (((li >= 0 ? li : i) << 4) | a.lead[i]) : -1;     // (a listed position is below NAMP_LOO_GROUP_MAX = 16)
   a.ctr1[r] = g; a.msk1[r] = a.mask[g]; a.S1[r] = a.S[g];
   if (k == 0) { a.idG[g] = g; a.ovG[g] = LOO_CEN_OV | g; }
 }
 
 // one wave per slot r: the edge codes of the phase-1 item (m, k) and of the phase-2 item (i, kq) that share the slot, the phase-2
 // flag and centre, and the edge codes of the own layers (after loo_prepare_kernel: reads rev / act1 of other slots)
-template <bool PAIRS>
+template <int TIE>
 static __global__ __launch_bounds__(256) void loo_edges_kernel(const LooPrepArgs a) {
+  constexpr bool PAIRS = TIE == LOO_TIE_PAIRS, GROUPS = TIE == LOO_TIE_GROUPS;
   const long R = (long)a.G * a.K;
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -107,6 +166,10 @@ static __global__ __launch_bounds__(256) void loo_edges_kernel(const LooPrepArgs
   const bool g_leads = !PAIRS || pg < 0 || a.lead[g] != 0;
   const int f_loc = g_leads ? c_loc : pg - b0;              // the listed-first member of g's stream, and the other one (-1: none)
   const int s_loc = pg < 0 ? -1 : (g_leads ? pg - b0 : c_loc);
+  // groups: the same streams, named by their leaders (-1: the residue alone)
+  const int lg = GROUPS ? a.pp[g] : -1, ln = GROUPS ? a.pp[n] : -1;
+  const bool grouped = lg >= 0;
+  const int sid = grouped ? lg : g;
   // n's layer-1 override in stream g: the slot of n that names the listed-first member if it is active, else the other member's
   int pf = a.rev[r], ps = -1;                               // positions of g / of its partner in E_idx[n]
   if (PAIRS && pg >= 0) {                                   // (wave-uniform)
@@ -115,42 +178,55 @@ static __global__ __launch_bounds__(256) void loo_edges_kernel(const LooPrepArgs
     if (!g_leads) { const int t = pf; pf = ps; ps = t; }
   }
   int ovn = -1;
-  if (PAIRS && ps >= 0 && a.act1[(long)n * a.K + ps] != 0) ovn = (int)((long)n * a.K + ps);
-  if (pf >= 0 && a.act1[(long)n * a.K + (pf >= 0 ? pf : 0)] != 0) ovn = (int)((long)n * a.K + pf);
+  if (GROUPS) {                                             // (... of the earliest-listed member whose slot is active)
+    ovn = loo_group_override(a, n, sid);
+  } else {
+    if (PAIRS && ps >= 0 && a.act1[(long)n * a.K + ps] != 0) ovn = (int)((long)n * a.K + ps);
+    if (pf >= 0 && a.act1[(long)n * a.K + (pf >= 0 ? pf : 0)] != 0) ovn = (int)((long)n * a.K + pf);
+  }
   const bool cen_ov = ovn >= 0;                             // n's layer-1 state is overridden in stream g
   bool any = false;
   for (int e = lane; e < a.K; e += 64) {
-    // phase 1, item (m = g, i = n): edge e of m; the edges to i and to i's partner are forward now
+    // phase 1, item (m = g, i = n): edge e of m; the edges to i and to i's partner (to every member of i's group) are forward now
     const int j_loc = loo_clamp(a.E_idx[(long)g * a.K + e], a.N), j = b0 + j_loc;
-    a.esrc1[r * a.K + e] = (j_loc == n_loc || j == pn || !(a.rank[j] < rk_g)) ? (LOO_FW | j) : j;
+    const bool j_tied = GROUPS && ln >= 0 && a.pp[j] == ln;
+    a.esrc1[r * a.K + e] = (j_loc == n_loc || j == pn || j_tied || !(a.rank[j] < rk_g)) ? (LOO_FW | j) : j;
     // phase 2, item (i = g, q = n): edge e of q
     const int m_loc = loo_clamp(a.E_idx[(long)n * a.K + e], a.N), mm = b0 + m_loc;
+    const bool m_tied = GROUPS && grouped && a.pp[mm] == lg;
     int code = LOO_FW | mm;
-    if (m_loc != c_loc && mm != pg && a.rank[mm] < rk_n) {
+    if (m_loc != c_loc && mm != pg && !m_tied && a.rank[mm] < rk_n) {
       code = mm;
-      int p1 = -1, p2 = -1;
-      for (int q = a.K - 1; q >= 0; --q) {
-        const int v = a.E_idx[(long)mm * a.K + q];
-        if (v == f_loc) p1 = q;
-        if (PAIRS && v == s_loc) p2 = q;
-      }
       int ov = -1;
-      if (PAIRS && s_loc >= 0 && p2 >= 0 && a.act1[(long)mm * a.K + p2] != 0) ov = (int)((long)mm * a.K + p2);
-      if (p1 >= 0 && a.act1[(long)mm * a.K + p1] != 0) ov = (int)((long)mm * a.K + p1);
+      if (GROUPS) {
+        ov = loo_group_override(a, mm, sid);
+      } else {
+        int p1 = -1, p2 = -1;
+        for (int q = a.K - 1; q >= 0; --q) {
+          const int v = a.E_idx[(long)mm * a.K + q];
+          if (v == f_loc) p1 = q;
+          if (PAIRS && v == s_loc) p2 = q;
+        }
+        if (PAIRS && s_loc >= 0 && p2 >= 0 && a.act1[(long)mm * a.K + p2] != 0) ov = (int)((long)mm * a.K + p2);
+        if (p1 >= 0 && a.act1[(long)mm * a.K + p1] != 0) ov = (int)((long)mm * a.K + p1);
+      }
       if (ov >= 0) { code = LOO_OV | ov; any = true; }
     }
     a.esrc2[r * a.K + e] = code;
   }
-  const bool part = PAIRS && pg >= 0 && n == pg;                     // the slot's neighbour is g's partner: no item, and its own edge codes
+  // the slot's neighbour is g's partner / another member of g's group: no item, and its own edge codes
+  const bool part = (PAIRS && pg >= 0 && n == pg) || (GROUPS && grouped && ln == lg && n_loc != c_loc);
   const bool on2 = n_loc != c_loc && !part && a.mask[n] != 0 && (cen_ov || __any(any));
   if (lane == 0) {
     a.act2[r] = on2 ? 1 : 0;
     a.ctr2[r] = n; a.msk2[r] = a.mask[n]; a.S2[r] = a.S[n];
     a.cen2[r] = cen_ov ? (LOO_CEN_OV | ovn) : n;
     // residue i = g itself: every neighbour backward, the self edge forward.  In a pair the listed-first member sees its partner
-    // forward; the other sees the first backward but without its token: Pfw[0] in layer 1, rows G + n of the forward tables in layers 2, 3
+    // forward; the other sees the first backward but without its token: Pfw[0] in layer 1, rows G + n of the forward tables in layers 2, 3.
+    // In a group member t sees every later-listed member forward and every earlier-listed one in that way.
     const bool self = n_loc == c_loc;
-    const int pc = LOO_FW | (g_leads ? n : a.G + n);
+    const bool later = GROUPS ? !(part && a.lead[n] < a.lead[g]) : g_leads;
+    const int pc = LOO_FW | (later ? n : a.G + n);
     a.eo1[r] = (self || part) ? (LOO_FW | n) : n;
     a.eo2[r] = self ? (LOO_FW | g) : part ? pc : cen_ov ? (LOO_OV | ovn) : n;
     a.eo3[r] = self ? (LOO_FW | g) : part ? pc : on2 ? (LOO_OV | (int)r) : n;
@@ -204,6 +280,46 @@ static __global__ __launch_bounds__(256) void loo_combine_kernel(float* __restri
   if (lane < vocab) {
     log_probs[(long)g * vocab + lane] = rg;
     log_probs[(long)p * vocab + lane] = rp;
+  }
+}
+
+// Groups: the input section holds next[G] in the place of partner[G] (include/namp.h).  One wave per group LEADER: it walks the cycle
+// twice, total[a] = sum_t w_t z_t[P_t[a]] over the members in listed order (the fma chain of dec_sample_kernel, as above), then
+// lp = log_softmax(total) and row_m[b] = lp[P_m[b]] for every member (the maps are involutions).  Cycles are disjoint (one successor
+// per residue), every read of a group's rows precedes its first write, and every load is clamped.
+static __global__ __launch_bounds__(256) void loo_group_combine_kernel(float* __restrict__ log_probs, const int32_t* __restrict__ gl,
+                                                                        const int32_t* __restrict__ next, const int32_t* __restrict__ map_idx,
+                                                                        const float* __restrict__ weight, const int32_t* __restrict__ maps,
+                                                                        const int n_maps, const int vocab, const int G, const int N) {
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= G || gl[g] != g) return;                          // (wave-uniform)
+  const int b0 = (g / N) * N;
+  const int a = lane < vocab ? lane : 0;
+  float tot = 0.f;
+  int cur = g;
+  for (int t = 0; t < NAMP_LOO_GROUP_MAX; ++t) {
+    const int P = loo_clamp(maps[loo_clamp(map_idx[cur], n_maps) * 64 + a], vocab);
+    const float z = log_probs[(long)cur * vocab + P];
+    tot = t == 0 ? weight[cur] * z : fmaf(weight[cur], z, tot);
+    cur = b0 + loo_clamp(next[cur], N);
+    if (cur == g) break;
+  }
+  if (lane >= vocab) tot = -INFINITY;
+  float mx = tot;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  float e = (lane < vocab) ? expf(tot - mx) : 0.f;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) e += __shfl_xor(e, o);
+  const float lp = (tot - mx) - logf(e);
+  cur = g;
+  for (int t = 0; t < NAMP_LOO_GROUP_MAX; ++t) {
+    const int P = loo_clamp(maps[loo_clamp(map_idx[cur], n_maps) * 64 + a], vocab);
+    const float row = __shfl(lp, P);
+    if (lane < vocab) log_probs[(long)cur * vocab + lane] = row;
+    cur = b0 + loo_clamp(next[cur], N);
+    if (cur == g) break;
   }
 }
 

@@ -1,5 +1,6 @@
 // Translation unit of the leave-one-out decoder (namp_loo.h): namp_loo_workspace_bytes / namp_decoder_loo of include/namp.h, and the
-// pair conditionals riding on it (namp_loo_pairs_workspace_bytes / namp_loo_pairs_offset / namp_loo_pairs).
+// pair conditionals riding on it (namp_loo_pairs_workspace_bytes / namp_loo_pairs_offset / namp_loo_pairs), and the group
+// conditionals (namp_loo_groups_workspace_bytes / namp_loo_groups_offset / namp_loo_groups).
 // Host code only validates, carves the caller's workspace and enqueues launches on the caller's stream.  The base stream's
 // per-layer states and tables come from the library's own building blocks (namp_node_linear, namp_dec_message_update, ...).
 #include "../../include/namp.h"
@@ -36,11 +37,13 @@ struct LooBuffers {
   int32_t *rev, *act1, *act2, *ctr1, *ctr2, *cen2, *msk1, *S1, *msk2, *S2, *eo1, *eo2, *eo3, *idG, *ovG, *esrc1, *esrc2;
   size_t bytes;
   // with pairs, behind everything above (so that a call without pairs carves exactly what it always did):
-  int32_t *pin;            // the caller-filled input section: partner[G], first[G], map_idx[G], weight[G], maps[n_maps][64]
-  int32_t *pp, *lead;      // [G] validated partner / listed-first flag (loo_pairs_kernel)
+  int32_t *pin;            // the caller-filled input section: partner[G] (groups: next[G]), first[G], map_idx[G], weight[G], maps[n_maps][64]
+  int32_t *pp, *lead;      // [G] validated partner / listed-first flag (loo_pairs_kernel); groups: leader / listed position (loo_groups_kernel)
   float *PfwQ[2];          // [2 G][128] the forward tables of layers 2 / 3 with pairs: rows G.. = W1v . (own layer-1 / layer-2 state), no
                            // token — what a pair's second member reads for the first
   size_t pin_off, pair_bytes;
+  int32_t *gkey;           // [R] with groups, behind the pair carve: the stream and listed position an active phase-1 slot names
+  size_t group_bytes;
 };
 
 LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0) {
@@ -68,6 +71,8 @@ LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0) {
   b.pp = (int32_t*)take((size_t)G); b.lead = (int32_t*)take((size_t)G);
   b.PfwQ[0] = (float*)take(2 * g128); b.PfwQ[1] = (float*)take(2 * g128);
   b.pair_bytes = off;
+  b.gkey = (int32_t*)take(R);
+  b.group_bytes = off;
   return b;
 }
 
@@ -102,6 +107,8 @@ void loo_proj(NodeTail& t, const float* img, const float* bias, const float* tok
 
 // the pair tables of the calling thread's NEXT namp_decoder_loo call (namp_loo_pairs): taken, and cleared, by that call
 thread_local int g_loo_pairs = 0;
+// ... or its group tables (namp_loo_groups); the later of the two attachments holds
+thread_local int g_loo_groups = 0;
 
 }  // namespace
 
@@ -116,8 +123,27 @@ size_t namp_loo_pairs_offset(int B, int N, int K, int n_dec) { return namp_loo_w
 
 int namp_loo_pairs(int n_maps) {
   g_loo_pairs = 0;
+  g_loo_groups = 0;
   if (n_maps < 1 || n_maps > 64) return lfail(NAMP_EINVAL, "namp_loo_pairs: n_maps=%ld must be in [1, 64]", n_maps);
   g_loo_pairs = n_maps;
+  return NAMP_OK;
+}
+
+// (the section of a call with groups has the layout and the place of the pair section; behind the pair carve it adds one [R] table)
+size_t namp_loo_groups_workspace_bytes(int B, int N, int K, int n_dec, int n_maps) {
+  if (namp_loo_pairs_workspace_bytes(B, N, K, n_dec, n_maps) == 0) return 0;
+  return loo_carve(nullptr, (long)B * N, K, n_maps).group_bytes;
+}
+
+size_t namp_loo_groups_offset(int B, int N, int K, int n_dec) { return namp_loo_workspace_bytes(B, N, K, n_dec); }
+
+int namp_loo_group_max(void) { return NAMP_LOO_GROUP_MAX; }
+
+int namp_loo_groups(int n_maps) {
+  g_loo_pairs = 0;
+  g_loo_groups = 0;
+  if (n_maps < 1 || n_maps > 64) return lfail(NAMP_EINVAL, "namp_loo_groups: n_maps=%ld must be in [1, 64]", n_maps);
+  g_loo_groups = n_maps;
   return NAMP_OK;
 }
 
@@ -129,11 +155,14 @@ size_t namp_loo_workspace_bytes(int B, int N, int K, int n_dec) {
 int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx, const int32_t* S,
                      const int32_t* mask, const int32_t* rank, float* log_probs, int32_t* counts, void* ws, size_t ws_bytes,
                      int B, int N, int K, void* stream) {
-  const int n_maps = g_loo_pairs;
+  const bool groups = g_loo_groups != 0;
+  const int n_maps = groups ? g_loo_groups : g_loo_pairs;
   g_loo_pairs = 0;                                               // (one call only, whatever becomes of it)
+  g_loo_groups = 0;
   if (!w || !h_V_enc || !h_E || !E_idx || !S || !mask || !rank || !log_probs || !counts || !ws)
-    return lfail(NAMP_EINVAL, n_maps ? "namp_decoder_loo: null pointer argument (pair tables were attached)"
-                                     : "namp_decoder_loo: null pointer argument");
+    return lfail(NAMP_EINVAL, groups   ? "namp_decoder_loo: null pointer argument (group tables were attached)"
+                              : n_maps ? "namp_decoder_loo: null pointer argument (pair tables were attached)"
+                                       : "namp_decoder_loo: null pointer argument");
   if ((((uintptr_t)h_V_enc | (uintptr_t)h_E | (uintptr_t)ws | (uintptr_t)log_probs) & 15u) != 0)
     return lfail(NAMP_EINVAL, "namp_decoder_loo: h_V_enc / h_E / log_probs / ws must be 16-byte aligned");
   if (w->n_dec != 3) return lfail(NAMP_EINVAL, "namp_decoder_loo: the cone kernels walk three decoder layers (n_dec=%ld): use the L-stream form", w->n_dec);
@@ -156,8 +185,9 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   if (!w->Wout_w || !w->Wout_b) return lfail(NAMP_EINVAL, "namp_decoder_loo: null output head");
   const long G = (long)B * N, R = G * K;
   LooBuffers b = loo_carve(ws, G, K, n_maps);
+  static_assert(NAMP_LOO_GROUP_MAX <= 16, "loo_prepare_kernel packs a listed position into 4 bits beside a residue index below 2^27");
   if (n_maps && 2 * G >= (1L << LOO_ROW_BITS)) return lfail(NAMP_EINVAL, "namp_decoder_loo: 2*B*N=%ld exceeds 2^28 table rows", 2 * G);
-  const size_t need = n_maps ? b.pair_bytes : b.bytes;
+  const size_t need = groups ? b.group_bytes : n_maps ? b.pair_bytes : b.bytes;
   if (need > ws_bytes) return lfail(NAMP_EWORKSPACE, "namp_decoder_loo: workspace too small (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
   std::call_once(g_loo_once, set_loo_attrs);
   if (g_loo_err != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(g_loo_err));
@@ -174,16 +204,20 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   const int32_t *p_first = b.pin + G, *p_map = b.pin + 2 * G, *p_maps = b.pin + 4 * G;
   const float* p_weight = (const float*)(b.pin + 3 * G);
   if (n_maps) {
-    hipLaunchKernelGGL(loo_pairs_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, b.pin, p_first, mask, b.pp, b.lead, (int)G, N);
-    pa.pp = b.pp; pa.lead = b.lead;
+    if (groups) hipLaunchKernelGGL(loo_groups_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, b.pin, p_first, mask, b.pp, b.lead, (int)G, N);
+    else hipLaunchKernelGGL(loo_pairs_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, b.pin, p_first, mask, b.pp, b.lead, (int)G, N);
+    pa.pp = b.pp; pa.lead = b.lead; pa.gkey = b.gkey;
     b.Pfw[1] = b.PfwQ[0]; b.Pfw[2] = b.PfwQ[1];                   // (the same rows 0 .. G-1 at another address)
   }
-  if (n_maps) {
-    hipLaunchKernelGGL(loo_prepare_kernel<true>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
-    hipLaunchKernelGGL(loo_edges_kernel<true>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
+  if (groups) {
+    hipLaunchKernelGGL(loo_prepare_kernel<LOO_TIE_GROUPS>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
+    hipLaunchKernelGGL(loo_edges_kernel<LOO_TIE_GROUPS>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
+  } else if (n_maps) {
+    hipLaunchKernelGGL(loo_prepare_kernel<LOO_TIE_PAIRS>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
+    hipLaunchKernelGGL(loo_edges_kernel<LOO_TIE_PAIRS>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
   } else {
-    hipLaunchKernelGGL(loo_prepare_kernel<false>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
-    hipLaunchKernelGGL(loo_edges_kernel<false>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
+    hipLaunchKernelGGL(loo_prepare_kernel<LOO_TIE_NONE>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
+    hipLaunchKernelGGL(loo_edges_kernel<LOO_TIE_NONE>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
   }
   hipLaunchKernelGGL(loo_count_kernel, dim3(1), dim3(1024), 0, s, b.act1, b.act2, counts, R);
   hipError_t e = hipGetLastError();
@@ -251,9 +285,13 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   loo_tail(a.tail, D2, mask, S, b.h3o);
   a.tail.head_w = w->Wout_w; a.tail.head_b = w->Wout_b; a.tail.log_probs = log_probs; a.tail.logits = nullptr; a.tail.vocab = w->vocab;
   if ((rc = launch_items(a, prec, s)) || !n_maps) return rc;
-  // pairs: the two members' rows -> the pair's conditional, through their token maps
-  hipLaunchKernelGGL(loo_combine_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.lead, p_map, p_weight, p_maps,
-                     n_maps, (int)w->vocab, (int)G);
+  // pairs: the two members' rows -> the pair's conditional, through their token maps; groups: every member's
+  if (groups)
+    hipLaunchKernelGGL(loo_group_combine_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.pin, p_map, p_weight,
+                       p_maps, n_maps, (int)w->vocab, (int)G, N);
+  else
+    hipLaunchKernelGGL(loo_combine_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.lead, p_map, p_weight, p_maps,
+                       n_maps, (int)w->vocab, (int)G);
   e = hipGetLastError();
   if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
   return NAMP_OK;

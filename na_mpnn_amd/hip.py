@@ -217,6 +217,10 @@ _PROTOTYPES = {
     "namp_loo_pairs_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "namp_loo_pairs_offset": (sz, [i32, i32, i32, i32]),
     "namp_loo_pairs": (i32, [i32]),
+    "namp_loo_groups_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "namp_loo_groups_offset": (sz, [i32, i32, i32, i32]),
+    "namp_loo_groups": (i32, [i32]),
+    "namp_loo_group_max": (i32, []),
 }
 
 KERNEL_KINDS = ["gather", "node_linear", "edge_embed", "enc_message", "enc_edge_update", "node_update",
@@ -257,6 +261,11 @@ def lib():
         raise RuntimeError(f"libnamp_hip.so ABI version {v} != expected {NAMP_ABI_VERSION}; rebuild")
     _lib = L
     return L
+
+
+def loo_group_max():
+    """NAMP_LOO_GROUP_MAX of include/namp.h, as the library was built with it: the largest tied group of the group conditionals."""
+    return int(lib().namp_loo_group_max())
 
 
 def check(rc: int, what: str = ""):

@@ -842,7 +842,7 @@ class ProteinMPNN(nn.Module):
     loo_dense_tokens = 65536
 
     @torch.no_grad()
-    def conditional_probs(self, feature_dict, method="auto"):
+    def conditional_probs(self, feature_dict, method="auto", tied=False):
         """Leave-one-out conditionals of every residue in one call: out["log_probs"][b, i, :] = log p(s_i | X, S_-i), row i of score()'s
         parallel decoder (model_utils.py:391-421) run with score()'s decoding order (:388-389) in which residue i is moved to the end,
         the true S teacher-forced everywhere (leave_one_out_ranks).  Returns {"S", "log_probs" [B, L, vocab], "decoding_order"};
@@ -864,9 +864,23 @@ class ProteinMPNN(nn.Module):
         and "auto" where the cone does not apply, is the SLOW route: the unpaired rows through the L streams, and ONE teacher-forced
         design call of the sampler per pair (the pair decoded last), whose two log_probs rows are combined as above.
         paired_wobble (pair classes are the follow-up), pairs together with symmetry_residues or state_weights: NotImplementedError;
-        pairs with more than one input complex: ValueError."""
+        pairs with more than one input complex: ValueError.
+        Group conditionals (tied=True).  Every tie sample() knows except pair classes is honoured: symmetry_residues /
+        symmetry_weights / symmetry_token_maps, state_weights (X [M, L, A, 3], the shared entries [1, L]; the result is [1, L, vocab]),
+        and paired_residues alone or joined with either.  A group (m_1, ..., m_n) is in the LISTED order of mapped_groups(fixed=None),
+        with states the union across the states on the flattened graph (flat residue m * L + i, state-major, weights w_m * w_member).
+        Its stream is score()'s order with all members taken out and appended as ..., m_1, ..., m_n, EVERY member's token hidden;
+        total[a] = sum_t w_t z_t[P_t[a]], lp = log_softmax(total), row_{m_t}[P_t[a]] = lp[a].  A group with a masked member is dropped
+        whole and a group of one is the ordinary leave-one-out row; a group of more than hip.loo_group_max() = 16 members, a residue in
+        two groups: ValueError; paired_wobble: NotImplementedError.  Also returned: "groups" int64 [n, max_size] padded with -1, the
+        groups actually tied (flat indices with states), and "group_log_probs" [n, vocab], the rows of their listed-first members.
+        The cone evaluates all groups in the one call (namp_loo_groups); "dense", and "auto" where the cone does not apply, is the
+        slow route: one teacher-forced design call of the sampler per group.  With tied=False (the default) nothing above applies:
+        symmetry_residues alone are not read, and the refusals of the pair conditionals stand."""
         if method not in ("auto", "dense", "cone"):
             raise ValueError(f"method must be 'auto', 'dense' or 'cone'; got {method!r}")
+        if tied:
+            return self._conditional_probs_tied(feature_dict, method)
         S_true, mask = feature_dict["S"], feature_dict["mask"]
         B, L = S_true.shape
         paired = self._pair_conditional_arguments(feature_dict, B, L)
@@ -929,6 +943,211 @@ class ProteinMPNN(nn.Module):
             self._pair_conditionals_by_sampling(feature_dict, o.order[0], paired, log_probs)
             out.update(pairs=pairs_dev, pair_log_probs=log_probs[0, pairs_dev[:, 0]])
         return out
+
+    def _group_conditional_arguments(self, fd, B, L, state_w):
+        """The tied groups of a conditional_probs(tied=True) call -> None without groups, else {"tied": [(members, weights, maps)] the
+        groups the device ties in flat indices (no masked member), "base": per tied group (residues in [0, L), their weights without
+        the state weight, their maps) for the slow route, "groups": int64 [n, max_size] padded with -1, "section": the int32 input
+        section of the workspace (include/namp.h: next, first, map_idx, weight bits, maps), "n_maps"}.  state_w: None or the M weights."""
+        pairs, sym = fd.get("paired_residues"), fd.get("symmetry_residues")
+        pairs = None if pairs is None or len(pairs) == 0 else pairs
+        sym = None if sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0) else sym
+        wobble = fd.get("paired_wobble")
+        if wobble is not None:
+            wobble = wobble.detach().reshape(-1).tolist() if torch.is_tensor(wobble) else wobble
+            if any(wobble) if hasattr(wobble, "__len__") else bool(wobble):
+                raise NotImplementedError("conditional_probs: paired_wobble is not supported; pair classes (DESIGN.md 5.8) change the combine")
+        if pairs is None and sym is None and state_w is None:
+            return None
+        if B != 1:
+            raise ValueError("tied groups expect one input complex (B == 1)")
+        if self.restype_to_int is None:
+            raise ValueError("tied groups need the model's restype_to_int")
+        m = self._host_list(fd["mask"], "mask")
+        dna = rna = None
+        if pairs is not None:
+            dna, rna = self._host_list(fd["dna_mask"], "dna_mask"), self._host_list(fd["rna_mask"], "rna_mask")
+        # the tables of the last call are kept: a resident feature_dict is scored many times (the host lists above are the SAME objects
+        # while their tensors are unchanged; the ties are compared by value in one normal form; a call with symmetry_token_maps is never
+        # served from the cache, and its own entry, whose key says so, serves no later call)
+        as_list = lambda v: v.tolist() if hasattr(v, "tolist") else v
+        listed = lambda v: None if v is None else [[as_list(x) for x in g] if hasattr(g, "__len__") else g for g in v]
+        key = (None if pairs is None else [(int(a), int(b)) for a, b in pairs], as_list(fd.get("paired_weights")),
+               None if sym is None else [[int(r) for r in g] for g in sym], listed(fd.get("symmetry_weights")) if sym is not None else None,
+               state_w, fd.get("symmetry_token_maps") is None)
+        last = getattr(self, "_group_tables", None)
+        if last is not None and key[5] and last[0] == key and all(x is y for x, y in zip(last[1], (dna, rna, m))):
+            return last[2]
+        polymer = None
+        if pairs is not None:
+            polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
+            for pr in pairs:                              # (a masked residue may come without a polymer flag: its partner's stands in, as in sample())
+                for r, q in ((int(pr[0]), int(pr[1])), (int(pr[1]), int(pr[0]))):
+                    if 0 <= r < L and 0 <= q < L and not m[r] and polymer[r] == 0 and polymer[q] in (1, 2) \
+                            and not self._host_list(fd["protein_mask"], "protein_mask")[r]:
+                        polymer[r] = polymer[q]
+        groups, weights, gmaps = [], [], []
+        if pairs is not None or sym is not None:
+            groups, weights, gmaps, _ = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, None, sym,
+                                                      fd.get("symmetry_weights") if sym is not None else None,
+                                                      fd.get("symmetry_token_maps"))     # (maps without groups: refused there)
+        members = [r for g in groups for r in g]
+        if len(set(members)) != len(members):
+            raise ValueError("conditional_probs: the tied groups must be disjoint")
+        M, sw = (1, [1.0]) if state_w is None else (len(state_w), state_w)
+        ident = list(range(len(spec.RESTYPES)))
+        if state_w is not None:                            # every residue is a group across the states
+            tied_res = set(members)
+            for i in range(L):
+                if i not in tied_res:
+                    groups.append([i]); weights.append([1.0]); gmaps.append([ident])
+        N = M * L
+        nxt, first, midx, w = [-1] * N, [0] * N, [0] * N, [1.0] * N
+        table, index = [list(range(64))], {tuple(range(64)): 0}
+        tied, base = [], []
+        for g, gw, gm in zip(groups, weights, gmaps):
+            if len(g) * M > hip.loo_group_max():
+                raise ValueError(f"conditional_probs: the group of residue {g[0]} has {len(g) * M} members; at most {hip.loo_group_max()} are tied")
+            if len(g) * M < 2:
+                continue
+            flat = [r + s_ * L for s_ in range(M) for r in g]                 # state-major, as _sample_states lists them
+            fw = [sw[s_] * float(v) for s_ in range(M) for v in gw]
+            fm = [P for s_ in range(M) for P in gm]
+            for t, (r, wr, P) in enumerate(zip(flat, fw, fm)):
+                P64 = tuple(P) + tuple(range(len(P), 64))
+                k = index.get(P64)
+                if k is None:
+                    k = index[P64] = len(table)
+                    table.append(list(P64))
+                nxt[r], midx[r], w[r] = flat[(t + 1) % len(flat)] , k, wr
+            first[flat[0]] = 1
+            if all(m[r] for r in g):                       # the device's rule: a group with a masked member is not tied
+                tied.append((flat, fw, [list(P) for P in fm]))
+                base.append((list(g), [float(v) for v in gw], [list(P) for P in gm]))
+        if len(table) > 64:
+            raise ValueError(f"conditional_probs: {len(table)} distinct token maps; at most 64")
+        width = max([len(t[0]) for t in tied], default=0)
+        section = torch.cat((torch.tensor(nxt + first + midx, dtype=torch.int32), torch.tensor(w, dtype=torch.float32).view(torch.int32),
+                             torch.tensor([t for P in table for t in P], dtype=torch.int32)))
+        out = {"tied": tied, "base": base, "section": section, "n_maps": len(table),
+               "groups": torch.tensor([t[0] + [-1] * (width - len(t[0])) for t in tied], dtype=torch.int64).reshape(-1, width)}
+        self._group_tables = (key, (dna, rna, m), out)
+        return out
+
+    def _conditional_probs_tied(self, fd, method):
+        """conditional_probs(tied=True): the group conditionals (see conditional_probs)."""
+        S_true, mask = fd["S"], fd["mask"]
+        B, L = S_true.shape
+        state_w, M = None, 1
+        if fd.get("state_weights") is not None:
+            fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
+            fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
+            fd_chk.pop("S_forced", None)
+            state_w, M, L, _, _ = self._states_arguments(fd_chk)
+        grp = self._group_conditional_arguments(fd, B, L, state_w)
+        if grp is None:
+            return self.conditional_probs(fd, method)
+        cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        if method == "cone" and not cone_ok:
+            raise NotImplementedError("conditional_probs(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
+                                      "use method='dense'")
+        use_cone = method == "cone" or (method == "auto" and cone_ok)
+        _require_device(fd["X"], "X")
+        dev, Lb, n_dec, N = S_true.device, hip.lib(), len(self.decoder_layers), M * L
+        K = int(min(self.k_neighbors, L))
+        ws = None
+        # The tables go up BEFORE the encoder is enqueued (a host-to-device copy waits for the stream), page-locked once with the cached tables
+        for key in ("section", "groups"):
+            if not grp[key].is_pinned():
+                grp[key] = grp[key].pin_memory()
+        if use_cone:
+            section, n_maps = grp["section"], grp["n_maps"]
+            ws = torch.empty(Lb.namp_loo_groups_workspace_bytes(1, N, K, n_dec, n_maps), dtype=torch.uint8, device=dev)
+            off = Lb.namp_loo_groups_offset(1, N, K, n_dec)
+            ws[off:off + 4 * section.numel()].view(torch.int32).copy_(section, non_blocking=True)
+        groups_dev = grp["groups"].to(dev, non_blocking=True)
+        o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1] if state_w is not None else fd["randn"])
+        fd_enc = fd
+        if state_w is not None:
+            fd_enc = dict(fd)
+            for k in self._STATE_SHARED:
+                fd_enc[k] = fd[k].expand(M, L)
+        V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
+        h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
+        self._check_tokens(S_true)
+        o.wait()
+        rank = o.rank[:1]
+        out = {"S": S_true, "decoding_order": o.order[0]}
+        if use_cone:
+            W = self._weights()
+            # the M states as ONE complex of M * L residues: the block-diagonal flattened graph (DESIGN.md 5.6); ranks repeat per block
+            E_f = E_idx if M == 1 else _i32(E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).contiguous()
+            rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
+            S32, m32, r32 = _i32(rep(self._as(S_true, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
+            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+            hip.check(Lb.namp_loo_groups(grp["n_maps"]), "loo_groups")          # the NEXT namp_decoder_loo call reads the section
+            counts = torch.empty(2, dtype=torch.int32, device=dev)
+            log_probs = torch.empty(1, N, self.num_letters, device=dev)
+            hip.check(Lb.namp_decoder_loo(W.model(), h_V.data_ptr(), h_E.data_ptr(), E_f.data_ptr(), S32.data_ptr(), m32.data_ptr(),
+                                          r32.data_ptr(), log_probs.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), 1, N, K,
+                                          hip.current_stream()), "decoder_loo")
+            out["cone_items"] = counts
+        else:
+            log_probs = torch.empty(M, L, self.num_letters, device=dev)
+            chunk = max(1, self.loo_dense_tokens // L)
+            for b in range(M):
+                for i0 in range(0, L, chunk):
+                    i1 = min(L, i0 + chunk)
+                    n = i1 - i0
+                    ranks = leave_one_out_ranks(rank, i0, i1)[0]
+                    lp = self.decode_graph(h_V[b:b + 1], h_E[b:b + 1], E_idx[b:b + 1].long(), S_true.expand(n, L), mask.expand(n, L), ranks)
+                    ar = torch.arange(n, device=dev)
+                    log_probs[b, i0:i1] = lp[ar, i0 + ar]
+            log_probs = log_probs.view(1, N, self.num_letters)
+            self._group_conditionals_by_sampling(fd, o.order[0], grp, log_probs, state_w)
+        lead = groups_dev[:, 0] if groups_dev.numel() else groups_dev.reshape(-1)
+        out.update(log_probs=log_probs[:, :L], groups=groups_dev, group_log_probs=log_probs[0, lead])
+        return out
+
+    def _group_conditionals_by_sampling(self, fd, order0, grp, log_probs, state_w):
+        """The slow route of the group conditionals: per tied group ONE teacher-forced design call — chain_mask all ones, a randn whose
+        sort is score()'s order with the group's residues moved to the end in listed order, T = 1, zero bias, the group as the call's
+        only symmetry group (with its maps) — whose member rows are combined into the group's rows of log_probs [1, M * L, vocab] (in place)."""
+        S_true, mask = fd["S"], fd["mask"]
+        L = S_true.shape[1]
+        dev = log_probs.device
+        keep = {k: v for k, v in fd.items() if k not in ("paired_residues", "paired_weights", "paired_wobble", "paired_wobble_bias",
+                                                          "symmetry_residues", "symmetry_weights", "symmetry_token_maps", "pair_bias",
+                                                          "S_forced")}
+        ones = torch.ones_like(fd["chain_mask"])
+        bias = torch.zeros(1, L, self.num_letters, device=dev)
+        pos = torch.arange(1, L + 1, dtype=torch.float32, device=dev)
+        ident = list(range(self.num_letters))
+        for (flat, fw, fm), (g, gw, gm) in zip(grp["tied"], grp["base"]):
+            g_t = torch.tensor(g, device=dev)
+            rest = order0[~torch.isin(order0, g_t)]
+            order = torch.cat((rest, g_t))
+            randn = torch.empty(L, device=dev)
+            randn[order] = pos
+            randn = torch.where(mask[0] != 0, randn, randn * 1e4)          # (a masked residue's sort key is 1e-4 |randn|: its place again)
+            one = dict(keep, chain_mask=ones, randn=randn[None], batch_size=1, temperature=1.0, bias=bias, S_forced=S_true)
+            if len(g) > 1:
+                one.update(symmetry_residues=[g], symmetry_weights=[gw])
+                if any(list(P) != ident for P in gm):
+                    one["symmetry_token_maps"] = [gm]
+            else:
+                one.update(symmetry_residues=[[]], symmetry_weights=[[]])
+            got = self._sample(one, self.sample_level_walk)
+            if not torch.equal(got["decoding_order"][0], order):
+                raise RuntimeError(f"conditional_probs: the design call of group {g} did not decode it last")
+            lp = got["log_probs"].reshape(-1, self.num_letters)             # [M * L, vocab]
+            maps_t = [torch.tensor(P, device=dev) for P in fm]
+            total = None
+            for r, wr, P in zip(flat, fw, maps_t):
+                total = wr * lp[r][P] if total is None else total + wr * lp[r][P]
+            row = torch.log_softmax(total, -1)
+            for r, P in zip(flat, maps_t):
+                log_probs[0, r, P] = row
 
     def _pair_conditional_arguments(self, fd, B, L):
         """The base pairs of a conditional_probs() call -> None without pairs, else {"tied": [(i, j, w_i, w_j, P_i, P_j)] the pairs the

@@ -816,6 +816,33 @@ size_t namp_loo_groups_offset(int B, int N, int K, int n_dec);
 int namp_loo_groups(int n_maps);
 int namp_loo_group_max(void);   /* NAMP_LOO_GROUP_MAX of the built library */
 
+/* ---- pair classes in the pair and group conditionals (G-U wobble), riding on either of the two above -------------------------
+ * The members of a tied pair or group speak through CLASS TABLES instead of token maps (the sampler's namp_sample_class_tables):
+ * tables[ti][c] is the member's token under class c, below 0 where it has none.  The stream is the pair / group stream above,
+ * unchanged; only the combine differs.  With z_t the members' head rows in listed order and `close` the LAST listed member,
+ *     total[c] = sum_t w_t z_t[C_t[c]] + bias[ti_close][c]     for the classes c < n_classes every member has a token for, else -inf
+ *     clp = log_softmax(total)
+ *     row_m[t] = logsumexp of clp[c] over { c : C_m[c] == t }  (the marginal in the member's alphabet; T = 1, special tokens kept)
+ * Below the vocabulary a table is a token map (an involution), so row_m[t] starts from clp[C_m[t]] and the classes vocab ..
+ * n_classes - 1 are folded in by two-term log-add-exp in ascending order.  Every member's row of log_probs holds that marginal.
+ * No entry point takes a pointer.  The INPUT SECTION sits at namp_loo_pairs_offset / namp_loo_groups_offset with the layout
+ *     int32 words, G = B * N:  partner[G] (groups = 0) or next[G] (groups = 1), first[G], table_idx[G], weight[G] (float bits),
+ *                              tables[n_tables][64]   entries in [-1, vocab)
+ *                              bias[n_tables][64]     float bits; read through the table index of the closing member
+ * and the OUTPUT SECTION, float [G][64], at namp_loo_classes_out_offset(B, N, K, n_dec, n_tables, groups) (256-byte aligned, behind
+ * the carve of the tie it rides on): row g holds clp of the pair / group whose listed-first member is g, -inf on absent lanes, and is
+ * all -inf for every other residue.  namp_loo_classes(n_tables, n_classes, groups), 1 <= n_tables <= 64, vocab <= n_classes <= 64,
+ * groups 0 (the pair path) or 1 (the group path) — NAMP_EINVAL otherwise, n_classes < vocab by the call itself — attaches them to the
+ * calling thread's NEXT namp_decoder_loo call, replacing a pair or group attachment as those replace this one; the call requires
+ * ws_bytes >= namp_loo_classes_workspace_bytes(...) (NAMP_EINVAL otherwise) and clears the attachment whatever becomes of it.
+ * partner / next / first are validated as above.  Table indices and entries are clamped; an entry below 0 is "absent", a pair or
+ * group that fails validation keeps its leave-one-out rows with a class row of -inf, and so does one without a single class all of
+ * its members have.  Plain stores, no atomics: two calls give identical bits.  Without this attachment the plain, pair and group
+ * calls keep their carve and their bits. */
+size_t namp_loo_classes_workspace_bytes(int B, int N, int K, int n_dec, int n_tables, int groups);
+size_t namp_loo_classes_out_offset(int B, int N, int K, int n_dec, int n_tables, int groups);
+int namp_loo_classes(int n_tables, int n_classes, int groups);
+
 /* ---- measurement hook (bench.py) ------------------------------------------------------------
  * When enabled (thread-local), every kernel launch made through this ABI is bracketed by HIP
  * events on the launch stream; namp_profile_collect() waits for them and returns the summed

@@ -76,6 +76,10 @@ def build_parser():
       "--symmetry_residues / --symmetry_weights, --multi_state 1 with --state_weights, and base pairs joined with either "
       "(ProteinMPNN.conditional_probs(tied=True)): the rows of a tied group hold the GROUP's conditional, and `groups` (padded with -1; "
       "flat indices state * L + residue with --multi_state) and `group_log_probs` are added")
+    a("--conditional_classes", type=int, default=0, help="1 - with --conditional_probs_only 1: score base pairs in PAIR CLASSES "
+      "(ProteinMPNN.conditional_probs(classes=True)), so that --paired_wobble 1 / --paired_wobble_bias are accepted and a pair with an "
+      "RNA member may also be G-U; with and without --conditional_tied 1; `pair_class_log_probs` or `group_class_log_probs` [n, 64] "
+      "(-inf on absent classes) is added")
     a("--load_residues_with_missing_atoms", type=int, default=0)
     a("--mode", type=str, default=None)
     a("--device", type=str, default="cuda:0")
@@ -168,6 +172,10 @@ def wobble_arguments(args, have_pairs):
 
 def main(argv=None):
     args = apply_mode_defaults(build_parser().parse_args(argv))
+    if args.conditional_classes not in (0, 1):
+        raise ValueError(f"--conditional_classes is 0 or 1; got {args.conditional_classes}")
+    if args.conditional_classes and not args.conditional_probs_only:
+        raise ValueError("--conditional_classes 1 goes with --conditional_probs_only 1")
     if args.model_type != "na_mpnn":
         print("Choose --model_type flag from currently available models")
         sys.exit()
@@ -283,7 +291,7 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
 
     pairs = parse_pairs(args.paired_residues, args.paired_strands, encoded, list(P["chain_letters"]))
     wobble = wobble_arguments(args, bool(pairs))
-    if pairs and args.conditional_probs_only and wobble:
+    if pairs and args.conditional_probs_only and wobble and not args.conditional_classes:
         raise ValueError("--conditional_probs_only scores base pairs by their Watson-Crick maps: it does not go with --paired_wobble")
 
     with torch.no_grad():
@@ -305,13 +313,18 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
         if args.conditional_probs_only:
             # one deterministic leave-one-out profile instead of draws: the decoding order's noise is the only random input
             fd["randn"] = torch.randn(1, L, device=device)
-            out = model.conditional_probs(fd, tied=bool(args.conditional_tied))
+            if args.conditional_classes:
+                out = model.conditional_probs(fd, tied=bool(args.conditional_tied), classes=True)
+            else:
+                out = model.conditional_probs(fd, tied=bool(args.conditional_tied))
             # with --paired_residues / --paired_strands the rows of paired residues hold the PAIR's conditional (each in its member's
             # alphabet) and `pairs` [n, 2] lists the pairs that were tied; without pair flags the file keeps its keys
             # with --conditional_tied 1 the rows of every tied group hold the GROUP's conditional; `groups` / `group_log_probs` name them
             extra = {"pairs": out["pairs"].cpu().numpy()} if pairs and "pairs" in out else {}
             if "groups" in out:
                 extra.update(groups=out["groups"].cpu().numpy(), group_log_probs=out["group_log_probs"].cpu().numpy())
+            # with --conditional_classes 1 the class rows of the tied pairs / groups
+            extra.update({k: out[k].cpu().numpy() for k in ("pair_class_log_probs", "group_class_log_probs") if k in out})
             np.savez(os.path.join(base, "conditional_probs", name + ".npz"),
                      log_probs=out["log_probs"][0].cpu().numpy(), S=P["S"].astype(np.int64), mask=P["mask"],
                      chain_mask=chain_mask, chain_labels=P["chain_labels"], decoding_order=out["decoding_order"].cpu().numpy(),

@@ -29,6 +29,11 @@
 // member are forward there, readers take the active phase-1 slot that names the earliest-listed member, member t reads an
 // earlier-listed member that is its neighbour without its token (Pfw[0], rows G + n in layers 2 / 3) and a later-listed one forward;
 // loo_group_combine_kernel loops over the members.  For n = 2 every table entry, and so every bit, is the pair path's.
+//
+// Pair classes (namp_loo_classes): on either of the two streams above the members speak through class tables instead
+// of token maps (G-U wobble).  Nothing in front of the combine changes — the streams hide every member's token —; the attachment
+// swaps loo_combine_kernel / loo_group_combine_kernel for loo_class_combine_kernel, which also writes the class rows into an output
+// section of the workspace.
 #pragma once
 #include "namp_kernels.h"
 
@@ -319,6 +324,82 @@ static __global__ __launch_bounds__(256) void loo_group_combine_kernel(float* __
     const float row = __shfl(lp, P);
     if (lane < vocab) log_probs[(long)cur * vocab + lane] = row;
     cur = b0 + loo_clamp(next[cur], N);
+    if (cur == g) break;
+  }
+}
+
+// Pair classes (namp_loo_classes): the members speak through CLASS TABLES instead of token maps — tables[ti][c] = the
+// member's token under class c, below 0: no such class — and the input section holds bias[n_tables][64] behind the tables.  One wave
+// per residue, lane = class; a wave that is no leader of a valid pair (GROUPS = 0: lead / the validated partner pp) or group (GROUPS =
+// 1: gl / the caller's successor cycle, the walk of loo_group_combine_kernel) writes a class row of -inf and ends.  The leader forms
+//   total[c] = sum_t w_t z_t[C_t[c]] + b[c]   (listed order, the fma chain of the kernels above; b through the table index of the LAST
+//                                              listed member, added once), -inf where some member has no token for c or c >= n_classes,
+//   clp = log_softmax(total)                  (the butterfly of loo_combine_kernel: absent lanes add the zeros the lanes >= vocab add there),
+//   row_m[t] = clp[C_m[t]], and for the classes c = vocab .. n_classes - 1 in ascending order with C_m[c] == t: log-add-exp(row_m[t], clp[c])
+// (below the vocabulary a table is a token map, an involution: the one class with C_m[c] == t is c = C_m[t]), and writes every
+// member's row and, at its own index, the class row [64].  Every read of a group's rows precedes its first write; every table index
+// and entry is clamped, the fetch of an absent lane reads a clamped address and its sum is not used; plain stores, one address per
+// lane.  A group none of whose classes is present keeps its leave-one-out rows.
+template <int GROUPS>
+static __global__ __launch_bounds__(256) void loo_class_combine_kernel(float* __restrict__ log_probs, const int32_t* __restrict__ gl,
+                                                                        const int32_t* __restrict__ lead, const int32_t* __restrict__ next,
+                                                                        const int32_t* __restrict__ tab_idx, const float* __restrict__ weight,
+                                                                        const int32_t* __restrict__ tables, const float* __restrict__ bias,
+                                                                        float* __restrict__ cls, const int n_tables, const int n_classes,
+                                                                        const int vocab, const int G, const int N) {
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= G) return;                                        // (wave-uniform)
+  if (GROUPS ? gl[g] != g : lead[g] == 0) {
+    cls[(long)g * 64 + lane] = -INFINITY;
+    return;
+  }
+  const int b0 = (g / N) * N;
+  const int steps = GROUPS ? NAMP_LOO_GROUP_MAX : 2;
+  const int c = lane < n_classes ? lane : 0;
+  float tot = 0.f;
+  bool have = lane < n_classes;
+  int cur = g, last = g;
+  for (int t = 0; t < steps; ++t) {
+    const int e = tables[loo_clamp(tab_idx[cur], n_tables) * 64 + c];
+    have = have && e >= 0;
+    const float z = log_probs[(long)cur * vocab + loo_clamp(e, vocab)];
+    tot = t == 0 ? weight[cur] * z : fmaf(weight[cur], z, tot);
+    last = cur;
+    cur = GROUPS ? b0 + loo_clamp(next[cur], N) : loo_clamp(gl[cur], G);
+    if (cur == g) break;
+  }
+  tot = have ? tot + bias[loo_clamp(tab_idx[last], n_tables) * 64 + c] : -INFINITY;
+  float mx = tot;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  if (!(mx > -INFINITY)) {                                   // (wave-uniform: no class, or nothing but -inf / NaN totals)
+    cls[(long)g * 64 + lane] = -INFINITY;
+    return;
+  }
+  float ex = have ? expf(tot - mx) : 0.f;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) ex += __shfl_xor(ex, o);
+  const float clp = have ? (tot - mx) - logf(ex) : -INFINITY;
+  cls[(long)g * 64 + lane] = clp;
+  const int tk = lane < vocab ? lane : 0;
+  cur = g;
+  for (int t = 0; t < steps; ++t) {
+    const int32_t* tab = tables + loo_clamp(tab_idx[cur], n_tables) * 64;
+    const int e_own = tab[tk];                               // the class below the vocabulary that gives this lane's token
+    const int e_cls = tab[c];                                // the token this lane's class gives the member
+    float row = __shfl(clp, loo_clamp(e_own, vocab));
+    if (e_own < 0) row = -INFINITY;
+    for (int k = vocab; k < n_classes; ++k) {
+      const float x = __shfl(clp, k);
+      const int tok = __shfl(e_cls, k);
+      if (tok == lane && x > -INFINITY) {
+        const float m = fmaxf(row, x);
+        row = row > -INFINITY ? m + logf(expf(row - m) + expf(x - m)) : x;
+      }
+    }
+    if (lane < vocab) log_probs[(long)cur * vocab + lane] = row;
+    cur = GROUPS ? b0 + loo_clamp(next[cur], N) : loo_clamp(gl[cur], G);
     if (cur == g) break;
   }
 }

@@ -1,6 +1,7 @@
 // Translation unit of the leave-one-out decoder (namp_loo.h): namp_loo_workspace_bytes / namp_decoder_loo of include/namp.h, and the
 // pair conditionals riding on it (namp_loo_pairs_workspace_bytes / namp_loo_pairs_offset / namp_loo_pairs), and the group
-// conditionals (namp_loo_groups_workspace_bytes / namp_loo_groups_offset / namp_loo_groups).
+// conditionals (namp_loo_groups_workspace_bytes / namp_loo_groups_offset / namp_loo_groups), and pair classes in either
+// (namp_loo_classes_workspace_bytes / namp_loo_classes_out_offset / namp_loo_classes).
 // Host code only validates, carves the caller's workspace and enqueues launches on the caller's stream.  The base stream's
 // per-layer states and tables come from the library's own building blocks (namp_node_linear, namp_dec_message_update, ...).
 #include "../../include/namp.h"
@@ -44,9 +45,13 @@ struct LooBuffers {
   size_t pin_off, pair_bytes;
   int32_t *gkey;           // [R] with groups, behind the pair carve: the stream and listed position an active phase-1 slot names
   size_t group_bytes;
+  // with pair classes (cls: 1 on the pair carve, 2 on the group carve) the input section also holds bias[n_maps][64], and behind the
+  // carve of the tie it rides on lies the OUTPUT section:
+  float *cls;              // [G][64] the class row of every residue (-inf rows on all but the leaders of valid pairs / groups)
+  size_t cls_off, cls_bytes;
 };
 
-LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0) {
+LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0, int cls = 0) {
   LooBuffers b;
   size_t off = 0;
   auto take = [&](size_t elems) {
@@ -67,12 +72,15 @@ LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0) {
   b.esrc1 = (int32_t*)take(R * K); b.esrc2 = (int32_t*)take(R * K);
   b.bytes = off;
   b.pin_off = off;
-  b.pin = (int32_t*)take((size_t)4 * G + (size_t)64 * n_maps);
+  b.pin = (int32_t*)take((size_t)4 * G + (size_t)64 * n_maps * (cls ? 2 : 1));
   b.pp = (int32_t*)take((size_t)G); b.lead = (int32_t*)take((size_t)G);
   b.PfwQ[0] = (float*)take(2 * g128); b.PfwQ[1] = (float*)take(2 * g128);
   b.pair_bytes = off;
+  b.cls = nullptr; b.cls_off = b.cls_bytes = 0;
+  if (cls == 1) { b.cls_off = off; b.cls = (float*)take((size_t)64 * G); b.cls_bytes = off; }
   b.gkey = (int32_t*)take(R);
   b.group_bytes = off;
+  if (cls == 2) { b.cls_off = off; b.cls = (float*)take((size_t)64 * G); b.cls_bytes = off; }
   return b;
 }
 
@@ -109,6 +117,8 @@ void loo_proj(NodeTail& t, const float* img, const float* bias, const float* tok
 thread_local int g_loo_pairs = 0;
 // ... or its group tables (namp_loo_groups); the later of the two attachments holds
 thread_local int g_loo_groups = 0;
+// ... spoken in pair classes (namp_loo_classes): the number of classes beside the tables of one of the two above, else 0
+thread_local int g_loo_classes = 0;
 
 }  // namespace
 
@@ -124,6 +134,7 @@ size_t namp_loo_pairs_offset(int B, int N, int K, int n_dec) { return namp_loo_w
 int namp_loo_pairs(int n_maps) {
   g_loo_pairs = 0;
   g_loo_groups = 0;
+  g_loo_classes = 0;
   if (n_maps < 1 || n_maps > 64) return lfail(NAMP_EINVAL, "namp_loo_pairs: n_maps=%ld must be in [1, 64]", n_maps);
   g_loo_pairs = n_maps;
   return NAMP_OK;
@@ -142,8 +153,32 @@ int namp_loo_group_max(void) { return NAMP_LOO_GROUP_MAX; }
 int namp_loo_groups(int n_maps) {
   g_loo_pairs = 0;
   g_loo_groups = 0;
+  g_loo_classes = 0;
   if (n_maps < 1 || n_maps > 64) return lfail(NAMP_EINVAL, "namp_loo_groups: n_maps=%ld must be in [1, 64]", n_maps);
   g_loo_groups = n_maps;
+  return NAMP_OK;
+}
+
+// (pair classes ride on either carve: the input section grows by the biases, the output section lies behind the carve)
+size_t namp_loo_classes_workspace_bytes(int B, int N, int K, int n_dec, int n_tables, int groups) {
+  if (namp_loo_pairs_workspace_bytes(B, N, K, n_dec, n_tables) == 0 || groups < 0 || groups > 1) return 0;
+  return loo_carve(nullptr, (long)B * N, K, n_tables, groups ? 2 : 1).cls_bytes;
+}
+
+size_t namp_loo_classes_out_offset(int B, int N, int K, int n_dec, int n_tables, int groups) {
+  if (namp_loo_pairs_workspace_bytes(B, N, K, n_dec, n_tables) == 0 || groups < 0 || groups > 1) return 0;
+  return loo_carve(nullptr, (long)B * N, K, n_tables, groups ? 2 : 1).cls_off;
+}
+
+int namp_loo_classes(int n_tables, int n_classes, int groups) {
+  g_loo_pairs = 0;
+  g_loo_groups = 0;
+  g_loo_classes = 0;
+  if (n_tables < 1 || n_tables > 64) return lfail(NAMP_EINVAL, "namp_loo_classes: n_tables=%ld must be in [1, 64]", n_tables);
+  if (n_classes < 1 || n_classes > 64) return lfail(NAMP_EINVAL, "namp_loo_classes: n_classes=%ld must be in [vocab, 64]", n_classes);
+  if (groups < 0 || groups > 1) return lfail(NAMP_EINVAL, "namp_loo_classes: groups=%ld must be 0 (pairs) or 1 (groups)", groups);
+  (groups ? g_loo_groups : g_loo_pairs) = n_tables;
+  g_loo_classes = n_classes;
   return NAMP_OK;
 }
 
@@ -157,8 +192,10 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
                      int B, int N, int K, void* stream) {
   const bool groups = g_loo_groups != 0;
   const int n_maps = groups ? g_loo_groups : g_loo_pairs;
+  const int n_classes = g_loo_classes;
   g_loo_pairs = 0;                                               // (one call only, whatever becomes of it)
   g_loo_groups = 0;
+  g_loo_classes = 0;
   if (!w || !h_V_enc || !h_E || !E_idx || !S || !mask || !rank || !log_probs || !counts || !ws)
     return lfail(NAMP_EINVAL, groups   ? "namp_decoder_loo: null pointer argument (group tables were attached)"
                               : n_maps ? "namp_decoder_loo: null pointer argument (pair tables were attached)"
@@ -167,6 +204,8 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
     return lfail(NAMP_EINVAL, "namp_decoder_loo: h_V_enc / h_E / log_probs / ws must be 16-byte aligned");
   if (w->n_dec != 3) return lfail(NAMP_EINVAL, "namp_decoder_loo: the cone kernels walk three decoder layers (n_dec=%ld): use the L-stream form", w->n_dec);
   if (w->vocab < 1 || w->vocab > 64) return lfail(NAMP_EINVAL, "namp_decoder_loo: vocab=%ld out of range", w->vocab);
+  if (n_classes && n_classes < w->vocab)
+    return lfail(NAMP_EINVAL, "namp_decoder_loo: n_classes=%ld of the attached class tables is below vocab=%ld", n_classes, w->vocab);
   int rc = loo_dims(B, N, K);
   if (rc) return rc;
   int prec = PREC_F32;
@@ -184,10 +223,12 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   }
   if (!w->Wout_w || !w->Wout_b) return lfail(NAMP_EINVAL, "namp_decoder_loo: null output head");
   const long G = (long)B * N, R = G * K;
-  LooBuffers b = loo_carve(ws, G, K, n_maps);
+  LooBuffers b = loo_carve(ws, G, K, n_maps, n_classes ? (groups ? 2 : 1) : 0);
   static_assert(NAMP_LOO_GROUP_MAX <= 16, "loo_prepare_kernel packs a listed position into 4 bits beside a residue index below 2^27");
   if (n_maps && 2 * G >= (1L << LOO_ROW_BITS)) return lfail(NAMP_EINVAL, "namp_decoder_loo: 2*B*N=%ld exceeds 2^28 table rows", 2 * G);
-  const size_t need = groups ? b.group_bytes : n_maps ? b.pair_bytes : b.bytes;
+  const size_t need = n_classes ? b.cls_bytes : groups ? b.group_bytes : n_maps ? b.pair_bytes : b.bytes;
+  if (need > ws_bytes && n_classes)                              // (the class section is part of the call's arguments: include/namp.h)
+    return lfail(NAMP_EINVAL, "namp_decoder_loo: workspace too small for the attached class tables (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
   if (need > ws_bytes) return lfail(NAMP_EWORKSPACE, "namp_decoder_loo: workspace too small (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
   std::call_once(g_loo_once, set_loo_attrs);
   if (g_loo_err != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(g_loo_err));
@@ -285,8 +326,16 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   loo_tail(a.tail, D2, mask, S, b.h3o);
   a.tail.head_w = w->Wout_w; a.tail.head_b = w->Wout_b; a.tail.log_probs = log_probs; a.tail.logits = nullptr; a.tail.vocab = w->vocab;
   if ((rc = launch_items(a, prec, s)) || !n_maps) return rc;
-  // pairs: the two members' rows -> the pair's conditional, through their token maps; groups: every member's
-  if (groups)
+  // pairs: the two members' rows -> the pair's conditional, through their token maps; groups: every member's; pair classes: through
+  // their class tables, with the class rows into the output section
+  const float* p_bias = (const float*)(p_maps + (size_t)64 * n_maps);
+  if (n_classes && groups)
+    hipLaunchKernelGGL(loo_class_combine_kernel<1>, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.lead, b.pin, p_map,
+                       p_weight, p_maps, p_bias, b.cls, n_maps, n_classes, (int)w->vocab, (int)G, N);
+  else if (n_classes)
+    hipLaunchKernelGGL(loo_class_combine_kernel<0>, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.lead, b.pin, p_map,
+                       p_weight, p_maps, p_bias, b.cls, n_maps, n_classes, (int)w->vocab, (int)G, N);
+  else if (groups)
     hipLaunchKernelGGL(loo_group_combine_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.pin, p_map, p_weight,
                        p_maps, n_maps, (int)w->vocab, (int)G, N);
   else

@@ -221,6 +221,9 @@ _PROTOTYPES = {
     "namp_loo_groups_offset": (sz, [i32, i32, i32, i32]),
     "namp_loo_groups": (i32, [i32]),
     "namp_loo_group_max": (i32, []),
+    "namp_loo_classes_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "namp_loo_classes_out_offset": (sz, [i32, i32, i32, i32, i32, i32]),
+    "namp_loo_classes": (i32, [i32, i32, i32]),
 }
 
 KERNEL_KINDS = ["gather", "node_linear", "edge_embed", "enc_message", "enc_edge_update", "node_update",

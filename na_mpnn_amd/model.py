@@ -842,7 +842,7 @@ class ProteinMPNN(nn.Module):
     loo_dense_tokens = 65536
 
     @torch.no_grad()
-    def conditional_probs(self, feature_dict, method="auto", tied=False):
+    def conditional_probs(self, feature_dict, method="auto", tied=False, classes=False):
         """Leave-one-out conditionals of every residue in one call: out["log_probs"][b, i, :] = log p(s_i | X, S_-i), row i of score()'s
         parallel decoder (model_utils.py:391-421) run with score()'s decoding order (:388-389) in which residue i is moved to the end,
         the true S teacher-forced everywhere (leave_one_out_ranks).  Returns {"S", "log_probs" [B, L, vocab], "decoding_order"};
@@ -876,9 +876,24 @@ class ProteinMPNN(nn.Module):
         groups actually tied (flat indices with states), and "group_log_probs" [n, vocab], the rows of their listed-first members.
         The cone evaluates all groups in the one call (namp_loo_groups); "dense", and "auto" where the cone does not apply, is the
         slow route: one teacher-forced design call of the sampler per group.  With tied=False (the default) nothing above applies:
-        symmetry_residues alone are not read, and the refusals of the pair conditionals stand."""
+        symmetry_residues alone are not read, and the refusals of the pair conditionals stand.
+        Pair classes (classes=True).  paired_wobble / paired_wobble_bias (a bool / float, or one per pair, as in
+        sample()) are honoured: the members of a pair or group speak through the class tables C_t and the group class bias b of
+        mapped_groups(..., wobble, wobble_bias), and on the SAME stream as above total[c] = sum_t w_t z_t[C_t[c]] + b[c] over the
+        classes c < spec.N_CLASSES every member has a token for (listed order, the bias added last; absent classes -inf),
+        clp = log_softmax(total), and a member's row is the log-marginal in its own alphabet, row_m[t] = logsumexp of clp[c] over
+        {c : C_m[c] == t} (T = 1, no `bias`, special tokens kept: the sampler removes the classes that close on a special token, the
+        conditional does not).  With tied=False: pairs only, the refusals above stand, and "pair_class_log_probs" [n, 64] (clp of every
+        tied pair, -inf on absent lanes) is returned beside "pair_log_probs", the marginal rows of the listed-first members.  With
+        tied=True: every tie above with class tables — wobble pairs joined with state_weights are groups of 2 M members, a wobble pair
+        with a member in a symmetry_residues group is mapped_groups' ValueError — and "group_class_log_probs" [n, 64] is returned.
+        Without paired_wobble, or with no pair that can wobble (DNA with DNA), the rows are the bits of the classes=False call and the
+        class rows hold -inf on lanes 33 / 34.  The cone combines in one launch (namp_loo_classes); the slow route is the per-group
+        design call above with the class combine applied in torch.  With classes=False (the default) paired_wobble stays refused."""
         if method not in ("auto", "dense", "cone"):
             raise ValueError(f"method must be 'auto', 'dense' or 'cone'; got {method!r}")
+        if classes:
+            return self._conditional_probs_classes(feature_dict, method, bool(tied))
         if tied:
             return self._conditional_probs_tied(feature_dict, method)
         S_true, mask = feature_dict["S"], feature_dict["mask"]
@@ -1109,7 +1124,7 @@ class ProteinMPNN(nn.Module):
         out.update(log_probs=log_probs[:, :L], groups=groups_dev, group_log_probs=log_probs[0, lead])
         return out
 
-    def _group_conditionals_by_sampling(self, fd, order0, grp, log_probs, state_w):
+    def _group_conditionals_by_sampling(self, fd, order0, grp, log_probs, state_w, classes=False):
         """The slow route of the group conditionals: per tied group ONE teacher-forced design call — chain_mask all ones, a randn whose
         sort is score()'s order with the group's residues moved to the end in listed order, T = 1, zero bias, the group as the call's
         only symmetry group (with its maps) — whose member rows are combined into the group's rows of log_probs [1, M * L, vocab] (in place)."""
@@ -1123,7 +1138,8 @@ class ProteinMPNN(nn.Module):
         bias = torch.zeros(1, L, self.num_letters, device=dev)
         pos = torch.arange(1, L + 1, dtype=torch.float32, device=dev)
         ident = list(range(self.num_letters))
-        for (flat, fw, fm), (g, gw, gm) in zip(grp["tied"], grp["base"]):
+        class_rows = []
+        for (flat, fw, fm, *cb), (g, gw, gm, *_) in zip(grp["tied"], grp["base"]):
             g_t = torch.tensor(g, device=dev)
             rest = order0[~torch.isin(order0, g_t)]
             order = torch.cat((rest, g_t))
@@ -1133,7 +1149,7 @@ class ProteinMPNN(nn.Module):
             one = dict(keep, chain_mask=ones, randn=randn[None], batch_size=1, temperature=1.0, bias=bias, S_forced=S_true)
             if len(g) > 1:
                 one.update(symmetry_residues=[g], symmetry_weights=[gw])
-                if any(list(P) != ident for P in gm):
+                if not classes and any(list(P) != ident for P in gm):    # (the members' own rows do not depend on the maps)
                     one["symmetry_token_maps"] = [gm]
             else:
                 one.update(symmetry_residues=[[]], symmetry_weights=[[]])
@@ -1141,6 +1157,11 @@ class ProteinMPNN(nn.Module):
             if not torch.equal(got["decoding_order"][0], order):
                 raise RuntimeError(f"conditional_probs: the design call of group {g} did not decode it last")
             lp = got["log_probs"].reshape(-1, self.num_letters)             # [M * L, vocab]
+            if classes:
+                rows, clp = self._class_combine(lp[flat], fw, fm, cb[0])
+                log_probs[0, flat] = rows
+                class_rows.append(clp)
+                continue
             maps_t = [torch.tensor(P, device=dev) for P in fm]
             total = None
             for r, wr, P in zip(flat, fw, maps_t):
@@ -1148,6 +1169,211 @@ class ProteinMPNN(nn.Module):
             row = torch.log_softmax(total, -1)
             for r, P in zip(flat, maps_t):
                 log_probs[0, r, P] = row
+        return class_rows
+
+    @staticmethod
+    def _class_combine(z, ws, tables, class_bias):
+        """The class combine of the slow route in torch: z [n, vocab] the members' rows in listed order, ws their weights, tables their
+        class tables [n][64], class_bias [64] -> (rows [n, vocab] the members' log-marginals, clp [64] with -inf on absent classes)."""
+        dev, vocab = z.device, z.shape[-1]
+        T = torch.tensor(tables, device=dev)
+        have = (T >= 0).all(0) & (torch.arange(T.shape[1], device=dev) < spec.N_CLASSES)
+        Tc = T.clamp(min=0)
+        total = None
+        for zt, wt, t in zip(z, ws, Tc):
+            total = float(wt) * zt[t] if total is None else total + float(wt) * zt[t]
+        total = total + torch.tensor(class_bias, dtype=z.dtype, device=dev)
+        neg = torch.full_like(total, -float("inf"))
+        clp = torch.log_softmax(torch.where(have, total, neg), -1)
+        tok = torch.arange(vocab, device=dev)
+        rows = [torch.logsumexp(torch.where((t[:, None] == tok[None, :]) & have[:, None], clp[:, None], neg[:, None]), 0) for t in T]
+        return torch.stack(rows), torch.where(have, clp, neg)
+
+    def _class_conditional_arguments(self, fd, B, L, state_w, tied):
+        """The tied pairs (tied=False) or groups (tied=True) of a conditional_probs(classes=True) call, spoken in pair classes -> None
+        with nothing to tie, else {"tied": [(members, weights, class tables, class bias)] what the device ties, in flat indices,
+        "base": the same per group in [0, L) without the state weight (the slow route), "groups": int64 [n, max_size] padded with -1
+        (tied=False: [n, 2]), "section": the int32 input section of the workspace (include/namp.h: partner / next, first, table_idx,
+        weight bits, tables, bias bits; told apart by (table, bias)), "n_tables"}.  The refusals are those of the classes=False call."""
+        pairs, sym = fd.get("paired_residues"), fd.get("symmetry_residues")
+        pairs = None if pairs is None or len(pairs) == 0 else pairs
+        sym = None if sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0) else sym
+        if not tied:
+            if pairs is None:
+                return None
+            if sym is not None:
+                raise NotImplementedError("conditional_probs: paired_residues together with symmetry_residues is not supported")
+            if fd.get("state_weights") is not None:
+                raise NotImplementedError("conditional_probs: paired_residues together with state_weights is not supported")
+            if B != 1:
+                raise ValueError("paired_residues expect one input complex (B == 1)")
+        else:
+            if pairs is None and sym is None and state_w is None:
+                return None
+            if B != 1:
+                raise ValueError("tied groups expect one input complex (B == 1)")
+        if self.restype_to_int is None:
+            raise ValueError("paired_residues / tied groups need the model's restype_to_int")
+        to_list = lambda v: v.detach().reshape(-1).tolist() if torch.is_tensor(v) else (list(v) if hasattr(v, "__len__") else v)
+        wobble, wobble_bias = to_list(fd.get("paired_wobble")), to_list(fd.get("paired_wobble_bias"))
+        n_pairs = 0 if pairs is None else len(pairs)
+        for v, what in ((wobble, "paired_wobble"), (wobble_bias, "paired_wobble_bias")):
+            if isinstance(v, list) and len(v) != n_pairs:
+                raise ValueError(f"{what} has {len(v)} entries for {n_pairs} pairs")
+        if (any(wobble) if isinstance(wobble, list) else bool(wobble)) and n_pairs == 0:
+            raise ValueError("paired_wobble needs paired_residues")
+        m = self._host_list(fd["mask"], "mask")
+        dna = rna = None
+        if pairs is not None:
+            dna, rna = self._host_list(fd["dna_mask"], "dna_mask"), self._host_list(fd["rna_mask"], "rna_mask")
+        # the tables of the last call are kept as without classes, keyed on `classes`, the wobble flags and the biases as well — in slots
+        # of their own beside _pair_tables / _group_tables: a specificity profile alternates the classes call with the canonical one
+        # on the same resident feature_dict, and in one slot each of the two would rebuild and page-lock its tables on every call
+        as_list = lambda v: v.tolist() if hasattr(v, "tolist") else v
+        listed = lambda v: None if v is None else [[as_list(x) for x in g] if hasattr(g, "__len__") else g for g in v]
+        key = ("classes", tied, None if pairs is None else [(int(a), int(b)) for a, b in pairs], as_list(fd.get("paired_weights")),
+               None if sym is None else [[int(r) for r in g] for g in sym], listed(fd.get("symmetry_weights")) if sym is not None else None,
+               state_w, wobble, wobble_bias, fd.get("symmetry_token_maps") is None)
+        last = getattr(self, "_group_class_tables" if tied else "_pair_class_tables", None)
+        if last is not None and key[-1] and last[0] == key and all(x is y for x, y in zip(last[1], (dna, rna, m))):
+            return last[2]
+        polymer = None
+        if pairs is not None:
+            polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
+            for pr in pairs:                              # (a masked residue may come without a polymer flag: its partner's stands in, as in sample())
+                for r, q in ((int(pr[0]), int(pr[1])), (int(pr[1]), int(pr[0]))):
+                    if 0 <= r < L and 0 <= q < L and not m[r] and polymer[r] == 0 and polymer[q] in (1, 2) \
+                            and not self._host_list(fd["protein_mask"], "protein_mask")[r]:
+                        polymer[r] = polymer[q]
+        groups, weights, gtabs, _, gbias = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, None, sym,
+                                                         fd.get("symmetry_weights") if sym is not None else None,
+                                                         fd.get("symmetry_token_maps"), False if wobble is None else wobble, wobble_bias)
+        members = [r for g in groups for r in g]
+        if len(set(members)) != len(members):
+            raise ValueError("conditional_probs: the tied groups must be disjoint")
+        M, sw = (1, [1.0]) if state_w is None else (len(state_w), state_w)
+        V = len(spec.RESTYPES)
+        ident, zero = list(range(V)) + [-1] * (spec.N_CLASS_LANES - V), [0.0] * spec.N_CLASS_LANES
+        if state_w is not None:                            # every residue is a group across the states
+            tied_res = set(members)
+            for i in range(L):
+                if i not in tied_res:
+                    groups.append([i]); weights.append([1.0]); gtabs.append([ident]); gbias.append(zero)
+        N = M * L
+        nxt, first, tidx, w = [-1] * N, [0] * N, [0] * N, [1.0] * N
+        table, bias, index = [ident], [zero], {(tuple(ident), tuple(zero)): 0}
+        tied_specs, base = [], []
+        for g, gw, gt, gb in zip(groups, weights, gtabs, gbias):
+            if len(g) * M > hip.loo_group_max():
+                raise ValueError(f"conditional_probs: the group of residue {g[0]} has {len(g) * M} members; at most {hip.loo_group_max()} are tied")
+            if len(g) * M < 2:
+                continue
+            flat = [r + s_ * L for s_ in range(M) for r in g]                 # state-major, as _sample_states lists them
+            fw = [sw[s_] * float(v) for s_ in range(M) for v in gw]
+            ft = [C for s_ in range(M) for C in gt]
+            for t, (r, wr, C) in enumerate(zip(flat, fw, ft)):
+                k = index.get((tuple(C), tuple(gb)))
+                if k is None:
+                    k = index[(tuple(C), tuple(gb))] = len(table)
+                    table.append(list(C)); bias.append([float(v) for v in gb])
+                nxt[r], tidx[r], w[r] = flat[(t + 1) % len(flat)], k, wr
+            first[flat[0]] = 1
+            if all(m[r] for r in g):                       # the device's rule: a pair / group with a masked member is not tied
+                tied_specs.append((flat, fw, [list(C) for C in ft], [float(v) for v in gb]))
+                base.append((list(g), [float(v) for v in gw], [list(C) for C in gt], [float(v) for v in gb]))
+        if len(table) > 64:
+            raise ValueError(f"conditional_probs: {len(table)} distinct class tables; at most 64")
+        width = 2 if not tied else max([len(t[0]) for t in tied_specs], default=0)
+        section = torch.cat((torch.tensor(nxt + first + tidx, dtype=torch.int32), torch.tensor(w, dtype=torch.float32).view(torch.int32),
+                             torch.tensor([t for C in table for t in C], dtype=torch.int32),
+                             torch.tensor([v for row in bias for v in row], dtype=torch.float32).view(torch.int32)))
+        out = {"tied": tied_specs, "base": base, "section": section, "n_tables": len(table),
+               "groups": torch.tensor([t[0] + [-1] * (width - len(t[0])) for t in tied_specs], dtype=torch.int64).reshape(-1, width)}
+        setattr(self, "_group_class_tables" if tied else "_pair_class_tables", (key, (dna, rna, m), out))
+        return out
+
+    def _conditional_probs_classes(self, fd, method, tied):
+        """conditional_probs(classes=True): the pair (tied=False) and group (tied=True) conditionals in pair classes (see conditional_probs)."""
+        S_true, mask = fd["S"], fd["mask"]
+        B, L = S_true.shape
+        state_w, M = None, 1
+        if tied and fd.get("state_weights") is not None:
+            fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
+            fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
+            fd_chk.pop("S_forced", None)
+            state_w, M, L, _, _ = self._states_arguments(fd_chk)
+        grp = self._class_conditional_arguments(fd, B, L, state_w, tied)
+        if grp is None:
+            return self.conditional_probs(fd, method)
+        cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        if method == "cone" and not cone_ok:
+            raise NotImplementedError("conditional_probs(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
+                                      "use method='dense'")
+        use_cone = method == "cone" or (method == "auto" and cone_ok)
+        _require_device(fd["X"], "X")
+        dev, Lb, n_dec, N = S_true.device, hip.lib(), len(self.decoder_layers), M * L
+        K = int(min(self.k_neighbors, L))
+        ws = None
+        # The tables go up BEFORE the encoder is enqueued (a host-to-device copy waits for the stream), page-locked once with the cached tables
+        for key in ("section", "groups"):
+            if not grp[key].is_pinned():
+                grp[key] = grp[key].pin_memory()
+        n_tab = grp["n_tables"]
+        if use_cone:
+            section = grp["section"]
+            ws = torch.empty(Lb.namp_loo_classes_workspace_bytes(1, N, K, n_dec, n_tab, int(tied)), dtype=torch.uint8, device=dev)
+            off = Lb.namp_loo_groups_offset(1, N, K, n_dec)
+            ws[off:off + 4 * section.numel()].view(torch.int32).copy_(section, non_blocking=True)
+        groups_dev = grp["groups"].to(dev, non_blocking=True)
+        o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1] if state_w is not None else fd["randn"])
+        if tied:
+            fd_enc = fd
+            if state_w is not None:
+                fd_enc = dict(fd)
+                for k in self._STATE_SHARED:
+                    fd_enc[k] = fd[k].expand(M, L)
+            V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
+            h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
+        else:
+            h_V, h_E, E_idx = self.encode(fd, order=o)
+        self._check_tokens(S_true)
+        o.wait()
+        rank = o.rank[:1]
+        out = {"S": S_true, "decoding_order": o.order[0]}
+        lead = groups_dev[:, 0] if groups_dev.numel() else groups_dev.reshape(-1)
+        if use_cone:
+            W = self._weights()
+            E_f = E_idx if M == 1 else _i32(E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).contiguous()
+            rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
+            E_f, S32, m32, r32 = _i32(E_f), _i32(rep(self._as(S_true, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
+            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+            hip.check(Lb.namp_loo_classes(n_tab, spec.N_CLASSES, int(tied)), "loo_classes")   # the NEXT namp_decoder_loo call reads the section
+            counts = torch.empty(2, dtype=torch.int32, device=dev)
+            log_probs = torch.empty(1, N, self.num_letters, device=dev)
+            hip.check(Lb.namp_decoder_loo(W.model(), h_V.data_ptr(), h_E.data_ptr(), E_f.data_ptr(), S32.data_ptr(), m32.data_ptr(),
+                                          r32.data_ptr(), log_probs.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), 1, N, K,
+                                          hip.current_stream()), "decoder_loo")
+            out["cone_items"] = counts
+            c_off = Lb.namp_loo_classes_out_offset(1, N, K, n_dec, n_tab, int(tied))
+            class_rows = ws[c_off:c_off + 4 * spec.N_CLASS_LANES * N].view(torch.float32).view(N, spec.N_CLASS_LANES)[lead]
+        else:
+            log_probs = torch.empty(M, L, self.num_letters, device=dev)
+            chunk = max(1, self.loo_dense_tokens // L)
+            for b in range(M):
+                for i0 in range(0, L, chunk):
+                    i1 = min(L, i0 + chunk)
+                    n = i1 - i0
+                    ranks = leave_one_out_ranks(rank, i0, i1)[0]
+                    lp = self.decode_graph(h_V[b:b + 1], h_E[b:b + 1], E_idx[b:b + 1].long(), S_true.expand(n, L), mask.expand(n, L), ranks)
+                    ar = torch.arange(n, device=dev)
+                    log_probs[b, i0:i1] = lp[ar, i0 + ar]
+            log_probs = log_probs.view(1, N, self.num_letters)
+            rows = self._group_conditionals_by_sampling(fd, o.order[0], grp, log_probs, state_w, classes=True)
+            class_rows = torch.stack(rows) if rows else torch.zeros(0, spec.N_CLASS_LANES, device=dev)
+        what = "group" if tied else "pair"
+        out.update({"log_probs": log_probs[:, :L], what + "s": groups_dev, what + "_log_probs": log_probs[0, lead],
+                    what + "_class_log_probs": class_rows})
+        return out
 
     def _pair_conditional_arguments(self, fd, B, L):
         """The base pairs of a conditional_probs() call -> None without pairs, else {"tied": [(i, j, w_i, w_j, P_i, P_j)] the pairs the

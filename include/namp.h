@@ -707,6 +707,37 @@ int namp_sample_token_maps(const int32_t* tok_maps, int n_maps);
  * namp_sample_token_maps with free members.  Not together with pair_bias (NAMP_EINVAL from the sampler call). */
 int namp_sample_class_tables(const int32_t* tables, int n_tables, int n_classes);
 
+/* ---- compact pair terms: a pair bias that names its partners --------------------------------------------------------
+ * The quantity of the dense pair_bias [B_enc][N][vocab][N][vocab] for the usual case that a residue reads a few partners: every
+ * residue i of an encoded complex has D slots d with partner[i][d] (local index in its complex, -1: none) and table[i][d], and
+ *     term(i)[a] = sum over d, in slot order and in fp32, of tables[table[i][d]][a][tok(partner[i][d])]
+ * — tok(j) the drawn token of j if j's group closed before the current group's first visit, else PAD (vocab - 1): the reference's
+ * running S (model_utils.py:157,171,265,281); the members of the group that is being drawn read as PAD.  With the slots sorted by
+ * partner this is the dense branch on pair_bias[b, i, a, j, b'] = sum over the slots d with partner j of tables[table[i][d]][a][b'],
+ * bit for bit where no partner repeats.  The term is added where the bias row is: before / T, before the special tokens are
+ * removed, with class tables before the restriction by pinned members.  members = 0 (the reference's rule, :300): the closing member
+ * c of a group counts, add[a] = term(c)[P_c[a]] — read through its token map as its bias row is, through C_c[class] with class
+ * tables; members = 1: every member counts, add[a] = sum over the members m in visit order of term(m)[P_m[a]], each through its own
+ * map or table (what a base pair needs: both strands feel their neighbours).  A singleton group is the same under both.
+ * No entry point takes a pointer: the arrays travel in a caller-filled INPUT SECTION of the sampler's `ws`,
+ *     namp_sample_pair_terms_offset(B_enc, B_dec, N, K, n_dec)   byte offset of the section in ws (256-byte aligned, behind the carve of
+ *                                                                namp_sample_workspace_bytes_n; the walk's barrier words stay the last
+ *                                                                4 KiB of that carve; 0 on bad arguments)
+ *     int32 words, G = B_enc * N:  partner[G][D]  table_idx[G][D]  tables[n_tables][vocab][vocab] (float bits; vocab: the weights' own)
+ * and namp_sample_pair_terms(D, n_tables, members), 1 <= D <= 64, 1 <= n_tables <= 256, members 0 / 1 (NAMP_EINVAL otherwise, and
+ * nothing stays attached), attaches them to the calling thread's NEXT namp_decoder_sample / _levels / _walk call, which then requires
+ * ws_bytes >= namp_sample_pair_terms_workspace_bytes(B_enc, B_dec, N, K, n_dec, D, n_tables) (the tables sized for vocab = 64; 0 on
+ * bad arguments; NAMP_EINVAL from the sampler call if ws is smaller) and clears the attachment whether it succeeds or not.  Together
+ * with the dense pair_bias pointer that call returns NAMP_EINVAL; together with namp_sample_token_maps / namp_sample_class_tables it
+ * is allowed.  The section is device data and is validated on the device: a partner outside [0, N) or the residue itself is
+ * absent (contributes 0), table indices are clamped to [0, n_tables).  partner[G][D] has the layout of namp_sample_levels_dep's
+ * dep_idx and is what the level decoders need as such: a step depends on its partners.  The sequential walk needs nothing.
+ * One wave per draw, lane = token or class; per counted member D agent-scope loads of S_out and D table loads; no atomics beyond those
+ * loads: two calls give identical bits.  Without an attachment every sampler call keeps its bits. */
+size_t namp_sample_pair_terms_workspace_bytes(int B_enc, int B_dec, int N, int K, int n_dec, int D, int n_tables);
+size_t namp_sample_pair_terms_offset(int B_enc, int B_dec, int N, int K, int n_dec);
+int namp_sample_pair_terms(int D, int n_tables, int members);
+
 /* ---- tied states: the plan of one sequence sampled over M backbone states of the same molecule -------------------
  * M states of N residues, encoded as a batch, are ONE symmetric design on the block-diagonal flattened graph of M * N residues:
  * residue n of state m is flat residue m * N + n, its neighbours are E_idx[m][n][:] + m * N, and the M copies of a residue form a

@@ -47,7 +47,11 @@ def build_parser():
     a("--redesigned_residues", type=str, default="")
     a("--parse_these_chains_only", type=str, default="")
     a("--bias_AA", type=str, default="")
-    a("--pair_bias_AA", type=str, default="", help="pair bias for sequence neighbours, e.g. 'KK:-10.0,KE:-10.0'")
+    a("--pair_bias_AA", type=str, default="", help="pair bias for sequence neighbours, e.g. 'KK:-10.0,KE:-10.0'; goes with "
+      "--paired_residues / --paired_strands / --paired_wobble / --multi_state")
+    a("--pair_bias_members", type=str, default="auto", choices=("auto", "closing", "all"), help="which members of a tied group feel "
+      "--pair_bias_AA: 'closing' - the group's last member only (the reference's rule); 'all' - every member, each in its own alphabet "
+      "(both strands of a base pair feel their neighbours); 'auto' (default) - 'all' when base pairs are given, else 'closing'")
     a("--symmetry_residues", type=str, default="", help="tied residues, e.g. 'A12,A13,A14|C2,C3'")
     a("--symmetry_weights", type=str, default="", help="weights matching --symmetry_residues, e.g. '1.0,1.0,1.0|-1.0,2.0'")
     a("--multi_state", type=int, default=0, help="1 - the MODELs of --pdb_path are states of one molecule: ONE sequence is designed "
@@ -127,6 +131,20 @@ def make_pair_bias(chain_labels, R_idx, pair_bias_AA):
     out[0, i, :, i + 1, :] = pair_bias_AA
     out[0, i + 1, :, i, :] = pair_bias_AA.t()
     return out
+
+
+def make_pair_terms(chain_labels, R_idx, pair_bias_AA, members="closing"):
+    """make_pair_bias's quantity in the compact form of ProteinMPNN.sample's feature_dict["pair_terms"]: tables [AA, AA.t()]; residue i
+    reads i-1 through AA.t() and i+1 through AA where the two are sequence neighbours on one chain (R_idx one apart)."""
+    L = R_idx.shape[0]
+    adj = (((R_idx[1:] - R_idx[:-1]) == 1) & (chain_labels[1:] == chain_labels[:-1])).cpu()
+    partner = torch.full((1, L, 2), -1, dtype=torch.int32)
+    table = torch.zeros(1, L, 2, dtype=torch.int32)
+    i = torch.nonzero(adj)[:, 0]
+    partner[0, i + 1, 0], table[0, i + 1, 0] = i.to(torch.int32), 1
+    partner[0, i, 1] = (i + 1).to(torch.int32)
+    AA = pair_bias_AA.detach().float().cpu()
+    return {"partner": partner, "table": table, "tables": torch.stack((AA, AA.t())).contiguous(), "members": members}
 
 
 def parse_pairs(paired_residues, paired_strands, encoded, chain_letters):
@@ -309,7 +327,8 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
             wn = torch.tensor(state_w, device=device)
             wn = wn / wn.sum() if float(wn.sum()) != 0 else torch.full_like(wn, 1.0 / len(state_w))
         if pair_bias_AA is not None:
-            fd["pair_bias"] = make_pair_bias(fd["chain_labels"][0], fd["R_idx"][0], pair_bias_AA)
+            members = args.pair_bias_members if args.pair_bias_members != "auto" else ("all" if pairs else "closing")
+            fd["pair_terms"] = make_pair_terms(fd["chain_labels"][0], fd["R_idx"][0], pair_bias_AA, members)
         if args.conditional_probs_only:
             # one deterministic leave-one-out profile instead of draws: the decoding order's noise is the only random input
             fd["randn"] = torch.randn(1, L, device=device)

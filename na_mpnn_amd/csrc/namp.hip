@@ -1257,6 +1257,28 @@ int namp_sample_class_tables(const int32_t* tables, int n_tables, int n_classes)
   return NAMP_OK;
 }
 
+// ---- compact pair terms: an INPUT SECTION of the sampler's ws behind the carve of namp_sample_workspace_bytes_n (include/namp.h) ----
+// the attachment of the calling thread's NEXT sampler call (namp_sample_pair_terms): taken, and cleared, by sample_prepare
+static thread_local int g_pair_terms = 0;                       // D | n_tables << 8 | members << 20 (SampleArgs.pair_terms)
+
+size_t namp_sample_pair_terms_offset(int B_enc, int B_dec, int N, int K, int n_dec) {
+  return (sample_ws_bytes(B_enc, B_dec, N, K, n_dec) + 255) & ~size_t(255);
+}
+// (the tables are sized for the largest vocabulary the sampler takes, 64: the call's own is known only with its weights)
+size_t namp_sample_pair_terms_workspace_bytes(int B_enc, int B_dec, int N, int K, int n_dec, int D, int n_tables) {
+  const size_t off = namp_sample_pair_terms_offset(B_enc, B_dec, N, K, n_dec);
+  if (off == 0 || D < 1 || D > 64 || n_tables < 1 || n_tables > 256) return 0;
+  return off + 4 * (2 * (size_t)B_enc * N * D + (size_t)n_tables * 64 * 64);
+}
+int namp_sample_pair_terms(int D, int n_tables, int members) {
+  g_pair_terms = 0;                                              // (an invalid attach leaves nothing attached)
+  REQUIRE(D >= 1 && D <= 64, "namp_sample_pair_terms: D=%d must be in [1, 64]", D);
+  REQUIRE(n_tables >= 1 && n_tables <= 256, "namp_sample_pair_terms: n_tables=%d must be in [1, 256]", n_tables);
+  REQUIRE(members == 0 || members == 1, "namp_sample_pair_terms: members=%d must be 0 (closing) or 1 (all)", members);
+  g_pair_terms = D | (n_tables << 8) | (members << 20);
+  return NAMP_OK;
+}
+
 static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
                           const int32_t* mask, const int32_t* mask_dec, const int32_t* chain_mask, const int32_t* S_true, const float* bias,
                           const int32_t* order, const int32_t* rank, const float* uniform, const int32_t* S_forced,
@@ -1267,6 +1289,9 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
                           SampleArgs* a_out, int* nwaves_out) {
   const int32_t* tok_maps = g_tok_maps; const int n_maps = g_n_maps;
   g_tok_maps = nullptr; g_n_maps = 0;                            // (one call only, whatever becomes of it)
+  const int pair_terms = g_pair_terms;
+  g_pair_terms = 0;
+  REQUIRE(pair_terms == 0 || pair_bias == nullptr, "namp_decoder_sample: pair terms and the dense pair_bias do not go together");
   REQUIRE(w != nullptr, "namp_decoder_sample: null weights");
   REQUIRE(tok_maps == nullptr || pair_bias == nullptr, "namp_decoder_sample: token maps / class tables and pair_bias do not go together");
   REQUIRE((group_first == nullptr) == (group_last == nullptr), "namp_decoder_sample: group_first and group_last go together");
@@ -1285,6 +1310,11 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
   const int Gd = B_dec * N, Ge = B_enc * N;
   Carver c(ws, ws_bytes);
   const int nd = w->n_dec;
+  if (pair_terms) {
+    // the section sits behind the carve (and the walk's barrier words, which stay the last 4 KiB of it)
+    const size_t need = namp_sample_pair_terms_workspace_bytes(B_enc, B_dec, N, K, nd, pair_terms & 0x7f, (pair_terms >> 8) & 0x1ff);
+    REQUIRE(need != 0 && ws_bytes >= need, "namp_decoder_sample: workspace too small for the pair-terms section (%zu bytes, needs %zu)", ws_bytes, need);
+  }
   float* Pfw[NAMP_MAX_LAYERS]; for (int l = 0; l < nd; ++l) Pfw[l] = c.take((size_t)Ge * NAMP_HIDDEN);
   float* Pa0 = c.take((size_t)Ge * NAMP_HIDDEN);
   float *Pa[NAMP_MAX_LAYERS] = {}, *Pv[NAMP_MAX_LAYERS] = {}, *hs[NAMP_MAX_LAYERS] = {};
@@ -1324,6 +1354,10 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
   a.uniform = uniform; a.S_forced = S_forced; a.group_first = group_first; a.group_last = group_last;
   a.sym_w = sym_weights; a.pair_bias = pair_bias; a.tok_maps = tok_maps; a.n_maps = n_maps & 0xffff; a.n_classes = n_maps >> 16; a.head_wT = head_wT; a.head_b = w->Wout_b; a.S_out = S_out;
   a.probs_out = probs_out; a.logp_out = logp_out; a.special = special_tokens; a.inv_T = 1.0f / temperature;
+  if (pair_terms) {
+    a.pair_bias = (const float*)((const char*)ws + namp_sample_pair_terms_offset(B_enc, B_dec, N, K, nd));
+    a.pair_terms = pair_terms;
+  }
   a.B_dec = B_dec; a.B_enc = B_enc; a.N = N; a.K = K; a.TPN = (K + 15) / 16; a.n_layers = w->n_dec; a.vocab = w->vocab;
   // 8 waves per workgroup (256 VGPRs per lane: no scratch) serve 8 / TPN streams; K > 128 falls back to the 12-wave form
   const int maxw = a.TPN <= 8 ? 8 : 12;

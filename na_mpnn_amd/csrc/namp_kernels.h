@@ -2163,7 +2163,7 @@ struct SampleArgs {
   const int32_t* group_first;  // optional [B_dec][N]: visit index of the first member of visit v's group (null: v itself)
   const int32_t* group_last;   // optional [B_dec][N]: 1 if visit v closes its group                       (null: always)
   const float* sym_w;          // optional [G_enc]: weight of a residue's logits in its group's sum        (null: 1)
-  const float* pair_bias;      // optional [G_enc][vocab][N][vocab] (model_utils.py:116,170-172)
+  const float* pair_bias;      // optional [G_enc][vocab][N][vocab] (model_utils.py:116,170-172); with pair_terms != 0 the compact section instead
   // mapped groups (base-paired design): member j of a group speaks the group's token a as P_j[a] — P_j an involution of the vocabulary
   const int32_t* tok_maps;     // optional [n_maps][64]: the token maps, identity beyond vocab, and behind them [G_enc]: the map of a residue
                                //          (null: every map is the identity)
@@ -2180,6 +2180,10 @@ struct SampleArgs {
                                // the fetch in `step` reads a.n_maps as the parent does.  With the 4 bytes of padding behind it the struct and the
                                // launch's own 40 argument bytes fill the 4,096 bytes exactly.)
   int n_maps;                  // (in the padding in front of l: the struct grows by the one pointer only)
+  int pair_terms;              // 0, or COMPACT PAIR TERMS: D | n_tables << 8 | members << 20 (members 1: every member of a group counts, 0: the closing
+                               // one).  pair_bias then points to the int32 section partner[G_enc][D] (-1: none), table_idx[G_enc][D],
+                               // tables[n_tables][vocab][vocab] (float bits) — the dense tensor is never there together with it, so the section needs no
+                               // pointer of its own, and this word fills the last 4 bytes of padding in front of l.
   SampleLayer l[NAMP_MAX_LAYERS];      // 8 x 480 B: with the scalars and the launch's own 40 argument bytes all 4,096 kernel-argument bytes
 };
 static_assert(sizeof(SampleArgs) + 40 <= 4096, "SampleArgs + the sampler launch's scalar arguments must fit the kernel-argument segment");
@@ -2262,7 +2266,7 @@ static __global__ __launch_bounds__(64) void sample_levels_kernel(const int32_t*
     if (dep_idx)
       for (int k = lane; k < D; k += 64) {
         const int j = dep_idx[((long)b_enc * N + i) * D + k];
-        if (j >= 0 && rk[j] < vf) d = max(d, lv[j]);
+        if (j >= 0 && j < N && rk[j] < vf) d = max(d, lv[j]);
       }
     d = (int)wave_max64((float)d);                               // (levels < 2^24: exact in fp32)
     dg = (vf == t) ? d : max(dg, d);
@@ -2346,6 +2350,47 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     const unsigned long long* dp = (const unsigned long long*)(sync + NAMP_SYNC_DEFER);
     zbuf = as_global((float*)dp[0]); close_list = as_global((const int32_t*)dp[1]); close_off = as_global((const int32_t*)dp[2]);
   }
+  // Compact pair terms (SampleArgs.pair_terms): what the group closing at visit t of stream bq adds to the logit of group token / class `lane`,
+  //   sum over the counted members m (the closing one, or all in visit order) of term(m)[tok_m(lane)],
+  //   term(m)[x] = sum over the slots d of m, in slot order, of tables[table[m][d]][x][tok(partner[m][d])]
+  // — tok(j) the token of j if j's group closed before this group's first visit v_first (rank[j] < v_first), else PAD: the reference's
+  // running S (model_utils.py:157,171,265,281), which the members of the open group have not entered yet.  tok_m(lane) is the member's
+  // token of `lane` through its map or class table (idx: the residues' map / table indices; null: the identity).  Equal to the dense
+  // branch below on the densified tensor, bit for bit: the slots come sorted by partner and the dense sum's other summands are zeros.
+  // Every load is unconditional on clamped indices; an absent slot (partner outside [0, N) or the residue itself) contributes 0.
+  auto pair_term = [&](const int bq, const int t, const int v_first, const int pt, const int32_t* idx) __attribute__((always_inline)) {
+    const int D = pt & 0x7f, n_tab = (pt >> 8) & 0x1ff, V = a.vocab;
+    const int e0 = (bq % a.B_enc) * a.N;
+    const int32_t* sec = (const int32_t*)a.pair_bias;
+    const int GD = a.B_enc * a.N * D;                              // (G * D <= 2^31 / 8: the section's offsets fit 32 bits)
+    const float* tabs = (const float*)(sec + 2 * (long)GD);
+    const int32_t* rk = a.rank + (long)bq * a.N;
+    const int32_t* So = a.S_out + (long)bq * a.N;
+    float sum = 0.f;
+#pragma unroll 1
+    for (int v = (pt >> 20) ? v_first : t; v <= t; ++v) {
+      const int im = a.order[(long)bq * a.N + v];
+      int x = idx ? a.tok_maps[idx[e0 + im] * 64 + lane] : lane;
+      x = (x < 0 ? 0 : (x < V ? x : V - 1)) * V;                   // the member's token of `lane`: its row of every table
+      const int32_t* slot = sec + (long)(e0 + im) * D;
+      float term = 0.f;
+#pragma unroll 1
+      for (int d = 0; d < D; ++d) {
+        const int j = slot[d];
+        int k = slot[GD + d];
+        const bool there = j >= 0 && j < a.N && j != im;
+        const int jc = there ? j : 0;
+        k = k < 0 ? 0 : (k < n_tab ? k : n_tab - 1);
+        // (one address for the whole wave: the token comes back as a scalar, and the table load is scalar base + the lane's row)
+        int Sj = __builtin_amdgcn_readfirstlane(__hip_atomic_load(So + jc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (rk[jc] >= v_first || Sj < 0 || Sj >= V) Sj = V - 1;
+        const float val = (tabs + (k * V * V + Sj))[x];
+        term += there ? val : 0.f;
+      }
+      sum += term;
+    }
+    return sum;
+  };
   // softmax((total + bias_t [+ pair_bias_t]) / T) with bias of the group's last residue (visit t of stream bq), special tokens removed,
   // renormalised (model_utils.py:194-205 / :300-312); inverse-CDF draw; the token goes to every member v_first .. t.  One wave.
   auto draw = [&](const int bq, const int t, const int v_first, const float total) __attribute__((always_inline)) {
@@ -2353,6 +2398,10 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     const int ne = (bq % a.B_enc) * a.N + iq;
     const long vis = (long)bq * a.N + t;
     const int nm = scalar_here(a.n_maps) | (scalar_here(a.n_classes) << 16);      // (both counts in one scalar register: n_maps <= 4096)
+    // (compact pair terms, once for all three forms: the residues' map / table indices sit behind the maps / tables in either case)
+    float pterm = 0.f;
+    const int pt = scalar_here(a.pair_terms);
+    if (pt) pterm = pair_term(bq, t, v_first, pt, a.tok_maps ? a.tok_maps + (nm & 0xffff) * 64 : nullptr);
     if (nm >> 16) {
       // Class tables: the group draws a PAIR CLASS c = lane, member j holds C_j[c].  Lanes < vocab are the group tokens of the maps (the
       // tables are involutions there), the lanes from vocab on are further classes (G-U wobble) that several classes may share a token with.
@@ -2363,7 +2412,8 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
       const int kc = tab_idx[ne];
       const int ce = a.tok_maps[kc * 64 + lane];
       const int bl = ce < 0 ? 0 : ce;                                  // the closing member's token of class `lane` (clamped: loads stay unconditional)
-      const float add = a.bias[(long)ne * a.vocab + bl] + cls_bias[kc * 64 + lane];
+      float add = a.bias[(long)ne * a.vocab + bl] + cls_bias[kc * 64 + lane];
+      if (pt) add += pterm;
       const float u = a.uniform[vis];
       // the classes of a group are those of its closing member's table: every member of a group has a token for the same classes (the
       // host builds the tables so), and the sum of any other class — some lane's logit, see the fetch in `step` — is never looked at
@@ -2418,7 +2468,9 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     const int32_t* map_idx = a.tok_maps + a.n_maps * 64;             // (read only where tok_maps is set)
     const int bl = a.tok_maps ? a.tok_maps[map_idx[ne] * 64 + lane] : lane;
     float add = (lane < a.vocab) ? a.bias[(long)ne * a.vocab + bl] : 0.f;
-    if (a.pair_bias && lane < a.vocab) {
+    if (pt) {
+      add += pterm;
+    } else if (a.pair_bias && lane < a.vocab) {
       const float* pb = a.pair_bias + ((long)ne * a.vocab + lane) * a.N * a.vocab;
       float acc_pb = 0.f;
       const int rk_i = LEVEL ? a.rank[(long)bq * a.N + iq] : 0;

@@ -309,6 +309,62 @@ def pair_bias_dependencies(pair_bias, max_deps=64):
     return torch.where(cols < L, cols, torch.full((), -1, device=dev)).to(torch.int32).contiguous(), n_dep
 
 
+PAIR_TERMS_MAX_SLOTS, PAIR_TERMS_MAX_TABLES = 64, 256          # namp_sample_pair_terms' limits (D: namp_sample_levels_dep's)
+
+
+def pair_terms_arguments(pair_terms, B, L, V):
+    """feature_dict["pair_terms"] checked on the host -> (partner int32 [B, L, D], table int32 [B, L, D], tables float32 [n, V, V], all
+    contiguous on the CPU, members: 0 "closing" / 1 "all").  The compact form of pair_bias: residue i reads partner[b, i, d] (-1: none)
+    through tables[table[b, i, d]], term(i)[a] = sum_d tables[table][a][token of the partner] (include/namp.h)."""
+    if not isinstance(pair_terms, dict) or not {"partner", "table", "tables"} <= set(pair_terms):
+        raise ValueError("pair_terms must be a dict with 'partner', 'table', 'tables' (and 'members')")
+    members = pair_terms.get("members", "closing")
+    if members not in ("closing", "all"):
+        raise ValueError(f"pair_terms['members'] must be 'closing' or 'all'; got {members!r}")
+    partner, table, tables = (torch.as_tensor(pair_terms[k]).detach().cpu() for k in ("partner", "table", "tables"))
+    if partner.dim() != 3 or tuple(partner.shape[:2]) != (B, L) or tuple(table.shape) != tuple(partner.shape):
+        raise ValueError(f"pair_terms['partner'] / ['table'] must both be [{B}, {L}, D]; got {tuple(partner.shape)} / {tuple(table.shape)}")
+    if partner.dtype.is_floating_point or table.dtype.is_floating_point or partner.dtype == torch.bool or table.dtype == torch.bool:
+        raise ValueError("pair_terms['partner'] / ['table'] must be integer tensors")
+    D = partner.shape[2]
+    if not 1 <= D <= PAIR_TERMS_MAX_SLOTS:
+        raise ValueError(f"pair_terms has D = {D} slots per residue; 1 <= D <= {PAIR_TERMS_MAX_SLOTS}")
+    if tables.dim() != 3 or tuple(tables.shape[1:]) != (V, V):
+        raise ValueError(f"pair_terms['tables'] must be [n_tables, {V}, {V}]; got {tuple(tables.shape)}")
+    if not 1 <= tables.shape[0] <= PAIR_TERMS_MAX_TABLES:
+        raise ValueError(f"pair_terms has {tables.shape[0]} tables; 1 <= n_tables <= {PAIR_TERMS_MAX_TABLES}")
+    return (partner.to(torch.int32).contiguous(), table.to(torch.int32).contiguous(), tables.to(torch.float32).contiguous(),
+            int(members == "all"))
+
+
+def sort_pair_slots(partner, table):
+    """The slots of every residue in the order the kernels sum them: by partner index, stable, absent slots (a partner outside [0, L) or
+    the residue itself) last and set to -1.  partner / table [..., L, D] on any device -> (partner, table), new tensors."""
+    L = partner.shape[-2]
+    own = torch.arange(L, device=partner.device).view(L, 1)
+    key = torch.where((partner < 0) | (partner >= L) | (partner == own), torch.full((), L, device=partner.device, dtype=partner.dtype), partner)
+    key, perm = torch.sort(key, dim=-1, stable=True)
+    return torch.where(key >= L, torch.full_like(key, -1), key), table.gather(-1, perm)
+
+
+def pair_terms_dense(pair_terms, L):
+    """The dense pair_bias [B, L, V, L, V] that feature_dict["pair_terms"] stands for: pair_bias[b, i, a, j, b'] = the sum over the slots d of
+    residue i with partner j of tables[table[b, i, d]][a][b'] (slots of one partner summed in sorted slot order).  For tests and small L."""
+    tables = torch.as_tensor(pair_terms["tables"]).detach().cpu().float()
+    V = tables.shape[-1]
+    partner, table = torch.as_tensor(pair_terms["partner"]).detach().cpu().long(), torch.as_tensor(pair_terms["table"]).detach().cpu().long()
+    partner, table = sort_pair_slots(partner, table)
+    B, _, D = partner.shape
+    out = torch.zeros(B, L, V, L, V)
+    for b in range(B):
+        for i in range(L):
+            for d in range(D):
+                j = int(partner[b, i, d])
+                if j >= 0:
+                    out[b, i, :, j, :] += tables[max(0, min(len(tables) - 1, int(table[b, i, d])))]      # (clamped, as on the device)
+    return out
+
+
 def leave_one_out_ranks(rank, start=0, stop=None):
     """Decoding ranks of the leave-one-out streams of conditional_probs(): stream i is the order of `rank` [B, L] (the inverse of a
     decoding order) with residue i taken out and appended at the end — rank_i[j] = rank[j] - (rank[j] > rank[i]) for j != i,
@@ -582,6 +638,42 @@ class ProteinMPNN(nn.Module):
             hip.check(Lb.namp_sample_class_tables(tok_maps.data_ptr(), n_maps, spec.N_CLASSES), "sample_class_tables")
         elif tok_maps is not None:
             hip.check(Lb.namp_sample_token_maps(tok_maps.data_ptr(), n_maps), "sample_token_maps")
+
+    def _pair_terms_of(self, fd, B, L):
+        """feature_dict["pair_terms"] checked (pair_terms_arguments), or None without the key."""
+        if fd.get("pair_terms") is None:
+            return None
+        if "pair_bias" in fd:
+            raise ValueError("pair_terms and pair_bias are two forms of one quantity: give one of them")
+        return pair_terms_arguments(fd["pair_terms"], B, L, self.num_letters)
+
+    def _pair_terms_section(self, pt, B, B_dec, N, K, dev, counted=None):
+        """The sampler's workspace with the pair-terms INPUT SECTION (include/namp.h) filled: ONE pinned copy — to be enqueued before the
+        encoder's launches, a host-to-device copy waits for the stream —, then the slots of every residue sorted by partner on the device.
+        N > L (tied states: the flattened graph of N = M * L residues): the rows go to state 0's copies, every other copy has no slot.
+        counted (bool per residue, optional): residues whose terms count; the others lose their slots.
+        -> {"ws", "dep": the section's partner block [B * N * D] int32 — namp_sample_levels_dep's dep_idx —, "D", "n_tables", "members"}."""
+        partner, table, tables, members = pt
+        Lb, n_dec = hip.lib(), len(self.decoder_layers)
+        L, D, n_tab, G = partner.shape[1], partner.shape[2], tables.shape[0], B * N
+        need = Lb.namp_sample_pair_terms_workspace_bytes(B, B_dec, N, K, n_dec, D, n_tab)
+        off = Lb.namp_sample_pair_terms_offset(B, B_dec, N, K, n_dec)
+        if need == 0:
+            raise ValueError(f"pair_terms: no sampler workspace for B={B} batch={B_dec} N={N} K={K} D={D} n_tables={n_tab}")
+        host = torch.empty(2 * G * D + tables.numel(), dtype=torch.int32, pin_memory=True)
+        p, t = host[:G * D].view(B, N, D), host[G * D:2 * G * D].view(B, N, D)
+        p.fill_(-1); t.zero_()
+        p[:, :L], t[:, :L] = torch.where(partner < L, partner, torch.full_like(partner, -1)), table
+        if counted is not None:
+            p[:, :L][:, ~torch.as_tensor(counted, dtype=torch.bool)] = -1
+        host[2 * G * D:] = tables.view(-1).view(torch.int32)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        sec = ws[off:off + 4 * host.numel()].view(torch.int32)
+        sec.copy_(host, non_blocking=True)
+        pd, td = sec[:G * D].view(B, N, D), sec[G * D:2 * G * D].view(B, N, D)
+        ps, ts = sort_pair_slots(pd, td)
+        pd.copy_(ps); td.copy_(ts)
+        return {"ws": ws, "dep": sec[:G * D], "D": D, "n_tables": n_tab, "members": members}
 
     def _as(self, t, kind):
         """`t` in the dtype / layout the kernels read ("i32": int32, "f32": float32; contiguous), converted ONCE per tensor object: a
@@ -1132,7 +1224,7 @@ class ProteinMPNN(nn.Module):
         L = S_true.shape[1]
         dev = log_probs.device
         keep = {k: v for k, v in fd.items() if k not in ("paired_residues", "paired_weights", "paired_wobble", "paired_wobble_bias",
-                                                          "symmetry_residues", "symmetry_weights", "symmetry_token_maps", "pair_bias",
+                                                          "symmetry_residues", "symmetry_weights", "symmetry_token_maps", "pair_bias", "pair_terms",
                                                           "S_forced")}
         ones = torch.ones_like(fd["chain_mask"])
         bias = torch.zeros(1, L, self.num_letters, device=dev)
@@ -1443,7 +1535,7 @@ class ProteinMPNN(nn.Module):
         L = S_true.shape[1]
         dev = log_probs.device
         keep = {k: v for k, v in fd.items() if k not in ("paired_residues", "paired_weights", "paired_wobble", "paired_wobble_bias",
-                                                          "symmetry_residues", "symmetry_weights", "symmetry_token_maps", "pair_bias",
+                                                          "symmetry_residues", "symmetry_weights", "symmetry_token_maps", "pair_bias", "pair_terms",
                                                           "S_forced")}
         ones = torch.ones_like(fd["chain_mask"])
         bias = torch.zeros(1, L, self.num_letters, device=dev)
@@ -1504,7 +1596,9 @@ class ProteinMPNN(nn.Module):
     @torch.no_grad()
     def sample(self, feature_dict):
         """ProteinMPNN.sample (model_utils.py:101-327; both the plain and the symmetry-tied branch, optional
-        ``pair_bias``) as one persistent HIP launch.
+        ``pair_bias``) as one persistent HIP launch.  ``feature_dict["pair_terms"]`` is the compact form of ``pair_bias`` —
+        {"partner", "table": int [B, L, D], "tables": float [n, V, V], "members": "closing" | "all"}, see pair_terms_arguments — and,
+        unlike the dense tensor, goes with every tie (symmetry_residues, paired_residues, paired_wobble, state_weights).
         The categorical draw uses torch.rand on the device (seed with torch.manual_seed) through an inverse
         CDF instead of torch.multinomial; ``feature_dict["S_forced"]`` (optional, [batch,L]) teacher-forces."""
         return self._sample(feature_dict, self.sample_level_walk)
@@ -1521,6 +1615,7 @@ class ProteinMPNN(nn.Module):
         dev = S_true.device
         tok_maps = pair_list = cls_bias = None
         n_maps = 0
+        pterms = self._pair_terms_of(fd, B, L)
         mapped = self._mapped_arguments(fd, B, L)                                 # base pairs / token maps: mapped symmetry groups
         if mapped is not None:
             sym, sym_weights, table, idx, pair_list, cls_bias = mapped
@@ -1529,6 +1624,9 @@ class ProteinMPNN(nn.Module):
         self._check_tokens(S_true)
         if fd.get("S_forced") is not None:
             self._check_tokens(fd["S_forced"], "S_forced")
+        if pterms is not None:                                                    # (its one copy goes up before anything is enqueued)
+            _require_device(fd["X"], "X")
+            pterms = self._pair_terms_section(pterms, B, B * bs, L, int(min(self.k_neighbors, L)), dev)
         o = self._decoding_order(mask, fd["chain_mask"], fd["randn"])               # [max(B, bs), L]; sorted by the featuriser launch
         order, rank = o.order, o.rank
         V, _, h_E, E_idx = self._featurize_hip(fd, want_E=False, want_hE=True, order=o)   # (E_idx stays int32: the kernels' dtype)
@@ -1538,6 +1636,8 @@ class ProteinMPNN(nn.Module):
         # the side stream behind the featuriser launch, beside the encoder launches (sample_levels_kernel is a serial walk of one wave per
         # stream: 62 us at 97 residues in front of the walk otherwise).
         early = None
+        # (pair terms add dependencies to the levels: the early levels receive the section's partner block — uploaded and sorted on this
+        # stream in front of the event —, the device plan of the pairs below stands aside)
         if (not symmetric and "pair_bias" not in fd and self.sample_level_parallel and walk and not o.pending and o.order32 is not None
                 and order.shape[0] == B_dec and L <= 16000 and E_idx.dtype == torch.int32 and E_idx.is_contiguous()
                 and hip.lib().namp_decoder_sample_walk_grid(B_dec, L, K) > 0):
@@ -1549,17 +1649,18 @@ class ProteinMPNN(nn.Module):
             n_levels = torch.empty(1, dtype=torch.int32, device=dev)
             ev_ = torch.cuda.Event(); ev_.record(main_)                              # the neighbour lists and the order are out
             side_.wait_event(ev_)
-            hip.check(Lb_.namp_sample_levels_dep(E_idx.data_ptr(), o.order32.data_ptr(), rank.data_ptr(), None, 0, None, None, level.data_ptr(),
-                                                 B_dec, B, L, K, side_.cuda_stream), "sample_levels")
+            dep_, n_dep_ = (None, 0) if pterms is None else (pterms["dep"], pterms["D"])
+            hip.check(Lb_.namp_sample_levels_dep(E_idx.data_ptr(), o.order32.data_ptr(), rank.data_ptr(), hip.ptr(dep_), n_dep_, None, None,
+                                                 level.data_ptr(), B_dec, B, L, K, side_.cuda_stream), "sample_levels")
             hip.check(Lb_.namp_sample_work_lists(level.data_ptr(), work.data_ptr(), level_off.data_ptr(), n_levels.data_ptr(), B_dec, L,
                                                  side_.cuda_stream), "sample_work_lists")
             o.event = torch.cuda.Event(); o.event.record(side_)                      # o.wait() orders the decoder behind both launches
-            for t_ in (E_idx, o.order32, rank, level, work, level_off, n_levels):    # (not recycled before the side stream is done)
-                t_.record_stream(side_)
+            for t_ in (E_idx, o.order32, rank, level, work, level_off, n_levels) + (() if pterms is None else (pterms["ws"],)):
+                t_.record_stream(side_)                                              # (not recycled before the side stream is done)
             early = (level, work, level_off, n_levels)
         # Base pairs only: the visit plan, the levels and the work lists are built on the device, beside the encoder, with nothing read back
         plan = None
-        if (pair_list and self.sample_pairs_device_plan and self.sample_level_parallel and walk and o.order32 is not None
+        if (pair_list and pterms is None and self.sample_pairs_device_plan and self.sample_level_parallel and walk and o.order32 is not None
                 and order.shape[0] == B_dec and L <= 8192 and E_idx.dtype == torch.int32 and E_idx.is_contiguous()
                 and hip.lib().namp_decoder_sample_walk_grid(B_dec, L, K) > 0):
             o.wait()                                                                 # (the sort, if the featuriser launch did not take it)
@@ -1602,7 +1703,7 @@ class ProteinMPNN(nn.Module):
         probs = torch.empty(B_dec, L, self.num_letters, device=dev)
         logp = torch.empty_like(probs)
         ws_bytes = Lb.namp_sample_workspace_bytes_n(B, B_dec, L, K, len(self.decoder_layers))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if pterms is None else pterms["ws"]      # (the section behind the carve)
         E32, cm32, St32 = _i32(E_idx), _i32(chain_mask), self._as(S_true, "i32")
         m32 = self._as(mask, "i32")
         md32, o32, r32 = (m32 if mask_dec is mask else _i32(mask_dec)), (o.order32 if early is not None else _i32(order)), _i32(rank)
@@ -1616,6 +1717,8 @@ class ProteinMPNN(nn.Module):
             if tuple(pair_bias.shape) != (B, L, self.num_letters, L, self.num_letters):
                 raise ValueError(f"pair_bias must be [B, L, {self.num_letters}, L, {self.num_letters}]; got {tuple(pair_bias.shape)}")
             deps = pair_bias_dependencies(pair_bias)
+        if pterms is not None:                                                # the section's partner block IS the levels' dep_idx
+            deps = (pterms["dep"], pterms["D"])
         common = (W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), m32.data_ptr(), md32.data_ptr(), cm32.data_ptr(),
                   St32.data_ptr(), bias_f.data_ptr(), o32.data_ptr(), r32.data_ptr(), uniform.data_ptr(), hip.ptr(forced),
                   hip.ptr(group_first), hip.ptr(group_last), hip.ptr(sym_w), hip.ptr(pair_bias))
@@ -1624,6 +1727,8 @@ class ProteinMPNN(nn.Module):
 
         def attach():       # the token maps go to the NEXT sampler call of this thread (namp_sample_token_maps / namp_sample_class_tables)
             self._attach_maps(tok_maps, n_maps, cls_bias is not None)
+            if pterms is not None:                                             # ... and the pair terms (namp_sample_pair_terms)
+                hip.check(Lb.namp_sample_pair_terms(pterms["D"], pterms["n_tables"], pterms["members"]), "sample_pair_terms")
         out = {"S": None, "sampling_probs": probs, "log_probs": logp, "decoding_order": order, "uniform": uniform}   # (S: after the launch)
         if not (self.sample_level_parallel and deps is not None):
             attach()
@@ -1793,7 +1898,19 @@ class ProteinMPNN(nn.Module):
             tok_maps, n_maps = self._token_map_array(table, idx * M, fd["S"].device, cls_bias), len(table)   # flat residue m * L + i speaks as residue i does
         S_true, mask = fd["S"], fd["mask"]
         dev, N, Vn = S_true.device, M * L, self.num_letters
+        pterms = self._pair_terms_of(fd, 1, L)
         _require_device(fd["X"], "X")
+        if pterms is not None:
+            # The rows sit on state 0's copies only — a residue counts once, not M times —, so the kernel counts EVERY member of a group
+            # (its closing member is a copy of the last state, which has no slots); under "closing" the residues that do not close their
+            # group lose their slots instead.  One copy, before anything is enqueued.
+            counted = None
+            if pterms[3] == 0 and symmetric:
+                counted = [True] * L
+                for g in sym_groups:
+                    for r in list(g)[:-1]:
+                        counted[int(r)] = False
+            pterms = self._pair_terms_section(pterms[:3] + (1,), 1, bs, N, int(min(self.k_neighbors, L)), dev, counted)
         self._check_tokens(S_true)
         if fd.get("S_forced") is not None:
             self._check_tokens(fd["S_forced"], "S_forced")
@@ -1808,7 +1925,7 @@ class ProteinMPNN(nn.Module):
         walk = bool(walk and self.sample_level_parallel and Lb.namp_decoder_sample_walk_grid(bs, N, K) > 0)
         close = close_off = zbuf = None
         device_plan = (self.sample_states_device_plan and walk and self.sample_split_groups and not symmetric and o.order32 is not None
-                       and L <= 8192)
+                       and L <= 8192 and pterms is None)                           # (pair terms add dependencies: the host route)
         if device_plan:
             # one launch writes the flattened neighbour lists, the visit plan of every stream, the levels and the level-sorted lists.  It
             # needs the neighbour lists and the decoding order only: enqueued on the side stream behind the featuriser launch, beside
@@ -1853,7 +1970,8 @@ class ProteinMPNN(nn.Module):
             step_of = torch.tensor(np.cumsum([int(v == f) for v, f in enumerate(gf)]) - 1, device=dev)     # visit -> its group's step
             E_f = _i32(E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).view(N, K)
             level = i32e(bs, N)
-            hip.check(Lb.namp_sample_levels_dep(E_f.data_ptr(), order_f.data_ptr(), rank_f.data_ptr(), None, 0, group_first.data_ptr(),
+            dep, n_dep = (None, 0) if pterms is None else (pterms["dep"], pterms["D"])
+            hip.check(Lb.namp_sample_levels_dep(E_f.data_ptr(), order_f.data_ptr(), rank_f.data_ptr(), hip.ptr(dep), n_dep, group_first.data_ptr(),
                                                 group_last.data_ptr(), level.data_ptr(), bs, 1, N, K, hip.current_stream()), "sample_levels")
             sel, flat, work_n, close, close_off = level_work_lists(level, group_first, group_last, order_f[0], E_f.long(),
                                                                    split=bool(walk and self.sample_split_groups))
@@ -1880,7 +1998,7 @@ class ProteinMPNN(nn.Module):
         if close is not None:
             zbuf = torch.empty(bs, N, Vn, device=dev)
         ws_bytes = Lb.namp_sample_workspace_bytes_n(1, bs, N, K, len(self.decoder_layers))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if pterms is None else pterms["ws"]
         h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
         common = (W.model(), h_V.data_ptr(), h_E.data_ptr(), E_f.data_ptr(), m_f.data_ptr(), md_f.data_ptr(), cm_f.data_ptr(),
                   S_f.data_ptr(), bias_f.data_ptr(), order_f.data_ptr(), rank_f.data_ptr(), u_f.data_ptr(), hip.ptr(forced),
@@ -1888,6 +2006,8 @@ class ProteinMPNN(nn.Module):
         tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
                 bs, 1, N, K, hip.current_stream())
         self._attach_maps(tok_maps, n_maps, cls_bias is not None)
+        if pterms is not None:
+            hip.check(Lb.namp_sample_pair_terms(pterms["D"], pterms["n_tables"], pterms["members"]), "sample_pair_terms")
         if not walk:
             counts = torch.bincount(flat).cpu().tolist()                       # per-level launches: one host sync
             hip.check(Lb.namp_decoder_sample_levels(*common, work.data_ptr(), work_n.data_ptr(), (C.c_int32 * len(counts))(*counts),

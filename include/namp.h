@@ -799,6 +799,8 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
  *     total[a] = w_i z_i[P_i[a]] + w_j z_j[P_j[a]],   lp = log_softmax(total),   row_m[P_m[a]] = lp[a]   for m in (i, j)
  * (P: the members' token maps, involutions of the vocabulary) and both rows of log_probs hold the pair's conditional, each in its
  * member's alphabet.  Rows of unpaired residues are bit-identical to a call without pairs; counts still reports the active items.
+ * A pair IS a group of two (below): a partner table is the successor cycle of its pairs, namp_loo_pairs attaches exactly what
+ * namp_loo_groups attaches, the workspace sizes and offsets of the two are equal, and the group rules validate the section.
  * No entry point takes a pointer: the tables travel in a caller-filled INPUT SECTION of `ws`,
  *     namp_loo_pairs_offset(B, N, K, n_dec)   byte offset of the section in ws (256-byte aligned; = namp_loo_workspace_bytes)
  *     int32 words, G = B * N:  partner[G]  local index of the partner in its complex, -1 for none
@@ -807,12 +809,12 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
  *                              weight[G]   w of the residue (float bits)
  *                              maps[n_maps][64]
  * and namp_loo_pairs(n_maps), 1 <= n_maps <= 64 (NAMP_EINVAL otherwise), attaches them to the calling thread's NEXT
- * namp_decoder_loo call, which then requires ws_bytes >= namp_loo_pairs_workspace_bytes(B, N, K, n_dec, n_maps) (the carve of
- * namp_loo_workspace_bytes, the section, [G] tables and two [2 G][128] row tables behind it; 0 where namp_loo_workspace_bytes is 0 or
- * n_maps is out of range) and clears the attachment whether it succeeds or not.  The section is device data and is validated on
- * the device: a member whose partner index is out of range or itself, whose partner does not name it back, or whose pair has a
- * masked member (mask == 0) is treated as unpaired — both residues get their ordinary leave-one-out rows; map indices and map
- * entries are clamped.  Without an attachment namp_decoder_loo is unchanged, bit for bit. */
+ * namp_decoder_loo call, which then requires ws_bytes >= namp_loo_pairs_workspace_bytes(B, N, K, n_dec, n_maps)
+ * (= namp_loo_groups_workspace_bytes; 0 where namp_loo_workspace_bytes is 0 or n_maps is out of range) and clears the attachment
+ * whether it succeeds or not.  The section is device data and is validated on the device: a member whose partner index is out of
+ * range or itself, whose partner does not name it back, whose pair has a masked member (mask == 0), or whose pair does not carry
+ * `first` on EXACTLY ONE of its two members (neither, or both) is treated as unpaired — both residues get their ordinary
+ * leave-one-out rows; map indices and map entries are clamped.  Without an attachment namp_decoder_loo is unchanged, bit for bit. */
 size_t namp_loo_pairs_workspace_bytes(int B, int N, int K, int n_dec, int n_maps);
 size_t namp_loo_pairs_offset(int B, int N, int K, int n_dec);
 int namp_loo_pairs(int n_maps);
@@ -824,7 +826,7 @@ int namp_loo_pairs(int n_maps);
  * of EVERY member hidden (member t reads an earlier-listed member that is its graph neighbour backward, through its decoder states
  * but without its token; later-listed members and itself forward).  With z_t the members' head rows there,
  *     total[a] = sum_t w_t z_t[P_t[a]]  (listed order),   lp = log_softmax(total),   row_{m_t}[P_t[a]] = lp[a]
- * and every member's row of log_probs holds the group's conditional in its own alphabet.  For n = 2 these are the pair path's bits.
+ * and every member's row of log_probs holds the group's conditional in its own alphabet.  n = 2 is the pair conditional above.
  * The tables travel in the INPUT SECTION of `ws`, at the place and with the layout of the pair section:
  *     namp_loo_groups_offset(B, N, K, n_dec)  byte offset of the section in ws (256-byte aligned; = namp_loo_workspace_bytes)
  *     int32 words, G = B * N:  next[G]     local index of the member listed AFTER this one in its complex (the last member names
@@ -834,9 +836,10 @@ int namp_loo_pairs(int n_maps);
  *                              weight[G]   w of the residue (float bits)
  *                              maps[n_maps][64]
  * namp_loo_groups(n_maps), 1 <= n_maps <= 64 (NAMP_EINVAL otherwise), attaches them to the calling thread's NEXT namp_decoder_loo
- * call (replacing a pair attachment, as namp_loo_pairs replaces this one), which then requires
- * ws_bytes >= namp_loo_groups_workspace_bytes(B, N, K, n_dec, n_maps) (the carve of namp_loo_pairs_workspace_bytes and one int32
- * table [G * K] behind it) and clears the attachment whether it succeeds or not.
+ * call (the calling thread holds ONE attachment record: the latest of namp_loo_pairs / namp_loo_groups / namp_loo_classes), which
+ * then requires ws_bytes >= namp_loo_groups_workspace_bytes(B, N, K, n_dec, n_maps) — ONE carve: that of namp_loo_workspace_bytes,
+ * then the section, two int32 tables [G], two row tables [2 G][128] and one int32 table [G * K] — and clears the attachment whether
+ * it succeeds or not.
  * The section is validated on the device, one walk of at most NAMP_LOO_GROUP_MAX steps per residue: a residue is grouped only if
  * the walk returns to it, every successor on the way lies in [0, N), exactly one member of the cycle carries `first` and no member
  * is masked.  Everything else — a self-loop, a tail that leads into a cycle, two `first` flags, a longer cycle, a masked member —
@@ -847,7 +850,7 @@ size_t namp_loo_groups_offset(int B, int N, int K, int n_dec);
 int namp_loo_groups(int n_maps);
 int namp_loo_group_max(void);   /* NAMP_LOO_GROUP_MAX of the built library */
 
-/* ---- pair classes in the pair and group conditionals (G-U wobble), riding on either of the two above -------------------------
+/* ---- pair classes in the pair and group conditionals (G-U wobble), riding on the attachment above ------------------------------
  * The members of a tied pair or group speak through CLASS TABLES instead of token maps (the sampler's namp_sample_class_tables):
  * tables[ti][c] is the member's token under class c, below 0 where it has none.  The stream is the pair / group stream above,
  * unchanged; only the combine differs.  With z_t the members' head rows in listed order and `close` the LAST listed member,
@@ -857,16 +860,17 @@ int namp_loo_group_max(void);   /* NAMP_LOO_GROUP_MAX of the built library */
  * Below the vocabulary a table is a token map (an involution), so row_m[t] starts from clp[C_m[t]] and the classes vocab ..
  * n_classes - 1 are folded in by two-term log-add-exp in ascending order.  Every member's row of log_probs holds that marginal.
  * No entry point takes a pointer.  The INPUT SECTION sits at namp_loo_pairs_offset / namp_loo_groups_offset with the layout
- *     int32 words, G = B * N:  partner[G] (groups = 0) or next[G] (groups = 1), first[G], table_idx[G], weight[G] (float bits),
+ *     int32 words, G = B * N:  next[G] (a partner table is one), first[G], table_idx[G], weight[G] (float bits),
  *                              tables[n_tables][64]   entries in [-1, vocab)
  *                              bias[n_tables][64]     float bits; read through the table index of the closing member
  * and the OUTPUT SECTION, float [G][64], at namp_loo_classes_out_offset(B, N, K, n_dec, n_tables, groups) (256-byte aligned, behind
- * the carve of the tie it rides on): row g holds clp of the pair / group whose listed-first member is g, -inf on absent lanes, and is
+ * the carve above; the same for groups = 0 and 1): row g holds clp of the pair / group whose listed-first member is g, -inf on absent lanes, and is
  * all -inf for every other residue.  namp_loo_classes(n_tables, n_classes, groups), 1 <= n_tables <= 64, vocab <= n_classes <= 64,
- * groups 0 (the pair path) or 1 (the group path) — NAMP_EINVAL otherwise, n_classes < vocab by the call itself — attaches them to the
- * calling thread's NEXT namp_decoder_loo call, replacing a pair or group attachment as those replace this one; the call requires
+ * groups 0 (pairs) or 1 (groups) — NAMP_EINVAL otherwise, n_classes < vocab by the call itself; one code path, sizes and offsets
+ * for both values of `groups`, which only names the attachment in messages — attaches them to the calling thread's NEXT
+ * namp_decoder_loo call, replacing a pair or group attachment as those replace this one; the call requires
  * ws_bytes >= namp_loo_classes_workspace_bytes(...) (NAMP_EINVAL otherwise) and clears the attachment whatever becomes of it.
- * partner / next / first are validated as above.  Table indices and entries are clamped; an entry below 0 is "absent", a pair or
+ * next / first are validated as above.  Table indices and entries are clamped; an entry below 0 is "absent", a pair or
  * group that fails validation keeps its leave-one-out rows with a class row of -inf, and so does one without a single class all of
  * its members have.  Plain stores, no atomics: two calls give identical bits.  Without this attachment the plain, pair and group
  * calls keep their carve and their bits. */

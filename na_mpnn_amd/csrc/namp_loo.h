@@ -12,28 +12,23 @@
 // edge_mlp_kernel<MODE_DEC_MSG> with the rank comparison replaced by indirection.  Every item owns its output rows (no atomics, two
 // runs are bit-identical); phases are separate launches (nothing waits on the device).
 //
-// Pair conditionals (namp_loo_pairs): residues i, j tied as a base pair share ONE stream, the order of score() with
-// both taken out and appended as ..., i, j (LISTED order), in which i's token is hidden.  Stream membership follows from the slot: a
-// slot whose neighbour (phase 1) or owner (phase 2, own) is a pair member belongs to that pair's stream, edges to BOTH members are
-// forward there, and a residue that used to see both members as decoded has two phase-1 slots that compute the same rows (each item
-// still owns its rows; readers take the listed-first member's slot if it is active).  j reads i as a backward neighbour WITHOUT its
-// token: layer 1 from Pfw[0][i], layers 2 / 3 from rows G + i of that layer's forward table, which hold W1v . (i's own-layer state):
-// with pairs the forward tables of layers 2 and 3 have 2 G rows and the own launches project the second half (dec_items_kernel
-// itself is unchanged).
-// loo_combine_kernel then sums the two members' head rows through their token maps and writes both rows.
-//
 // Group conditionals (namp_loo_groups): a tied group (m_1, ..., m_n), n <= NAMP_LOO_GROUP_MAX, in LISTED order shares
-// one stream, the order of score() with all members taken out and appended as ..., m_1, ..., m_n, every member's token hidden.  The
-// third instantiation of the table kernels (LOO_TIE_GROUPS): loo_groups_kernel turns the caller's successor cycle into (leader,
+// ONE stream, the order of score() with all members taken out and appended as ..., m_1, ..., m_n, every member's token hidden.  The
+// second instantiation of the table kernels (LOO_TIE_GROUPS): loo_groups_kernel turns the caller's successor cycle into (leader,
 // listed position) per residue; a slot belongs to the stream of its neighbour's (phase 1) or owner's (phase 2, own) group, edges to ANY
-// member are forward there, readers take the active phase-1 slot that names the earliest-listed member, member t reads an
-// earlier-listed member that is its neighbour without its token (Pfw[0], rows G + n in layers 2 / 3) and a later-listed one forward;
-// loo_group_combine_kernel loops over the members.  For n = 2 every table entry, and so every bit, is the pair path's.
+// member are forward there, and a residue that used to see several members as decoded has as many phase-1 slots that compute the
+// same rows (each item still owns its rows; readers take the active slot that names the earliest-listed member).  Member t reads an
+// earlier-listed member that is its neighbour without its token — layer 1 from Pfw[0], layers 2 / 3 from rows G + n of that layer's
+// forward table, which hold W1v . (n's own-layer state): with an attachment the forward tables of layers 2 and 3 have 2 G rows and
+// the own launches project the second half (dec_items_kernel itself is unchanged) — and a later-listed one forward.
+// loo_group_combine_kernel then sums the members' head rows through their token maps and writes every member's row.
 //
-// Pair classes (namp_loo_classes): on either of the two streams above the members speak through class tables instead
-// of token maps (G-U wobble).  Nothing in front of the combine changes — the streams hide every member's token —; the attachment
-// swaps loo_combine_kernel / loo_group_combine_kernel for loo_class_combine_kernel, which also writes the class rows into an output
-// section of the workspace.
+// Pair conditionals (namp_loo_pairs) are the groups of two: a base pair's partner table IS its successor cycle, and
+// namp_loo_pairs attaches what namp_loo_groups does.
+//
+// Pair classes (namp_loo_classes): the members speak through class tables instead of token maps (G-U wobble).
+// Nothing in front of the combine changes — the stream hides every member's token —; the attachment swaps loo_group_combine_kernel
+// for loo_class_combine_kernel, which also writes the class rows into an output section of the workspace.
 #pragma once
 #include "namp_kernels.h"
 
@@ -50,9 +45,9 @@ struct LooPrepArgs {
   const int32_t* rank;    // [G]
   const int32_t* mask;    // [G]
   const int32_t* S;       // [G]
-  const int32_t* pp;      // [G] validated pair partner (global residue index) or -1, from loo_pairs_kernel (PAIRS launches only);
-                          //     GROUPS launches: the leader (listed-first member, global index) of the residue's valid group or -1
-  const int32_t* lead;    // [G] 1 on the listed-first member of a valid pair; GROUPS launches: the residue's listed position (0: ungrouped)
+  const int32_t* pp;      // [G] GROUPS launches: the leader (listed-first member, global index) of the residue's valid group or -1,
+                          //     from loo_groups_kernel
+  const int32_t* lead;    // [G] GROUPS launches: the residue's listed position (0: the leader, or ungrouped)
   int32_t* rev;           // [R] edge (a, k) -> b: position of a in E_idx[b], or -1
   int32_t* act1;          // [R] phase-1 item (m, k) is active
   int32_t* act2;          // [R] phase-2 item (i, kq) is active
@@ -69,23 +64,7 @@ struct LooPrepArgs {
 
 __device__ __forceinline__ int loo_clamp(const int v, const int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
-// The partner table is caller-supplied device data: one thread per residue validates it.  A member counts as unpaired when its
-// partner index is out of range or itself, when the partner does not name it back, or when either of the two is masked.
-static __global__ __launch_bounds__(256) void loo_pairs_kernel(const int32_t* __restrict__ partner, const int32_t* __restrict__ first,
-                                                                const int32_t* __restrict__ mask, int32_t* __restrict__ pp,
-                                                                int32_t* __restrict__ lead, const int G, const int N) {
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  if (g >= G) return;
-  const int b0 = (g / N) * N, g_loc = g - b0;
-  const int p_loc = partner[g];
-  const int p = b0 + loo_clamp(p_loc, N);
-  const bool ok = p_loc >= 0 && p_loc < N && p_loc != g_loc && partner[p] == g_loc && mask[g] != 0 && mask[p] != 0;
-  const bool fg = first[g] != 0, fp = first[p] != 0;
-  pp[g] = ok ? p : -1;
-  lead[g] = (ok && (fg != fp ? fg : g < p)) ? 1 : 0;       // (flags that do not tell the two apart: the lower index leads)
-}
-
-// Groups: the caller's table is a successor cycle in LISTED order (next[g] = local index of the member listed after g, the last
+// The caller's table is device data, a successor cycle in LISTED order (next[g] = local index of the member listed after g, the last
 // names the first) with first[g] = 1 on the listed-first member.  One thread per residue walks its cycle, at most NAMP_LOO_GROUP_MAX
 // steps.  g is grouped only if the walk returns to it, every successor on the way is inside [0, N), exactly one member carries
 // `first` and no member is masked; a self-loop, a tail that leads into a cycle, a longer cycle: ungrouped.  Every member of a cycle
@@ -112,8 +91,7 @@ static __global__ __launch_bounds__(256) void loo_groups_kernel(const int32_t* _
 }
 
 #define LOO_TIE_NONE 0
-#define LOO_TIE_PAIRS 1
-#define LOO_TIE_GROUPS 2
+#define LOO_TIE_GROUPS 1
 
 // groups: the active phase-1 slot of residue x (global) that names the earliest-listed member of stream `sid` (the leader of a
 // group, or the residue of a stream of one), or -1: one pass over the keys loo_prepare_kernel left.  Duplicate slots are bounded by
@@ -129,10 +107,10 @@ __device__ __forceinline__ int loo_group_override(const LooPrepArgs& a, const in
 }
 
 // one thread per slot r = (g, k): reverse-edge index, phase-1 flag, the phase-1 items' centres
-// (TIE = LOO_TIE_NONE is the code of a call without pairs: no table of partners is read)
+// (TIE = LOO_TIE_NONE is the code of a call without an attachment: no table of the caller's is read)
 template <int TIE>
 static __global__ __launch_bounds__(256) void loo_prepare_kernel(const LooPrepArgs a) {
-  constexpr bool PAIRS = TIE == LOO_TIE_PAIRS, GROUPS = TIE == LOO_TIE_GROUPS;
+  constexpr bool GROUPS = TIE == LOO_TIE_GROUPS;
   const long R = (long)a.G * a.K;
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= R) return;
@@ -143,10 +121,9 @@ static __global__ __launch_bounds__(256) void loo_prepare_kernel(const LooPrepAr
   for (int q = a.K - 1; q >= 0; --q)
     if (a.E_idx[(long)i * a.K + q] == m_loc) p = q;
   a.rev[r] = p;
-  const int pi = PAIRS ? a.pp[i] : -1;                      // m is not an item of its own pair's stream
-  const int li = GROUPS ? a.pp[i] : -1;                     // ... nor of its own group's
+  const int li = GROUPS ? a.pp[i] : -1;                     // m is not an item of its own group's stream
   const bool same = GROUPS && li >= 0 && li == a.pp[g];
-  const bool on1 = i_loc != m_loc && pi != g && !same && a.rank[i] < a.rank[g] && a.mask[g] != 0;
+  const bool on1 = i_loc != m_loc && !same && a.rank[i] < a.rank[g] && a.mask[g] != 0;
   a.act1[r] = on1 ? 1 : 0;
   if (GROUPS) a.gkey[r] = on1 ? (((li >= 0 ? li : i) << 4) | a.lead[i]) : -1;     // (a listed position is below NAMP_LOO_GROUP_MAX = 16)
   a.ctr1[r] = g; a.msk1[r] = a.mask[g]; a.S1[r] = a.S[g];
@@ -157,7 +134,7 @@ static __global__ __launch_bounds__(256) void loo_prepare_kernel(const LooPrepAr
 // flag and centre, and the edge codes of the own layers (after loo_prepare_kernel: reads rev / act1 of other slots)
 template <int TIE>
 static __global__ __launch_bounds__(256) void loo_edges_kernel(const LooPrepArgs a) {
-  constexpr bool PAIRS = TIE == LOO_TIE_PAIRS, GROUPS = TIE == LOO_TIE_GROUPS;
+  constexpr bool GROUPS = TIE == LOO_TIE_GROUPS;
   const long R = (long)a.G * a.K;
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -166,71 +143,58 @@ static __global__ __launch_bounds__(256) void loo_edges_kernel(const LooPrepArgs
   const int b0 = (g / a.N) * a.N, c_loc = g - b0;           // g = the slot's residue: m of the phase-1 item, i of the phase-2 item
   const int n_loc = loo_clamp(a.E_idx[r], a.N), n = b0 + n_loc;   // its k-th neighbour: i of the phase-1 item, q of the phase-2 item
   const int rk_g = a.rank[g], rk_n = a.rank[n];
-  // pairs: the stream of the phase-1 item is that of n's pair, the stream of the phase-2 item and of the own layers that of g's pair
-  const int pg = PAIRS ? a.pp[g] : -1, pn = PAIRS ? a.pp[n] : -1;
-  const bool g_leads = !PAIRS || pg < 0 || a.lead[g] != 0;
-  const int f_loc = g_leads ? c_loc : pg - b0;              // the listed-first member of g's stream, and the other one (-1: none)
-  const int s_loc = pg < 0 ? -1 : (g_leads ? pg - b0 : c_loc);
-  // groups: the same streams, named by their leaders (-1: the residue alone)
+  // groups: the stream of the phase-1 item is that of n's group, the stream of the phase-2 item and of the own layers that of g's
+  // group; streams are named by their leaders (-1: the residue alone)
   const int lg = GROUPS ? a.pp[g] : -1, ln = GROUPS ? a.pp[n] : -1;
   const bool grouped = lg >= 0;
   const int sid = grouped ? lg : g;
-  // n's layer-1 override in stream g: the slot of n that names the listed-first member if it is active, else the other member's
-  int pf = a.rev[r], ps = -1;                               // positions of g / of its partner in E_idx[n]
-  if (PAIRS && pg >= 0) {                                   // (wave-uniform)
-    for (int q = a.K - 1; q >= 0; --q)
-      if (a.E_idx[(long)n * a.K + q] == pg - b0) ps = q;
-    if (!g_leads) { const int t = pf; pf = ps; ps = t; }
-  }
+  // n's layer-1 override in stream g: the slot of n that names g if it is active (groups: the active slot that names the
+  // earliest-listed member)
+  const int pf = a.rev[r];                                  // position of g in E_idx[n]
   int ovn = -1;
-  if (GROUPS) {                                             // (... of the earliest-listed member whose slot is active)
+  if (GROUPS) {
     ovn = loo_group_override(a, n, sid);
   } else {
-    if (PAIRS && ps >= 0 && a.act1[(long)n * a.K + ps] != 0) ovn = (int)((long)n * a.K + ps);
     if (pf >= 0 && a.act1[(long)n * a.K + (pf >= 0 ? pf : 0)] != 0) ovn = (int)((long)n * a.K + pf);
   }
   const bool cen_ov = ovn >= 0;                             // n's layer-1 state is overridden in stream g
   bool any = false;
   for (int e = lane; e < a.K; e += 64) {
-    // phase 1, item (m = g, i = n): edge e of m; the edges to i and to i's partner (to every member of i's group) are forward now
+    // phase 1, item (m = g, i = n): edge e of m; the edges to i and to every member of i's group are forward now
     const int j_loc = loo_clamp(a.E_idx[(long)g * a.K + e], a.N), j = b0 + j_loc;
     const bool j_tied = GROUPS && ln >= 0 && a.pp[j] == ln;
-    a.esrc1[r * a.K + e] = (j_loc == n_loc || j == pn || j_tied || !(a.rank[j] < rk_g)) ? (LOO_FW | j) : j;
+    a.esrc1[r * a.K + e] = (j_loc == n_loc || j_tied || !(a.rank[j] < rk_g)) ? (LOO_FW | j) : j;
     // phase 2, item (i = g, q = n): edge e of q
     const int m_loc = loo_clamp(a.E_idx[(long)n * a.K + e], a.N), mm = b0 + m_loc;
     const bool m_tied = GROUPS && grouped && a.pp[mm] == lg;
     int code = LOO_FW | mm;
-    if (m_loc != c_loc && mm != pg && !m_tied && a.rank[mm] < rk_n) {
+    if (m_loc != c_loc && !m_tied && a.rank[mm] < rk_n) {
       code = mm;
       int ov = -1;
       if (GROUPS) {
         ov = loo_group_override(a, mm, sid);
       } else {
-        int p1 = -1, p2 = -1;
-        for (int q = a.K - 1; q >= 0; --q) {
-          const int v = a.E_idx[(long)mm * a.K + q];
-          if (v == f_loc) p1 = q;
-          if (PAIRS && v == s_loc) p2 = q;
-        }
-        if (PAIRS && s_loc >= 0 && p2 >= 0 && a.act1[(long)mm * a.K + p2] != 0) ov = (int)((long)mm * a.K + p2);
+        int p1 = -1;
+        for (int q = a.K - 1; q >= 0; --q)
+          if (a.E_idx[(long)mm * a.K + q] == c_loc) p1 = q;
         if (p1 >= 0 && a.act1[(long)mm * a.K + p1] != 0) ov = (int)((long)mm * a.K + p1);
       }
       if (ov >= 0) { code = LOO_OV | ov; any = true; }
     }
     a.esrc2[r * a.K + e] = code;
   }
-  // the slot's neighbour is g's partner / another member of g's group: no item, and its own edge codes
-  const bool part = (PAIRS && pg >= 0 && n == pg) || (GROUPS && grouped && ln == lg && n_loc != c_loc);
+  // the slot's neighbour is another member of g's group: no item, and its own edge codes
+  const bool part = GROUPS && grouped && ln == lg && n_loc != c_loc;
   const bool on2 = n_loc != c_loc && !part && a.mask[n] != 0 && (cen_ov || __any(any));
   if (lane == 0) {
     a.act2[r] = on2 ? 1 : 0;
     a.ctr2[r] = n; a.msk2[r] = a.mask[n]; a.S2[r] = a.S[n];
     a.cen2[r] = cen_ov ? (LOO_CEN_OV | ovn) : n;
-    // residue i = g itself: every neighbour backward, the self edge forward.  In a pair the listed-first member sees its partner
-    // forward; the other sees the first backward but without its token: Pfw[0] in layer 1, rows G + n of the forward tables in layers 2, 3.
-    // In a group member t sees every later-listed member forward and every earlier-listed one in that way.
+    // residue i = g itself: every neighbour backward, the self edge forward.  In a group member t sees every later-listed member
+    // forward and every earlier-listed one backward but without its token: Pfw[0] in layer 1, rows G + n of the forward tables in
+    // layers 2, 3.
     const bool self = n_loc == c_loc;
-    const bool later = GROUPS ? !(part && a.lead[n] < a.lead[g]) : g_leads;
+    const bool later = !(GROUPS && part && a.lead[n] < a.lead[g]);
     const int pc = LOO_FW | (later ? n : a.G + n);
     a.eo1[r] = (self || part) ? (LOO_FW | n) : n;
     a.eo2[r] = self ? (LOO_FW | g) : part ? pc : cen_ov ? (LOO_OV | ovn) : n;
@@ -255,43 +219,12 @@ static __global__ __launch_bounds__(1024) void loo_count_kernel(const int32_t* _
   }
 }
 
-// The input section of a call with pairs (include/namp.h): int32 words partner[G], first[G], map_idx[G], weight[G] (float bits),
-// maps[n_maps][64].
-// One wave per residue; the listed-first member g of a valid pair forms total[a] = w_g z_g[P_g[a]] + w_p z_p[P_p[a]] from the two
-// head rows (log-softmax rows: they differ from the logits by one constant per member, which cancels; members in listed order, the
-// fma chain of dec_sample_kernel), lp = log_softmax(total), and writes row_m[b] = lp[P_m[b]] for both members (the maps are
-// involutions, so this gather IS row_m[P_m[a]] = lp[a]; it stays a plain in-bounds store per lane whatever the maps hold).
-static __global__ __launch_bounds__(256) void loo_combine_kernel(float* __restrict__ log_probs, const int32_t* __restrict__ pp,
-                                                                  const int32_t* __restrict__ lead, const int32_t* __restrict__ map_idx,
-                                                                  const float* __restrict__ weight, const int32_t* __restrict__ maps,
-                                                                  const int n_maps, const int vocab, const int G) {
-  const int lane = threadIdx.x & 63;
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= G || lead[g] == 0) return;                        // (wave-uniform)
-  const int p = loo_clamp(pp[g], G);
-  const int a = lane < vocab ? lane : 0;
-  const int Pg = loo_clamp(maps[loo_clamp(map_idx[g], n_maps) * 64 + a], vocab);
-  const int Pp = loo_clamp(maps[loo_clamp(map_idx[p], n_maps) * 64 + a], vocab);
-  const float zg = log_probs[(long)g * vocab + Pg], zp = log_probs[(long)p * vocab + Pp];
-  const float tot = lane < vocab ? fmaf(weight[p], zp, weight[g] * zg) : -INFINITY;
-  float mx = tot;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  float e = (lane < vocab) ? expf(tot - mx) : 0.f;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) e += __shfl_xor(e, o);
-  const float lp = (tot - mx) - logf(e);
-  const float rg = __shfl(lp, Pg), rp = __shfl(lp, Pp);
-  if (lane < vocab) {
-    log_probs[(long)g * vocab + lane] = rg;
-    log_probs[(long)p * vocab + lane] = rp;
-  }
-}
-
-// Groups: the input section holds next[G] in the place of partner[G] (include/namp.h).  One wave per group LEADER: it walks the cycle
-// twice, total[a] = sum_t w_t z_t[P_t[a]] over the members in listed order (the fma chain of dec_sample_kernel, as above), then
-// lp = log_softmax(total) and row_m[b] = lp[P_m[b]] for every member (the maps are involutions).  Cycles are disjoint (one successor
-// per residue), every read of a group's rows precedes its first write, and every load is clamped.
+// The input section of a call with an attachment (include/namp.h): int32 words next[G], first[G], map_idx[G], weight[G] (float bits),
+// maps[n_maps][64].  One wave per group LEADER: it walks the cycle twice, total[a] = sum_t w_t z_t[P_t[a]] over the members in listed
+// order from their head rows (log-softmax rows: they differ from the logits by one constant per member, which cancels; the fma chain
+// of dec_sample_kernel), then lp = log_softmax(total) and row_m[b] = lp[P_m[b]] for every member (the maps are involutions, so this
+// gather IS row_m[P_m[a]] = lp[a]; it stays a plain in-bounds store per lane whatever the maps hold).  Cycles are disjoint (one
+// successor per residue), every read of a group's rows precedes its first write, and every load is clamped.
 static __global__ __launch_bounds__(256) void loo_group_combine_kernel(float* __restrict__ log_probs, const int32_t* __restrict__ gl,
                                                                         const int32_t* __restrict__ next, const int32_t* __restrict__ map_idx,
                                                                         const float* __restrict__ weight, const int32_t* __restrict__ maps,
@@ -330,19 +263,18 @@ static __global__ __launch_bounds__(256) void loo_group_combine_kernel(float* __
 
 // Pair classes (namp_loo_classes): the members speak through CLASS TABLES instead of token maps — tables[ti][c] = the
 // member's token under class c, below 0: no such class — and the input section holds bias[n_tables][64] behind the tables.  One wave
-// per residue, lane = class; a wave that is no leader of a valid pair (GROUPS = 0: lead / the validated partner pp) or group (GROUPS =
-// 1: gl / the caller's successor cycle, the walk of loo_group_combine_kernel) writes a class row of -inf and ends.  The leader forms
+// per residue, lane = class; a wave that is no leader of a valid group (gl, and the walk of loo_group_combine_kernel over the
+// caller's successor cycle) writes a class row of -inf and ends.  The leader forms
 //   total[c] = sum_t w_t z_t[C_t[c]] + b[c]   (listed order, the fma chain of the kernels above; b through the table index of the LAST
 //                                              listed member, added once), -inf where some member has no token for c or c >= n_classes,
-//   clp = log_softmax(total)                  (the butterfly of loo_combine_kernel: absent lanes add the zeros the lanes >= vocab add there),
+//   clp = log_softmax(total)                  (the butterfly of loo_group_combine_kernel: absent lanes add the zeros the lanes >= vocab add there),
 //   row_m[t] = clp[C_m[t]], and for the classes c = vocab .. n_classes - 1 in ascending order with C_m[c] == t: log-add-exp(row_m[t], clp[c])
 // (below the vocabulary a table is a token map, an involution: the one class with C_m[c] == t is c = C_m[t]), and writes every
 // member's row and, at its own index, the class row [64].  Every read of a group's rows precedes its first write; every table index
 // and entry is clamped, the fetch of an absent lane reads a clamped address and its sum is not used; plain stores, one address per
 // lane.  A group none of whose classes is present keeps its leave-one-out rows.
-template <int GROUPS>
 static __global__ __launch_bounds__(256) void loo_class_combine_kernel(float* __restrict__ log_probs, const int32_t* __restrict__ gl,
-                                                                        const int32_t* __restrict__ lead, const int32_t* __restrict__ next,
+                                                                        const int32_t* __restrict__ next,
                                                                         const int32_t* __restrict__ tab_idx, const float* __restrict__ weight,
                                                                         const int32_t* __restrict__ tables, const float* __restrict__ bias,
                                                                         float* __restrict__ cls, const int n_tables, const int n_classes,
@@ -350,23 +282,22 @@ static __global__ __launch_bounds__(256) void loo_class_combine_kernel(float* __
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (g >= G) return;                                        // (wave-uniform)
-  if (GROUPS ? gl[g] != g : lead[g] == 0) {
+  if (gl[g] != g) {
     cls[(long)g * 64 + lane] = -INFINITY;
     return;
   }
   const int b0 = (g / N) * N;
-  const int steps = GROUPS ? NAMP_LOO_GROUP_MAX : 2;
   const int c = lane < n_classes ? lane : 0;
   float tot = 0.f;
   bool have = lane < n_classes;
   int cur = g, last = g;
-  for (int t = 0; t < steps; ++t) {
+  for (int t = 0; t < NAMP_LOO_GROUP_MAX; ++t) {
     const int e = tables[loo_clamp(tab_idx[cur], n_tables) * 64 + c];
     have = have && e >= 0;
     const float z = log_probs[(long)cur * vocab + loo_clamp(e, vocab)];
     tot = t == 0 ? weight[cur] * z : fmaf(weight[cur], z, tot);
     last = cur;
-    cur = GROUPS ? b0 + loo_clamp(next[cur], N) : loo_clamp(gl[cur], G);
+    cur = b0 + loo_clamp(next[cur], N);
     if (cur == g) break;
   }
   tot = have ? tot + bias[loo_clamp(tab_idx[last], n_tables) * 64 + c] : -INFINITY;
@@ -384,7 +315,7 @@ static __global__ __launch_bounds__(256) void loo_class_combine_kernel(float* __
   cls[(long)g * 64 + lane] = clp;
   const int tk = lane < vocab ? lane : 0;
   cur = g;
-  for (int t = 0; t < steps; ++t) {
+  for (int t = 0; t < NAMP_LOO_GROUP_MAX; ++t) {
     const int32_t* tab = tables + loo_clamp(tab_idx[cur], n_tables) * 64;
     const int e_own = tab[tk];                               // the class below the vocabulary that gives this lane's token
     const int e_cls = tab[c];                                // the token this lane's class gives the member
@@ -399,7 +330,7 @@ static __global__ __launch_bounds__(256) void loo_class_combine_kernel(float* __
       }
     }
     if (lane < vocab) log_probs[(long)cur * vocab + lane] = row;
-    cur = GROUPS ? b0 + loo_clamp(next[cur], N) : loo_clamp(gl[cur], G);
+    cur = b0 + loo_clamp(next[cur], N);
     if (cur == g) break;
   }
 }

@@ -1,6 +1,6 @@
 // Translation unit of the leave-one-out decoder (namp_loo.h): namp_loo_workspace_bytes / namp_decoder_loo of include/namp.h, and the
-// pair conditionals riding on it (namp_loo_pairs_workspace_bytes / namp_loo_pairs_offset / namp_loo_pairs), and the group
-// conditionals (namp_loo_groups_workspace_bytes / namp_loo_groups_offset / namp_loo_groups), and pair classes in either
+// group conditionals riding on it (namp_loo_groups_workspace_bytes / namp_loo_groups_offset / namp_loo_groups; the pair entry
+// points namp_loo_pairs_workspace_bytes / namp_loo_pairs_offset / namp_loo_pairs attach the same thing), and pair classes on them
 // (namp_loo_classes_workspace_bytes / namp_loo_classes_out_offset / namp_loo_classes).
 // Host code only validates, carves the caller's workspace and enqueues launches on the caller's stream.  The base stream's
 // per-layer states and tables come from the library's own building blocks (namp_node_linear, namp_dec_message_update, ...).
@@ -37,21 +37,19 @@ struct LooBuffers {
   float *h1O, *Pa2O, *Pbw2O, *h2O, *Pbw3O;
   int32_t *rev, *act1, *act2, *ctr1, *ctr2, *cen2, *msk1, *S1, *msk2, *S2, *eo1, *eo2, *eo3, *idG, *ovG, *esrc1, *esrc2;
   size_t bytes;
-  // with pairs, behind everything above (so that a call without pairs carves exactly what it always did):
-  int32_t *pin;            // the caller-filled input section: partner[G] (groups: next[G]), first[G], map_idx[G], weight[G], maps[n_maps][64]
-  int32_t *pp, *lead;      // [G] validated partner / listed-first flag (loo_pairs_kernel); groups: leader / listed position (loo_groups_kernel)
-  float *PfwQ[2];          // [2 G][128] the forward tables of layers 2 / 3 with pairs: rows G.. = W1v . (own layer-1 / layer-2 state), no
-                           // token — what a pair's second member reads for the first
-  size_t pin_off, pair_bytes;
-  int32_t *gkey;           // [R] with groups, behind the pair carve: the stream and listed position an active phase-1 slot names
-  size_t group_bytes;
-  // with pair classes (cls: 1 on the pair carve, 2 on the group carve) the input section also holds bias[n_maps][64], and behind the
-  // carve of the tie it rides on lies the OUTPUT section:
-  float *cls;              // [G][64] the class row of every residue (-inf rows on all but the leaders of valid pairs / groups)
+  // with an attachment, behind everything above (so that a call without one carves exactly what it always did):
+  int32_t *pin;            // the caller-filled input section: next[G], first[G], map_idx[G], weight[G], maps[n_maps][64] (classes: + bias[n_maps][64])
+  int32_t *gl, *gpos;      // [G] leader / listed position of every residue (loo_groups_kernel)
+  float *PfwQ[2];          // [2 G][128] the forward tables of layers 2 / 3: rows G.. = W1v . (own layer-1 / layer-2 state), no token — what
+                           // a member reads for an earlier-listed one
+  int32_t *gkey;           // [R] the stream and listed position an active phase-1 slot names
+  size_t pin_off, group_bytes;
+  // with pair classes, behind those, the OUTPUT section:
+  float *cls;              // [G][64] the class row of every residue (-inf rows on all but the leaders of valid groups)
   size_t cls_off, cls_bytes;
 };
 
-LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0, int cls = 0) {
+LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0, bool classes = false) {
   LooBuffers b;
   size_t off = 0;
   auto take = [&](size_t elems) {
@@ -72,15 +70,14 @@ LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0, int cls = 0) {
   b.esrc1 = (int32_t*)take(R * K); b.esrc2 = (int32_t*)take(R * K);
   b.bytes = off;
   b.pin_off = off;
-  b.pin = (int32_t*)take((size_t)4 * G + (size_t)64 * n_maps * (cls ? 2 : 1));
-  b.pp = (int32_t*)take((size_t)G); b.lead = (int32_t*)take((size_t)G);
+  b.pin = (int32_t*)take((size_t)4 * G + (size_t)64 * n_maps * (classes ? 2 : 1));
+  b.gl = (int32_t*)take((size_t)G); b.gpos = (int32_t*)take((size_t)G);
   b.PfwQ[0] = (float*)take(2 * g128); b.PfwQ[1] = (float*)take(2 * g128);
-  b.pair_bytes = off;
-  b.cls = nullptr; b.cls_off = b.cls_bytes = 0;
-  if (cls == 1) { b.cls_off = off; b.cls = (float*)take((size_t)64 * G); b.cls_bytes = off; }
   b.gkey = (int32_t*)take(R);
   b.group_bytes = off;
-  if (cls == 2) { b.cls_off = off; b.cls = (float*)take((size_t)64 * G); b.cls_bytes = off; }
+  b.cls_off = off;
+  b.cls = (float*)take((size_t)64 * G);
+  b.cls_bytes = off;
   return b;
 }
 
@@ -113,36 +110,33 @@ void loo_proj(NodeTail& t, const float* img, const float* bias, const float* tok
   p.img = img; p.bias = bias; p.tok = tok; p.out = out;
 }
 
-// the pair tables of the calling thread's NEXT namp_decoder_loo call (namp_loo_pairs): taken, and cleared, by that call
-thread_local int g_loo_pairs = 0;
-// ... or its group tables (namp_loo_groups); the later of the two attachments holds
-thread_local int g_loo_groups = 0;
-// ... spoken in pair classes (namp_loo_classes): the number of classes beside the tables of one of the two above, else 0
-thread_local int g_loo_classes = 0;
+// what the calling thread's NEXT namp_decoder_loo call ties: taken, and cleared, by that call; the latest attachment holds
+struct LooAttachment {
+  int n_tables;            // token maps / class tables in the input section, 0: nothing attached
+  int n_classes;           // namp_loo_classes: the classes the tables speak of, else 0
+  bool as_pairs;           // attached through namp_loo_pairs / namp_loo_classes(..., 0): what the call's messages name
+};
+thread_local LooAttachment g_loo_attached = {};
 
 }  // namespace
 
 extern "C" {
 
 size_t namp_loo_pairs_workspace_bytes(int B, int N, int K, int n_dec, int n_maps) {
-  if (namp_loo_workspace_bytes(B, N, K, n_dec) == 0 || n_maps < 1 || n_maps > 64) return 0;
-  return loo_carve(nullptr, (long)B * N, K, n_maps).pair_bytes;
+  return namp_loo_groups_workspace_bytes(B, N, K, n_dec, n_maps);
 }
 
 size_t namp_loo_pairs_offset(int B, int N, int K, int n_dec) { return namp_loo_workspace_bytes(B, N, K, n_dec); }
 
 int namp_loo_pairs(int n_maps) {
-  g_loo_pairs = 0;
-  g_loo_groups = 0;
-  g_loo_classes = 0;
+  g_loo_attached = {};
   if (n_maps < 1 || n_maps > 64) return lfail(NAMP_EINVAL, "namp_loo_pairs: n_maps=%ld must be in [1, 64]", n_maps);
-  g_loo_pairs = n_maps;
+  g_loo_attached = {n_maps, 0, true};
   return NAMP_OK;
 }
 
-// (the section of a call with groups has the layout and the place of the pair section; behind the pair carve it adds one [R] table)
 size_t namp_loo_groups_workspace_bytes(int B, int N, int K, int n_dec, int n_maps) {
-  if (namp_loo_pairs_workspace_bytes(B, N, K, n_dec, n_maps) == 0) return 0;
+  if (namp_loo_workspace_bytes(B, N, K, n_dec) == 0 || n_maps < 1 || n_maps > 64) return 0;
   return loo_carve(nullptr, (long)B * N, K, n_maps).group_bytes;
 }
 
@@ -151,34 +145,29 @@ size_t namp_loo_groups_offset(int B, int N, int K, int n_dec) { return namp_loo_
 int namp_loo_group_max(void) { return NAMP_LOO_GROUP_MAX; }
 
 int namp_loo_groups(int n_maps) {
-  g_loo_pairs = 0;
-  g_loo_groups = 0;
-  g_loo_classes = 0;
+  g_loo_attached = {};
   if (n_maps < 1 || n_maps > 64) return lfail(NAMP_EINVAL, "namp_loo_groups: n_maps=%ld must be in [1, 64]", n_maps);
-  g_loo_groups = n_maps;
+  g_loo_attached = {n_maps, 0, false};
   return NAMP_OK;
 }
 
-// (pair classes ride on either carve: the input section grows by the biases, the output section lies behind the carve)
+// (pair classes: the input section grows by the biases, the output section lies behind the carve; `groups` only has to be valid)
 size_t namp_loo_classes_workspace_bytes(int B, int N, int K, int n_dec, int n_tables, int groups) {
-  if (namp_loo_pairs_workspace_bytes(B, N, K, n_dec, n_tables) == 0 || groups < 0 || groups > 1) return 0;
-  return loo_carve(nullptr, (long)B * N, K, n_tables, groups ? 2 : 1).cls_bytes;
+  if (namp_loo_groups_workspace_bytes(B, N, K, n_dec, n_tables) == 0 || groups < 0 || groups > 1) return 0;
+  return loo_carve(nullptr, (long)B * N, K, n_tables, true).cls_bytes;
 }
 
 size_t namp_loo_classes_out_offset(int B, int N, int K, int n_dec, int n_tables, int groups) {
-  if (namp_loo_pairs_workspace_bytes(B, N, K, n_dec, n_tables) == 0 || groups < 0 || groups > 1) return 0;
-  return loo_carve(nullptr, (long)B * N, K, n_tables, groups ? 2 : 1).cls_off;
+  if (namp_loo_groups_workspace_bytes(B, N, K, n_dec, n_tables) == 0 || groups < 0 || groups > 1) return 0;
+  return loo_carve(nullptr, (long)B * N, K, n_tables, true).cls_off;
 }
 
 int namp_loo_classes(int n_tables, int n_classes, int groups) {
-  g_loo_pairs = 0;
-  g_loo_groups = 0;
-  g_loo_classes = 0;
+  g_loo_attached = {};
   if (n_tables < 1 || n_tables > 64) return lfail(NAMP_EINVAL, "namp_loo_classes: n_tables=%ld must be in [1, 64]", n_tables);
   if (n_classes < 1 || n_classes > 64) return lfail(NAMP_EINVAL, "namp_loo_classes: n_classes=%ld must be in [vocab, 64]", n_classes);
   if (groups < 0 || groups > 1) return lfail(NAMP_EINVAL, "namp_loo_classes: groups=%ld must be 0 (pairs) or 1 (groups)", groups);
-  (groups ? g_loo_groups : g_loo_pairs) = n_tables;
-  g_loo_classes = n_classes;
+  g_loo_attached = {n_tables, n_classes, groups == 0};
   return NAMP_OK;
 }
 
@@ -190,16 +179,13 @@ size_t namp_loo_workspace_bytes(int B, int N, int K, int n_dec) {
 int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx, const int32_t* S,
                      const int32_t* mask, const int32_t* rank, float* log_probs, int32_t* counts, void* ws, size_t ws_bytes,
                      int B, int N, int K, void* stream) {
-  const bool groups = g_loo_groups != 0;
-  const int n_maps = groups ? g_loo_groups : g_loo_pairs;
-  const int n_classes = g_loo_classes;
-  g_loo_pairs = 0;                                               // (one call only, whatever becomes of it)
-  g_loo_groups = 0;
-  g_loo_classes = 0;
+  const LooAttachment att = g_loo_attached;
+  g_loo_attached = {};                                           // (one call only, whatever becomes of it)
+  const int n_maps = att.n_tables, n_classes = att.n_classes;
   if (!w || !h_V_enc || !h_E || !E_idx || !S || !mask || !rank || !log_probs || !counts || !ws)
-    return lfail(NAMP_EINVAL, groups   ? "namp_decoder_loo: null pointer argument (group tables were attached)"
-                              : n_maps ? "namp_decoder_loo: null pointer argument (pair tables were attached)"
-                                       : "namp_decoder_loo: null pointer argument");
+    return lfail(NAMP_EINVAL, !n_maps        ? "namp_decoder_loo: null pointer argument"
+                              : att.as_pairs ? "namp_decoder_loo: null pointer argument (pair tables were attached)"
+                                             : "namp_decoder_loo: null pointer argument (group tables were attached)");
   if ((((uintptr_t)h_V_enc | (uintptr_t)h_E | (uintptr_t)ws | (uintptr_t)log_probs) & 15u) != 0)
     return lfail(NAMP_EINVAL, "namp_decoder_loo: h_V_enc / h_E / log_probs / ws must be 16-byte aligned");
   if (w->n_dec != 3) return lfail(NAMP_EINVAL, "namp_decoder_loo: the cone kernels walk three decoder layers (n_dec=%ld): use the L-stream form", w->n_dec);
@@ -223,10 +209,10 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   }
   if (!w->Wout_w || !w->Wout_b) return lfail(NAMP_EINVAL, "namp_decoder_loo: null output head");
   const long G = (long)B * N, R = G * K;
-  LooBuffers b = loo_carve(ws, G, K, n_maps, n_classes ? (groups ? 2 : 1) : 0);
+  LooBuffers b = loo_carve(ws, G, K, n_maps, n_classes != 0);
   static_assert(NAMP_LOO_GROUP_MAX <= 16, "loo_prepare_kernel packs a listed position into 4 bits beside a residue index below 2^27");
   if (n_maps && 2 * G >= (1L << LOO_ROW_BITS)) return lfail(NAMP_EINVAL, "namp_decoder_loo: 2*B*N=%ld exceeds 2^28 table rows", 2 * G);
-  const size_t need = n_classes ? b.cls_bytes : groups ? b.group_bytes : n_maps ? b.pair_bytes : b.bytes;
+  const size_t need = n_classes ? b.cls_bytes : n_maps ? b.group_bytes : b.bytes;
   if (need > ws_bytes && n_classes)                              // (the class section is part of the call's arguments: include/namp.h)
     return lfail(NAMP_EINVAL, "namp_decoder_loo: workspace too small for the attached class tables (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
   if (need > ws_bytes) return lfail(NAMP_EWORKSPACE, "namp_decoder_loo: workspace too small (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
@@ -245,17 +231,11 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   const int32_t *p_first = b.pin + G, *p_map = b.pin + 2 * G, *p_maps = b.pin + 4 * G;
   const float* p_weight = (const float*)(b.pin + 3 * G);
   if (n_maps) {
-    if (groups) hipLaunchKernelGGL(loo_groups_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, b.pin, p_first, mask, b.pp, b.lead, (int)G, N);
-    else hipLaunchKernelGGL(loo_pairs_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, b.pin, p_first, mask, b.pp, b.lead, (int)G, N);
-    pa.pp = b.pp; pa.lead = b.lead; pa.gkey = b.gkey;
+    hipLaunchKernelGGL(loo_groups_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, b.pin, p_first, mask, b.gl, b.gpos, (int)G, N);
+    pa.pp = b.gl; pa.lead = b.gpos; pa.gkey = b.gkey;
     b.Pfw[1] = b.PfwQ[0]; b.Pfw[2] = b.PfwQ[1];                   // (the same rows 0 .. G-1 at another address)
-  }
-  if (groups) {
     hipLaunchKernelGGL(loo_prepare_kernel<LOO_TIE_GROUPS>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
     hipLaunchKernelGGL(loo_edges_kernel<LOO_TIE_GROUPS>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
-  } else if (n_maps) {
-    hipLaunchKernelGGL(loo_prepare_kernel<LOO_TIE_PAIRS>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
-    hipLaunchKernelGGL(loo_edges_kernel<LOO_TIE_PAIRS>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
   } else {
     hipLaunchKernelGGL(loo_prepare_kernel<LOO_TIE_NONE>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, pa);
     hipLaunchKernelGGL(loo_edges_kernel<LOO_TIE_NONE>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, pa);
@@ -309,7 +289,7 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   a = items(D0, G, nullptr, b.idG, b.idG, b.eo1, b.Pa1, b.Pa1, h_V_enc, h_V_enc, b.Pbw1, b.Pfw[0], b.Pbw1);
   loo_tail(a.tail, D0, mask, S, b.h1o);
   loo_proj(a.tail, D1->W1a_img, D1->b1, nullptr, b.Pa2o);
-  if (n_maps) loo_proj(a.tail, D1->W1v_img, nullptr, nullptr, b.PfwQ[0] + G * NAMP_HIDDEN);      // what the second member of a pair reads for the first, layer 2
+  if (n_maps) loo_proj(a.tail, D1->W1v_img, nullptr, nullptr, b.PfwQ[0] + G * NAMP_HIDDEN);      // what a member reads for an earlier-listed one, layer 2
   if ((rc = launch_items(a, prec, s))) return rc;
   // phase 2: layer 2 at i's neighbours that a phase-1 output reaches (table of layer 3 for the own layer 3)
   a = items(D1, R, b.act2, b.ctr2, b.cen2, b.esrc2, b.Pa2, b.Pa2O, b.h1, b.h1O, b.Pbw2, b.Pfw[1], b.Pbw2O);
@@ -326,21 +306,15 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   loo_tail(a.tail, D2, mask, S, b.h3o);
   a.tail.head_w = w->Wout_w; a.tail.head_b = w->Wout_b; a.tail.log_probs = log_probs; a.tail.logits = nullptr; a.tail.vocab = w->vocab;
   if ((rc = launch_items(a, prec, s)) || !n_maps) return rc;
-  // pairs: the two members' rows -> the pair's conditional, through their token maps; groups: every member's; pair classes: through
-  // their class tables, with the class rows into the output section
+  // every member's row -> the group's conditional, through the token maps; pair classes: through the class tables, with the class
+  // rows into the output section
   const float* p_bias = (const float*)(p_maps + (size_t)64 * n_maps);
-  if (n_classes && groups)
-    hipLaunchKernelGGL(loo_class_combine_kernel<1>, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.lead, b.pin, p_map,
-                       p_weight, p_maps, p_bias, b.cls, n_maps, n_classes, (int)w->vocab, (int)G, N);
-  else if (n_classes)
-    hipLaunchKernelGGL(loo_class_combine_kernel<0>, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.lead, b.pin, p_map,
-                       p_weight, p_maps, p_bias, b.cls, n_maps, n_classes, (int)w->vocab, (int)G, N);
-  else if (groups)
-    hipLaunchKernelGGL(loo_group_combine_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.pin, p_map, p_weight,
-                       p_maps, n_maps, (int)w->vocab, (int)G, N);
+  if (n_classes)
+    hipLaunchKernelGGL(loo_class_combine_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.gl, b.pin, p_map, p_weight,
+                       p_maps, p_bias, b.cls, n_maps, n_classes, (int)w->vocab, (int)G, N);
   else
-    hipLaunchKernelGGL(loo_combine_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.pp, b.lead, p_map, p_weight, p_maps,
-                       n_maps, (int)w->vocab, (int)G);
+    hipLaunchKernelGGL(loo_group_combine_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s, log_probs, b.gl, b.pin, p_map, p_weight,
+                       p_maps, n_maps, (int)w->vocab, (int)G, N);
   e = hipGetLastError();
   if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
   return NAMP_OK;

@@ -472,6 +472,7 @@ class ProteinMPNN(nn.Module):
         self._conv = {}               # (id(tensor), kind) -> (weakref, version, converted): see _as
         self._zeros = {}              # (shape, device) -> int32 zeros (the N_na masks of a model built without include_pred_na_N)
         self._v_cache = None          # (weakref to R_polymer_type, version, weights signature, V)
+        self._tie_tables = {}         # (tied, classes) -> (key, host lists, tables) of the last conditional_probs of that kind
         # per-edge message / edge-update GEMMs: "x3" (default, parity mode) = three bf16 products of split operands with fp32
         # accumulation, fp32-equivalent to ~2^-16 (3e-5 on log-probs, arg-max unchanged) at 3/16 of the fp32 MFMA cost;
         # "fp32" = exact fp32 MFMA; "bf16" = plain bf16 inputs, BASELINE configs[2]'s throughput mode (~1e-2 on log-probs).
@@ -558,17 +559,9 @@ class ProteinMPNN(nn.Module):
         "paired_wobble_bias": a float, or one per pair) true for some pair the maps are class tables (table 0: the identity below the
         vocabulary, -1 beyond) and the last entry holds the 64 class biases of every table: tables are told apart by (table, bias)."""
         pairs, maps = fd.get("paired_residues"), fd.get("symmetry_token_maps")
-        wobble, wobble_bias = fd.get("paired_wobble"), fd.get("paired_wobble_bias")
-        to_list = lambda v: v.detach().reshape(-1).tolist() if torch.is_tensor(v) else (list(v) if hasattr(v, "__len__") else v)
-        wobble, wobble_bias = to_list(wobble), to_list(wobble_bias)
-        n_pairs = 0 if pairs is None else len(pairs)
-        for v, what in ((wobble, "paired_wobble"), (wobble_bias, "paired_wobble_bias")):
-            if isinstance(v, list) and len(v) != n_pairs:
-                raise ValueError(f"{what} has {len(v)} entries for {n_pairs} pairs")
-        if not (any(wobble) if isinstance(wobble, list) else bool(wobble)):
+        wobble, wobble_bias, asked = self._wobble_arguments(fd, 0 if pairs is None else len(pairs))
+        if not asked:
             wobble = None                                                        # no pair asks for wobble: the token maps, as without the key
-        elif n_pairs == 0:
-            raise ValueError("paired_wobble needs paired_residues")
         if (pairs is None or len(pairs) == 0) and maps is None:
             return None
         if self.restype_to_int is None:
@@ -580,16 +573,10 @@ class ProteinMPNN(nn.Module):
         polymer = fixed = None
         if pairs is not None and len(pairs):
             dna, rna = self._host_list(fd["dna_mask"], "dna_mask"), self._host_list(fd["rna_mask"], "rna_mask")
-            polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
             m, cm = self._host_list(fd["mask"], "mask"), self._host_list(fd["chain_mask"], "chain_mask")
             fixed = [not (a and b) for a, b in zip(m, cm)]                       # (a masked residue keeps its token as a fixed one does)
-            # A residue the parser masks (a 5' nucleotide without its phosphate) comes without a polymer flag.  It is fixed, so all the
-            # map does is hand the complement of its token to its partner: the partner's polymer type stands in for its own.
-            for pr in pairs:
-                for r, q in ((int(pr[0]), int(pr[1])), (int(pr[1]), int(pr[0]))):
-                    if 0 <= r < L and 0 <= q < L and not m[r] and polymer[r] == 0 and polymer[q] in (1, 2) \
-                            and not self._host_list(fd["protein_mask"], "protein_mask")[r]:
-                        polymer[r] = polymer[q]
+            # (a masked residue without a polymer flag is fixed, so all the map does is hand the complement of its token to its partner)
+            polymer = self._pair_polymer(fd, pairs, L, dna, rna, m)
         groups, weights, gmaps, pair_list, *gbias = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, fixed,
                                                                   fd.get("symmetry_residues"), fd.get("symmetry_weights"), maps,
                                                                   wobble, wobble_bias)
@@ -984,242 +971,245 @@ class ProteinMPNN(nn.Module):
         design call above with the class combine applied in torch.  With classes=False (the default) paired_wobble stays refused."""
         if method not in ("auto", "dense", "cone"):
             raise ValueError(f"method must be 'auto', 'dense' or 'cone'; got {method!r}")
-        if classes:
-            return self._conditional_probs_classes(feature_dict, method, bool(tied))
-        if tied:
-            return self._conditional_probs_tied(feature_dict, method)
-        S_true, mask = feature_dict["S"], feature_dict["mask"]
+        fd, tied, classes = feature_dict, bool(tied), bool(classes)
+        S_true, mask = fd["S"], fd["mask"]
         B, L = S_true.shape
-        paired = self._pair_conditional_arguments(feature_dict, B, L)
+        state_w, M = None, 1
+        if tied and fd.get("state_weights") is not None:
+            fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
+            fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
+            fd_chk.pop("S_forced", None)
+            state_w, M, L, _, _ = self._states_arguments(fd_chk)
+        ties = self._conditional_arguments(fd, B, L, state_w, tied, classes)
         cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
         if method == "cone" and not cone_ok:
             raise NotImplementedError("conditional_probs(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
                                       "use method='dense'")
         use_cone = method == "cone" or (method == "auto" and cone_ok)
+        Lb, n_dec, N = hip.lib(), len(self.decoder_layers), M * L
+        K = int(min(self.k_neighbors, L))
         ws = None
-        if paired is not None and S_true.is_cuda:
-            # The pair tables go up BEFORE the encoder is enqueued (a host-to-device copy waits for the stream): with the cone into the
-            # input section of the call's workspace — ONE copy —, and the list of tied pairs for the result.
-            Lb, n_dec, K = hip.lib(), len(self.decoder_layers), int(min(self.k_neighbors, L))
-            for key in ("section", "pairs"):               # (page-locked once, with the cached tables: the copies below do not stall the host)
-                if not paired[key].is_pinned():
-                    paired[key] = paired[key].pin_memory()
+        if ties is not None:
+            # The tables go up BEFORE the encoder is enqueued (a host-to-device copy waits for the stream), page-locked once with the
+            # cached tables: with the cone into the input section of the call's workspace — ONE copy —, and the index of the ties for the result.
+            _require_device(fd["X"], "X")
+            dev, n_tab = S_true.device, ties["n_tables"]
+            for key in ("section", "index"):
+                if not ties[key].is_pinned():
+                    ties[key] = ties[key].pin_memory()
             if use_cone:
-                section, n_maps = paired["section"], paired["n_maps"]
-                ws = torch.empty(Lb.namp_loo_pairs_workspace_bytes(B, L, K, n_dec, n_maps), dtype=torch.uint8, device=S_true.device)
-                off = Lb.namp_loo_pairs_offset(B, L, K, n_dec)
+                section = ties["section"]
+                nbytes = Lb.namp_loo_classes_workspace_bytes(1, N, K, n_dec, n_tab, int(tied)) if classes else \
+                    (Lb.namp_loo_groups_workspace_bytes if tied else Lb.namp_loo_pairs_workspace_bytes)(1, N, K, n_dec, n_tab)
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                off = (Lb.namp_loo_groups_offset if tied else Lb.namp_loo_pairs_offset)(1, N, K, n_dec)
                 ws[off:off + 4 * section.numel()].view(torch.int32).copy_(section, non_blocking=True)
-            pairs_dev = paired["pairs"].to(S_true.device, non_blocking=True)
-        o = self._decoding_order(mask, feature_dict["chain_mask"], feature_dict["randn"])
-        h_V, h_E, E_idx = self.encode(feature_dict, order=o)
+            index = ties["index"].to(dev, non_blocking=True)
+            lead = index[:, 0] if index.numel() else index.reshape(-1)
+        o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1] if state_w is not None else fd["randn"])
+        if tied and ties is not None:                      # the states (one without state_weights) side by side, as _sample_states featurises them
+            fd_enc = fd
+            if state_w is not None:
+                fd_enc = dict(fd)
+                for k in self._STATE_SHARED:
+                    fd_enc[k] = fd[k].expand(M, L)
+            V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
+            h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
+        else:
+            h_V, h_E, E_idx = self.encode(fd, order=o)
         self._check_tokens(S_true)
         o.wait()
         rank = o.rank[:B]
         out = {"S": S_true, "decoding_order": o.order[0]}
+        dev = h_V.device
         if use_cone:
             W = self._weights()
-            Lb = hip.lib()
-            K = E_idx.shape[-1]
-            dev = h_V.device
-            E32, S32, m32, r32 = _i32(E_idx), self._as(S_true, "i32"), self._as(mask, "i32"), _i32(rank)
-            if paired is None:
-                ws = torch.empty(Lb.namp_loo_workspace_bytes(B, L, K, len(self.decoder_layers)), dtype=torch.uint8, device=dev)
+            # the M states as ONE complex of M * L residues: the block-diagonal flattened graph (DESIGN.md 5.6); ranks repeat per block
+            E_f = E_idx if M == 1 else (E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).contiguous()
+            rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
+            E32, S32, m32, r32 = _i32(E_f), _i32(rep(self._as(S_true, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
+            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+            if ties is None:
+                ws = torch.empty(Lb.namp_loo_workspace_bytes(B, N, K, n_dec), dtype=torch.uint8, device=dev)
+            elif classes:                                  # the NEXT namp_decoder_loo call reads the section
+                hip.check(Lb.namp_loo_classes(n_tab, spec.N_CLASSES, int(tied)), "loo_classes")
             else:
-                hip.check(Lb.namp_loo_pairs(paired["n_maps"]), "loo_pairs")      # the NEXT namp_decoder_loo call reads the section
+                hip.check((Lb.namp_loo_groups if tied else Lb.namp_loo_pairs)(n_tab), "loo_groups" if tied else "loo_pairs")
             counts = torch.empty(2, dtype=torch.int32, device=dev)
-            log_probs = torch.empty(B, L, self.num_letters, device=dev)
+            log_probs = torch.empty(B, N, self.num_letters, device=dev)
             hip.check(Lb.namp_decoder_loo(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
-                                          r32.data_ptr(), log_probs.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), B, L, K,
+                                          r32.data_ptr(), log_probs.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), B, N, K,
                                           hip.current_stream()), "decoder_loo")
-            out.update(log_probs=log_probs, cone_items=counts)
-            if paired is not None:
-                out.update(pairs=pairs_dev, pair_log_probs=log_probs[0, pairs_dev[:, 0]])
+            out["cone_items"] = counts
+            if classes and ties is not None:
+                c_off = Lb.namp_loo_classes_out_offset(1, N, K, n_dec, n_tab, int(tied))
+                class_rows = ws[c_off:c_off + 4 * spec.N_CLASS_LANES * N].view(torch.float32).view(N, spec.N_CLASS_LANES)[lead]
+        else:
+            log_probs = self._loo_dense(h_V, h_E, E_idx, S_true, mask, rank)
+            if ties is not None:
+                log_probs = log_probs.view(1, N, self.num_letters)
+                rows = self._tied_conditionals_by_sampling(fd, o.order[0], ties, log_probs, tied, classes)
+                if classes:
+                    class_rows = torch.stack(rows) if rows else torch.zeros(0, spec.N_CLASS_LANES, device=dev)
+        if ties is None:
+            out["log_probs"] = log_probs
             return out
-        log_probs = torch.empty(B, L, self.num_letters, device=h_V.device)
+        what = "group" if tied else "pair"
+        out.update({"log_probs": log_probs[:, :L], what + "s": index, what + "_log_probs": log_probs[0, lead]})
+        if classes:
+            out[what + "_class_log_probs"] = class_rows
+        return out
+
+    def _loo_dense(self, h_V, h_E, E_idx, S, mask, rank):
+        """The L-stream form: per encoded block (a complex of the batch, or a state under the one S / mask / rank) L streams through the
+        ordinary decoder, chunked over streams -> the leave-one-out rows [blocks, L, vocab]."""
+        nb, L = h_V.shape[:2]
+        log_probs = torch.empty(nb, L, self.num_letters, device=h_V.device)
         chunk = max(1, self.loo_dense_tokens // L)
-        for b in range(B):
+        for b in range(nb):
+            S_b, m_b, r_b = (t[b:b + 1] if t.shape[0] == nb else t[:1] for t in (S, mask, rank))
             for i0 in range(0, L, chunk):
                 i1 = min(L, i0 + chunk)
                 n = i1 - i0
-                ranks = leave_one_out_ranks(rank[b:b + 1], i0, i1)[0]
-                lp = self.decode_graph(h_V[b:b + 1], h_E[b:b + 1], E_idx[b:b + 1], S_true[b:b + 1].expand(n, L), mask[b:b + 1].expand(n, L), ranks)
+                ranks = leave_one_out_ranks(r_b, i0, i1)[0]
+                lp = self.decode_graph(h_V[b:b + 1], h_E[b:b + 1], E_idx[b:b + 1], S_b.expand(n, L), m_b.expand(n, L), ranks)
                 ar = torch.arange(n, device=lp.device)
                 log_probs[b, i0:i1] = lp[ar, i0 + ar]
-        out["log_probs"] = log_probs
-        if paired is not None:
-            self._pair_conditionals_by_sampling(feature_dict, o.order[0], paired, log_probs)
-            out.update(pairs=pairs_dev, pair_log_probs=log_probs[0, pairs_dev[:, 0]])
-        return out
+        return log_probs
 
-    def _group_conditional_arguments(self, fd, B, L, state_w):
-        """The tied groups of a conditional_probs(tied=True) call -> None without groups, else {"tied": [(members, weights, maps)] the
-        groups the device ties in flat indices (no masked member), "base": per tied group (residues in [0, L), their weights without
-        the state weight, their maps) for the slow route, "groups": int64 [n, max_size] padded with -1, "section": the int32 input
-        section of the workspace (include/namp.h: next, first, map_idx, weight bits, maps), "n_maps"}.  state_w: None or the M weights."""
+    def _wobble_arguments(self, fd, n_pairs=None):
+        """feature_dict["paired_wobble"] / ["paired_wobble_bias"] in one normal form -> (wobble, wobble_bias, asked): each None, a scalar
+        or a list with one entry per pair; asked: some pair asks for wobble.  With n_pairs the lists are checked against the pairs."""
+        to_list = lambda v: v.detach().reshape(-1).tolist() if torch.is_tensor(v) else (list(v) if hasattr(v, "__len__") else v)
+        wobble, wobble_bias = to_list(fd.get("paired_wobble")), to_list(fd.get("paired_wobble_bias"))
+        asked = any(wobble) if isinstance(wobble, list) else bool(wobble)
+        if n_pairs is not None:
+            for v, what in ((wobble, "paired_wobble"), (wobble_bias, "paired_wobble_bias")):
+                if isinstance(v, list) and len(v) != n_pairs:
+                    raise ValueError(f"{what} has {len(v)} entries for {n_pairs} pairs")
+            if asked and n_pairs == 0:
+                raise ValueError("paired_wobble needs paired_residues")
+        return wobble, wobble_bias, asked
+
+    def _pair_polymer(self, fd, pairs, L, dna, rna, m):
+        """The polymer type of every residue for mapped_groups (1 DNA, 2 RNA, else 0).  A residue the parser masks (a 5' nucleotide
+        without its phosphate) comes without a polymer flag: its pair partner's type stands in for its own."""
+        polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
+        for pr in pairs:
+            for r, q in ((int(pr[0]), int(pr[1])), (int(pr[1]), int(pr[0]))):
+                if 0 <= r < L and 0 <= q < L and not m[r] and polymer[r] == 0 and polymer[q] in (1, 2) \
+                        and not self._host_list(fd["protein_mask"], "protein_mask")[r]:
+                    polymer[r] = polymer[q]
+        return polymer
+
+    def _conditional_arguments(self, fd, B, L, state_w=None, tied=False, classes=False):
+        """The ties of a conditional_probs(tied, classes) call — base pairs alone with tied=False, every tie with tied=True; spoken in
+        token maps, with classes=True in class tables — -> None with nothing to tie, else
+        {"tied": [(members, weights, tables, class bias or None, listed weights)] what the device ties (no masked member): flat indices
+        (state-major with states), the weights with the state weight, a map [vocab] or class table [64] per member; listed weights: those
+        of the members in [0, L) without the state weight, for the slow route's design call,
+        "index": int64 [n, width] the members padded with -1 (tied=False: [n, 2]),
+        "section": the int32 input section of the workspace (include/namp.h: next, first, table_idx, weight bits, tables [n_tables][64],
+        with classes the bias bits [n_tables][64]; table 0 is the identity; tables are told apart by (table, bias)), "n_tables"}.
+        state_w: None or the M state weights."""
         pairs, sym = fd.get("paired_residues"), fd.get("symmetry_residues")
         pairs = None if pairs is None or len(pairs) == 0 else pairs
         sym = None if sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0) else sym
-        wobble = fd.get("paired_wobble")
-        if wobble is not None:
-            wobble = wobble.detach().reshape(-1).tolist() if torch.is_tensor(wobble) else wobble
-            if any(wobble) if hasattr(wobble, "__len__") else bool(wobble):
+        wobble, wobble_bias, asked = self._wobble_arguments(fd)
+        if not tied:
+            if pairs is None:
+                return None
+            if asked and not classes:
+                raise NotImplementedError("conditional_probs: paired_wobble is not supported; pair classes (DESIGN.md 5.8) are the follow-up")
+            if sym is not None:
+                raise NotImplementedError("conditional_probs: paired_residues together with symmetry_residues is not supported")
+            if fd.get("state_weights") is not None:
+                raise NotImplementedError("conditional_probs: paired_residues together with state_weights is not supported")
+        else:
+            if asked and not classes:
                 raise NotImplementedError("conditional_probs: paired_wobble is not supported; pair classes (DESIGN.md 5.8) change the combine")
-        if pairs is None and sym is None and state_w is None:
-            return None
+            if pairs is None and sym is None and state_w is None:
+                return None
+        who = "tied groups" if tied else "paired_residues"
         if B != 1:
-            raise ValueError("tied groups expect one input complex (B == 1)")
+            raise ValueError(f"{who} expect one input complex (B == 1)")
         if self.restype_to_int is None:
-            raise ValueError("tied groups need the model's restype_to_int")
+            raise ValueError(("paired_residues / tied groups need" if classes else who + " need") + " the model's restype_to_int")
+        if classes:
+            self._wobble_arguments(fd, 0 if pairs is None else len(pairs))
         m = self._host_list(fd["mask"], "mask")
         dna = rna = None
         if pairs is not None:
             dna, rna = self._host_list(fd["dna_mask"], "dna_mask"), self._host_list(fd["rna_mask"], "rna_mask")
-        # the tables of the last call are kept: a resident feature_dict is scored many times (the host lists above are the SAME objects
-        # while their tensors are unchanged; the ties are compared by value in one normal form; a call with symmetry_token_maps is never
-        # served from the cache, and its own entry, whose key says so, serves no later call)
+        # The tables of the last call of every kind (tied, classes) are kept: a resident feature_dict is scored many times, and a
+        # specificity profile alternates the kinds on it — in one slot each would rebuild and page-lock its tables on every call.  The
+        # host lists above are the SAME objects while their tensors are unchanged; the ties are compared by value in one normal form; a
+        # call with symmetry_token_maps is never served from the cache, and its own entry, whose key says so, serves no later call.
         as_list = lambda v: v.tolist() if hasattr(v, "tolist") else v
         listed = lambda v: None if v is None else [[as_list(x) for x in g] if hasattr(g, "__len__") else g for g in v]
         key = (None if pairs is None else [(int(a), int(b)) for a, b in pairs], as_list(fd.get("paired_weights")),
                None if sym is None else [[int(r) for r in g] for g in sym], listed(fd.get("symmetry_weights")) if sym is not None else None,
-               state_w, fd.get("symmetry_token_maps") is None)
-        last = getattr(self, "_group_tables", None)
-        if last is not None and key[5] and last[0] == key and all(x is y for x, y in zip(last[1], (dna, rna, m))):
+               state_w, wobble if classes else None, wobble_bias if classes else None, fd.get("symmetry_token_maps") is None)
+        last = self._tie_tables.get((tied, classes))
+        if last is not None and key[-1] and last[0] == key and all(x is y for x, y in zip(last[1], (dna, rna, m))):
             return last[2]
-        polymer = None
-        if pairs is not None:
-            polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
-            for pr in pairs:                              # (a masked residue may come without a polymer flag: its partner's stands in, as in sample())
-                for r, q in ((int(pr[0]), int(pr[1])), (int(pr[1]), int(pr[0]))):
-                    if 0 <= r < L and 0 <= q < L and not m[r] and polymer[r] == 0 and polymer[q] in (1, 2) \
-                            and not self._host_list(fd["protein_mask"], "protein_mask")[r]:
-                        polymer[r] = polymer[q]
-        groups, weights, gmaps = [], [], []
-        if pairs is not None or sym is not None:
-            groups, weights, gmaps, _ = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, None, sym,
-                                                      fd.get("symmetry_weights") if sym is not None else None,
-                                                      fd.get("symmetry_token_maps"))     # (maps without groups: refused there)
+        polymer = None if pairs is None else self._pair_polymer(fd, pairs, L, dna, rna, m)
+        groups, weights, gtabs, _, *gbias = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, None, sym,
+                                                          fd.get("symmetry_weights") if sym is not None else None,
+                                                          fd.get("symmetry_token_maps"),            # (maps without groups: refused there)
+                                                          (False if wobble is None else wobble) if classes else None, wobble_bias)
         members = [r for g in groups for r in g]
         if len(set(members)) != len(members):
             raise ValueError("conditional_probs: the tied groups must be disjoint")
         M, sw = (1, [1.0]) if state_w is None else (len(state_w), state_w)
-        ident = list(range(len(spec.RESTYPES)))
+        V, lanes = len(spec.RESTYPES), spec.N_CLASS_LANES
+        # a token map goes into the section with the identity beyond the vocabulary, a class table with no class there
+        ident, zero = list(range(V)) + ([-1] * (lanes - V) if classes else list(range(V, lanes))), [0.0] * lanes
+        gbias = gbias[0] if classes else [zero] * len(groups)
         if state_w is not None:                            # every residue is a group across the states
             tied_res = set(members)
             for i in range(L):
                 if i not in tied_res:
-                    groups.append([i]); weights.append([1.0]); gmaps.append([ident])
+                    groups.append([i]); weights.append([1.0]); gtabs.append([ident[:lanes if classes else V]]); gbias.append(zero)
         N = M * L
-        nxt, first, midx, w = [-1] * N, [0] * N, [0] * N, [1.0] * N
-        table, index = [list(range(64))], {tuple(range(64)): 0}
-        tied, base = [], []
-        for g, gw, gm in zip(groups, weights, gmaps):
+        nxt, first, tidx, w = [-1] * N, [0] * N, [0] * N, [1.0] * N
+        table, bias, index = [ident], [zero], {(tuple(ident), tuple(zero)): 0}
+        tied_specs = []
+        for g, gw, gt, gb in zip(groups, weights, gtabs, gbias):
             if len(g) * M > hip.loo_group_max():
                 raise ValueError(f"conditional_probs: the group of residue {g[0]} has {len(g) * M} members; at most {hip.loo_group_max()} are tied")
             if len(g) * M < 2:
                 continue
             flat = [r + s_ * L for s_ in range(M) for r in g]                 # state-major, as _sample_states lists them
             fw = [sw[s_] * float(v) for s_ in range(M) for v in gw]
-            fm = [P for s_ in range(M) for P in gm]
-            for t, (r, wr, P) in enumerate(zip(flat, fw, fm)):
-                P64 = tuple(P) + tuple(range(len(P), 64))
-                k = index.get(P64)
+            ft = [C for s_ in range(M) for C in gt]
+            for t, (r, wr, C) in enumerate(zip(flat, fw, ft)):
+                row = (tuple(C) + tuple(range(len(C), lanes)), tuple(gb))
+                k = index.get(row)
                 if k is None:
-                    k = index[P64] = len(table)
-                    table.append(list(P64))
-                nxt[r], midx[r], w[r] = flat[(t + 1) % len(flat)] , k, wr
+                    k = index[row] = len(table)
+                    table.append(list(row[0])); bias.append([float(v) for v in gb])
+                nxt[r], tidx[r], w[r] = flat[(t + 1) % len(flat)], k, wr
             first[flat[0]] = 1
-            if all(m[r] for r in g):                       # the device's rule: a group with a masked member is not tied
-                tied.append((flat, fw, [list(P) for P in fm]))
-                base.append((list(g), [float(v) for v in gw], [list(P) for P in gm]))
+            if all(m[r] for r in g):                       # the device's rule: a pair / group with a masked member is not tied
+                tied_specs.append((flat, fw, [list(C) for C in ft], [float(v) for v in gb] if classes else None, [float(v) for v in gw]))
         if len(table) > 64:
-            raise ValueError(f"conditional_probs: {len(table)} distinct token maps; at most 64")
-        width = max([len(t[0]) for t in tied], default=0)
-        section = torch.cat((torch.tensor(nxt + first + midx, dtype=torch.int32), torch.tensor(w, dtype=torch.float32).view(torch.int32),
-                             torch.tensor([t for P in table for t in P], dtype=torch.int32)))
-        out = {"tied": tied, "base": base, "section": section, "n_maps": len(table),
-               "groups": torch.tensor([t[0] + [-1] * (width - len(t[0])) for t in tied], dtype=torch.int64).reshape(-1, width)}
-        self._group_tables = (key, (dna, rna, m), out)
+            raise ValueError(f"conditional_probs: {len(table)} distinct {'class tables' if classes else 'token maps'}; at most 64")
+        width = 2 if not tied else max([len(t[0]) for t in tied_specs], default=0)
+        words = [torch.tensor(nxt + first + tidx, dtype=torch.int32), torch.tensor(w, dtype=torch.float32).view(torch.int32),
+                 torch.tensor([t for C in table for t in C], dtype=torch.int32)]
+        if classes:
+            words.append(torch.tensor([v for row in bias for v in row], dtype=torch.float32).view(torch.int32))
+        out = {"tied": tied_specs, "section": torch.cat(words), "n_tables": len(table),
+               "index": torch.tensor([t[0] + [-1] * (width - len(t[0])) for t in tied_specs], dtype=torch.int64).reshape(-1, width)}
+        self._tie_tables[(tied, classes)] = (key, (dna, rna, m), out)
         return out
 
-    def _conditional_probs_tied(self, fd, method):
-        """conditional_probs(tied=True): the group conditionals (see conditional_probs)."""
-        S_true, mask = fd["S"], fd["mask"]
-        B, L = S_true.shape
-        state_w, M = None, 1
-        if fd.get("state_weights") is not None:
-            fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
-            fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
-            fd_chk.pop("S_forced", None)
-            state_w, M, L, _, _ = self._states_arguments(fd_chk)
-        grp = self._group_conditional_arguments(fd, B, L, state_w)
-        if grp is None:
-            return self.conditional_probs(fd, method)
-        cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
-        if method == "cone" and not cone_ok:
-            raise NotImplementedError("conditional_probs(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
-                                      "use method='dense'")
-        use_cone = method == "cone" or (method == "auto" and cone_ok)
-        _require_device(fd["X"], "X")
-        dev, Lb, n_dec, N = S_true.device, hip.lib(), len(self.decoder_layers), M * L
-        K = int(min(self.k_neighbors, L))
-        ws = None
-        # The tables go up BEFORE the encoder is enqueued (a host-to-device copy waits for the stream), page-locked once with the cached tables
-        for key in ("section", "groups"):
-            if not grp[key].is_pinned():
-                grp[key] = grp[key].pin_memory()
-        if use_cone:
-            section, n_maps = grp["section"], grp["n_maps"]
-            ws = torch.empty(Lb.namp_loo_groups_workspace_bytes(1, N, K, n_dec, n_maps), dtype=torch.uint8, device=dev)
-            off = Lb.namp_loo_groups_offset(1, N, K, n_dec)
-            ws[off:off + 4 * section.numel()].view(torch.int32).copy_(section, non_blocking=True)
-        groups_dev = grp["groups"].to(dev, non_blocking=True)
-        o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1] if state_w is not None else fd["randn"])
-        fd_enc = fd
-        if state_w is not None:
-            fd_enc = dict(fd)
-            for k in self._STATE_SHARED:
-                fd_enc[k] = fd[k].expand(M, L)
-        V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
-        h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
-        self._check_tokens(S_true)
-        o.wait()
-        rank = o.rank[:1]
-        out = {"S": S_true, "decoding_order": o.order[0]}
-        if use_cone:
-            W = self._weights()
-            # the M states as ONE complex of M * L residues: the block-diagonal flattened graph (DESIGN.md 5.6); ranks repeat per block
-            E_f = E_idx if M == 1 else _i32(E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).contiguous()
-            rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
-            S32, m32, r32 = _i32(rep(self._as(S_true, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
-            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
-            hip.check(Lb.namp_loo_groups(grp["n_maps"]), "loo_groups")          # the NEXT namp_decoder_loo call reads the section
-            counts = torch.empty(2, dtype=torch.int32, device=dev)
-            log_probs = torch.empty(1, N, self.num_letters, device=dev)
-            hip.check(Lb.namp_decoder_loo(W.model(), h_V.data_ptr(), h_E.data_ptr(), E_f.data_ptr(), S32.data_ptr(), m32.data_ptr(),
-                                          r32.data_ptr(), log_probs.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), 1, N, K,
-                                          hip.current_stream()), "decoder_loo")
-            out["cone_items"] = counts
-        else:
-            log_probs = torch.empty(M, L, self.num_letters, device=dev)
-            chunk = max(1, self.loo_dense_tokens // L)
-            for b in range(M):
-                for i0 in range(0, L, chunk):
-                    i1 = min(L, i0 + chunk)
-                    n = i1 - i0
-                    ranks = leave_one_out_ranks(rank, i0, i1)[0]
-                    lp = self.decode_graph(h_V[b:b + 1], h_E[b:b + 1], E_idx[b:b + 1].long(), S_true.expand(n, L), mask.expand(n, L), ranks)
-                    ar = torch.arange(n, device=dev)
-                    log_probs[b, i0:i1] = lp[ar, i0 + ar]
-            log_probs = log_probs.view(1, N, self.num_letters)
-            self._group_conditionals_by_sampling(fd, o.order[0], grp, log_probs, state_w)
-        lead = groups_dev[:, 0] if groups_dev.numel() else groups_dev.reshape(-1)
-        out.update(log_probs=log_probs[:, :L], groups=groups_dev, group_log_probs=log_probs[0, lead])
-        return out
-
-    def _group_conditionals_by_sampling(self, fd, order0, grp, log_probs, state_w, classes=False):
-        """The slow route of the group conditionals: per tied group ONE teacher-forced design call — chain_mask all ones, a randn whose
-        sort is score()'s order with the group's residues moved to the end in listed order, T = 1, zero bias, the group as the call's
-        only symmetry group (with its maps) — whose member rows are combined into the group's rows of log_probs [1, M * L, vocab] (in place)."""
+    def _tied_conditionals_by_sampling(self, fd, order0, ties, log_probs, tied, classes):
+        """The slow route of the tied conditionals: per tie ONE teacher-forced design call — chain_mask all ones, a randn whose sort is
+        score()'s order with the tie's residues moved to the end in listed order, T = 1, zero bias; a base pair of a tied=False call as
+        the call's only pair, anything else as its only symmetry group (with its maps) — whose member rows are combined into the tie's
+        rows of log_probs [1, M * L, vocab] (in place).  Returns the class rows with classes, else []."""
         S_true, mask = fd["S"], fd["mask"]
         L = S_true.shape[1]
         dev = log_probs.device
@@ -1231,7 +1221,8 @@ class ProteinMPNN(nn.Module):
         pos = torch.arange(1, L + 1, dtype=torch.float32, device=dev)
         ident = list(range(self.num_letters))
         class_rows = []
-        for (flat, fw, fm, *cb), (g, gw, gm, *_) in zip(grp["tied"], grp["base"]):
+        for flat, fw, ft, gb, gw in ties["tied"]:
+            g, gm = flat[:len(gw)], ft[:len(gw)]               # the members in [0, L): state 0's
             g_t = torch.tensor(g, device=dev)
             rest = order0[~torch.isin(order0, g_t)]
             order = torch.cat((rest, g_t))
@@ -1239,7 +1230,9 @@ class ProteinMPNN(nn.Module):
             randn[order] = pos
             randn = torch.where(mask[0] != 0, randn, randn * 1e4)          # (a masked residue's sort key is 1e-4 |randn|: its place again)
             one = dict(keep, chain_mask=ones, randn=randn[None], batch_size=1, temperature=1.0, bias=bias, S_forced=S_true)
-            if len(g) > 1:
+            if not tied and not classes:
+                one.update(paired_residues=[tuple(g)], paired_weights=tuple(gw))
+            elif len(g) > 1:
                 one.update(symmetry_residues=[g], symmetry_weights=[gw])
                 if not classes and any(list(P) != ident for P in gm):    # (the members' own rows do not depend on the maps)
                     one["symmetry_token_maps"] = [gm]
@@ -1250,11 +1243,11 @@ class ProteinMPNN(nn.Module):
                 raise RuntimeError(f"conditional_probs: the design call of group {g} did not decode it last")
             lp = got["log_probs"].reshape(-1, self.num_letters)             # [M * L, vocab]
             if classes:
-                rows, clp = self._class_combine(lp[flat], fw, fm, cb[0])
+                rows, clp = self._class_combine(lp[flat], fw, ft, gb)
                 log_probs[0, flat] = rows
                 class_rows.append(clp)
                 continue
-            maps_t = [torch.tensor(P, device=dev) for P in fm]
+            maps_t = [torch.tensor(P, device=dev) for P in ft]
             total = None
             for r, wr, P in zip(flat, fw, maps_t):
                 total = wr * lp[r][P] if total is None else total + wr * lp[r][P]
@@ -1280,283 +1273,6 @@ class ProteinMPNN(nn.Module):
         tok = torch.arange(vocab, device=dev)
         rows = [torch.logsumexp(torch.where((t[:, None] == tok[None, :]) & have[:, None], clp[:, None], neg[:, None]), 0) for t in T]
         return torch.stack(rows), torch.where(have, clp, neg)
-
-    def _class_conditional_arguments(self, fd, B, L, state_w, tied):
-        """The tied pairs (tied=False) or groups (tied=True) of a conditional_probs(classes=True) call, spoken in pair classes -> None
-        with nothing to tie, else {"tied": [(members, weights, class tables, class bias)] what the device ties, in flat indices,
-        "base": the same per group in [0, L) without the state weight (the slow route), "groups": int64 [n, max_size] padded with -1
-        (tied=False: [n, 2]), "section": the int32 input section of the workspace (include/namp.h: partner / next, first, table_idx,
-        weight bits, tables, bias bits; told apart by (table, bias)), "n_tables"}.  The refusals are those of the classes=False call."""
-        pairs, sym = fd.get("paired_residues"), fd.get("symmetry_residues")
-        pairs = None if pairs is None or len(pairs) == 0 else pairs
-        sym = None if sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0) else sym
-        if not tied:
-            if pairs is None:
-                return None
-            if sym is not None:
-                raise NotImplementedError("conditional_probs: paired_residues together with symmetry_residues is not supported")
-            if fd.get("state_weights") is not None:
-                raise NotImplementedError("conditional_probs: paired_residues together with state_weights is not supported")
-            if B != 1:
-                raise ValueError("paired_residues expect one input complex (B == 1)")
-        else:
-            if pairs is None and sym is None and state_w is None:
-                return None
-            if B != 1:
-                raise ValueError("tied groups expect one input complex (B == 1)")
-        if self.restype_to_int is None:
-            raise ValueError("paired_residues / tied groups need the model's restype_to_int")
-        to_list = lambda v: v.detach().reshape(-1).tolist() if torch.is_tensor(v) else (list(v) if hasattr(v, "__len__") else v)
-        wobble, wobble_bias = to_list(fd.get("paired_wobble")), to_list(fd.get("paired_wobble_bias"))
-        n_pairs = 0 if pairs is None else len(pairs)
-        for v, what in ((wobble, "paired_wobble"), (wobble_bias, "paired_wobble_bias")):
-            if isinstance(v, list) and len(v) != n_pairs:
-                raise ValueError(f"{what} has {len(v)} entries for {n_pairs} pairs")
-        if (any(wobble) if isinstance(wobble, list) else bool(wobble)) and n_pairs == 0:
-            raise ValueError("paired_wobble needs paired_residues")
-        m = self._host_list(fd["mask"], "mask")
-        dna = rna = None
-        if pairs is not None:
-            dna, rna = self._host_list(fd["dna_mask"], "dna_mask"), self._host_list(fd["rna_mask"], "rna_mask")
-        # the tables of the last call are kept as without classes, keyed on `classes`, the wobble flags and the biases as well — in slots
-        # of their own beside _pair_tables / _group_tables: a specificity profile alternates the classes call with the canonical one
-        # on the same resident feature_dict, and in one slot each of the two would rebuild and page-lock its tables on every call
-        as_list = lambda v: v.tolist() if hasattr(v, "tolist") else v
-        listed = lambda v: None if v is None else [[as_list(x) for x in g] if hasattr(g, "__len__") else g for g in v]
-        key = ("classes", tied, None if pairs is None else [(int(a), int(b)) for a, b in pairs], as_list(fd.get("paired_weights")),
-               None if sym is None else [[int(r) for r in g] for g in sym], listed(fd.get("symmetry_weights")) if sym is not None else None,
-               state_w, wobble, wobble_bias, fd.get("symmetry_token_maps") is None)
-        last = getattr(self, "_group_class_tables" if tied else "_pair_class_tables", None)
-        if last is not None and key[-1] and last[0] == key and all(x is y for x, y in zip(last[1], (dna, rna, m))):
-            return last[2]
-        polymer = None
-        if pairs is not None:
-            polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
-            for pr in pairs:                              # (a masked residue may come without a polymer flag: its partner's stands in, as in sample())
-                for r, q in ((int(pr[0]), int(pr[1])), (int(pr[1]), int(pr[0]))):
-                    if 0 <= r < L and 0 <= q < L and not m[r] and polymer[r] == 0 and polymer[q] in (1, 2) \
-                            and not self._host_list(fd["protein_mask"], "protein_mask")[r]:
-                        polymer[r] = polymer[q]
-        groups, weights, gtabs, _, gbias = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, None, sym,
-                                                         fd.get("symmetry_weights") if sym is not None else None,
-                                                         fd.get("symmetry_token_maps"), False if wobble is None else wobble, wobble_bias)
-        members = [r for g in groups for r in g]
-        if len(set(members)) != len(members):
-            raise ValueError("conditional_probs: the tied groups must be disjoint")
-        M, sw = (1, [1.0]) if state_w is None else (len(state_w), state_w)
-        V = len(spec.RESTYPES)
-        ident, zero = list(range(V)) + [-1] * (spec.N_CLASS_LANES - V), [0.0] * spec.N_CLASS_LANES
-        if state_w is not None:                            # every residue is a group across the states
-            tied_res = set(members)
-            for i in range(L):
-                if i not in tied_res:
-                    groups.append([i]); weights.append([1.0]); gtabs.append([ident]); gbias.append(zero)
-        N = M * L
-        nxt, first, tidx, w = [-1] * N, [0] * N, [0] * N, [1.0] * N
-        table, bias, index = [ident], [zero], {(tuple(ident), tuple(zero)): 0}
-        tied_specs, base = [], []
-        for g, gw, gt, gb in zip(groups, weights, gtabs, gbias):
-            if len(g) * M > hip.loo_group_max():
-                raise ValueError(f"conditional_probs: the group of residue {g[0]} has {len(g) * M} members; at most {hip.loo_group_max()} are tied")
-            if len(g) * M < 2:
-                continue
-            flat = [r + s_ * L for s_ in range(M) for r in g]                 # state-major, as _sample_states lists them
-            fw = [sw[s_] * float(v) for s_ in range(M) for v in gw]
-            ft = [C for s_ in range(M) for C in gt]
-            for t, (r, wr, C) in enumerate(zip(flat, fw, ft)):
-                k = index.get((tuple(C), tuple(gb)))
-                if k is None:
-                    k = index[(tuple(C), tuple(gb))] = len(table)
-                    table.append(list(C)); bias.append([float(v) for v in gb])
-                nxt[r], tidx[r], w[r] = flat[(t + 1) % len(flat)], k, wr
-            first[flat[0]] = 1
-            if all(m[r] for r in g):                       # the device's rule: a pair / group with a masked member is not tied
-                tied_specs.append((flat, fw, [list(C) for C in ft], [float(v) for v in gb]))
-                base.append((list(g), [float(v) for v in gw], [list(C) for C in gt], [float(v) for v in gb]))
-        if len(table) > 64:
-            raise ValueError(f"conditional_probs: {len(table)} distinct class tables; at most 64")
-        width = 2 if not tied else max([len(t[0]) for t in tied_specs], default=0)
-        section = torch.cat((torch.tensor(nxt + first + tidx, dtype=torch.int32), torch.tensor(w, dtype=torch.float32).view(torch.int32),
-                             torch.tensor([t for C in table for t in C], dtype=torch.int32),
-                             torch.tensor([v for row in bias for v in row], dtype=torch.float32).view(torch.int32)))
-        out = {"tied": tied_specs, "base": base, "section": section, "n_tables": len(table),
-               "groups": torch.tensor([t[0] + [-1] * (width - len(t[0])) for t in tied_specs], dtype=torch.int64).reshape(-1, width)}
-        setattr(self, "_group_class_tables" if tied else "_pair_class_tables", (key, (dna, rna, m), out))
-        return out
-
-    def _conditional_probs_classes(self, fd, method, tied):
-        """conditional_probs(classes=True): the pair (tied=False) and group (tied=True) conditionals in pair classes (see conditional_probs)."""
-        S_true, mask = fd["S"], fd["mask"]
-        B, L = S_true.shape
-        state_w, M = None, 1
-        if tied and fd.get("state_weights") is not None:
-            fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
-            fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
-            fd_chk.pop("S_forced", None)
-            state_w, M, L, _, _ = self._states_arguments(fd_chk)
-        grp = self._class_conditional_arguments(fd, B, L, state_w, tied)
-        if grp is None:
-            return self.conditional_probs(fd, method)
-        cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
-        if method == "cone" and not cone_ok:
-            raise NotImplementedError("conditional_probs(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
-                                      "use method='dense'")
-        use_cone = method == "cone" or (method == "auto" and cone_ok)
-        _require_device(fd["X"], "X")
-        dev, Lb, n_dec, N = S_true.device, hip.lib(), len(self.decoder_layers), M * L
-        K = int(min(self.k_neighbors, L))
-        ws = None
-        # The tables go up BEFORE the encoder is enqueued (a host-to-device copy waits for the stream), page-locked once with the cached tables
-        for key in ("section", "groups"):
-            if not grp[key].is_pinned():
-                grp[key] = grp[key].pin_memory()
-        n_tab = grp["n_tables"]
-        if use_cone:
-            section = grp["section"]
-            ws = torch.empty(Lb.namp_loo_classes_workspace_bytes(1, N, K, n_dec, n_tab, int(tied)), dtype=torch.uint8, device=dev)
-            off = Lb.namp_loo_groups_offset(1, N, K, n_dec)
-            ws[off:off + 4 * section.numel()].view(torch.int32).copy_(section, non_blocking=True)
-        groups_dev = grp["groups"].to(dev, non_blocking=True)
-        o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1] if state_w is not None else fd["randn"])
-        if tied:
-            fd_enc = fd
-            if state_w is not None:
-                fd_enc = dict(fd)
-                for k in self._STATE_SHARED:
-                    fd_enc[k] = fd[k].expand(M, L)
-            V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
-            h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
-        else:
-            h_V, h_E, E_idx = self.encode(fd, order=o)
-        self._check_tokens(S_true)
-        o.wait()
-        rank = o.rank[:1]
-        out = {"S": S_true, "decoding_order": o.order[0]}
-        lead = groups_dev[:, 0] if groups_dev.numel() else groups_dev.reshape(-1)
-        if use_cone:
-            W = self._weights()
-            E_f = E_idx if M == 1 else _i32(E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).contiguous()
-            rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
-            E_f, S32, m32, r32 = _i32(E_f), _i32(rep(self._as(S_true, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
-            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
-            hip.check(Lb.namp_loo_classes(n_tab, spec.N_CLASSES, int(tied)), "loo_classes")   # the NEXT namp_decoder_loo call reads the section
-            counts = torch.empty(2, dtype=torch.int32, device=dev)
-            log_probs = torch.empty(1, N, self.num_letters, device=dev)
-            hip.check(Lb.namp_decoder_loo(W.model(), h_V.data_ptr(), h_E.data_ptr(), E_f.data_ptr(), S32.data_ptr(), m32.data_ptr(),
-                                          r32.data_ptr(), log_probs.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), 1, N, K,
-                                          hip.current_stream()), "decoder_loo")
-            out["cone_items"] = counts
-            c_off = Lb.namp_loo_classes_out_offset(1, N, K, n_dec, n_tab, int(tied))
-            class_rows = ws[c_off:c_off + 4 * spec.N_CLASS_LANES * N].view(torch.float32).view(N, spec.N_CLASS_LANES)[lead]
-        else:
-            log_probs = torch.empty(M, L, self.num_letters, device=dev)
-            chunk = max(1, self.loo_dense_tokens // L)
-            for b in range(M):
-                for i0 in range(0, L, chunk):
-                    i1 = min(L, i0 + chunk)
-                    n = i1 - i0
-                    ranks = leave_one_out_ranks(rank, i0, i1)[0]
-                    lp = self.decode_graph(h_V[b:b + 1], h_E[b:b + 1], E_idx[b:b + 1].long(), S_true.expand(n, L), mask.expand(n, L), ranks)
-                    ar = torch.arange(n, device=dev)
-                    log_probs[b, i0:i1] = lp[ar, i0 + ar]
-            log_probs = log_probs.view(1, N, self.num_letters)
-            rows = self._group_conditionals_by_sampling(fd, o.order[0], grp, log_probs, state_w, classes=True)
-            class_rows = torch.stack(rows) if rows else torch.zeros(0, spec.N_CLASS_LANES, device=dev)
-        what = "group" if tied else "pair"
-        out.update({"log_probs": log_probs[:, :L], what + "s": groups_dev, what + "_log_probs": log_probs[0, lead],
-                    what + "_class_log_probs": class_rows})
-        return out
-
-    def _pair_conditional_arguments(self, fd, B, L):
-        """The base pairs of a conditional_probs() call -> None without pairs, else {"tied": [(i, j, w_i, w_j, P_i, P_j)] the pairs the
-        device ties (both members unmasked), "pairs": int64 [n, 2] of those, "section": the int32 input section of the workspace
-        (include/namp.h: partner, first, map_idx, weight bits, maps), "n_maps"}."""
-        pairs = fd.get("paired_residues")
-        if pairs is None or len(pairs) == 0:
-            return None
-        wobble = fd.get("paired_wobble")
-        if wobble is not None:
-            wobble = wobble.detach().reshape(-1).tolist() if torch.is_tensor(wobble) else wobble
-            if any(wobble) if hasattr(wobble, "__len__") else bool(wobble):
-                raise NotImplementedError("conditional_probs: paired_wobble is not supported; pair classes (DESIGN.md 5.8) are the follow-up")
-        sym = fd.get("symmetry_residues")
-        if sym is not None and not (len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0)):
-            raise NotImplementedError("conditional_probs: paired_residues together with symmetry_residues is not supported")
-        if fd.get("state_weights") is not None:
-            raise NotImplementedError("conditional_probs: paired_residues together with state_weights is not supported")
-        if B != 1:
-            raise ValueError("paired_residues expect one input complex (B == 1)")
-        if self.restype_to_int is None:
-            raise ValueError("paired_residues need the model's restype_to_int")
-        dna, rna = self._host_list(fd["dna_mask"], "dna_mask"), self._host_list(fd["rna_mask"], "rna_mask")
-        m = self._host_list(fd["mask"], "mask")
-        # the tables of the last call are kept: a resident feature_dict is scored many times (the host lists above are the SAME objects
-        # while their tensors are unchanged; pairs and weights are compared by value)
-        pw = fd.get("paired_weights")
-        pw = pw.tolist() if hasattr(pw, "tolist") else pw
-        key = ([(int(a), int(b)) for a, b in pairs], pw, fd.get("symmetry_token_maps") is None)
-        last = getattr(self, "_pair_tables", None)
-        if last is not None and key[2] and last[0] == key and all(x is y for x, y in zip(last[1], (dna, rna, m))):
-            return last[2]
-        polymer = [1 if d else (2 if r else 0) for d, r in zip(dna, rna)]
-        for pr in pairs:                                  # (a masked residue may come without a polymer flag: its partner's stands in, as in sample())
-            for r, q in ((int(pr[0]), int(pr[1])), (int(pr[1]), int(pr[0]))):
-                if 0 <= r < L and 0 <= q < L and not m[r] and polymer[r] == 0 and polymer[q] in (1, 2) \
-                        and not self._host_list(fd["protein_mask"], "protein_mask")[r]:
-                    polymer[r] = polymer[q]
-        groups, weights, gmaps, _ = mapped_groups(L, self.restype_to_int, pairs, fd.get("paired_weights"), polymer, None,
-                                                  None, None, fd.get("symmetry_token_maps"))
-        partner, first, midx, w = [-1] * L, [0] * L, [0] * L, [1.0] * L
-        table, index = [list(range(64))], {tuple(range(64)): 0}
-        tied = []
-        for g, gw, gm in zip(groups, weights, gmaps):
-            (i, j), Ps = g, [list(P) + list(range(len(P), 64)) for P in gm]
-            partner[i], partner[j], first[i] = j, i, 1
-            for r, wr, P in zip(g, gw, Ps):
-                k = index.get(tuple(P))
-                if k is None:
-                    k = index[tuple(P)] = len(table)
-                    table.append(P)
-                midx[r], w[r] = k, wr
-            if m[i] and m[j]:                             # the device's rule: a pair with a masked member is not tied
-                tied.append((i, j, gw[0], gw[1], gm[0], gm[1]))
-        section = torch.cat((torch.tensor(partner + first + midx, dtype=torch.int32), torch.tensor(w, dtype=torch.float32).view(torch.int32),
-                             torch.tensor([t for P in table for t in P], dtype=torch.int32)))
-        out = {"tied": tied, "pairs": torch.tensor([(t[0], t[1]) for t in tied], dtype=torch.int64).reshape(-1, 2),
-               "section": section, "n_maps": len(table)}
-        self._pair_tables = (key, (dna, rna, m), out)
-        return out
-
-    def _pair_conditionals_by_sampling(self, fd, order0, paired, log_probs):
-        """The slow route of the pair conditionals: per tied pair ONE teacher-forced design call — chain_mask all ones, a randn whose
-        sort is score()'s order with the pair moved to the end as ..., i, j, T = 1, zero bias — whose two log_probs rows are combined
-        into the pair's rows of log_probs [1, L, vocab] (in place)."""
-        S_true, mask = fd["S"], fd["mask"]
-        L = S_true.shape[1]
-        dev = log_probs.device
-        keep = {k: v for k, v in fd.items() if k not in ("paired_residues", "paired_weights", "paired_wobble", "paired_wobble_bias",
-                                                          "symmetry_residues", "symmetry_weights", "symmetry_token_maps", "pair_bias", "pair_terms",
-                                                          "S_forced")}
-        ones = torch.ones_like(fd["chain_mask"])
-        bias = torch.zeros(1, L, self.num_letters, device=dev)
-        pos = torch.arange(1, L + 1, dtype=torch.float32, device=dev)
-        for i, j, wi, wj, Pi, Pj in paired["tied"]:
-            rest = order0[(order0 != i) & (order0 != j)]
-            order = torch.cat((rest, torch.tensor([i, j], device=dev)))
-            randn = torch.empty(L, device=dev)
-            randn[order] = pos
-            randn = torch.where(mask[0] != 0, randn, randn * 1e4)          # (a masked residue's sort key is 1e-4 |randn|: its place again)
-            one = dict(keep, chain_mask=ones, randn=randn[None], batch_size=1, temperature=1.0, bias=bias, S_forced=S_true,
-                       paired_residues=[(i, j)], paired_weights=(wi, wj))
-            got = self._sample(one, self.sample_level_walk)
-            if not torch.equal(got["decoding_order"][0], order):
-                raise RuntimeError(f"conditional_probs: the design call of pair ({i}, {j}) did not decode it last")
-            lp = got["log_probs"][0]
-            Pi_t, Pj_t = torch.tensor(Pi, device=dev), torch.tensor(Pj, device=dev)
-            total = wi * lp[i][Pi_t] + wj * lp[j][Pj_t]
-            row = torch.log_softmax(total, -1)
-            log_probs[0, i, Pi_t] = row
-            log_probs[0, j, Pj_t] = row
 
     def forward(self, feature_dict, decoding_randn=None):
         """Training-copy surface (na_model_utils.py:589-646): feature_dict -> (log_probs, probs).

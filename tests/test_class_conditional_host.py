@@ -162,8 +162,8 @@ def test_class_tables_of_the_host_section():
     m = make_model()
     fd = C.case_inputs("l48_k16")
     L = fd["S"].shape[1]
-    a = m._class_conditional_arguments(fd, 1, L, None, False)
-    assert a is m._class_conditional_arguments(fd, 1, L, None, False)                        # served from the cache
+    a = m._conditional_arguments(fd, 1, L, None, False, True)
+    assert a is m._conditional_arguments(fd, 1, L, None, False, True)                        # served from the cache
     n = a["n_tables"]
     assert n == 5 and a["section"].numel() == 4 * L + 2 * 64 * n                             # identity, first / second, first / second with the bias
     tabs = a["section"][4 * L:4 * L + 64 * n].view(n, 64)
@@ -172,20 +172,20 @@ def test_class_tables_of_the_host_section():
     i, j = fd["paired_residues"][2]
     ti, tj = int(a["section"][2 * L + i]), int(a["section"][2 * L + j])
     assert bias[tj, C.GU] == bias[tj, C.UG] == 1.5 and bias[ti, C.GU] == 1.5 and float(bias[tj, :V].abs().max()) == 0
-    assert a["groups"].tolist() == [list(p) for p in fd["paired_residues"]]
-    b = m._class_conditional_arguments(dict(fd, paired_wobble_bias=[0.0, 0.0, 0.5, 0.0, 0.0]), 1, L, None, False)
+    assert a["index"].tolist() == [list(p) for p in fd["paired_residues"]]
+    b = m._conditional_arguments(dict(fd, paired_wobble_bias=[0.0, 0.0, 0.5, 0.0, 0.0]), 1, L, None, False, True)
     assert b is not a and float(b["section"][4 * L + 64 * n:].view(torch.float32).max()) == 0.5
-    c = m._class_conditional_arguments(dict(fd, paired_wobble=False), 1, L, None, False)
+    c = m._conditional_arguments(dict(fd, paired_wobble=False), 1, L, None, False, True)
     assert c["n_tables"] == 2 and bool((c["section"][4 * L:4 * L + 128].view(2, 64)[:, V:] == -1).all())
-    g = m._class_conditional_arguments(fd, 1, L, None, True)
+    g = m._conditional_arguments(fd, 1, L, None, True, True)
     assert g is not a and torch.equal(g["section"], a["section"])                            # a pair's successor cycle IS its partner table
     plain = {k: v for k, v in fd.items() if k not in ("paired_wobble", "paired_wobble_bias")}
-    p = m._pair_conditional_arguments(plain, 1, L)
-    assert p["section"].numel() == 4 * L + 64 * p["n_maps"] and "base" not in p
-    a2 = m._class_conditional_arguments(fd, 1, L, None, False)
+    p = m._conditional_arguments(plain, 1, L)
+    assert p["section"].numel() == 4 * L + 64 * p["n_tables"] and "base" not in p
+    a2 = m._conditional_arguments(fd, 1, L, None, False, True)
     assert a2 is not p and torch.equal(a2["section"], a["section"])
-    assert m._pair_conditional_arguments(plain, 1, L) is p and m._class_conditional_arguments(fd, 1, L, None, False) is a2      # neither evicts the other
-    assert m._class_conditional_arguments(fd, 1, L, None, True) is g
+    assert m._conditional_arguments(plain, 1, L) is p and m._conditional_arguments(fd, 1, L, None, False, True) is a2      # neither evicts the other
+    assert m._conditional_arguments(fd, 1, L, None, True, True) is g
 
 
 def test_class_entry_points_validate_without_a_gpu():

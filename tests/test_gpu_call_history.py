@@ -192,8 +192,8 @@ def test_in_place_edits_reach_the_caches(weights_np):
     pfd = dict(fd, paired_residues=pairs)
     c0 = step(m, cone, pfd, "paired cone, first")
     assert c0["pairs"].shape[0] == 20
-    tables, lists = m._pair_tables[2], {k: m._tokens_ok[("host", k)][2] for k in ("dna_mask", "rna_mask", "mask")}
-    assert step(m, cone, pfd, "paired cone, unchanged")["pairs"].shape[0] == 20 and m._pair_tables[2] is tables     # (the cache does hit)
+    tables, lists = m._tie_tables[(False, False)][2], {k: m._tokens_ok[("host", k)][2] for k in ("dna_mask", "rna_mask", "mask")}
+    assert step(m, cone, pfd, "paired cone, unchanged")["pairs"].shape[0] == 20 and m._tie_tables[(False, False)][2] is tables     # (the cache does hit)
     i, j = pairs[4]
     pfd["mask"][0, i] = 0                                                    # this pair is no longer tied
     a, _ = pairs[9]                                                          # a DNA member becomes an RNA residue: another token map
@@ -201,7 +201,7 @@ def test_in_place_edits_reach_the_caches(weights_np):
     pfd["dna_mask"][0, a] = 0
     pfd["rna_mask"][0, a] = 1
     c1 = step(m, cone, pfd, "paired cone after the edits")
-    assert m._pair_tables[2] is not tables
+    assert m._tie_tables[(False, False)][2] is not tables
     assert all(m._tokens_ok[("host", k)][2] is not v for k, v in lists.items())
     assert c1["pairs"].shape[0] == 19 and [i, j] not in c1["pairs"].tolist()
     assert not torch.equal(c1["log_probs"][0, a], c0["log_probs"][0, a])

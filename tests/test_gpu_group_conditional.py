@@ -164,7 +164,8 @@ def test_cone_equals_the_slow_route(weights_np, name, prec):
 @pytest.mark.parametrize("prec", ["x3", "fp32"])
 def test_a_group_of_two_is_the_pair_path_bit_for_bit(weights_np, prec):
     """The pairs of test_gpu_pair_conditional's l48_k16 case with weights (1.0, 0.5): through namp_loo_groups every row and both counts
-    are the bits of namp_loo_pairs."""
+    are the bits of namp_loo_pairs.  The two entry points attach the same tables: what differs is the host route, encode() with
+    tied=False and the featurise-as-states path with tied=True, and the test pins the two against each other."""
     _, fd_cpu, pairs = paired_ref.make_case(L=48, bs=1, T=1.0, n_pairs=5, seed=11, fixed_every=0)
     fd_cpu["paired_weights"] = (1.0, 0.5)
     m = make_model(weights_np, 16, prec)

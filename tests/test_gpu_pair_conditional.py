@@ -221,11 +221,12 @@ def test_pair_conditional_arguments(weights_np):
 
 
 # ---- memory contract of a call with pairs attached ---------------------------------------------------------------------------
-def section_of(N, pairs, weights, maps, n_maps):
-    """The input section of include/namp.h for one complex: partner, first, map_idx, weight bits, maps[n_maps][64] as int32 words."""
+def section_of(N, pairs, weights, maps, n_maps, second=None):
+    """The input section of include/namp.h for one complex: partner, first, map_idx, weight bits, maps[n_maps][64] as int32 words.
+    second: the map index of every pair's second member (default: map 1 where there is one)."""
     partner, first, midx, w = [-1] * N, [0] * N, [0] * N, [1.0] * N
-    for (i, j), (wi, wj) in zip(pairs, weights):
-        partner[i], partner[j], first[i], midx[i], midx[j], w[i], w[j] = j, i, 1, 0, 1 % n_maps, wi, wj
+    for n, ((i, j), (wi, wj)) in enumerate(zip(pairs, weights)):
+        partner[i], partner[j], first[i], midx[i], midx[j], w[i], w[j] = j, i, 1, 0, (1 % n_maps if second is None else second[n]), wi, wj
     return torch.cat((torch.tensor(partner + first + midx, dtype=torch.int32), torch.tensor(w).view(torch.int32),
                       torch.tensor(maps, dtype=torch.int32).reshape(-1)))
 
@@ -236,7 +237,9 @@ def test_memory_contract_with_pairs_attached(weights_np, shape, prec):
     """namp_decoder_loo with pairs attached, under guarded buffers as the contract table's row runs it without: the smallest shape of
     that row (one residue: the tables hold no pair) and the smallest at which a pair exists.  ws is sized by
     namp_loo_pairs_workspace_bytes and pre-filled by the arena; the test writes the input section and finds it unchanged afterwards.
-    A second call with a corrupt partner table (out of range, self, not mutual) returns NAMP_OK and the rows of the unpaired call."""
+    A second call with a corrupt partner table (out of range, self, not mutual) returns NAMP_OK and the rows of the unpaired call.
+    A pair is a group of two, tied where exactly one member carries `first`: a section whose first pair has the flag on neither
+    member, and one with it on both, each return NAMP_OK and give the rows and counts of the call that ties only the second pair."""
     import test_gpu_memory_contract as mc
     from guarded import Arena, run_contract
     env = mc.Env(weights_np)
@@ -292,6 +295,15 @@ def test_memory_contract_with_pairs_attached(weights_np, shape, prec):
         P = torch.tensor(maps[1][:33])
         for i, j in pairs:
             assert torch.equal(lp_pairs[0, i][P], lp_pairs[0, j]) and not torch.equal(lp_pairs[0, i], lp_pairs[0, j])
+        lp_other, c_other = run(section_of(N, pairs[1:], [(1.0, 0.5)], maps, 2))
+        assert not torch.equal(lp_other, lp_pairs) and not torch.equal(lp_other, lp_none)
+        neither, both = good.clone(), good.clone()
+        neither[N + pairs[0][0]] = 0
+        both[N + pairs[0][1]] = 1
+        assert [int(neither[N + r]) for r in pairs[0]] == [0, 0] and [int(both[N + r]) for r in pairs[0]] == [1, 1]
+        for section in (neither, both):
+            lp_flags, c_flags = run(section)
+            assert torch.equal(lp_flags, lp_other) and torch.equal(c_flags, c_other)
     else:
         assert torch.equal(lp_pairs, lp_none) and torch.equal(c_pairs, c_none)
 

@@ -189,7 +189,8 @@ def test_group_entry_points_validate_without_a_gpu():
     off = L.namp_loo_groups_offset(1, 1000, 48, 3)
     assert off == base == L.namp_loo_pairs_offset(1, 1000, 48, 3) and off % 256 == 0
     pair_need = L.namp_loo_pairs_workspace_bytes(1, 1000, 48, 3, 3)
-    assert pair_need + 4 * 48000 <= need < pair_need + 4 * 48000 + 256                       # one row per residue whatever the group size, one [R] table
+    assert pair_need == need                                                                 # a pair is a group of two: one carve
+    assert need - base >= 4 * 48000 + 4 * (4 * 1000 + 3 * 64) + 2 * 1000 + 2 * 2 * 1000 * 128 * 4     # ... with one [R] table, one row per residue whatever the group size
     assert need >= off + 4 * (4 * 1000 + 3 * 64) + 2 * 1000 * 128 * 4
     for args in ((1, 100, 24, 4, 2), (0, 100, 24, 3, 2), (1, 100, 24, 3, 0), (1, 100, 24, 3, 65)):
         assert L.namp_loo_groups_workspace_bytes(*args) == 0, args
@@ -240,11 +241,11 @@ def test_tied_arguments_are_handled_before_any_device_work(weights_np):
     # a call with maps leaves nothing behind that a call without maps on the same resident feature_dict could pick up
     fdm = G.case_inputs("trimer_maps_l24")
     fdn = {k: v for k, v in fdm.items() if k != "symmetry_token_maps"}
-    with_maps = m._group_conditional_arguments(fdm, 1, 24, None)
-    without = m._group_conditional_arguments(fdn, 1, 24, None)
-    assert with_maps["n_maps"] == 2 and without["n_maps"] == 1 and not torch.equal(with_maps["section"], without["section"])
-    assert m._group_conditional_arguments(fdn, 1, 24, None) is without                      # (and the entry without maps is kept)
-    assert m._group_conditional_arguments(fdm, 1, 24, None) is not with_maps
+    with_maps = m._conditional_arguments(fdm, 1, 24, None, True)
+    without = m._conditional_arguments(fdn, 1, 24, None, True)
+    assert with_maps["n_tables"] == 2 and without["n_tables"] == 1 and not torch.equal(with_maps["section"], without["section"])
+    assert m._conditional_arguments(fdn, 1, 24, None, True) is without                      # (and the entry without maps is kept)
+    assert m._conditional_arguments(fdm, 1, 24, None, True) is not with_maps
     # nine states of a pair are 18 members
     fd9 = G.case_inputs("cap_m8_l16")
     fd9 = dict(fd9, X=torch.cat((fd9["X"], fd9["X"][:1])), X_m=torch.cat((fd9["X_m"], fd9["X_m"][:1])), state_weights=[1 / 9] * 9)
@@ -255,17 +256,17 @@ def test_tied_arguments_are_handled_before_any_device_work(weights_np):
         fdc = G.case_inputs(name)
         M = 1 if fdc.get("state_weights") is None else fdc["X"].shape[0]
         L = fdc["S"].shape[1]
-        grp = m._group_conditional_arguments(fdc, 1, L, fdc.get("state_weights"))
+        grp = m._conditional_arguments(fdc, 1, L, fdc.get("state_weights"), True)
         specs = G.group_specs(fdc, spec.restype_to_int())
         assert [t[0] for t in grp["tied"]] == [s[0] for s in specs]
         for t, s in zip(grp["tied"], specs):
             assert np.allclose(t[1], s[1]) and t[2] == s[2]
         N = M * L
         sec = grp["section"]
-        assert sec.numel() == 4 * N + 64 * grp["n_maps"]
+        assert sec.numel() == 4 * N + 64 * grp["n_tables"]
         nxt, first, midx, wts = sec[:N].tolist(), sec[N:2 * N].tolist(), sec[2 * N:3 * N].tolist(), sec[3 * N:4 * N].view(torch.float32).tolist()
         maps = sec[4 * N:].view(-1, 64).tolist()
         for g, gw, gm in specs:
             assert [nxt[r] for r in g] == g[1:] + g[:1] and [first[r] for r in g] == [1] + [0] * (len(g) - 1)
             assert np.allclose([wts[r] for r in g], gw) and [maps[midx[r]][:33] for r in g] == gm
-        assert grp["groups"].shape == (len(specs), max(len(s[0]) for s in specs))
+        assert grp["index"].shape == (len(specs), max(len(s[0]) for s in specs))

@@ -125,7 +125,7 @@ def test_pair_entry_points_validate_without_a_gpu():
     off = L.namp_loo_pairs_offset(1, 1000, 48, 3)
     assert off == base and off % 256 == 0 and L.namp_loo_pairs_offset(1, 97, 32, 3) % 256 == 0
     assert need >= off + 4 * (4 * 1000 + 3 * 64) + 2 * 1000 * 128 * 4                       # the section and the two row buffers
-    assert need - base < (1 << 21)                                                           # residue-sized additions only
+    assert need - base < (1 << 21) + 4 * 48000 + 256                                         # residue-sized additions and one [G*K] int32 table (the group carve)
     assert L.namp_loo_pairs_workspace_bytes(1, 3000, 48, 3, 3) < 3 * need + (1 << 20)        # linear in N
     for args in ((1, 100, 24, 4, 2), (0, 100, 24, 3, 2), (1, 100, 24, 3, 0), (1, 100, 24, 3, 65)):
         assert L.namp_loo_pairs_workspace_bytes(*args) == 0, args
@@ -157,3 +157,31 @@ def test_pair_arguments_are_refused_before_any_device_work(weights_np):
         m.conditional_probs(fd2)
     with pytest.raises(ValueError, match="two pairs"):
         m.conditional_probs(dict(fd, paired_residues=pairs + [(pairs[0][0], 20)]))
+
+
+def test_a_pair_only_call_builds_one_section_through_either_route():
+    """A feature_dict with base pairs alone gives the builder the same input section, number of tables and index of the ties with
+    tied=False and tied=True (a pair's partner table IS its successor cycle), in token maps and in class tables; in token maps it is
+    the section that section_of of the GPU pair tests lays out independently from the same pairs, weights and maps."""
+    from na_mpnn_amd.model import ProteinMPNN
+    import class_loo_ref
+    from test_gpu_pair_conditional import section_of
+    m = ProteinMPNN(num_letters=33, vocab=33, k_neighbors=K, atom_dict=spec.atom_dict(), restype_to_int=spec.restype_to_int(),
+                    polytype_to_int=spec.polytype_to_int())
+    _, fd, pairs = paired_ref.make_case(L=48, bs=1, T=1.0, n_pairs=5, seed=11, fixed_every=0)
+    fd = dict(fd, paired_weights=(1.0, 0.5))
+    for classes, fdc in ((False, fd), (True, class_loo_ref.case_inputs("l48_k16"))):
+        a, b = m._conditional_arguments(fdc, 1, 48, None, False, classes), m._conditional_arguments(fdc, 1, 48, None, True, classes)
+        assert a is not b and a["n_tables"] == b["n_tables"]
+        assert a["section"].dtype == torch.int32 and torch.equal(a["section"], b["section"])
+        assert a["index"].dtype == torch.int64 and torch.equal(a["index"], b["index"])
+        assert a["index"].tolist() == [list(p) for p in fdc["paired_residues"]]
+    # the first member reads through the identity, the second through the Watson-Crick map of the pair's kind (RNA with RNA, DNA with
+    # DNA: "same"; DNA with RNA: "cross"), the maps numbered as the pairs first need them
+    a = m._conditional_arguments(fd, 1, 48)
+    dna = fd["dna_mask"][0].tolist()
+    kinds = ["same" if dna[i] == dna[j] else "cross" for i, j in pairs]
+    assert kinds == ["same", "cross", "cross", "same", "same"]
+    maps = [list(range(64))] + [spec.token_map(spec.restype_to_int(), kind) + list(range(33, 64)) for kind in ("same", "cross")]
+    want = section_of(48, pairs, [(1.0, 0.5)] * 5, maps, 3, second=[1 + ("same", "cross").index(kind) for kind in kinds])
+    assert a["n_tables"] == 3 and torch.equal(a["section"], want)

@@ -878,6 +878,42 @@ size_t namp_loo_classes_workspace_bytes(int B, int N, int K, int n_dec, int n_ta
 size_t namp_loo_classes_out_offset(int B, int N, int K, int n_dec, int n_tables, int groups);
 int namp_loo_classes(int n_tables, int n_classes, int groups);
 
+/* ---- library scoring: the token log-probs of n candidate sequences on one complex, riding on namp_decoder_fwd ----------------
+ * Candidates that differ from S at n_var listed positions only share the decoder states of every row no varying token reaches.
+ * With rank the decoding ranks of score(), var the listed positions and act_0 = 0,
+ *     act_l[i] = mask[i] and (act_{l-1}[i] or exists k: rank[E_idx[i,k]] < rank[i] and (var[E_idx[i,k]] or act_{l-1}[E_idx[i,k]]))
+ * for l = 1..3 (model_utils.py:391-421; the neighbour's own mask is not consulted), and row i's log-prob row depends on the candidate
+ * iff act_3[i].  An attached namp_decoder_fwd call (B_dec = B_enc = 1; mask required, logits and h_V_dec NULL) runs the base stream
+ * once — log_probs [N, vocab] is what the unattached call writes for S, up to the summation order of its fused launches —, plans
+ * the three row lists U_l = act_l + var (ascending; a listed position outside act_l is evaluated from base inputs, so that one
+ * projection path writes everything a later layer reads per candidate), and evaluates per layer the items (candidate, row of U_l)
+ * through dec_items_kernel (namp_loo.h, unchanged): a backward edge to a neighbour in U_{l-1} (U_0 = var) reads the override row
+ * layer l-1's items projected for (candidate, neighbour), every other edge the base tables.  Behind layer 3 a head applies W_out and
+ * log_softmax to the items' states and keeps the candidate's own entry; all other entries are base_log_probs[i][token of i].
+ * No entry point takes a pointer.  With the same eight ints (N, K, n_dec, n_var, n_chunk, rows1, rows2, rows3),
+ *     namp_library_workspace_bytes(...)   what the attached call requires of ws_bytes (NAMP_EINVAL if smaller); 0 where unsupported:
+ *                                         n_dec != 3, K > N or NAMP_MAX_K, n_var outside [0, N], rows_l outside [0, N],
+ *                                         max(n_chunk, 1) * N >= 2^28
+ *     namp_library_in_offset(...)         byte offset in ws of the caller-filled INPUT SECTION (256-byte aligned), int32 words
+ *                                             positions[n_var]            residue of every column, ascending and unique
+ *                                             tokens[n_chunk][n_var]      the candidates' tokens at those residues
+ *     namp_library_out_offset(...)        byte offset in ws of the library-written OUTPUT SECTION (256-byte aligned)
+ *                                             int32 [64]                  words 0-2 |act_1..3|, 3-5 |U_1..3|, 6-8 min(|U_l|, rows_l)
+ *                                             float [n_chunk][N]          token_log_probs
+ * and namp_library(n_var, n_chunk, rows1, rows2, rows3) (all >= 0, NAMP_EINVAL otherwise and nothing stays attached) attaches them to
+ * the calling thread's NEXT namp_decoder_fwd call, which clears the attachment whether it succeeds or not.  rows_l is the capacity of
+ * list l the workspace is sized for: a caller attaches once with n_chunk = 0 (plan and counts only; rows_l = 0), reads words 3-5
+ * back, and sizes every chunk by them.  Three decoder layers of one precision, split-bf16 or exact fp32 (NAMP_EINVAL otherwise).
+ * The sections are device data: positions are clamped to [0, N) and tokens to [0, vocab); of positions that clamp to one residue the
+ * LAST listed column is the residue's; a row beyond rows_l is treated as base (not per candidate): a malformed section gives a
+ * defined result and nothing outside ws and log_probs is written.  The input section is not written.  Separate launches on `stream`,
+ * plain stores, every item owns its rows: two calls give identical bits.  Without an attachment namp_decoder_fwd is unchanged, bit
+ * for bit. */
+size_t namp_library_workspace_bytes(int N, int K, int n_dec, int n_var, int n_chunk, int rows1, int rows2, int rows3);
+size_t namp_library_in_offset(int N, int K, int n_dec, int n_var, int n_chunk, int rows1, int rows2, int rows3);
+size_t namp_library_out_offset(int N, int K, int n_dec, int n_var, int n_chunk, int rows1, int rows2, int rows3);
+int namp_library(int n_var, int n_chunk, int rows1, int rows2, int rows3);
+
 /* ---- measurement hook (bench.py) ------------------------------------------------------------
  * When enabled (thread-local), every kernel launch made through this ABI is bracketed by HIP
  * events on the launch stream; namp_profile_collect() waits for them and returns the summed

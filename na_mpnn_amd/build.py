@@ -17,6 +17,7 @@ INC = os.path.join("..", "..", "include", "namp.h")
 UNITS = {"namp.hip": ["namp.hip", "namp_kernels.h", "namp_bf16s32.h", "namp_bf16p.h", "namp_node_w.h", "namp_order.h", "namp_device.h", INC],
          "namp_persist.hip": ["namp_persist.hip", "namp_kernels.h", "namp_device.h"],
          "namp_loo.hip": ["namp_loo.hip", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
+         "namp_library.hip": ["namp_library.hip", "namp_library.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_states.hip": ["namp_states.hip", "namp_states.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_pairs.hip": ["namp_pairs.hip", "namp_pairs.h", INC],
          "namp_train.hip": ["namp_train.hip", "namp_train.h", "namp_train_dw.h", "namp_metrics.h", "namp_device.h", INC],

@@ -84,6 +84,10 @@ def build_parser():
       "(ProteinMPNN.conditional_probs(classes=True)), so that --paired_wobble 1 / --paired_wobble_bias are accepted and a pair with an "
       "RNA member may also be G-U; with and without --conditional_tied 1; `pair_class_log_probs` or `group_class_log_probs` [n, 64] "
       "(-inf on absent classes) is added")
+    a("--score_fasta", type=str, default="", help="no sampling: score the sequences of FILE (the format of seqs/<name>.fa: the "
+      "alphabet of the designs, chains in alphabetical order separated by '/', header lines ignored) on --pdb_path with "
+      "ProteinMPNN.score_sequences and write scores/<name>.npz; the sequences may differ from the structure only where the usual flags "
+      "(--chains_to_design, --fixed_residues, --redesigned_residues, --design_na_only) make it designable")
     a("--load_residues_with_missing_atoms", type=int, default=0)
     a("--mode", type=str, default=None)
     a("--device", type=str, default="cuda:0")
@@ -175,6 +179,47 @@ def parse_pairs(paired_residues, paired_strands, encoded, chain_letters):
     return pairs
 
 
+def read_fasta(path):
+    """The sequences of a seqs/<name>.fa: -> (names, sequences), one name per sequence (its header line without '>', or 'sequence k')."""
+    names, seqs, header = [], [], None
+    with open(path) as fh:
+        for line in fh:
+            line = line.strip()
+            if not line:
+                continue
+            if line.startswith(">"):
+                header = line[1:]
+                continue
+            seqs.append(line)
+            names.append(header if header is not None else f"sequence {len(seqs)}")
+            header = None
+    return names, seqs
+
+
+def fasta_tokens(names, seqs, S, chain_letters, designable, str_to_int, encoded):
+    """The sequences of read_fasta as tokens int64 [n, L] in residue order — seq_string inverted: the chains in alphabetical order,
+    separated by '/'.  A sequence of the wrong length, with an unknown letter, or one that differs from the structure's S outside
+    `designable` (bool [L]) is a ValueError that names the sequence (and the first offending residue)."""
+    L = len(S)
+    index = [i for c in sorted(set(chain_letters)) for i, cl in enumerate(chain_letters) if cl == c]
+    lengths = [sum(1 for cl in chain_letters if cl == c) for c in sorted(set(chain_letters))]
+    out = np.empty((len(seqs), L), np.int64)
+    for k, (nm, seq) in enumerate(zip(names, seqs)):
+        parts = seq.split("/")
+        if [len(p) for p in parts] != lengths:
+            raise ValueError(f"--score_fasta: sequence '{nm}' has chains of {[len(p) for p in parts]} residues; the structure has "
+                             f"{lengths} ({L} residues)")
+        for i, ch in zip(index, "".join(parts)):
+            if ch not in str_to_int:
+                raise ValueError(f"--score_fasta: sequence '{nm}' holds the unknown letter '{ch}' at residue {encoded[i]}")
+            out[k, i] = str_to_int[ch]
+        bad = np.nonzero((out[k] != np.asarray(S)) & ~np.asarray(designable, bool))[0]
+        if len(bad):
+            raise ValueError(f"--score_fasta: sequence '{nm}' differs from the structure at residue {encoded[int(bad[0])]}, which is "
+                             "not designable")
+    return out
+
+
 def wobble_arguments(args, have_pairs):
     """--paired_wobble / --paired_wobble_bias as the feature_dict keys of ProteinMPNN.sample ({} without wobble)."""
     if args.paired_wobble not in (0, 1):
@@ -194,6 +239,10 @@ def main(argv=None):
         raise ValueError(f"--conditional_classes is 0 or 1; got {args.conditional_classes}")
     if args.conditional_classes and not args.conditional_probs_only:
         raise ValueError("--conditional_classes 1 goes with --conditional_probs_only 1")
+    if args.score_fasta and (args.multi_state or args.paired_residues or args.paired_strands or args.paired_wobble or
+                             args.conditional_probs_only):
+        raise ValueError("--score_fasta scores given sequences on one structure: it does not go with --multi_state, --paired_residues, "
+                         "--paired_strands, --paired_wobble or --conditional_probs_only")
     if args.model_type != "na_mpnn":
         print("Choose --model_type flag from currently available models")
         sys.exit()
@@ -241,6 +290,9 @@ def main(argv=None):
         raise ValueError("--conditional_tied 1 goes with --conditional_probs_only 1")
     if args.conditional_probs_only:
         os.makedirs(base + "conditional_probs", exist_ok=True)
+        args.output_pdbs = args.output_sequences = args.output_specificity = 0
+    elif args.score_fasta:
+        os.makedirs(base + "scores", exist_ok=True)
         args.output_pdbs = args.output_sequences = args.output_specificity = 0
     else:
         os.makedirs(base + "seqs", exist_ok=True)
@@ -348,6 +400,22 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
                      log_probs=out["log_probs"][0].cpu().numpy(), S=P["S"].astype(np.int64), mask=P["mask"],
                      chain_mask=chain_mask, chain_labels=P["chain_labels"], decoding_order=out["decoding_order"].cpu().numpy(),
                      encoded_residues=encoded, **extra)
+            return
+        if args.score_fasta:
+            # the library of the file on this structure: one decoding order (its noise is the only random input), every sequence scored
+            # as it stands
+            fd["randn"] = torch.randn(1, L, device=device)
+            names, seqs = read_fasta(args.score_fasta)
+            str_to_int = {}
+            for t, ch in int_to_str.items():
+                str_to_int[ch] = t
+                if ch in dna_to_rna:
+                    str_to_int[dna_to_rna[ch]] = t
+            lib = fasta_tokens(names, seqs, P["S"], list(P["chain_letters"]), (P["mask"] * chain_mask) != 0, str_to_int, encoded)
+            out = model.score_sequences(fd, torch.from_numpy(lib).to(device))
+            np.savez(os.path.join(base, "scores", name + ".npz"), token_log_probs=out["token_log_probs"].cpu().numpy(),
+                     loss=out["loss"].cpu().numpy(), sequences=lib, mask=P["mask"], chain_mask=chain_mask,
+                     decoding_order=out["decoding_order"].cpu().numpy(), seed=seed)
             return
         S_l, lp_l, sp_l, loss_l, lpr_l = [], [], [], [], []
         cmask = (fd["mask"] * fd["chain_mask"]).float()

@@ -35,6 +35,13 @@ __attribute__((visibility("hidden"))) int namp_internal_launch_persistent(const 
 
 // error text setter for namp_train.hip (same thread-local buffer; not part of the ABI)
 __attribute__((visibility("hidden"))) int namp_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
+// library scoring rides on namp_decoder_fwd (namp_library.hip)
+__attribute__((visibility("hidden"))) int namp_internal_library_take(int* n_var, int* n_chunk, int* rows);
+__attribute__((visibility("hidden"))) int namp_internal_library_run(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
+                                                                     const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs,
+                                                                     const float* logits, const float* h_V_dec, void* ws, size_t ws_bytes,
+                                                                     int B_dec, int B_enc, int N, int K, int n_var, int n_chunk, const int* rows,
+                                                                     void* stream);
 
 namespace {
 
@@ -2171,6 +2178,12 @@ int namp_encdec_fwd(const NampModelW* w, const float* V, const float* E, const i
 int namp_decoder_fwd(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
                      const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs, float* logits,
                      float* h_V_dec, void* ws, size_t ws_bytes, int B_dec, int B_enc, int N, int K, void* stream) {
+  {     // a library attached by namp_library (namp_library.hip): this call scores it, and the attachment is gone whatever becomes of the call
+    int n_var = 0, n_chunk = 0, rows[3] = {0, 0, 0};
+    if (namp_internal_library_take(&n_var, &n_chunk, rows))
+      return namp_internal_library_run(w, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, logits, h_V_dec, ws, ws_bytes, B_dec, B_enc, N, K,
+                                       n_var, n_chunk, rows, stream);
+  }
   REQUIRE(w != nullptr, "namp_decoder_fwd: null weights");
   REQUIRE(w->n_dec >= 1 && w->n_dec <= NAMP_MAX_LAYERS, "namp_decoder_fwd: n_dec=%d out of range", w->n_dec);
   REQUIRE_PTR(h_V_enc); REQUIRE_PTR(h_E); REQUIRE_PTR(ws); OPTIONAL_PTR(h_V_dec);

@@ -481,3 +481,89 @@ __global__ __launch_bounds__(768) void dec_items_kernel(const LooItemArgs a) {
   const int nrows = a.R - row0 < 16 ? a.R - row0 : 16;
   node_tail<false>(a.tail, x, 0.f, row0, nrows, a.R, (float*)smem, tid, wave, nwaves, lane);
 }
+
+// ---- host helpers of the translation units that launch dec_items_kernel (namp_loo.hip, namp_library.hip): each unit holds its own
+// instances of the kernel, so each sets their attributes once
+#include <cstdio>
+#include <mutex>
+
+__attribute__((visibility("hidden"))) int namp_internal_fail(int code, const char* msg);
+
+static inline hipError_t loo_items_ready() {
+  static std::once_flag once;
+  static hipError_t err = hipSuccess;
+  std::call_once(once, [] {
+    auto set = [](const void* f) {
+      hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LOO_ITEMS_LDS);
+      if (e != hipSuccess) err = e;
+    };
+    set((const void*)dec_items_kernel<PREC_F32>);
+    set((const void*)dec_items_kernel<PREC_X3>);
+  });
+  return err;
+}
+
+// what dec_items_kernel needs of the weights: three decoder layers of one precision (split-bf16 or exact fp32) with their images
+static inline int loo_check_weights(const NampModelW* w, const char* who, int* prec_out) {
+  char buf[256];
+  auto bad = [&](const char* fmt, long v) {
+    char f[224];
+    snprintf(f, sizeof(f), "%s: %s", who, fmt);
+    snprintf(buf, sizeof(buf), f, v);
+    return namp_internal_fail(NAMP_EINVAL, buf);
+  };
+  if (w->n_dec != 3) return bad("the cone kernels walk three decoder layers (n_dec=%ld): use the L-stream form", w->n_dec);
+  if (w->vocab < 1 || w->vocab > 64) return bad("vocab=%ld out of range", w->vocab);
+  int prec = PREC_F32;
+  for (int l = 0; l < 3; ++l) {
+    const NampDecLayerW* D = &w->dec[l];
+    if (D->flags & NAMP_FLAG_BF16) return bad("split-bf16 and exact fp32 evaluation only (layer %ld is bf16)", l);
+    const int p = (D->flags & NAMP_FLAG_X3) ? PREC_X3 : PREC_F32;
+    if (l && p != prec) return bad("the decoder layers must share one precision (layer %ld)", l);
+    prec = p;
+    const void* need[] = {D->W1a_img, D->W1e_img, D->W1v_img, D->b1, D->tok, D->W2_img, D->b2, D->W3_img, D->b3, D->Win_img, D->b_in,
+                          D->Wout_img, D->b_out, D->ln1_g, D->ln1_b, D->ln2_g, D->ln2_b, p == PREC_X3 ? D->W1e_ximg : D->W1e_img,
+                          p == PREC_X3 ? D->W2_ximg : D->W2_img};
+    for (const void* q : need)
+      if (!q || ((uintptr_t)q & 15u)) return bad("decoder layer %ld lacks a weight image (or it is misaligned)", l);
+  }
+  if (!w->Wout_w || !w->Wout_b) return bad("null output head (vocab=%ld)", w->vocab);
+  *prec_out = prec;
+  return NAMP_OK;
+}
+
+// the arguments of one launch over `rows` items of decoder layer D (the tail is filled by loo_tail / loo_proj)
+static inline LooItemArgs loo_items(const NampDecLayerW* D, const int prec, const float* h_E, const int K, const long rows, const int32_t* act,
+                                    const int32_t* ctr, const int32_t* cen, const int32_t* esrc, const float* Pa0, const float* Pa1,
+                                    const float* hV0, const float* hV1, const float* T0, const float* T1, const float* T2) {
+  LooItemArgs a = {};
+  a.hE = h_E; a.act = act; a.ctr = ctr; a.cen = cen; a.esrc = esrc; a.Pa0 = Pa0; a.Pa1 = Pa1; a.hV0 = hV0; a.hV1 = hV1;
+  a.T0 = T0; a.T1 = T1; a.T2 = T2;
+  a.W1_img = prec == PREC_X3 ? D->W1e_ximg : D->W1e_img; a.W2_img = prec == PREC_X3 ? D->W2_ximg : D->W2_img; a.b2 = D->b2;
+  a.m3_img = D->W3_img; a.m3_b = D->b3;
+  a.R = (int)rows; a.K = K;
+  return a;
+}
+
+static inline int launch_items(LooItemArgs a, int prec, hipStream_t s) {
+  a.TPN = (a.K + 15) / 16;
+  a.tail.m3_img = nullptr; a.tail.m3_b = nullptr; a.tail.hV = nullptr;
+  const int grid = (a.R + 15) / 16;
+  if (prec == PREC_X3) hipLaunchKernelGGL(dec_items_kernel<PREC_X3>, dim3(grid), dim3(768), LOO_ITEMS_LDS, s, a);
+  else hipLaunchKernelGGL(dec_items_kernel<PREC_F32>, dim3(grid), dim3(768), LOO_ITEMS_LDS, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+  return NAMP_OK;
+}
+
+static inline void loo_tail(NodeTail& t, const NampDecLayerW* D, const int32_t* mask, const int32_t* S, float* hV_out) {
+  t = NodeTail{};
+  t.mask = mask; t.S = S; t.hV_out = hV_out;
+  t.ln1_g = D->ln1_g; t.ln1_b = D->ln1_b; t.Win_img = D->Win_img; t.b_in = D->b_in; t.Wout_img = D->Wout_img; t.b_out = D->b_out;
+  t.ln2_g = D->ln2_g; t.ln2_b = D->ln2_b;
+}
+
+static inline void loo_proj(NodeTail& t, const float* img, const float* bias, const float* tok, float* out) {
+  ProjDesc& p = t.p[t.nproj++];
+  p.img = img; p.bias = bias; p.tok = tok; p.out = out;
+}

@@ -8,7 +8,6 @@
 #include "namp_loo.h"
 
 #include <cstdio>
-#include <mutex>
 
 __attribute__((visibility("hidden"))) int namp_internal_fail(int code, const char* msg);
 
@@ -18,17 +17,6 @@ int lfail(int code, const char* fmt, long a = 0, long b = 0, long c = 0) {
   char buf[256];
   snprintf(buf, sizeof(buf), fmt, a, b, c);
   return namp_internal_fail(code, buf);
-}
-
-std::once_flag g_loo_once;
-hipError_t g_loo_err = hipSuccess;
-void set_loo_attrs() {
-  auto set = [](const void* f) {
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LOO_ITEMS_LDS);
-    if (e != hipSuccess) g_loo_err = e;
-  };
-  set((const void*)dec_items_kernel<PREC_F32>);
-  set((const void*)dec_items_kernel<PREC_X3>);
 }
 
 // the call's buffers, carved in one fixed order (base == nullptr: sizes only)
@@ -85,29 +73,6 @@ int loo_dims(long B, long N, long K) {
   if (B < 1 || N < 1 || K < 1 || K > NAMP_MAX_K || K > N) return lfail(NAMP_EINVAL, "namp_decoder_loo: bad dims B=%ld N=%ld K=%ld", B, N, K);
   if (B * N * K >= (1L << LOO_ROW_BITS)) return lfail(NAMP_EINVAL, "namp_decoder_loo: B*N*K=%ld exceeds 2^28 item rows", B * N * K);
   return NAMP_OK;
-}
-
-int launch_items(LooItemArgs a, int prec, hipStream_t s) {
-  a.TPN = (a.K + 15) / 16;
-  a.tail.m3_img = nullptr; a.tail.m3_b = nullptr; a.tail.hV = nullptr;
-  const int grid = (a.R + 15) / 16;
-  if (prec == PREC_X3) hipLaunchKernelGGL(dec_items_kernel<PREC_X3>, dim3(grid), dim3(768), LOO_ITEMS_LDS, s, a);
-  else hipLaunchKernelGGL(dec_items_kernel<PREC_F32>, dim3(grid), dim3(768), LOO_ITEMS_LDS, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
-  return NAMP_OK;
-}
-
-void loo_tail(NodeTail& t, const NampDecLayerW* D, const int32_t* mask, const int32_t* S, float* hV_out) {
-  t = NodeTail{};
-  t.mask = mask; t.S = S; t.hV_out = hV_out;
-  t.ln1_g = D->ln1_g; t.ln1_b = D->ln1_b; t.Win_img = D->Win_img; t.b_in = D->b_in; t.Wout_img = D->Wout_img; t.b_out = D->b_out;
-  t.ln2_g = D->ln2_g; t.ln2_b = D->ln2_b;
-}
-
-void loo_proj(NodeTail& t, const float* img, const float* bias, const float* tok, float* out) {
-  ProjDesc& p = t.p[t.nproj++];
-  p.img = img; p.bias = bias; p.tok = tok; p.out = out;
 }
 
 // what the calling thread's NEXT namp_decoder_loo call ties: taken, and cleared, by that call; the latest attachment holds
@@ -188,26 +153,12 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
                                              : "namp_decoder_loo: null pointer argument (group tables were attached)");
   if ((((uintptr_t)h_V_enc | (uintptr_t)h_E | (uintptr_t)ws | (uintptr_t)log_probs) & 15u) != 0)
     return lfail(NAMP_EINVAL, "namp_decoder_loo: h_V_enc / h_E / log_probs / ws must be 16-byte aligned");
-  if (w->n_dec != 3) return lfail(NAMP_EINVAL, "namp_decoder_loo: the cone kernels walk three decoder layers (n_dec=%ld): use the L-stream form", w->n_dec);
-  if (w->vocab < 1 || w->vocab > 64) return lfail(NAMP_EINVAL, "namp_decoder_loo: vocab=%ld out of range", w->vocab);
+  int prec = PREC_F32;
+  int rc = loo_check_weights(w, "namp_decoder_loo", &prec);
+  if (rc) return rc;
   if (n_classes && n_classes < w->vocab)
     return lfail(NAMP_EINVAL, "namp_decoder_loo: n_classes=%ld of the attached class tables is below vocab=%ld", n_classes, w->vocab);
-  int rc = loo_dims(B, N, K);
-  if (rc) return rc;
-  int prec = PREC_F32;
-  for (int l = 0; l < 3; ++l) {
-    const NampDecLayerW* D = &w->dec[l];
-    if (D->flags & NAMP_FLAG_BF16) return lfail(NAMP_EINVAL, "namp_decoder_loo: split-bf16 and exact fp32 evaluation only (layer %ld is bf16)", l);
-    const int p = (D->flags & NAMP_FLAG_X3) ? PREC_X3 : PREC_F32;
-    if (l && p != prec) return lfail(NAMP_EINVAL, "namp_decoder_loo: the decoder layers must share one precision");
-    prec = p;
-    const void* need[] = {D->W1a_img, D->W1e_img, D->W1v_img, D->b1, D->tok, D->W2_img, D->b2, D->W3_img, D->b3, D->Win_img, D->b_in,
-                          D->Wout_img, D->b_out, D->ln1_g, D->ln1_b, D->ln2_g, D->ln2_b, p == PREC_X3 ? D->W1e_ximg : D->W1e_img,
-                          p == PREC_X3 ? D->W2_ximg : D->W2_img};
-    for (const void* q : need)
-      if (!q || ((uintptr_t)q & 15u)) return lfail(NAMP_EINVAL, "namp_decoder_loo: decoder layer %ld lacks a weight image (or it is misaligned)", l);
-  }
-  if (!w->Wout_w || !w->Wout_b) return lfail(NAMP_EINVAL, "namp_decoder_loo: null output head");
+  if ((rc = loo_dims(B, N, K))) return rc;
   const long G = (long)B * N, R = G * K;
   LooBuffers b = loo_carve(ws, G, K, n_maps, n_classes != 0);
   static_assert(NAMP_LOO_GROUP_MAX <= 16, "loo_prepare_kernel packs a listed position into 4 bits beside a residue index below 2^27");
@@ -216,8 +167,8 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   if (need > ws_bytes && n_classes)                              // (the class section is part of the call's arguments: include/namp.h)
     return lfail(NAMP_EINVAL, "namp_decoder_loo: workspace too small for the attached class tables (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
   if (need > ws_bytes) return lfail(NAMP_EWORKSPACE, "namp_decoder_loo: workspace too small (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
-  std::call_once(g_loo_once, set_loo_attrs);
-  if (g_loo_err != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(g_loo_err));
+  const hipError_t ready = loo_items_ready();
+  if (ready != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(ready));
   hipStream_t s = (hipStream_t)stream;
   const NampDecLayerW *D0 = &w->dec[0], *D1 = &w->dec[1], *D2 = &w->dec[2];
 
@@ -271,13 +222,7 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   auto items = [&](const NampDecLayerW* D, long rows, const int32_t* act, const int32_t* ctr, const int32_t* cen, const int32_t* esrc,
                    const float* Pa0, const float* Pa1, const float* hV0, const float* hV1, const float* T0, const float* T1,
                    const float* T2) {
-    LooItemArgs a = {};
-    a.hE = h_E; a.act = act; a.ctr = ctr; a.cen = cen; a.esrc = esrc; a.Pa0 = Pa0; a.Pa1 = Pa1; a.hV0 = hV0; a.hV1 = hV1;
-    a.T0 = T0; a.T1 = T1; a.T2 = T2;
-    a.W1_img = prec == PREC_X3 ? D->W1e_ximg : D->W1e_img; a.W2_img = prec == PREC_X3 ? D->W2_ximg : D->W2_img; a.b2 = D->b2;
-    a.m3_img = D->W3_img; a.m3_b = D->b3;
-    a.R = (int)rows; a.K = K;
-    return a;
+    return loo_items(D, prec, h_E, K, rows, act, ctr, cen, esrc, Pa0, Pa1, hV0, hV1, T0, T1, T2);
   };
   // phase 1: layer 1 at the residues that lose i from their decoded neighbours (tables of layer 2 for phase 2 and the own layer 2)
   LooItemArgs a = items(D0, R, b.act1, b.ctr1, b.ctr1, b.esrc1, b.Pa1, b.Pa1, h_V_enc, h_V_enc, b.Pbw1, b.Pfw[0], b.Pbw1);

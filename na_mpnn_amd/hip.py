@@ -227,6 +227,10 @@ _PROTOTYPES = {
     "namp_loo_classes_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
     "namp_loo_classes_out_offset": (sz, [i32, i32, i32, i32, i32, i32]),
     "namp_loo_classes": (i32, [i32, i32, i32]),
+    "namp_library_workspace_bytes": (sz, [i32] * 8),
+    "namp_library_in_offset": (sz, [i32] * 8),
+    "namp_library_out_offset": (sz, [i32] * 8),
+    "namp_library": (i32, [i32] * 5),
 }
 
 KERNEL_KINDS = ["gather", "node_linear", "edge_embed", "enc_message", "enc_edge_update", "node_update",

@@ -1077,6 +1077,147 @@ class ProteinMPNN(nn.Module):
                 log_probs[b, i0:i1] = lp[ar, i0 + ar]
         return log_probs
 
+    # tokens (sequences x L) per decoder call of the dense route of score_sequences(); the active route spends the same budget on the
+    # rows it evaluates: 3 * score_library_tokens layer evaluations per call
+    score_library_tokens = 65536
+
+    def _library_arguments(self, fd, S_lib, positions):
+        """The checked arguments of score_sequences() (no device needed): -> positions int64 [n_var] as a host list, the tokens at the
+        positions [n, n_var] and the full sequences [n, L] (int64, on S_lib's device)."""
+        S_true, mask = fd["S"], fd["mask"]
+        if S_true.dim() != 2 or S_true.shape[0] != 1:
+            raise ValueError(f"score_sequences expects one input complex (B == 1); got S of shape {tuple(S_true.shape)}")
+        if fd.get("state_weights") is not None:
+            raise NotImplementedError("score_sequences does not take state_weights (a library over several backbone states)")
+        L = S_true.shape[1]
+        if positions is None:
+            pos = torch.nonzero((mask[0] * fd["chain_mask"][0]) != 0).reshape(-1).tolist()
+        else:
+            p = torch.as_tensor(positions)
+            if p.dim() != 1 or p.dtype.is_floating_point or p.dtype == torch.bool:
+                raise ValueError("positions must be a one-dimensional integer tensor")
+            pos = [int(v) for v in p.tolist()]
+            if any(v < 0 or v >= L for v in pos):
+                raise ValueError(f"positions must lie in [0, {L})")
+            if any(b <= a for a, b in zip(pos, pos[1:])):
+                raise ValueError("positions must be ascending and unique")
+        S_lib = torch.as_tensor(S_lib)
+        n_var = len(pos)
+        if S_lib.dim() != 2 or S_lib.dtype.is_floating_point or S_lib.shape[1] not in (L, n_var):
+            raise ValueError(f"S_lib must be an integer tensor [n, {L}] (full sequences) or [n, {n_var}] (tokens at the positions); "
+                             f"got {tuple(S_lib.shape)}")
+        idx = torch.tensor(pos, dtype=torch.long, device=S_lib.device)
+        tokens = (S_lib[:, idx] if S_lib.shape[1] == L else S_lib).long().contiguous()
+        if tokens.numel():
+            self._check_tokens(tokens, "S_lib")
+        S_full = S_true.to(S_lib.device).long().expand(S_lib.shape[0], L).clone()
+        S_full[:, idx] = tokens
+        return pos, tokens, S_full
+
+    def _library_auto(self, n_var, L, n):
+        """The rule of score_sequences(method="auto") where the active route applies — from what the host knows without a read-back:
+        at most half of the residues are library positions (see the docstring of score_sequences)."""
+        return 2 * n_var <= L
+
+    @torch.no_grad()
+    def score_sequences(self, feature_dict, S_lib, positions=None, method="auto"):
+        """The log-likelihoods of a LIBRARY of candidate sequences on one complex: for sequence k exactly what score() returns when
+        feature_dict["S"] is replaced by sequence k — the same randn, batch_size = 1, hence the same decoding order — reduced to the
+        token's own entry.  One input complex (B != 1: ValueError); state_weights: NotImplementedError; ties are not read (a given
+        sequence is scored as it stands).
+        positions: the library positions, an int tensor [n_var], ascending and unique, inside [0, L) (ValueError otherwise); default:
+        the residues with mask * chain_mask != 0.  S_lib: int [n, L] (full sequences: everything outside `positions` is IGNORED and
+        taken from feature_dict["S"]) or [n, n_var] (the tokens at `positions`); ids outside [0, vocab) raise IndexError, special
+        tokens are legal.
+        Returns "token_log_probs" float32 [n, L] (log_probs_k[i, S_k[i]], for masked residues what the reference computes for them),
+        "loss" [n] (get_score's mean of -token_log_probs over mask * chain_mask, data_utils.py:36-52), "S" the full sequences [n, L],
+        "decoding_order", "base_log_probs" [1, L, vocab] (the rows of feature_dict["S"]), "chunks" (decoder calls the library took) and,
+        on the active route, "active_rows": an int32 [3] device tensor (|act_1|, |act_2|, |act_3|).
+        method: "dense" — every sequence is a stream of the ordinary decoder (namp_decoder_fwd), score_library_tokens // L sequences
+        per call, the entry gathered in torch: every number of decoder layers and every precision mode.  "active" — with chain_mask
+        the fixed residues decode first, so only the rows a varying token reaches need a per-sequence evaluation: with var the
+        library positions and act_0 = 0, act_l[i] = mask[i] and (act_{l-1}[i] or some earlier-decoded neighbour j of i has var[j]
+        or act_{l-1}[j]); one pass over feature_dict["S"] gives the base tables and base_log_probs, and per layer the items
+        (sequence, row of act_l or var) run through the item kernel of the cone conditionals with the rows a varying token changed
+        overridden (namp_library, include/namp.h; DESIGN.md 5.13), 3 * score_library_tokens // sum_l |act_l + var| sequences per
+        call.  The host reads the three row counts back ONCE per call, to size the chunks (never per chunk).  Three decoder layers
+        and message_precision "x3" or "fp32" (NotImplementedError otherwise).  "auto" — the active route where it applies (three
+        decoder layers, "x3" / "fp32") and 2 * n_var <= L, the dense route otherwise.  The rule reads n_var and L only (no read-back):
+        with every residue designed the active route evaluates as many rows as the dense one and is measured 1.46x ("x3") / 1.14x
+        ("fp32") slower per row (390 residues, K = 32, n = 1,000: 25.6 / 40.7 ms against 17.5 / 35.7 ms,
+        profiles/score_library_time.log — item tables and 16-row item tiles against the decoder's fused launches), so it pays
+        while fewer than about two thirds of the rows are evaluated; a layer usually holds about n_var rows (the designed residues
+        decode last), and n_var <= L / 2 leaves room for fixed rows that a designed residue decoded early reaches."""
+        if method not in ("auto", "dense", "active"):
+            raise ValueError(f"method must be 'auto', 'dense' or 'active'; got {method!r}")
+        fd = feature_dict
+        pos, tokens, S_full = self._library_arguments(fd, S_lib, positions)
+        S_true, mask = fd["S"], fd["mask"]
+        L, n, n_var = S_true.shape[1], S_full.shape[0], len(pos)
+        active_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        if method == "active" and not active_ok:
+            raise NotImplementedError("score_sequences(method='active') needs three decoder layers and message_precision 'x3' or 'fp32'; "
+                                      "use method='dense'")
+        use_active = method == "active" or (method == "auto" and active_ok and self._library_auto(n_var, L, n))
+        _require_device(fd["X"], "X")
+        dev = fd["X"].device
+        tokens, S_full = tokens.to(dev), S_full.to(dev)
+        o = self._decoding_order(mask, fd["chain_mask"], fd["randn"])
+        h_V, h_E, E_idx = self.encode(fd, order=o)
+        self._check_tokens(S_true)
+        o.wait()
+        rank = o.rank[:1]
+        out = {"S": S_full, "decoding_order": o.order[0]}
+        tlp = torch.empty(n, L, device=dev)
+        chunks = 0
+        if use_active:
+            W, Lb = self._weights(), hip.lib()
+            K = E_idx.shape[2]
+            E32, S32, m32, r32 = _i32(E_idx), _i32(self._as(S_true, "i32")), _i32(self._as(mask, "i32")), _i32(rank)
+            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+            pos32 = torch.tensor(pos, dtype=torch.int32).to(dev)
+            tok32 = tokens.to(torch.int32)
+            base = torch.empty(1, L, self.num_letters, device=dev)
+
+            def call(k0, k1, rows):
+                """One attached decoder call over sequences k0 .. k1 - 1 -> its workspace and the offset of its output section."""
+                dims = (L, K, 3, n_var, k1 - k0) + tuple(rows)
+                need = Lb.namp_library_workspace_bytes(*dims)
+                if need == 0:
+                    raise ValueError(f"score_sequences: no library workspace for L={L} K={K} n_var={n_var} sequences={k1 - k0}")
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                sec = ws[Lb.namp_library_in_offset(*dims):][:4 * (n_var + (k1 - k0) * n_var)].view(torch.int32)
+                sec[:n_var] = pos32
+                sec[n_var:] = tok32[k0:k1].reshape(-1)
+                hip.check(Lb.namp_library(n_var, k1 - k0, *rows), "library")
+                hip.check(Lb.namp_decoder_fwd(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
+                                              r32.data_ptr(), base.data_ptr(), None, None, ws.data_ptr(), ws.numel(), 1, 1, L, K,
+                                              hip.current_stream()), "decoder_fwd (library)")
+                return ws, Lb.namp_library_out_offset(*dims)
+
+            ws, ooff = call(0, 0, (0, 0, 0))                     # the plan alone: the counts, and base_log_probs
+            counts = ws[ooff:ooff + 24].view(torch.int32).clone()
+            out["active_rows"] = counts[:3]
+            rows = [int(v) for v in counts[3:6].tolist()]        # the call's ONE read-back: the chunks are sized by it
+            chunk = max(1, min(3 * self.score_library_tokens // max(1, sum(rows)), ((1 << 28) - 1) // L))
+            for k0 in range(0, n, chunk):
+                k1 = min(n, k0 + chunk)
+                ws, ooff = call(k0, k1, rows)
+                tlp[k0:k1] = ws[ooff + 256:ooff + 256 + 4 * (k1 - k0) * L].view(torch.float32).view(k1 - k0, L)
+                chunks += 1
+        else:
+            base = self.decode_graph(h_V, h_E, E_idx, S_true, mask, rank)
+            chunk = max(1, self.score_library_tokens // L)
+            for k0 in range(0, n, chunk):
+                k1 = min(n, k0 + chunk)
+                S_k = S_full[k0:k1]
+                lp = self.decode_graph(h_V, h_E, E_idx, S_k, mask.expand(k1 - k0, L), rank.expand(k1 - k0, L))
+                tlp[k0:k1] = lp.gather(2, S_k[:, :, None])[:, :, 0]
+                chunks += 1
+        cm = (mask * fd["chain_mask"])[0].to(tlp.dtype)
+        out.update({"token_log_probs": tlp, "loss": (-tlp * cm).sum(-1) / (cm.sum() + 1e-8), "base_log_probs": base, "chunks": chunks})
+        return out
+
     def _wobble_arguments(self, fd, n_pairs=None):
         """feature_dict["paired_wobble"] / ["paired_wobble_bias"] in one normal form -> (wobble, wobble_bias, asked): each None, a scalar
         or a list with one entry per pair; asked: some pair asks for wobble.  With n_pairs the lists are checked against the pairs."""

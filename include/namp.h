@@ -914,6 +914,54 @@ size_t namp_library_in_offset(int N, int K, int n_dec, int n_var, int n_chunk, i
 size_t namp_library_out_offset(int N, int K, int n_dec, int n_var, int n_chunk, int rows1, int rows2, int rows3);
 int namp_library(int n_var, int n_chunk, int rows1, int rows2, int rows3);
 
+/* ---- mutational scan: the change of the joint log-likelihood under every variant of a list, riding on namp_decoder_fwd --------
+ * A SITE is a set of 1 to NAMP_MUT_MAX_EDITS distinct residues, a VARIANT a site plus one token per residue of the site; every
+ * other residue keeps S.  With the sets of library scoring (above) for var = the site, act_l(site) and U_l(site) = act_l(site) +
+ * site, a variant differs from the base stream on U_3(site) only.  An attached namp_decoder_fwd call (B_dec = B_enc = 1; mask
+ * required, logits and h_V_dec NULL) runs the base stream once (log_probs [N, vocab], as with a library attached), plans PER SITE
+ * the three ascending lists U_1..3(site) — integer work in a fixed order, no atomics; the variants of a site share its lists —,
+ * lays the items (variant, row of U_l(site)) of layer l out by the prefix sums of the list sizes over the variants, and evaluates
+ * them through dec_items_kernel (namp_loo.h, unchanged), one launch per layer: a backward edge to a neighbour j reads the override
+ * row of (variant, j) iff j is in U_{l-1}(site) (U_0 = the site: Pfw_1[j] + tok_1[token]), found by a binary search in the site's
+ * sorted segment; the centre follows the same rule.  Behind layer 3 every item keeps the variant's own entry log p(S_v[i]), and
+ * delta[v] = sum over the rows i of U_3(site of v), in list order, of w_i * (entry - base entry) — every product and sum rounded
+ * once in fp32.
+ * No entry point takes a pointer.  With the same eleven ints (N, K, n_dec, n_sites, n_variants, list1..3, items1..3),
+ *     namp_mutations_workspace_bytes(...)  what the attached call requires of ws_bytes (NAMP_EINVAL if smaller); 0 where
+ *                                          unsupported: n_dec != 3, K > N or NAMP_MAX_K, a negative count, variants without a
+ *                                          site, 8 * n_variants, n_sites, N or a capacity >= 2^28
+ *     namp_mutations_in_offset(...)        byte offset in ws of the caller-filled INPUT SECTION (256-byte aligned), 32-bit words
+ *                                              sites[n_sites][8]      int32 residues of the site, a negative word: no edit
+ *                                              variants[n_variants][9] int32 site index, then one token per word of the site
+ *                                              w[N]                   float weight of residue i in delta (mask * chain_mask)
+ *     namp_mutations_out_offset(...)       byte offset in ws of the OUTPUT SECTION (256-byte aligned); its four arrays follow each
+ *                                          other, each padded to a multiple of 256 bytes counted with ONE extra element
+ *                                              int32 [n_sites][3]     |U_1..3(site)|, whatever the capacities
+ *                                              float [n_variants]     delta
+ *                                              int32 [items3]         residue of every layer-3 item row (-1: no item)
+ *                                              float [items3]         the variant's own entry at that row
+ * and namp_mutations(n_sites, n_variants, list1, list2, list3, items1, items2, items3) (all >= 0, NAMP_EINVAL otherwise and
+ * nothing stays attached) attaches them to the calling thread's NEXT namp_decoder_fwd call, which clears the attachment whether
+ * it succeeds or not (a call that finds a library attached as well runs neither: NAMP_EINVAL).  list_l is the capacity of the
+ * lists of layer l (the sum of |U_l(site)| over the call's sites), items_l that of its item rows (the sum over the variants of
+ * |U_l(site of the variant)|); the rows of variant v in layer 3 are the items3-prefix sums in the order of the section.  A
+ * caller attaches once with n_variants = 0 and zero capacities (plan and sizes only), reads the sizes back, and cuts its variants
+ * into calls by them, each with its own sites.  Three decoder layers of one precision, split-bf16 or exact fp32.
+ * The sections are device data: a residue >= N is clamped to N - 1 (a negative word is no edit), tokens are clamped to
+ * [0, vocab), site indices to [0, n_sites); of two edits of a site that clamp to one residue the LAST listed is the residue's;
+ * list entries and item rows beyond a capacity are dropped, and what would have read them reads base rows: a malformed section
+ * gives a defined result and nothing outside ws and log_probs is written.  The input section is not written.  Separate launches
+ * on `stream`, plain stores, every item owns its rows: two calls give identical bits, and a variant's bits depend neither on the
+ * call it travels in nor on the other variants of that call.  Without an attachment namp_decoder_fwd is unchanged, bit for bit. */
+#define NAMP_MUT_MAX_EDITS 8
+size_t namp_mutations_workspace_bytes(int N, int K, int n_dec, int n_sites, int n_variants, int list1, int list2, int list3, int items1,
+                                      int items2, int items3);
+size_t namp_mutations_in_offset(int N, int K, int n_dec, int n_sites, int n_variants, int list1, int list2, int list3, int items1,
+                                int items2, int items3);
+size_t namp_mutations_out_offset(int N, int K, int n_dec, int n_sites, int n_variants, int list1, int list2, int list3, int items1,
+                                 int items2, int items3);
+int namp_mutations(int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3);
+
 /* ---- measurement hook (bench.py) ------------------------------------------------------------
  * When enabled (thread-local), every kernel launch made through this ABI is bracketed by HIP
  * events on the launch stream; namp_profile_collect() waits for them and returns the summed

@@ -88,6 +88,11 @@ def build_parser():
       "alphabet of the designs, chains in alphabetical order separated by '/', header lines ignored) on --pdb_path with "
       "ProteinMPNN.score_sequences and write scores/<name>.npz; the sequences may differ from the structure only where the usual flags "
       "(--chains_to_design, --fixed_residues, --redesigned_residues, --design_na_only) make it designable")
+    a("--mutation_scan", type=int, default=0, help="1: no sampling: every point mutation of the residues the usual flags make designable "
+      "(--chains_to_design, --fixed_residues, --redesigned_residues, --design_na_only), over the letters of the residue's own polymer, "
+      "scored with ProteinMPNN.score_mutations as the change of the structure's joint log-likelihood; with --paired_residues / "
+      "--paired_strands a paired residue is mutated together with its partner (canonical duplexes, pairs=True); writes "
+      "mutations/<name>.npz (residues, tokens, delta [P, T], base_loss, wild_type_token, site_rows)")
     a("--load_residues_with_missing_atoms", type=int, default=0)
     a("--mode", type=str, default=None)
     a("--device", type=str, default="cuda:0")
@@ -243,6 +248,11 @@ def main(argv=None):
                              args.conditional_probs_only):
         raise ValueError("--score_fasta scores given sequences on one structure: it does not go with --multi_state, --paired_residues, "
                          "--paired_strands, --paired_wobble or --conditional_probs_only")
+    if args.mutation_scan not in (0, 1):
+        raise ValueError(f"--mutation_scan is 0 or 1; got {args.mutation_scan}")
+    if args.mutation_scan and (args.score_fasta or args.conditional_probs_only or args.multi_state or args.paired_wobble):
+        raise ValueError("--mutation_scan 1 scans one structure: it does not go with --score_fasta, --conditional_probs_only, "
+                         "--multi_state or --paired_wobble")
     if args.model_type != "na_mpnn":
         print("Choose --model_type flag from currently available models")
         sys.exit()
@@ -293,6 +303,9 @@ def main(argv=None):
         args.output_pdbs = args.output_sequences = args.output_specificity = 0
     elif args.score_fasta:
         os.makedirs(base + "scores", exist_ok=True)
+        args.output_pdbs = args.output_sequences = args.output_specificity = 0
+    elif args.mutation_scan:
+        os.makedirs(base + "mutations", exist_ok=True)
         args.output_pdbs = args.output_sequences = args.output_specificity = 0
     else:
         os.makedirs(base + "seqs", exist_ok=True)
@@ -416,6 +429,17 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
             np.savez(os.path.join(base, "scores", name + ".npz"), token_log_probs=out["token_log_probs"].cpu().numpy(),
                      loss=out["loss"].cpu().numpy(), sequences=lib, mask=P["mask"], chain_mask=chain_mask,
                      decoding_order=out["decoding_order"].cpu().numpy(), seed=seed)
+            return
+        if args.mutation_scan:
+            # the saturation scan of the designable residues under one decoding order (its noise is the only random input); a paired
+            # residue is mutated with its partner and listed once, under the pair's first member
+            fd["randn"] = torch.randn(1, L, device=device)
+            out = model.score_mutations(fd, pairs=bool(pairs))
+            scanned = out["positions"].cpu().numpy()
+            np.savez(os.path.join(base, "mutations", name + ".npz"), residues=np.array([encoded[i] for i in scanned]),
+                     tokens=np.array([int_to_str.get(int(t), "?") for t in out["tokens"].tolist()]), delta=out["delta"].cpu().numpy(),
+                     base_loss=out["base_loss"].cpu().numpy(), wild_type_token=np.asarray(P["S"])[scanned],
+                     site_rows=(out["site_rows"].cpu().numpy() if out["site_rows"] is not None else np.zeros((0, 3), np.int32)))
             return
         S_l, lp_l, sp_l, loss_l, lpr_l = [], [], [], [], []
         cmask = (fd["mask"] * fd["chain_mask"]).float()

@@ -42,6 +42,12 @@ __attribute__((visibility("hidden"))) int namp_internal_library_run(const NampMo
                                                                      const float* logits, const float* h_V_dec, void* ws, size_t ws_bytes,
                                                                      int B_dec, int B_enc, int N, int K, int n_var, int n_chunk, const int* rows,
                                                                      void* stream);
+// so does the mutational scan (namp_mutations.hip); dims: n_sites, n_variants, list capacities [3], item capacities [3]
+__attribute__((visibility("hidden"))) int namp_internal_mutations_take(int* dims);
+__attribute__((visibility("hidden"))) int namp_internal_mutations_run(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
+                                                                       const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs,
+                                                                       const float* logits, const float* h_V_dec, void* ws, size_t ws_bytes,
+                                                                       int B_dec, int B_enc, int N, int K, const int* dims, void* stream);
 
 namespace {
 
@@ -2179,8 +2185,14 @@ int namp_decoder_fwd(const NampModelW* w, const float* h_V_enc, const float* h_E
                      const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs, float* logits,
                      float* h_V_dec, void* ws, size_t ws_bytes, int B_dec, int B_enc, int N, int K, void* stream) {
   {     // a library attached by namp_library (namp_library.hip): this call scores it, and the attachment is gone whatever becomes of the call
-    int n_var = 0, n_chunk = 0, rows[3] = {0, 0, 0};
-    if (namp_internal_library_take(&n_var, &n_chunk, rows))
+    int n_var = 0, n_chunk = 0, rows[3] = {0, 0, 0}, mut[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int have_lib = namp_internal_library_take(&n_var, &n_chunk, rows);
+    if (namp_internal_mutations_take(mut)) {     // (namp_mutations, namp_mutations.hip: taken and cleared in the same way)
+      if (have_lib) return fail(NAMP_EINVAL, "namp_decoder_fwd: a library and a mutational scan were both attached; neither is run");
+      return namp_internal_mutations_run(w, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, logits, h_V_dec, ws, ws_bytes, B_dec, B_enc, N, K, mut,
+                                         stream);
+    }
+    if (have_lib)
       return namp_internal_library_run(w, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, logits, h_V_dec, ws, ws_bytes, B_dec, B_enc, N, K,
                                        n_var, n_chunk, rows, stream);
   }

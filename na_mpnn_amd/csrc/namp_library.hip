@@ -19,8 +19,7 @@ int bfail(int code, const char* fmt, long a = 0, long b = 0, long c = 0) {
 struct LibDims { int N, K, n_var, n_chunk, rows[3]; };
 
 // the call's buffers, carved in one fixed order (base == nullptr: sizes only)
-struct LibBuffers {
-  float *Pa1, *Pbw1, *Pfw[3], *h1, *Pa2, *Pbw2, *h2, *Pa3, *Pbw3, *h3, *partial;     // the base stream
+struct LibBuffers : LooBaseStream {                                                    // (the base stream's tables and states first)
   int32_t *vpos, *flag[3], *pos[3], *list[3];                                         // the plan
   int32_t* in;                                                                         // INPUT section: positions[n_var], tokens[n_chunk][n_var]
   float *ov1;                                                                          // [n_chunk * n_var][128] layer 1's override rows
@@ -115,38 +114,13 @@ __attribute__((visibility("hidden"))) int namp_internal_library_run(const NampMo
   const hipError_t ready = loo_items_ready();
   if (ready != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(ready));
   hipStream_t s = (hipStream_t)stream;
-  const NampDecLayerW *D0 = &w->dec[0], *D1 = &w->dec[1], *D2 = &w->dec[2];
+  const NampDecLayerW* D0 = &w->dec[0];
 
   // ---- base stream: tables of every layer, the states behind layers 1 and 2, the head behind layer 3
-  NampProj pf[5] = {{D0->W1v_img, nullptr, nullptr, b.Pfw[0]}, {D1->W1v_img, nullptr, nullptr, b.Pfw[1]}, {D2->W1v_img, nullptr, nullptr, b.Pfw[2]},
-                    {D0->W1a_img, D0->b1, nullptr, b.Pa1}, {D0->W1v_img, nullptr, D0->tok, b.Pbw1}};
-  if ((rc = namp_node_linear(h_V_enc, S, 1, 1, N, pf, 5, nullptr, stream))) return rc;
-  const bool fused = N <= namp_fused_tail_max_residues();
+  if ((rc = loo_base_stream(w, b, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, N, K, stream))) return rc;
   const float* Pa[3] = {b.Pa1, b.Pa2, b.Pa3};
   const float* Pbw[3] = {b.Pbw1, b.Pbw2, b.Pbw3};
   const float* hin[3] = {h_V_enc, b.h1, b.h2};
-  float* hout[3] = {b.h1, b.h2, b.h3};
-  for (int l = 0; l < 3; ++l) {
-    const NampDecLayerW* D = &w->dec[l];
-    const bool last = l == 2;
-    NampProj pn[2] = {{}, {}};
-    if (!last) {
-      const NampDecLayerW* Dn = &w->dec[l + 1];
-      pn[0] = {Dn->W1a_img, Dn->b1, nullptr, l ? b.Pa3 : b.Pa2};
-      pn[1] = {Dn->W1v_img, nullptr, Dn->tok, l ? b.Pbw3 : b.Pbw2};
-    }
-    if (fused) {
-      if ((rc = namp_dec_message_update(D, h_E, E_idx, rank, Pa[l], Pbw[l], b.Pfw[l], hin[l], mask, hout[l], pn, last ? 0 : 2, S,
-                                        last ? w->Wout_w : nullptr, w->Wout_b, log_probs, nullptr, w->vocab, 1, 1, N, K, stream)))
-        return rc;
-    } else {
-      if ((rc = namp_dec_message(D, h_E, E_idx, rank, Pa[l], Pbw[l], b.Pfw[l], b.partial, 1, 1, N, K, stream))) return rc;
-      if ((rc = namp_node_update(D->ln1_g, D->ln1_b, D->Win_img, D->b_in, D->Wout_img, D->b_out, D->ln2_g, D->ln2_b, hin[l], b.partial,
-                                 D->W3_img, D->b3, mask, hout[l], pn, last ? 0 : 2, S, N, K, stream)))
-        return rc;
-    }
-  }
-  if (!fused && (rc = namp_logits_log_softmax(w->Wout_w, w->Wout_b, b.h3, log_probs, nullptr, N, w->vocab, stream))) return rc;
 
   // ---- the plan
   LibPlanArgs pa = {};

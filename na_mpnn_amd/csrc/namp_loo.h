@@ -567,3 +567,47 @@ static inline void loo_proj(NodeTail& t, const float* img, const float* bias, co
   ProjDesc& p = t.p[t.nproj++];
   p.img = img; p.bias = bias; p.tok = tok; p.out = out;
 }
+
+// ---- the BASE STREAM of the calls that ride on namp_decoder_fwd with items on top (namp_library.hip, namp_mutations.hip; both include
+// include/namp.h first): one pass over S at B = 1 through the library's own building blocks that keeps the tables and states of all
+// three layers, with the head -> log_probs.  One sequence of launches, hence one summation order, for every such call.
+struct LooBaseStream {
+  float *Pa1, *Pbw1, *Pfw[3], *h1, *Pa2, *Pbw2, *h2, *Pa3, *Pbw3, *h3;     // [N][128] each
+  float* partial;                                                          // [N][ceil(K / 16)][129] (+ 3) of the unfused form
+};
+
+static inline int loo_base_stream(const NampModelW* w, const LooBaseStream& b, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
+                                  const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs, int N, int K, void* stream) {
+  const NampDecLayerW *D0 = &w->dec[0], *D1 = &w->dec[1], *D2 = &w->dec[2];
+  int rc;
+  NampProj pf[5] = {{D0->W1v_img, nullptr, nullptr, b.Pfw[0]}, {D1->W1v_img, nullptr, nullptr, b.Pfw[1]}, {D2->W1v_img, nullptr, nullptr, b.Pfw[2]},
+                    {D0->W1a_img, D0->b1, nullptr, b.Pa1}, {D0->W1v_img, nullptr, D0->tok, b.Pbw1}};
+  if ((rc = namp_node_linear(h_V_enc, S, 1, 1, N, pf, 5, nullptr, stream))) return rc;
+  const bool fused = N <= namp_fused_tail_max_residues();
+  const float* Pa[3] = {b.Pa1, b.Pa2, b.Pa3};
+  const float* Pbw[3] = {b.Pbw1, b.Pbw2, b.Pbw3};
+  const float* hin[3] = {h_V_enc, b.h1, b.h2};
+  float* hout[3] = {b.h1, b.h2, b.h3};
+  for (int l = 0; l < 3; ++l) {
+    const NampDecLayerW* D = &w->dec[l];
+    const bool last = l == 2;
+    NampProj pn[2] = {{}, {}};
+    if (!last) {
+      const NampDecLayerW* Dn = &w->dec[l + 1];
+      pn[0] = {Dn->W1a_img, Dn->b1, nullptr, l ? b.Pa3 : b.Pa2};
+      pn[1] = {Dn->W1v_img, nullptr, Dn->tok, l ? b.Pbw3 : b.Pbw2};
+    }
+    if (fused) {
+      if ((rc = namp_dec_message_update(D, h_E, E_idx, rank, Pa[l], Pbw[l], b.Pfw[l], hin[l], mask, hout[l], pn, last ? 0 : 2, S,
+                                        last ? w->Wout_w : nullptr, w->Wout_b, log_probs, nullptr, w->vocab, 1, 1, N, K, stream)))
+        return rc;
+    } else {
+      if ((rc = namp_dec_message(D, h_E, E_idx, rank, Pa[l], Pbw[l], b.Pfw[l], b.partial, 1, 1, N, K, stream))) return rc;
+      if ((rc = namp_node_update(D->ln1_g, D->ln1_b, D->Win_img, D->b_in, D->Wout_img, D->b_out, D->ln2_g, D->ln2_b, hin[l], b.partial,
+                                 D->W3_img, D->b3, mask, hout[l], pn, last ? 0 : 2, S, N, K, stream)))
+        return rc;
+    }
+  }
+  if (!fused && (rc = namp_logits_log_softmax(w->Wout_w, w->Wout_b, b.h3, log_probs, nullptr, N, w->vocab, stream))) return rc;
+  return NAMP_OK;
+}

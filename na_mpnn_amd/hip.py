@@ -231,6 +231,10 @@ _PROTOTYPES = {
     "namp_library_in_offset": (sz, [i32] * 8),
     "namp_library_out_offset": (sz, [i32] * 8),
     "namp_library": (i32, [i32] * 5),
+    "namp_mutations_workspace_bytes": (sz, [i32] * 11),
+    "namp_mutations_in_offset": (sz, [i32] * 11),
+    "namp_mutations_out_offset": (sz, [i32] * 11),
+    "namp_mutations": (i32, [i32] * 8),
 }
 
 KERNEL_KINDS = ["gather", "node_linear", "edge_embed", "enc_message", "enc_edge_update", "node_update",

@@ -365,6 +365,41 @@ def pair_terms_dense(pair_terms, L):
     return out
 
 
+MUT_MAX_EDITS = 8     # NAMP_MUT_MAX_EDITS of include/namp.h: residues per site of score_mutations()
+
+
+def mutation_chunks(site_index, site_rows, budget):
+    """The chunk cutter of score_mutations(method="cone"); needs no device.  site_index [n]: the site of every variant; site_rows
+    [n_sites][3]: |U_1..3(site)|; budget: item rows (all three layers) per decoder call.  -> (perm, cuts): perm the variants in a
+    stable order by site (the variants of a site are neighbours and share its plan), cuts [(q0, q1), ...] the chunks as ranges of
+    perm.  A chunk closes before the variant that would take its item total past the budget; a variant that exceeds the budget alone
+    is a chunk of its own."""
+    site_index = [int(s) for s in site_index]
+    perm = sorted(range(len(site_index)), key=lambda v: site_index[v])
+    cuts, q0, total = [], 0, 0
+    for q, v in enumerate(perm):
+        rows = sum(int(r) for r in site_rows[site_index[v]])
+        if q > q0 and total + rows > budget:
+            cuts.append((q0, q))
+            q0, total = q, 0
+        total += rows
+    if len(perm) > q0:
+        cuts.append((q0, len(perm)))
+    return perm, cuts
+
+
+def mutations_dense(out, L):
+    """The result of score_mutations() as dense token log-probs [n, L]: the base entries, overwritten by the sparse rows (for tests
+    and small cases: n * L floats)."""
+    base = out["base_token_log_probs"]
+    n = out["row_offsets"].numel() - 1
+    dense = base[None].expand(n, L).clone()
+    counts = out["row_offsets"][1:] - out["row_offsets"][:-1]
+    variant = torch.repeat_interleave(torch.arange(n, device=counts.device), counts)
+    dense[variant, out["row_residue"].long()] = out["row_token_log_prob"]
+    return dense
+
+
 def leave_one_out_ranks(rank, start=0, stop=None):
     """Decoding ranks of the leave-one-out streams of conditional_probs(): stream i is the order of `rank` [B, L] (the inverse of a
     decoding order) with residue i taken out and appended at the end — rank_i[j] = rank[j] - (rank[j] > rank[i]) for j != i,
@@ -1216,6 +1251,263 @@ class ProteinMPNN(nn.Module):
                 chunks += 1
         cm = (mask * fd["chain_mask"])[0].to(tlp.dtype)
         out.update({"token_log_probs": tlp, "loss": (-tlp * cm).sum(-1) / (cm.sum() + 1e-8), "base_log_probs": base, "chunks": chunks})
+        return out
+
+    def _mutation_arguments(self, fd, positions, tokens, sites, site_tokens, pairs):
+        """The checked arguments of score_mutations() (no device needed) -> (sites int64 [n_sites, M] padded with -1, site_tokens int64
+        [n, 1 + M] (0 in the padded columns), scan): both numpy; scan is None in the general form, else {"positions": the scanned
+        residues (of a pair its first listed member), "tokens": the token axis, "valid": bool [P, T]}."""
+        S_true = fd["S"]
+        if S_true.dim() != 2 or S_true.shape[0] != 1:
+            raise ValueError(f"score_mutations expects one input complex (B == 1); got S of shape {tuple(S_true.shape)}")
+        if fd.get("state_weights") is not None:
+            raise NotImplementedError("score_mutations does not take state_weights (a scan over several backbone states)")
+        L = S_true.shape[1]
+        general = sites is not None or site_tokens is not None
+        if general and (positions is not None or tokens is not None):
+            raise ValueError("score_mutations takes positions / tokens (the scan form) or sites / site_tokens (the general form), not both")
+        if general:
+            if sites is None or site_tokens is None:
+                raise ValueError("the general form of score_mutations needs both sites and site_tokens")
+            if pairs:
+                raise ValueError("pairs=True belongs to the scan form: a general site lists its residues itself")
+            st, tk = torch.as_tensor(sites), torch.as_tensor(site_tokens)
+            if st.dim() != 2 or st.dtype.is_floating_point or st.dtype == torch.bool or st.shape[1] < 1:
+                raise ValueError("sites must be an integer tensor [n_sites, M]")
+            M = st.shape[1]
+            if M > MUT_MAX_EDITS:
+                raise ValueError(f"a site holds at most {MUT_MAX_EDITS} residues; got M = {M}")
+            if tk.dim() != 2 or tk.dtype.is_floating_point or tk.shape[1] != 1 + M:
+                raise ValueError(f"site_tokens must be an integer tensor [n, {1 + M}] (a site index, then one token per column of sites)")
+            st, tk = st.cpu().numpy().astype(np.int64), tk.cpu().numpy().astype(np.int64).copy()
+            for s, row in enumerate(st):
+                res = [int(r) for r in row if r >= 0]
+                if not res or any(r >= L for r in res) or any(r < -1 for r in row):
+                    raise ValueError(f"sites[{s}] must hold 1 to {M} residues of [0, {L}) (padding: -1)")
+                if len(set(res)) != len(res):
+                    raise ValueError(f"sites[{s}] repeats a residue")
+            if len(tk) and (tk[:, 0].min() < 0 or tk[:, 0].max() >= len(st)):
+                raise ValueError(f"site_tokens: a site index is outside [0, {len(st)})")
+            if len(tk):
+                tk[:, 1:][st[tk[:, 0]] < 0] = 0
+                self._check_tokens(torch.from_numpy(tk[:, 1:]), "site_tokens")
+            return st, tk, None
+        host = lambda key: [int(v) for v in fd[key][0].reshape(-1).tolist()]
+        w = [a * b for a, b in zip(fd["mask"][0].reshape(-1).tolist(), fd["chain_mask"][0].reshape(-1).tolist())]
+        if positions is None:
+            pos = [i for i in range(L) if w[i] != 0]
+        else:
+            p = torch.as_tensor(positions)
+            if p.dim() != 1 or p.dtype.is_floating_point or p.dtype == torch.bool:
+                raise ValueError("positions must be a one-dimensional integer tensor")
+            pos = [int(v) for v in p.tolist()]
+            if any(v < 0 or v >= L for v in pos):
+                raise ValueError(f"positions must lie in [0, {L})")
+            if any(b <= a for a, b in zip(pos, pos[1:])):
+                raise ValueError("positions must be ascending and unique")
+        S0, prot, dna, rna = host("S"), host("protein_mask"), host("dna_mask"), host("rna_mask")
+        partner = {}
+        if pairs:
+            if fd.get("paired_wobble") is not None and self._wobble_arguments(fd)[2]:
+                raise NotImplementedError("score_mutations(pairs=True) walks canonical duplexes: paired_wobble is not supported")
+            pr = fd.get("paired_residues")
+            if pr is None or self.restype_to_int is None:
+                raise ValueError("pairs=True needs feature_dict['paired_residues'] and the model's restype_to_int")
+            polymer = self._pair_polymer(fd, pr, L, dna, rna, host("mask"))
+            for i, j, _, _, kind in mapped_groups(L, self.restype_to_int, pr, None, polymer, None)[3]:
+                partner[i] = partner[j] = (i, j, spec.token_map(self.restype_to_int, kind))
+
+        def alphabet(i):
+            """synth.make_complex's ranges: the 20 amino acids, the 4 DNA and the 4 RNA letters."""
+            if dna[i] or (not prot[i] and not rna[i] and 21 <= S0[i] < 26):
+                return range(21, 25)
+            if rna[i] or (not prot[i] and 26 <= S0[i] < 31):
+                return range(26, 30)
+            return range(0, 20)
+        site_list, seen = [], set()
+        for p in pos:                                            # a pair is one site, scanned once from its first listed member
+            members = partner[p][:2] if p in partner else (p,)
+            if members[0] not in seen:
+                seen.add(members[0])
+                site_list.append(members)
+        if tokens is None:
+            T = sorted({t for m in site_list for t in alphabet(m[0])})
+            valid = np.array([[t in alphabet(m[0]) for t in T] for m in site_list], bool).reshape(len(site_list), len(T))
+        else:
+            t = torch.as_tensor(tokens)
+            if t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise ValueError("tokens must be a one-dimensional integer tensor")
+            if t.numel():
+                self._check_tokens(t, "tokens")
+            T = [int(v) for v in t.tolist()]
+            valid = np.ones((len(site_list), len(T)), bool)
+        M = 2 if partner else 1
+        st = np.full((len(site_list), M), -1, np.int64)
+        rows = []
+        for s, members in enumerate(site_list):
+            st[s, :len(members)] = members
+            for q, t in enumerate(T):
+                if valid[s, q]:
+                    rows.append([s, t] + ([partner[members[0]][2][t]] if len(members) == 2 else [0] * (M - 1)))
+        tk = np.array(rows, np.int64).reshape(len(rows), 1 + M)
+        return st, tk, {"positions": [m[0] for m in site_list], "tokens": T, "valid": valid}
+
+    @torch.no_grad()
+    def score_mutations(self, feature_dict, positions=None, tokens=None, sites=None, site_tokens=None, pairs=False, method="auto"):
+        """A mutational scan: for every VARIANT — a SITE of 1 to 8 distinct residues with one token per residue, every other residue
+        keeping feature_dict["S"] — the change of the joint log-likelihood score() reports, delta = sum_i w_i (log p_v(S_v[i]) -
+        log p(S[i])) with w = mask * chain_mask, under score()'s own decoding order (the same randn, batch_size = 1: the definition
+        of score_sequences()).  One input complex (B != 1: ValueError); state_weights: NotImplementedError; ties other than
+        paired_residues with pairs=True are not read.
+        The scan form: positions int [P], ascending and unique (default: mask * chain_mask != 0) x tokens int [T] (default: every
+        letter of the residue's own polymer alphabet — 0..19, 21..24, 26..29 — and the token axis is their union; a given `tokens`
+        is applied to every position as it stands).  pairs=True with feature_dict["paired_residues"]: scanning a paired residue
+        edits its partner too, with the token of the involution paired sample() uses (mapped_groups: spec.WC_SAME / WC_CROSS) — the
+        site is the pair, scanned once, from its first listed member; paired_wobble: NotImplementedError.  The general form:
+        sites int [n_sites, M <= 8] padded with -1 and site_tokens int [n, 1 + M] (a site index, then the tokens; padded columns
+        are ignored).  Both forms at once, positions out of range or not ascending, M > 8, a repeated residue: ValueError; token ids
+        outside [0, vocab): IndexError.
+        Returns "delta_log_likelihood" float32 [n], "loss" [n] (get_score's mean for the variant: base_loss - delta / sum(w)),
+        "base_loss", "base_token_log_probs" [L], "base_log_probs" [1, L, vocab], "decoding_order", "site_index" [n], "sites",
+        "site_tokens", the sparse rows "row_offsets" int64 [n + 1], "row_residue" int32 [nnz], "row_token_log_prob" float32 [nnz]
+        (the variant's own entry on every row of U_3(site), ascending; mutations_dense(out, L) spreads them over [n, L]),
+        "site_rows" int32 [n_sites, 3] (|U_1..3(site)|, read back once; None where the cone route does not apply or "dense" was
+        asked for), "chunks", "method" (the route taken) and, in the scan form, "positions", "tokens" and "delta" [P, T] (NaN where
+        a token lies outside the residue's alphabet).
+        method: "cone" — per site the rows a variant can differ on, U_l(site) = act_l(site) + site (the sets of score_sequences with
+        var = the site), are planned on the device; the items (variant, row of U_l(site)) run through the item kernel of the cone
+        conditionals, laid out by prefix sums, the override rows found by binary search in the site's sorted list (namp_mutations,
+        include/namp.h).  One attached call with zero variants gives the sizes; the host reads them back ONCE and
+        cuts the variants, grouped by site, into calls of at most 3 * score_library_tokens item rows.  Three decoder layers and
+        message_precision "x3" or "fp32" (NotImplementedError otherwise).  "dense" — the explicit library through
+        score_sequences(method="dense"), reduced in torch (every row is listed): every layer count and precision mode.  "auto" —
+        decided after the read-back: the cone where it applies and the mean of sum_l |U_l(site)| over the variants is at most 2 L
+        (two thirds of the dense route's 3 L rows: the break-even measured for the item route, score_sequences()), else dense."""
+        if method not in ("auto", "cone", "dense"):
+            raise ValueError(f"method must be 'auto', 'cone' or 'dense'; got {method!r}")
+        fd = feature_dict
+        st, tk, scan = self._mutation_arguments(fd, positions, tokens, sites, site_tokens, pairs)
+        S_true, mask = fd["S"], fd["mask"]
+        L, n, n_sites, M = S_true.shape[1], len(tk), st.shape[0], st.shape[1]
+        cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        if method == "cone" and not cone_ok:
+            raise NotImplementedError("score_mutations(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
+                                      "use method='dense'")
+        _require_device(fd["X"], "X")
+        dev = fd["X"].device
+        w = (mask * fd["chain_mask"])[0].float()
+        out = {"site_index": torch.from_numpy(tk[:, 0].copy()).to(dev), "sites": torch.from_numpy(st).to(dev),
+               "site_tokens": torch.from_numpy(tk).to(dev), "site_rows": None}
+        use_cone, rows_host, base = False, None, None
+        if cone_ok and method != "dense" and n_sites:
+            o = self._decoding_order(mask, fd["chain_mask"], fd["randn"])
+            h_V, h_E, E_idx = self.encode(fd, order=o)
+            self._check_tokens(S_true)
+            o.wait()
+            W, Lb = self._weights(), hip.lib()
+            K = E_idx.shape[2]
+            E32, S32, m32, r32 = _i32(E_idx), _i32(self._as(S_true, "i32")), _i32(self._as(mask, "i32")), _i32(o.rank[:1])
+            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+            base = torch.empty(1, L, self.num_letters, device=dev)
+            sites8 = np.full((n_sites, MUT_MAX_EDITS), -1, np.int32)
+            sites8[:, :M] = st
+            tok9 = np.zeros((n, 1 + MUT_MAX_EDITS), np.int32)
+            tok9[:, :1 + M] = tk
+
+            def call(site_ids, variant_ids, lcap, icap):
+                """One attached decoder call over the listed sites and variants -> its workspace and the offset of its output section."""
+                ns, nv = len(site_ids), len(variant_ids)
+                dims = (L, K, 3, ns, nv) + tuple(lcap) + tuple(icap)
+                need = Lb.namp_mutations_workspace_bytes(*dims)
+                if need == 0:
+                    raise ValueError(f"score_mutations: no workspace for L={L} K={K} sites={ns} variants={nv}")
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                local = np.zeros(n_sites, np.int32)
+                local[site_ids] = np.arange(ns, dtype=np.int32)
+                var = tok9[variant_ids].copy()
+                var[:, 0] = local[var[:, 0]]
+                sec = torch.from_numpy(np.concatenate((sites8[site_ids].reshape(-1), var.reshape(-1))))
+                ioff = Lb.namp_mutations_in_offset(*dims)
+                ws[ioff:ioff + 4 * sec.numel()].view(torch.int32).copy_(sec)
+                ws[ioff + 4 * sec.numel():ioff + 4 * (sec.numel() + L)].view(torch.float32).copy_(w)     # (the weights never leave the device)
+                hip.check(Lb.namp_mutations(*dims[3:]), "mutations")
+                hip.check(Lb.namp_decoder_fwd(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
+                                              r32.data_ptr(), base.data_ptr(), None, None, ws.data_ptr(), ws.numel(), 1, 1, L, K,
+                                              hip.current_stream()), "decoder_fwd (mutations)")
+                return ws, Lb.namp_mutations_out_offset(*dims)
+
+            ws, ooff = call(np.arange(n_sites), np.zeros(0, np.int64), (0, 0, 0), (0, 0, 0))      # the plan alone: the sizes, and base_log_probs
+            out["site_rows"] = ws[ooff:ooff + 12 * n_sites].view(torch.int32).view(n_sites, 3).clone()
+            rows_host = out["site_rows"].cpu().numpy().astype(np.int64)           # the call's ONE read-back: route and chunks hang on it
+            use_cone = method == "cone" or int(rows_host[tk[:, 0]].sum()) <= 2 * L * n
+        pad = lambda elems: (4 * (elems + 1) + 255) & ~255                        # (the arrays of the output section, include/namp.h)
+        if n == 0:
+            one = dict(fd)
+            one["batch_size"] = 1
+            sc = self.score(one)
+            base, order = sc["log_probs"], sc["decoding_order"]
+            delta = torch.zeros(0, device=dev)
+            rres, rlp = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev)
+            offs = torch.zeros(1, dtype=torch.int64, device=dev)
+            chunks = 0
+        elif use_cone:
+            order = o.order[0]
+            perm, cuts = mutation_chunks(tk[:, 0].tolist(), rows_host.tolist(), 3 * self.score_library_tokens)
+            perm = np.asarray(perm, np.int64)
+            d_l, r_l, e_l = [], [], []
+            for q0, q1 in cuts:
+                vids = perm[q0:q1]
+                sids = np.unique(tk[vids, 0])                                     # (perm is ordered by site: the order of appearance)
+                lcap = rows_host[sids].sum(0).tolist()
+                icap = rows_host[tk[vids, 0]].sum(0).tolist()
+                ws, ooff = call(sids, vids, lcap, icap)
+                a = ooff + pad(3 * len(sids))
+                b = a + pad(len(vids))
+                c = b + pad(icap[2])
+                d_l.append(ws[a:a + 4 * len(vids)].view(torch.float32).clone())
+                r_l.append(ws[b:b + 4 * icap[2]].view(torch.int32).clone())
+                e_l.append(ws[c:c + 4 * icap[2]].view(torch.float32).clone())
+            delta_s, rres, rlp = torch.cat(d_l), torch.cat(r_l), torch.cat(e_l)
+            counts = torch.from_numpy(rows_host[tk[:, 0], 2])
+            offs = torch.cat((torch.zeros(1, dtype=torch.int64), counts.cumsum(0)))
+            pt = torch.from_numpy(perm)
+            delta = torch.empty_like(delta_s)
+            delta[pt.to(dev)] = delta_s
+            if not np.array_equal(perm, np.arange(n)):                                          # the rows back into the order the variants were given in
+                start_sorted = torch.cat((torch.zeros(1, dtype=torch.int64), counts[pt].cumsum(0)))[:-1]
+                start = torch.empty(n, dtype=torch.int64)
+                start[pt] = start_sorted
+                idx = (torch.repeat_interleave(start - offs[:-1], counts) + torch.arange(int(offs[-1]))).to(dev)
+                rres, rlp = rres[idx], rlp[idx]
+            offs = offs.to(dev)
+            chunks = len(cuts)
+        else:
+            S_full = S_true.long().expand(n, L).clone()
+            vi = torch.from_numpy(np.repeat(np.arange(n), M)[(st[tk[:, 0]] >= 0).reshape(-1)]).to(dev)
+            res = st[tk[:, 0]].reshape(-1)
+            keep = res >= 0
+            S_full[vi, torch.from_numpy(res[keep]).to(dev)] = torch.from_numpy(tk[:, 1:].reshape(-1)[keep]).to(dev)
+            union = torch.tensor(sorted({int(r) for r in res[keep]}), dtype=torch.long)
+            lib = self.score_sequences(fd, S_full, union, method="dense")
+            base, order = lib["base_log_probs"], lib["decoding_order"]
+            tlp = lib["token_log_probs"]
+            btlp = base[0].gather(1, S_true[0].long()[:, None])[:, 0]
+            delta = ((tlp - btlp[None]) * w[None]).sum(-1)
+            offs = torch.arange(n + 1, dtype=torch.int64, device=dev) * L
+            rres = torch.arange(L, dtype=torch.int32, device=dev).repeat(n)
+            rlp = tlp.reshape(-1)
+            chunks = lib["chunks"]
+        btlp = base[0].gather(1, S_true[0].long()[:, None])[:, 0]
+        denom = w.sum() + 1e-8
+        base_loss = (-btlp * w).sum() / denom
+        out.update({"delta_log_likelihood": delta, "loss": base_loss - delta / denom, "base_loss": base_loss, "base_token_log_probs": btlp,
+                    "base_log_probs": base, "decoding_order": order, "row_offsets": offs, "row_residue": rres, "row_token_log_prob": rlp,
+                    "chunks": chunks, "method": "cone" if use_cone else "dense"})
+        if scan is not None:
+            grid = torch.full((len(scan["positions"]), len(scan["tokens"])), float("nan"), device=dev)
+            grid[torch.from_numpy(scan["valid"]).to(dev)] = delta
+            out.update({"positions": torch.tensor(scan["positions"], dtype=torch.long, device=dev),
+                        "tokens": torch.tensor(scan["tokens"], dtype=torch.long, device=dev), "delta": grid})
         return out
 
     def _wobble_arguments(self, fd, n_pairs=None):

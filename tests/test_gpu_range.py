@@ -150,8 +150,9 @@ def test_graph_path_parity_modes(name, shape, joint, prec):
 @pytest.mark.parametrize("shape,joint", [("small", False), ("large", True)])
 @pytest.mark.parametrize("name", GRAPH_VARIANTS)
 def test_graph_path_bf16_mode(name, shape, joint):
-    """bf16 MFMA per-edge GEMMs (separate calls, small shape) and additionally bf16 storage of h_E and the gathered tables (joint call, large
-    shape) against the fp64 oracle.  Bar: the accuracy class of the reference's own whole-model bf16 autocast evaluated on the same inputs
+    """bf16 MFMA per-edge GEMMs (separate calls, small shape; joint call, large shape) against the fp64 oracle.  (The joint call stores h_E
+    and the gathered tables as bf16 only with more edge workgroups than two per compute unit: 3 x 840 x 17 has 420, so on 256 compute units
+    it runs the large-batch launches with h_E in fp32 — tests/test_gpu_solvable.py asserts which path a shape takes.)  Bar: the accuracy class of the reference's own whole-model bf16 autocast evaluated on the same inputs
     (cpu_ref under torch.autocast against the fp64 oracle), margin 1 x: max |dlogp| <= max(0.055, autocast's), arg-max agreement >=
     min(0.99, autocast's).  On `shift` and `head` autocast itself falls apart (max |dlogp| above 0.6): finiteness and normalisation only."""
     L = hip.lib()

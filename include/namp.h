@@ -962,6 +962,50 @@ size_t namp_mutations_out_offset(int N, int K, int n_dec, int n_sites, int n_var
                                  int items2, int items3);
 int namp_mutations(int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3);
 
+/* ---- tied score: the joint log-likelihood of tie-consistent sequences, riding on namp_decoder_fwd ----------------------------
+ * What the tied branch of the sampler computes when every token is forced, evaluated in parallel (T = 1, no bias, special tokens
+ * kept).  The carrier runs on the FLATTENED graph of N residues (M backbone states of L residues side by side, block-diagonal E_idx)
+ * with rank = rank0, the ranks of score() repeated per block.  With the groups of the INPUT SECTION (below),
+ *     key(i) = (min of rank0 over i's group) << 4 | listed position of i          (an ungrouped residue: rank0[i] << 4)
+ * and an edge i <- j = E_idx[i, k] is FORWARD when key(j) >= key(i) (the encoder state, no token), HIDDEN-BACKWARD when key(j) <
+ * key(i) and j is in i's group (j's decoder state of the layer without j's token) and BACKWARD otherwise (the decoder state plus the
+ * token of the sequence at j).  Every (sequence, residue) is an item of every layer of dec_items_kernel (namp_loo.h, unchanged);
+ * behind layer 3 the logits rows z are combined per group in listed order, close = the LAST listed member:
+ *     total[c] = sum_t w_t z_t[C_t[c]] + bias[ti_close][c]   for the classes c < n_classes every member has a token for, else -inf
+ *     clp = log_softmax(total);   unit = logsumexp of clp[c] over { c : C_t[c] == S_k[m_t] for every member t }, -inf if there is none
+ * (without classes: n_classes = vocab, the tables are the token maps and the bias is zero; then at most one c matches and the unit
+ * is clp[c]).  An ungrouped residue's unit is the own entry of log_softmax(z).
+ * No entry point takes a pointer.  With the same six ints (N, K, n_dec, n_tables, n_classes, n_chunk),
+ *     namp_tied_score_workspace_bytes(...)  what the attached call requires of ws_bytes (NAMP_EINVAL if smaller); 0 where unsupported:
+ *                                           n_dec != 3, K > N or NAMP_MAX_K, n_tables outside [1, 64], n_classes outside [1, 64]
+ *                                           (n_classes < vocab: NAMP_EINVAL by the call itself), max(n_chunk, 1) * N >= 2^28
+ *     namp_tied_score_in_offset(...)        byte offset in ws of the caller-filled INPUT SECTION (256-byte aligned), 32-bit words: the
+ *                                           group section of namp_loo_classes with B = 1,
+ *                                               next[N], first[N], table_idx[N], weight[N] (float bits),
+ *                                               tables[n_tables][64], bias[n_tables][64] (float bits),
+ *                                           followed by sequences[n_chunk][N] (int32 tokens on the flattened graph)
+ *     namp_tied_score_out_offset(...)       byte offset in ws of the OUTPUT SECTION (256-byte aligned)
+ *                                               int32 [64]            word 0 grouped residues, word 1 hidden-backward edges
+ *                                               float [n_chunk][N]    unit_log_probs: every member of a group carries its value
+ *                                               float [n_chunk][N]    member_log_probs: the own entry of the residue's own log-softmax
+ *                                           the two float arrays follow each other, each padded to a multiple of 256 bytes counted
+ *                                           with ONE extra element
+ * and namp_tied_score(n_tables, n_classes, n_chunk) (NAMP_EINVAL outside the ranges above, and nothing stays attached) attaches them
+ * to the calling thread's NEXT namp_decoder_fwd call (B_dec = B_enc = 1; mask required, logits and h_V_dec NULL), which clears the
+ * attachment whether it succeeds or not; a call that finds a library or a mutational scan attached as well runs none of them
+ * (NAMP_EINVAL).  log_probs [N, vocab] receives the members' own log-softmax rows of the chunk's FIRST sequence; with n_chunk = 0 the
+ * call plans only (the header) and leaves log_probs unwritten.  Three decoder layers of one precision, split-bf16 or exact fp32.
+ * The sections are device data: next / first are validated as for namp_loo_groups (a malformed cycle or one with a masked member:
+ * its residues are ungrouped), table indices, table entries and tokens are clamped, an entry below 0 is "absent": a malformed
+ * section gives a defined result and nothing outside ws and log_probs is written.  The input section is not written.  Separate
+ * launches on `stream`, plain stores, every item owns its rows: two calls give identical bits, and a sequence's bits depend neither
+ * on the call it travels in, nor on its place in it, nor on the other sequences.  Without an attachment namp_decoder_fwd is
+ * unchanged, bit for bit. */
+size_t namp_tied_score_workspace_bytes(int N, int K, int n_dec, int n_tables, int n_classes, int n_chunk);
+size_t namp_tied_score_in_offset(int N, int K, int n_dec, int n_tables, int n_classes, int n_chunk);
+size_t namp_tied_score_out_offset(int N, int K, int n_dec, int n_tables, int n_classes, int n_chunk);
+int namp_tied_score(int n_tables, int n_classes, int n_chunk);
+
 /* ---- measurement hook (bench.py) ------------------------------------------------------------
  * When enabled (thread-local), every kernel launch made through this ABI is bracketed by HIP
  * events on the launch stream; namp_profile_collect() waits for them and returns the summed

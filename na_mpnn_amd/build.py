@@ -19,6 +19,7 @@ UNITS = {"namp.hip": ["namp.hip", "namp_kernels.h", "namp_bf16s32.h", "namp_bf16
          "namp_loo.hip": ["namp_loo.hip", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_library.hip": ["namp_library.hip", "namp_library.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_mutations.hip": ["namp_mutations.hip", "namp_mutations.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
+         "namp_tied.hip": ["namp_tied.hip", "namp_tied.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_states.hip": ["namp_states.hip", "namp_states.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_pairs.hip": ["namp_pairs.hip", "namp_pairs.h", INC],
          "namp_train.hip": ["namp_train.hip", "namp_train.h", "namp_train_dw.h", "namp_metrics.h", "namp_device.h", INC],

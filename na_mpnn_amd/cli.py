@@ -88,6 +88,10 @@ def build_parser():
       "alphabet of the designs, chains in alphabetical order separated by '/', header lines ignored) on --pdb_path with "
       "ProteinMPNN.score_sequences and write scores/<name>.npz; the sequences may differ from the structure only where the usual flags "
       "(--chains_to_design, --fixed_residues, --redesigned_residues, --design_na_only) make it designable")
+    a("--score_tied", type=int, default=0, help="1 - with --score_fasta: the sequences are scored with ProteinMPNN.score_tied, the joint "
+      "log-likelihood under the distribution a TIED design draws from, so that --multi_state 1 / --state_weights, --symmetry_residues, "
+      "--paired_residues / --paired_strands and --paired_wobble 1 are accepted; scores/<name>.npz then holds token_log_probs, leader, "
+      "S, log_likelihood, member_log_probs, consistent, state_weights, decoding_order and chunks (a sequence that breaks a tie: -inf)")
     a("--mutation_scan", type=int, default=0, help="1: no sampling: every point mutation of the residues the usual flags make designable "
       "(--chains_to_design, --fixed_residues, --redesigned_residues, --design_na_only), over the letters of the residue's own polymer, "
       "scored with ProteinMPNN.score_mutations as the change of the structure's joint log-likelihood; with --paired_residues / "
@@ -244,7 +248,11 @@ def main(argv=None):
         raise ValueError(f"--conditional_classes is 0 or 1; got {args.conditional_classes}")
     if args.conditional_classes and not args.conditional_probs_only:
         raise ValueError("--conditional_classes 1 goes with --conditional_probs_only 1")
-    if args.score_fasta and (args.multi_state or args.paired_residues or args.paired_strands or args.paired_wobble or
+    if args.score_tied not in (0, 1):
+        raise ValueError(f"--score_tied is 0 or 1; got {args.score_tied}")
+    if args.score_tied and (not args.score_fasta or args.conditional_probs_only):
+        raise ValueError("--score_tied 1 goes with --score_fasta FILE (and not with --conditional_probs_only)")
+    if args.score_fasta and not args.score_tied and (args.multi_state or args.paired_residues or args.paired_strands or args.paired_wobble or
                              args.conditional_probs_only):
         raise ValueError("--score_fasta scores given sequences on one structure: it does not go with --multi_state, --paired_residues, "
                          "--paired_strands, --paired_wobble or --conditional_probs_only")
@@ -425,6 +433,15 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
                 if ch in dna_to_rna:
                     str_to_int[dna_to_rna[ch]] = t
             lib = fasta_tokens(names, seqs, P["S"], list(P["chain_letters"]), (P["mask"] * chain_mask) != 0, str_to_int, encoded)
+            if args.score_tied:
+                # the joint log-likelihood under the ties of the flags: a unit (a tied group, or a residue alone) counts once
+                out = model.score_tied(fd, torch.from_numpy(lib).to(device))
+                np.savez(os.path.join(base, "scores", name + ".npz"), token_log_probs=out["token_log_probs"].cpu().numpy(),
+                         leader=out["leader"].cpu().numpy(), log_likelihood=out["log_likelihood"].cpu().numpy(),
+                         member_log_probs=out["member_log_probs"].cpu().numpy(), consistent=out["consistent"].cpu().numpy(),
+                         state_weights=np.asarray(state_w if state_w is not None else [1.0], np.float32), S=lib,
+                         decoding_order=out["decoding_order"].cpu().numpy(), chunks=out["chunks"])
+                return
             out = model.score_sequences(fd, torch.from_numpy(lib).to(device))
             np.savez(os.path.join(base, "scores", name + ".npz"), token_log_probs=out["token_log_probs"].cpu().numpy(),
                      loss=out["loss"].cpu().numpy(), sequences=lib, mask=P["mask"], chain_mask=chain_mask,

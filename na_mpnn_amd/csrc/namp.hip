@@ -48,6 +48,12 @@ __attribute__((visibility("hidden"))) int namp_internal_mutations_run(const Namp
                                                                        const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs,
                                                                        const float* logits, const float* h_V_dec, void* ws, size_t ws_bytes,
                                                                        int B_dec, int B_enc, int N, int K, const int* dims, void* stream);
+// and the tied score (namp_tied.hip); dims: n_tables, n_classes, n_chunk
+__attribute__((visibility("hidden"))) int namp_internal_tied_take(int* dims);
+__attribute__((visibility("hidden"))) int namp_internal_tied_run(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
+                                                                  const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs,
+                                                                  const float* logits, const float* h_V_dec, void* ws, size_t ws_bytes,
+                                                                  int B_dec, int B_enc, int N, int K, const int* dims, void* stream);
 
 namespace {
 
@@ -2186,8 +2192,14 @@ int namp_decoder_fwd(const NampModelW* w, const float* h_V_enc, const float* h_E
                      float* h_V_dec, void* ws, size_t ws_bytes, int B_dec, int B_enc, int N, int K, void* stream) {
   {     // a library attached by namp_library (namp_library.hip): this call scores it, and the attachment is gone whatever becomes of the call
     int n_var = 0, n_chunk = 0, rows[3] = {0, 0, 0}, mut[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int tied[3] = {0, 0, 0};
     const int have_lib = namp_internal_library_take(&n_var, &n_chunk, rows);
-    if (namp_internal_mutations_take(mut)) {     // (namp_mutations, namp_mutations.hip: taken and cleared in the same way)
+    const int have_mut = namp_internal_mutations_take(mut);     // (namp_mutations, namp_mutations.hip: taken and cleared in the same way)
+    if (namp_internal_tied_take(tied)) {                        // (namp_tied_score, namp_tied.hip: likewise)
+      if (have_lib || have_mut) return fail(NAMP_EINVAL, "namp_decoder_fwd: a tied score and a library or mutational scan were both attached; none is run");
+      return namp_internal_tied_run(w, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, logits, h_V_dec, ws, ws_bytes, B_dec, B_enc, N, K, tied, stream);
+    }
+    if (have_mut) {
       if (have_lib) return fail(NAMP_EINVAL, "namp_decoder_fwd: a library and a mutational scan were both attached; neither is run");
       return namp_internal_mutations_run(w, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, logits, h_V_dec, ws, ws_bytes, B_dec, B_enc, N, K, mut,
                                          stream);

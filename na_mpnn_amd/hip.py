@@ -235,6 +235,10 @@ _PROTOTYPES = {
     "namp_mutations_in_offset": (sz, [i32] * 11),
     "namp_mutations_out_offset": (sz, [i32] * 11),
     "namp_mutations": (i32, [i32] * 8),
+    "namp_tied_score_workspace_bytes": (sz, [i32] * 6),
+    "namp_tied_score_in_offset": (sz, [i32] * 6),
+    "namp_tied_score_out_offset": (sz, [i32] * 6),
+    "namp_tied_score": (i32, [i32] * 3),
 }
 
 KERNEL_KINDS = ["gather", "node_linear", "edge_embed", "enc_message", "enc_edge_update", "node_update",

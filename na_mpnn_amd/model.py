@@ -155,6 +155,21 @@ def symmetry_visits(groups, weights, order0, L):
     return visits, gf, gl, w
 
 
+def tied_stream_keys(rank0, groups):
+    """The keys of the forced tied stream (score_tied): rank0 [N] the ranks of score()'s order, groups the tied groups
+    (lists of residues in LISTED order, disjoint) -> (key [N], leader [N]) as lists: key(i) = (min of rank0 over i's group) << 4 |
+    listed position of i (an ungrouped residue: rank0[i] << 4), leader(i) = the listed-first member of i's group (i itself when
+    ungrouped).  Sorting the residues by key gives the visits of symmetry_visits; an edge i <- j is forward when key(j) >= key(i),
+    hidden-backward when key(j) < key(i) and leader(j) == leader(i), backward otherwise."""
+    rank0 = [int(r) for r in rank0]
+    key, leader = [r << 4 for r in rank0], list(range(len(rank0)))
+    for g in groups:
+        mn = min(rank0[int(r)] for r in g)
+        for t, r in enumerate(g):
+            key[int(r)], leader[int(r)] = (mn << 4) | t, int(g[0])
+    return key, leader
+
+
 def mapped_groups(L, restype_to_int, pairs=None, pair_weights=None, polymer=None, fixed=None, groups=None, weights=None, maps=None,
                   wobble=None, wobble_bias=None):
     """Groups of mapped symmetry-tied sampling — base pairs (feature_dict["paired_residues"]) and explicit token maps
@@ -1509,6 +1524,255 @@ class ProteinMPNN(nn.Module):
             out.update({"positions": torch.tensor(scan["positions"], dtype=torch.long, device=dev),
                         "tokens": torch.tensor(scan["tokens"], dtype=torch.long, device=dev), "delta": grid})
         return out
+
+    @staticmethod
+    def _tied_combine_plan(ties, classes, dev):
+        """The tied groups of a score_tied() call, bucketed by their size, as device tensors -> [(members [G, m], tables [G, m, W],
+        weights [G, m], have [G, W]: the classes every member has, class bias [G, W] or None)]; W = vocab (token maps) or 64."""
+        buckets = {}
+        for flat, fw, ft, gb, _ in (ties["tied"] if ties is not None else ()):
+            buckets.setdefault(len(flat), []).append((flat, fw, ft, gb))
+        plan = []
+        for m_, groups in sorted(buckets.items()):
+            idx = torch.tensor([g[0] for g in groups], device=dev)
+            w = torch.tensor([g[1] for g in groups], dtype=torch.float32, device=dev)
+            T = torch.tensor([g[2] for g in groups], device=dev)
+            have = (T >= 0).all(1)
+            bias = None
+            if classes:
+                have = have & (torch.arange(T.shape[2], device=dev) < spec.N_CLASSES)[None, :]
+                bias = torch.tensor([g[3] for g in groups], dtype=torch.float32, device=dev)
+            plan.append((idx, T, w, have, bias))
+        return plan
+
+    @staticmethod
+    def _tied_combine(rows, S_flat, plan):
+        """The combine of score_tied()'s torch routes: rows [n, N, vocab] the members' logits or log-softmax rows (one constant per
+        member cancels), S_flat [n, N] the sequences on the flattened graph, plan: _tied_combine_plan -> (unit log-probs [n, N], every
+        member of a group carrying the group's value, -inf where the sequence breaks the tie; the own entries of the own log-softmax
+        [n, N]).  Per group the members are summed in listed order; the bias is added last."""
+        own = torch.log_softmax(rows, -1).gather(2, S_flat[:, :, None])[:, :, 0]
+        unit = own.clone()
+        n, ninf = rows.shape[0], float("-inf")
+        for idx, T, w, have, bias in plan:
+            G, m_, W = T.shape
+            s = S_flat[:, idx]                                                 # [n, G, m]
+            z = rows[:, idx].gather(3, T.clamp(min=0)[None].expand(n, G, m_, W))     # [n, G, m, W]: z_t[C_t[c]]
+            total = w[None, :, 0, None] * z[:, :, 0]
+            for t in range(1, m_):
+                total = total + w[None, :, t, None] * z[:, :, t]
+            if bias is not None:
+                total = total + bias[None]
+            clp = torch.log_softmax(torch.where(have[None], total, torch.full_like(total, ninf)), -1)
+            match = have[None] & (T[None] == s[..., None]).all(2)
+            hit = torch.where(match, clp, torch.full_like(clp, ninf))
+            mx = hit.max(-1).values
+            val = mx + torch.log(torch.exp(hit - torch.where(mx > ninf, mx, torch.zeros_like(mx))[..., None]).sum(-1))
+            unit[:, idx.reshape(-1)] = torch.where(mx > ninf, val, mx)[:, :, None].expand(n, G, m_).reshape(n, G * m_)
+        return unit, own
+
+    @torch.no_grad()
+    def score_tied(self, feature_dict, S_lib=None, method="auto"):
+        """The joint log-likelihood of one or many tie-consistent sequences under exactly the distribution tied sample() draws from
+        (DESIGN.md 5.15): what the tied branch of the sampler computes when every token is forced — T = 1, no `bias`, no omit, no pair
+        terms, special tokens kept: the conventions of conditional_probs().  One input complex (B != 1: ValueError); with state_weights
+        X is [M, L, A, 3] and the shared entries [1, L], as in sample().  S_lib: int [n, L], None = feature_dict["S"] as the one
+        sequence; ids outside [0, vocab) raise IndexError; n = 0 is legal.
+        Ties are read as conditional_probs(tied=True, classes=<paired_wobble asked>) reads them (mapped_groups(fixed=None), LISTED
+        order; with states the union across the states in flat indices m * L + i, state-major, weights w_m * w_member; a group with a
+        masked member is not tied: its residues are units of one; more than hip.loo_group_max() members, more than 64 distinct tables,
+        a residue in two groups: ValueError).
+        The stream.  With order0 score()'s order on the flattened graph, groups are visited when order0 reaches their first member and
+        the members follow each other in listed order: key(i) = (min of rank0 over i's group, listed position of i).  An edge i <- j
+        is forward when key(j) >= key(i) (the encoder state, no token), hidden-backward when key(j) < key(i) and j is in i's group (j's
+        decoder state of the layer WITHOUT j's token) and backward otherwise (the decoder state plus the token S_k[j]).  Per group with
+        member logits z_t, without classes total[a] = sum_t w_t z_t[P_t[a]] in listed order, lp = log_softmax(total), the group token is
+        a = P_1[S_k[m_1]], the unit's log-prob lp[a] if P_t[a] == S_k[m_t] for every t; with classes total[c] = sum_t w_t z_t[C_t[c]] +
+        b[c] over the classes every member has, clp = log_softmax(total), the unit's log-prob the logsumexp of clp[c] over {c : C_t[c] ==
+        S_k[m_t] for all t}.  A sequence that breaks the tie of a group has -inf there.  A unit of one is the own entry of log_softmax(z).
+        Returns "S" [n, L]; "token_log_probs" float32 [n, L] (the log-prob of the unit residue i belongs to: every member of a group
+        carries the group's value); "leader" int64 [L] (the listed-first member of each residue's unit, in state 0's block);
+        "log_likelihood" [n] (the sum of token_log_probs[:, leader] over the distinct units whose leader has mask * chain_mask != 0);
+        "member_log_probs" [n, M, L] (the own-entry untied log-prob of every state's copy, from the same stream; M = 1 without states);
+        "consistent" bool [n] (every counted unit finite); "decoding_order"; "chunks" (decoder calls made); "method" (the route taken).
+        method: "items" — every (sequence, flat residue) of a chunk is an item of every layer of the item kernel of the cone
+        conditionals (namp_tied_score, include/namp.h), score_library_tokens // (M L) sequences per call, nothing read back: three
+        decoder layers and message_precision "x3" or "fp32" (NotImplementedError otherwise).  "stream" — the ordinary decoder with the
+        M states as the encoder batch and the sequences times M as streams, combined in torch; hidden-backward edges are the one
+        difference from the ordinary decoder run with `key` as its rank and exist only where two members of a group are graph
+        neighbours, so the route is defined with state_weights alone or no tie at all (ValueError otherwise).  "sampler" — the slow
+        route and on-device check: teacher-forced design calls (chain_mask all ones, a randn whose sort reproduces order0, T = 1, zero
+        bias, S_forced = the sequences as batch_size streams, the groups without a masked member as symmetry groups), the log_probs rows
+        combined in torch: every number of decoder layers and every precision mode.  "auto" — stream where defined, else items where
+        it applies, else sampler; decided from what the host knows, with no read-back."""
+        if method not in ("auto", "items", "stream", "sampler"):
+            raise ValueError(f"method must be 'auto', 'items', 'stream' or 'sampler'; got {method!r}")
+        fd = feature_dict
+        S_true, mask = fd["S"], fd["mask"]
+        if S_true.dim() != 2 or S_true.shape[0] != 1:
+            raise ValueError(f"score_tied expects one input complex (B == 1); got S of shape {tuple(S_true.shape)}")
+        L = S_true.shape[1]
+        state_w, M = None, 1
+        if fd.get("state_weights") is not None:
+            fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
+            fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
+            fd_chk.pop("S_forced", None)
+            state_w, M, L, _, _ = self._states_arguments(fd_chk)
+        classes = self._wobble_arguments(fd)[2]
+        ties = self._conditional_arguments(fd, 1, L, state_w, True, classes)
+        if S_lib is None:
+            S_lib = S_true
+        S_lib = torch.as_tensor(S_lib)
+        if S_lib.dim() != 2 or S_lib.dtype.is_floating_point or S_lib.dtype == torch.bool or S_lib.shape[1] != L:
+            raise ValueError(f"S_lib must be an integer tensor [n, {L}]; got {tuple(S_lib.shape)}")
+        n = S_lib.shape[0]
+        if n:
+            self._check_tokens(S_lib, "S_lib")
+        pairs, sym = fd.get("paired_residues"), fd.get("symmetry_residues")
+        listed = not (pairs is None or len(pairs) == 0) or not (sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0))
+        items_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        if method == "stream" and listed:
+            raise ValueError("score_tied(method='stream') is defined with state_weights alone or no tie at all: two members of a listed "
+                             "group can be graph neighbours; use method='items' or 'sampler'")
+        if method == "items" and not items_ok:
+            raise NotImplementedError("score_tied(method='items') needs three decoder layers and message_precision 'x3' or 'fp32'; "
+                                      "use method='sampler'")
+        if method == "auto":
+            method = "stream" if not listed else ("items" if items_ok else "sampler")
+        _require_device(fd["X"], "X")
+        dev, N, Vn = fd["X"].device, M * L, self.num_letters
+        S_lib = S_lib.to(dev).long().contiguous()
+        leader = list(range(L))
+        for flat, *_ in (ties["tied"] if ties is not None else ()):
+            for r in flat:
+                if r < L:
+                    leader[r] = flat[0]
+        leader = torch.tensor(leader, dtype=torch.long, device=dev)
+        unit_lp, member_lp = torch.empty(n, N, device=dev), torch.empty(n, N, device=dev)
+        chunk = max(1, min(self.score_library_tokens // N, ((1 << 28) - 1) // N))
+        chunks = 0
+        if method == "sampler":
+            o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1])
+            o.wait()
+            order0 = o.order[0]
+            keep = {k: v for k, v in fd.items() if k not in ("paired_residues", "paired_weights", "paired_wobble", "paired_wobble_bias",
+                                                              "symmetry_residues", "symmetry_weights", "symmetry_token_maps", "pair_bias",
+                                                              "pair_terms", "S_forced")}
+            randn = torch.empty(L, device=dev)
+            randn[order0] = torch.arange(1, L + 1, dtype=torch.float32, device=dev)
+            randn = torch.where(mask[0] != 0, randn, randn * 1e4)              # (a masked residue's sort key is 1e-4 |randn|: its place again)
+            ident = list(range(Vn))
+            groups = [(flat[:len(gw)], gw, ft[:len(gw)]) for flat, _, ft, _, gw in (ties["tied"] if ties is not None else ()) if len(gw) > 1]
+            one = dict(keep, chain_mask=torch.ones_like(fd["chain_mask"]), temperature=1.0, bias=torch.zeros(1, L, Vn, device=dev))
+            if groups:
+                one.update(symmetry_residues=[g for g, _, _ in groups], symmetry_weights=[gw for _, gw, _ in groups])
+                if not classes and any(list(P) != ident for _, _, gm in groups for P in gm):    # (the members' own rows do not depend on the maps)
+                    one["symmetry_token_maps"] = [gm for _, _, gm in groups]
+            else:
+                one.update(symmetry_residues=[[]], symmetry_weights=[[]])
+            plan = self._tied_combine_plan(ties, classes, dev)
+            # what the design call must report: with states score()'s order (the states of a residue side by side are implied), else
+            # the residues sorted by their keys — the groups visited when order0 reaches their first member, in listed order
+            visits = order0
+            if groups and state_w is None and n:
+                rank0 = [0] * L
+                for t, r in enumerate(order0.tolist()):
+                    rank0[r] = t
+                key = tied_stream_keys(rank0, [g for g, _, _ in groups])[0]
+                visits = torch.tensor(sorted(range(L), key=key.__getitem__), device=dev)
+            for k0 in range(0, n, chunk):
+                k1 = min(n, k0 + chunk)
+                S_k = S_lib[k0:k1]
+                got = self._sample(dict(one, randn=randn[None].expand(k1 - k0, L).contiguous(), batch_size=k1 - k0, S_forced=S_k),
+                                   self.sample_level_walk)
+                if not torch.equal(got["decoding_order"][0], visits):
+                    raise RuntimeError("score_tied: the design call did not visit the residues in the order of the tied stream")
+                u, own = self._tied_combine(got["log_probs"].reshape(k1 - k0, N, Vn), S_k.repeat(1, M), plan)
+                unit_lp[k0:k1], member_lp[k0:k1] = u, own
+                chunks += 1
+        else:
+            o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1] if state_w is not None else fd["randn"])
+            fd_enc = fd
+            if state_w is not None:
+                fd_enc = dict(fd)
+                for k in self._STATE_SHARED:
+                    fd_enc[k] = fd[k].expand(M, L)
+            V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
+            h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
+            self._check_tokens(S_true)
+            o.wait()
+            order0, rank = o.order[0], o.rank[:1]
+        if method == "stream":
+            # no group has two members in one state's block: the ordinary decoder with key = the rank of score() is the tied stream
+            sw = torch.tensor([1.0] if state_w is None else state_w, dtype=torch.float32, device=dev)
+            tied_res = (mask[0] != 0) if (state_w is not None and M > 1) else torch.zeros(L, dtype=torch.bool, device=dev)
+            E_long = E_idx.long()
+            for k0 in range(0, n, max(1, chunk)):
+                k1 = min(n, k0 + chunk)
+                nk = k1 - k0
+                S_k = S_lib[k0:k1]
+                S_dec = S_k[:, None, :].expand(nk, M, L).reshape(nk * M, L)
+                lp, lg = self.decode_graph(h_V, h_E, E_long, S_dec, mask.expand(nk * M, L), rank.expand(nk * M, L), want_logits=True)
+                lp, lg = lp.view(nk, M, L, Vn), lg.view(nk, M, L, Vn)
+                own = lp.gather(3, S_k[:, None, :, None].expand(nk, M, L, 1))[..., 0]          # [nk, M, L]
+                total = None
+                for m_ in range(M):                                                            # (listed order: state-major)
+                    term = sw[m_] * lg[:, m_]
+                    total = term if total is None else total + term
+                tied_lp = torch.log_softmax(total, -1).gather(2, S_k[:, :, None])[:, :, 0]     # [nk, L]
+                u = torch.where(tied_res[None, None, :], tied_lp[:, None, :].expand(nk, M, L), own)
+                unit_lp[k0:k1], member_lp[k0:k1] = u.reshape(nk, N), own.reshape(nk, N)
+                chunks += 1
+        elif method == "items":
+            W, Lb = self._weights(), hip.lib()
+            K = E_idx.shape[2]
+            n_cls = spec.N_CLASSES if classes else Vn
+            if ties is None:                               # no tie at all: every residue a unit of one under the identity table
+                ident = list(range(Vn)) + list(range(Vn, spec.N_CLASS_LANES))
+                section = torch.tensor([-1] * N + [0] * N + [0] * N, dtype=torch.int32)
+                section = torch.cat((section, torch.ones(N, dtype=torch.float32).view(torch.int32), torch.tensor(ident, dtype=torch.int32),
+                                     torch.zeros(spec.N_CLASS_LANES, dtype=torch.int32)))
+                n_tab = 1
+            else:
+                section, n_tab = ties["section"], ties["n_tables"]
+                if not classes:                            # (token maps come without a bias block: zeros)
+                    section = torch.cat((section, torch.zeros(n_tab * spec.N_CLASS_LANES, dtype=torch.int32)))
+            section = section.to(dev)
+            E_f = E_idx if M == 1 else (E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).contiguous()
+            rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
+            E32, S32, m32, r32 = _i32(E_f), _i32(rep(self._as(S_true, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
+            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+            seq32 = rep(S_lib).to(torch.int32)
+            rows0 = torch.empty(1, N, Vn, device=dev)             # the carrier's log_probs (the first sequence's own rows): the call requires it
+            for k0 in range(0, n, chunk):
+                k1 = min(n, k0 + chunk)
+                nk = k1 - k0
+                dims = (N, K, 3, n_tab, n_cls, nk)
+                need = Lb.namp_tied_score_workspace_bytes(*dims)
+                if need == 0:
+                    raise ValueError(f"score_tied: no workspace for N={N} K={K} tables={n_tab} sequences={nk}")
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                sec = ws[Lb.namp_tied_score_in_offset(*dims):][:4 * (section.numel() + nk * N)].view(torch.int32)
+                sec[:section.numel()] = section
+                sec[section.numel():] = seq32[k0:k1].reshape(-1)
+                hip.check(Lb.namp_tied_score(n_tab, n_cls, nk), "tied_score")
+                hip.check(Lb.namp_decoder_fwd(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
+                                              r32.data_ptr(), rows0.data_ptr(), None, None, ws.data_ptr(), ws.numel(), 1, 1, N, K,
+                                              hip.current_stream()), "decoder_fwd (tied score)")
+                ooff = Lb.namp_tied_score_out_offset(*dims) + 256
+                span = (4 * (nk * N + 1) + 255) & ~255
+                unit_lp[k0:k1] = ws[ooff:ooff + 4 * nk * N].view(torch.float32).view(nk, N)
+                member_lp[k0:k1] = ws[ooff + span:ooff + span + 4 * nk * N].view(torch.float32).view(nk, N)
+                chunks += 1
+        tlp = unit_lp[:, :L].contiguous()
+        cm = (mask * fd["chain_mask"])[0] != 0
+        counted = torch.zeros(L, dtype=torch.bool, device=dev)
+        counted[leader] = True                                                 # one slot per distinct unit: its leader's
+        counted &= cm
+        picked = tlp[:, counted]
+        return {"S": S_lib, "token_log_probs": tlp, "leader": leader, "log_likelihood": picked.sum(-1), "units": counted.sum(),
+                "member_log_probs": member_lp.view(n, M, L), "consistent": torch.isfinite(picked).all(-1), "decoding_order": order0,
+                "chunks": chunks, "method": method}
 
     def _wobble_arguments(self, fd, n_pairs=None):
         """feature_dict["paired_wobble"] / ["paired_wobble_bias"] in one normal form -> (wobble, wobble_bias, asked): each None, a scalar

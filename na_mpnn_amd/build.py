@@ -14,12 +14,12 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libnamp_hip.so")
 INC = os.path.join("..", "..", "include", "namp.h")
 # translation unit -> files it depends on (each unit is compiled to its own object, in parallel, then linked)
-UNITS = {"namp.hip": ["namp.hip", "namp_kernels.h", "namp_bf16s32.h", "namp_bf16p.h", "namp_node_w.h", "namp_order.h", "namp_device.h", INC],
+UNITS = {"namp.hip": ["namp.hip", "namp_kernels.h", "namp_bf16s32.h", "namp_bf16p.h", "namp_node_w.h", "namp_order.h", "namp_device.h", "namp_attach.h", INC],
          "namp_persist.hip": ["namp_persist.hip", "namp_kernels.h", "namp_device.h"],
-         "namp_loo.hip": ["namp_loo.hip", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
-         "namp_library.hip": ["namp_library.hip", "namp_library.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
-         "namp_mutations.hip": ["namp_mutations.hip", "namp_mutations.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
-         "namp_tied.hip": ["namp_tied.hip", "namp_tied.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
+         "namp_loo.hip": ["namp_loo.hip", "namp_loo.h", "namp_attach.h", "namp_kernels.h", "namp_device.h", INC],
+         "namp_library.hip": ["namp_library.hip", "namp_library.h", "namp_attach.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
+         "namp_mutations.hip": ["namp_mutations.hip", "namp_mutations.h", "namp_attach.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
+         "namp_tied.hip": ["namp_tied.hip", "namp_tied.h", "namp_attach.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_states.hip": ["namp_states.hip", "namp_states.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_pairs.hip": ["namp_pairs.hip", "namp_pairs.h", INC],
          "namp_train.hip": ["namp_train.hip", "namp_train.h", "namp_train_dw.h", "namp_metrics.h", "namp_device.h", INC],

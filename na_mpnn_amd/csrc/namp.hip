@@ -8,9 +8,11 @@
 #include "namp_bf16p.h"
 #include "namp_node_w.h"
 #include "namp_order.h"
+#include "namp_attach.h"
 
 #include <cstdarg>
 #include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 #include <cstdio>
 #include <mutex>
@@ -35,25 +37,6 @@ __attribute__((visibility("hidden"))) int namp_internal_launch_persistent(const 
 
 // error text setter for namp_train.hip (same thread-local buffer; not part of the ABI)
 __attribute__((visibility("hidden"))) int namp_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
-// library scoring rides on namp_decoder_fwd (namp_library.hip)
-__attribute__((visibility("hidden"))) int namp_internal_library_take(int* n_var, int* n_chunk, int* rows);
-__attribute__((visibility("hidden"))) int namp_internal_library_run(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
-                                                                     const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs,
-                                                                     const float* logits, const float* h_V_dec, void* ws, size_t ws_bytes,
-                                                                     int B_dec, int B_enc, int N, int K, int n_var, int n_chunk, const int* rows,
-                                                                     void* stream);
-// so does the mutational scan (namp_mutations.hip); dims: n_sites, n_variants, list capacities [3], item capacities [3]
-__attribute__((visibility("hidden"))) int namp_internal_mutations_take(int* dims);
-__attribute__((visibility("hidden"))) int namp_internal_mutations_run(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
-                                                                       const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs,
-                                                                       const float* logits, const float* h_V_dec, void* ws, size_t ws_bytes,
-                                                                       int B_dec, int B_enc, int N, int K, const int* dims, void* stream);
-// and the tied score (namp_tied.hip); dims: n_tables, n_classes, n_chunk
-__attribute__((visibility("hidden"))) int namp_internal_tied_take(int* dims);
-__attribute__((visibility("hidden"))) int namp_internal_tied_run(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
-                                                                  const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs,
-                                                                  const float* logits, const float* h_V_dec, void* ws, size_t ws_bytes,
-                                                                  int B_dec, int B_enc, int N, int K, const int* dims, void* stream);
 
 namespace {
 
@@ -2190,23 +2173,21 @@ int namp_encdec_fwd(const NampModelW* w, const float* V, const float* E, const i
 int namp_decoder_fwd(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
                      const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs, float* logits,
                      float* h_V_dec, void* ws, size_t ws_bytes, int B_dec, int B_enc, int N, int K, void* stream) {
-  {     // a library attached by namp_library (namp_library.hip): this call scores it, and the attachment is gone whatever becomes of the call
-    int n_var = 0, n_chunk = 0, rows[3] = {0, 0, 0}, mut[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int tied[3] = {0, 0, 0};
-    const int have_lib = namp_internal_library_take(&n_var, &n_chunk, rows);
-    const int have_mut = namp_internal_mutations_take(mut);     // (namp_mutations, namp_mutations.hip: taken and cleared in the same way)
-    if (namp_internal_tied_take(tied)) {                        // (namp_tied_score, namp_tied.hip: likewise)
-      if (have_lib || have_mut) return fail(NAMP_EINVAL, "namp_decoder_fwd: a tied score and a library or mutational scan were both attached; none is run");
-      return namp_internal_tied_run(w, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, logits, h_V_dec, ws, ws_bytes, B_dec, B_enc, N, K, tied, stream);
+  {     // what the thread attached (namp_attach.h): this call carries it, and every attachment is gone whatever becomes of the call
+    static int (*const run[ATTACH_KINDS])(const AttachedCall&, const int*) = {namp_internal_library_run, namp_internal_mutations_run,
+                                                                              namp_internal_tied_run};
+    Attachment att[ATTACH_KINDS];
+    const unsigned on = namp_internal_take_attached(att);
+    if (on & (on - 1)) {                                        // more than one kind: none is run, before any pointer is looked at
+      char names[96] = "";
+      for (int k = 0; k < ATTACH_KINDS; ++k)
+        if (on >> k & 1) snprintf(names + strlen(names), sizeof(names) - strlen(names), "%s%s", names[0] ? " and " : "", ATTACH_NOUN[k]);
+      return fail(NAMP_EINVAL, "namp_decoder_fwd: %s were attached together; none is run", names);
     }
-    if (have_mut) {
-      if (have_lib) return fail(NAMP_EINVAL, "namp_decoder_fwd: a library and a mutational scan were both attached; neither is run");
-      return namp_internal_mutations_run(w, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, logits, h_V_dec, ws, ws_bytes, B_dec, B_enc, N, K, mut,
-                                         stream);
-    }
-    if (have_lib)
-      return namp_internal_library_run(w, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, logits, h_V_dec, ws, ws_bytes, B_dec, B_enc, N, K,
-                                       n_var, n_chunk, rows, stream);
+    for (int k = 0; k < ATTACH_KINDS; ++k)
+      if (on >> k & 1)
+        return run[k](AttachedCall{w, h_V_enc, h_E, E_idx, S, mask, rank, log_probs, logits, h_V_dec, ws, ws_bytes, B_dec, B_enc, N, K, stream},
+                      att[k].dims);
   }
   REQUIRE(w != nullptr, "namp_decoder_fwd: null weights");
   REQUIRE(w->n_dec >= 1 && w->n_dec <= NAMP_MAX_LAYERS, "namp_decoder_fwd: n_dec=%d out of range", w->n_dec);

@@ -611,3 +611,44 @@ static inline int loo_base_stream(const NampModelW* w, const LooBaseStream& b, c
   if (!fused && (rc = namp_logits_log_softmax(w->Wout_w, w->Wout_b, b.h3, log_probs, nullptr, N, w->vocab, stream))) return rc;
   return NAMP_OK;
 }
+
+// ---- the ITEM LAYERS on top of the base stream (namp_library.hip, namp_mutations.hip): per layer the caller's table kernel, then one
+// dec_items_kernel launch over R[l] items whose centre overrides and override rows come from the layer in front
+struct LooItemRows {
+  float* ov1;                        // layer 1's override rows (from the tokens)
+  float *hO[3], *PaO[2], *ovO[2];    // [R_l][128] outputs of layer l's items: states, and the next layer's centre / override rows
+};
+
+// tables(l, R): enqueues the launch that fills tab[l] for R items.  An empty layer ends the walk (stop_at_empty) or is stepped over.
+template <class Tables, class LaunchTables>
+static inline int loo_item_layers(const NampModelW* w, int prec, const float* h_V_enc, const float* h_E, int K, const LooBaseStream& b,
+                                  const LooItemRows& o, const Tables* tab, const long* R, bool stop_at_empty, hipStream_t s,
+                                  LaunchTables tables) {
+  const float* Pa[3] = {b.Pa1, b.Pa2, b.Pa3};
+  const float* Pbw[3] = {b.Pbw1, b.Pbw2, b.Pbw3};
+  const float* hin[3] = {h_V_enc, b.h1, b.h2};
+  const float* cenPa[3] = {b.Pa1, o.PaO[0], o.PaO[1]};
+  const float* cenH[3] = {h_V_enc, o.hO[0], o.hO[1]};
+  const float* ov[3] = {o.ov1, o.ovO[0], o.ovO[1]};
+  for (int l = 0; l < 3; ++l) {
+    if (R[l] == 0) {
+      if (stop_at_empty) break;
+      continue;
+    }
+    const NampDecLayerW* D = &w->dec[l];
+    const Tables& t = tab[l];
+    tables(l, R[l]);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+    LooItemArgs a = loo_items(D, prec, h_E, K, R[l], t.act, t.ctr, t.cen, t.esrc, Pa[l], cenPa[l], hin[l], cenH[l], Pbw[l], b.Pfw[l], ov[l]);
+    loo_tail(a.tail, D, t.msk, t.tok, o.hO[l]);
+    if (l < 2) {
+      const NampDecLayerW* Dn = &w->dec[l + 1];
+      loo_proj(a.tail, Dn->W1a_img, Dn->b1, nullptr, o.PaO[l]);
+      loo_proj(a.tail, Dn->W1v_img, nullptr, Dn->tok, o.ovO[l]);
+    }
+    const int rc = launch_items(a, prec, s);
+    if (rc) return rc;
+  }
+  return NAMP_OK;
+}

@@ -6,18 +6,9 @@
 // per-layer states and tables come from the library's own building blocks (namp_node_linear, namp_dec_message_update, ...).
 #include "../../include/namp.h"
 #include "namp_loo.h"
-
-#include <cstdio>
-
-__attribute__((visibility("hidden"))) int namp_internal_fail(int code, const char* msg);
+#include "namp_attach.h"
 
 namespace {
-
-int lfail(int code, const char* fmt, long a = 0, long b = 0, long c = 0) {
-  char buf[256];
-  snprintf(buf, sizeof(buf), fmt, a, b, c);
-  return namp_internal_fail(code, buf);
-}
 
 // the call's buffers, carved in one fixed order (base == nullptr: sizes only)
 struct LooBuffers {
@@ -39,39 +30,34 @@ struct LooBuffers {
 
 LooBuffers loo_carve(void* base, long G, int K, int n_maps = 0, bool classes = false) {
   LooBuffers b;
-  size_t off = 0;
-  auto take = [&](size_t elems) {
-    void* p = base ? (void*)((char*)base + off) : nullptr;
-    off += (elems * 4 + 255) & ~size_t(255);
-    return p;
-  };
+  WsCarver c(base);
   const size_t g128 = (size_t)G * NAMP_HIDDEN, R = (size_t)G * K, r128 = R * NAMP_HIDDEN, tpn = (K + 15) / 16;
   float** gs[] = {&b.Pa1, &b.Pbw1, &b.Pfw[0], &b.Pfw[1], &b.Pfw[2], &b.h1, &b.Pa2, &b.Pbw2, &b.h2, &b.Pa3, &b.Pbw3,
                   &b.h1o, &b.Pa2o, &b.h2o, &b.Pa3o, &b.h3o};
-  for (float** p : gs) *p = (float*)take(g128);
-  b.partial = (float*)take((size_t)G * tpn * (NAMP_HIDDEN + 1) + 3);
+  for (float** p : gs) *p = c.take<float>(g128);
+  b.partial = c.take<float>((size_t)G * tpn * (NAMP_HIDDEN + 1) + 3);
   float** rs[] = {&b.h1O, &b.Pa2O, &b.Pbw2O, &b.h2O, &b.Pbw3O};
-  for (float** p : rs) *p = (float*)take(r128);
+  for (float** p : rs) *p = c.take<float>(r128);
   int32_t** ri[] = {&b.rev, &b.act1, &b.act2, &b.ctr1, &b.ctr2, &b.cen2, &b.msk1, &b.S1, &b.msk2, &b.S2, &b.eo1, &b.eo2, &b.eo3};
-  for (int32_t** p : ri) *p = (int32_t*)take(R);
-  b.idG = (int32_t*)take((size_t)G); b.ovG = (int32_t*)take((size_t)G);
-  b.esrc1 = (int32_t*)take(R * K); b.esrc2 = (int32_t*)take(R * K);
-  b.bytes = off;
-  b.pin_off = off;
-  b.pin = (int32_t*)take((size_t)4 * G + (size_t)64 * n_maps * (classes ? 2 : 1));
-  b.gl = (int32_t*)take((size_t)G); b.gpos = (int32_t*)take((size_t)G);
-  b.PfwQ[0] = (float*)take(2 * g128); b.PfwQ[1] = (float*)take(2 * g128);
-  b.gkey = (int32_t*)take(R);
-  b.group_bytes = off;
-  b.cls_off = off;
-  b.cls = (float*)take((size_t)64 * G);
-  b.cls_bytes = off;
+  for (int32_t** p : ri) *p = c.take<int32_t>(R);
+  b.idG = c.take<int32_t>((size_t)G); b.ovG = c.take<int32_t>((size_t)G);
+  b.esrc1 = c.take<int32_t>(R * K); b.esrc2 = c.take<int32_t>(R * K);
+  b.bytes = c.off;
+  b.pin_off = c.off;
+  b.pin = c.take<int32_t>((size_t)4 * G + (size_t)64 * n_maps * (classes ? 2 : 1));
+  b.gl = c.take<int32_t>((size_t)G); b.gpos = c.take<int32_t>((size_t)G);
+  b.PfwQ[0] = c.take<float>(2 * g128); b.PfwQ[1] = c.take<float>(2 * g128);
+  b.gkey = c.take<int32_t>(R);
+  b.group_bytes = c.off;
+  b.cls_off = c.off;
+  b.cls = c.take<float>((size_t)64 * G);
+  b.cls_bytes = c.off;
   return b;
 }
 
 int loo_dims(long B, long N, long K) {
-  if (B < 1 || N < 1 || K < 1 || K > NAMP_MAX_K || K > N) return lfail(NAMP_EINVAL, "namp_decoder_loo: bad dims B=%ld N=%ld K=%ld", B, N, K);
-  if (B * N * K >= (1L << LOO_ROW_BITS)) return lfail(NAMP_EINVAL, "namp_decoder_loo: B*N*K=%ld exceeds 2^28 item rows", B * N * K);
+  if (B < 1 || N < 1 || K < 1 || K > NAMP_MAX_K || K > N) return namp_failf(NAMP_EINVAL, "namp_decoder_loo: bad dims B=%ld N=%ld K=%ld", B, N, K);
+  if (B * N * K >= (1L << LOO_ROW_BITS)) return namp_failf(NAMP_EINVAL, "namp_decoder_loo: B*N*K=%ld exceeds 2^28 item rows", B * N * K);
   return NAMP_OK;
 }
 
@@ -95,7 +81,7 @@ size_t namp_loo_pairs_offset(int B, int N, int K, int n_dec) { return namp_loo_w
 
 int namp_loo_pairs(int n_maps) {
   g_loo_attached = {};
-  if (n_maps < 1 || n_maps > 64) return lfail(NAMP_EINVAL, "namp_loo_pairs: n_maps=%ld must be in [1, 64]", n_maps);
+  if (n_maps < 1 || n_maps > 64) return namp_failf(NAMP_EINVAL, "namp_loo_pairs: n_maps=%ld must be in [1, 64]", n_maps);
   g_loo_attached = {n_maps, 0, true};
   return NAMP_OK;
 }
@@ -111,7 +97,7 @@ int namp_loo_group_max(void) { return NAMP_LOO_GROUP_MAX; }
 
 int namp_loo_groups(int n_maps) {
   g_loo_attached = {};
-  if (n_maps < 1 || n_maps > 64) return lfail(NAMP_EINVAL, "namp_loo_groups: n_maps=%ld must be in [1, 64]", n_maps);
+  if (n_maps < 1 || n_maps > 64) return namp_failf(NAMP_EINVAL, "namp_loo_groups: n_maps=%ld must be in [1, 64]", n_maps);
   g_loo_attached = {n_maps, 0, false};
   return NAMP_OK;
 }
@@ -129,9 +115,9 @@ size_t namp_loo_classes_out_offset(int B, int N, int K, int n_dec, int n_tables,
 
 int namp_loo_classes(int n_tables, int n_classes, int groups) {
   g_loo_attached = {};
-  if (n_tables < 1 || n_tables > 64) return lfail(NAMP_EINVAL, "namp_loo_classes: n_tables=%ld must be in [1, 64]", n_tables);
-  if (n_classes < 1 || n_classes > 64) return lfail(NAMP_EINVAL, "namp_loo_classes: n_classes=%ld must be in [vocab, 64]", n_classes);
-  if (groups < 0 || groups > 1) return lfail(NAMP_EINVAL, "namp_loo_classes: groups=%ld must be 0 (pairs) or 1 (groups)", groups);
+  if (n_tables < 1 || n_tables > 64) return namp_failf(NAMP_EINVAL, "namp_loo_classes: n_tables=%ld must be in [1, 64]", n_tables);
+  if (n_classes < 1 || n_classes > 64) return namp_failf(NAMP_EINVAL, "namp_loo_classes: n_classes=%ld must be in [vocab, 64]", n_classes);
+  if (groups < 0 || groups > 1) return namp_failf(NAMP_EINVAL, "namp_loo_classes: groups=%ld must be 0 (pairs) or 1 (groups)", groups);
   g_loo_attached = {n_tables, n_classes, groups == 0};
   return NAMP_OK;
 }
@@ -148,25 +134,25 @@ int namp_decoder_loo(const NampModelW* w, const float* h_V_enc, const float* h_E
   g_loo_attached = {};                                           // (one call only, whatever becomes of it)
   const int n_maps = att.n_tables, n_classes = att.n_classes;
   if (!w || !h_V_enc || !h_E || !E_idx || !S || !mask || !rank || !log_probs || !counts || !ws)
-    return lfail(NAMP_EINVAL, !n_maps        ? "namp_decoder_loo: null pointer argument"
+    return namp_failf(NAMP_EINVAL, !n_maps        ? "namp_decoder_loo: null pointer argument"
                               : att.as_pairs ? "namp_decoder_loo: null pointer argument (pair tables were attached)"
                                              : "namp_decoder_loo: null pointer argument (group tables were attached)");
   if ((((uintptr_t)h_V_enc | (uintptr_t)h_E | (uintptr_t)ws | (uintptr_t)log_probs) & 15u) != 0)
-    return lfail(NAMP_EINVAL, "namp_decoder_loo: h_V_enc / h_E / log_probs / ws must be 16-byte aligned");
+    return namp_failf(NAMP_EINVAL, "namp_decoder_loo: h_V_enc / h_E / log_probs / ws must be 16-byte aligned");
   int prec = PREC_F32;
   int rc = loo_check_weights(w, "namp_decoder_loo", &prec);
   if (rc) return rc;
   if (n_classes && n_classes < w->vocab)
-    return lfail(NAMP_EINVAL, "namp_decoder_loo: n_classes=%ld of the attached class tables is below vocab=%ld", n_classes, w->vocab);
+    return namp_failf(NAMP_EINVAL, "namp_decoder_loo: n_classes=%ld of the attached class tables is below vocab=%ld", n_classes, w->vocab);
   if ((rc = loo_dims(B, N, K))) return rc;
   const long G = (long)B * N, R = G * K;
   LooBuffers b = loo_carve(ws, G, K, n_maps, n_classes != 0);
   static_assert(NAMP_LOO_GROUP_MAX <= 16, "loo_prepare_kernel packs a listed position into 4 bits beside a residue index below 2^27");
-  if (n_maps && 2 * G >= (1L << LOO_ROW_BITS)) return lfail(NAMP_EINVAL, "namp_decoder_loo: 2*B*N=%ld exceeds 2^28 table rows", 2 * G);
+  if (n_maps && 2 * G >= (1L << LOO_ROW_BITS)) return namp_failf(NAMP_EINVAL, "namp_decoder_loo: 2*B*N=%ld exceeds 2^28 table rows", 2 * G);
   const size_t need = n_classes ? b.cls_bytes : n_maps ? b.group_bytes : b.bytes;
   if (need > ws_bytes && n_classes)                              // (the class section is part of the call's arguments: include/namp.h)
-    return lfail(NAMP_EINVAL, "namp_decoder_loo: workspace too small for the attached class tables (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
-  if (need > ws_bytes) return lfail(NAMP_EWORKSPACE, "namp_decoder_loo: workspace too small (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
+    return namp_failf(NAMP_EINVAL, "namp_decoder_loo: workspace too small for the attached class tables (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
+  if (need > ws_bytes) return namp_failf(NAMP_EWORKSPACE, "namp_decoder_loo: workspace too small (%ld bytes, %ld needed)", (long)ws_bytes, (long)need);
   const hipError_t ready = loo_items_ready();
   if (ready != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(ready));
   hipStream_t s = (hipStream_t)stream;

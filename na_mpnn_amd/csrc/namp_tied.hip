@@ -4,20 +4,11 @@
 // encoder state, the keys, the item tables, per layer one dec_items_kernel launch over (sequence, residue) items, the head, the combine.
 #include "../../include/namp.h"
 #include "namp_tied.h"
-
-#include <cstdio>
+#include "namp_attach.h"
 
 namespace {
 
-int bfail(int code, const char* fmt, long a = 0, long b = 0, long c = 0) {
-  char buf[256];
-  snprintf(buf, sizeof(buf), fmt, a, b, c);
-  return namp_internal_fail(code, buf);
-}
-
-struct TiedDims { int N, K, n_tables, n_classes, n_chunk; };
-
-// the call's buffers, carved in one fixed order (base == nullptr: sizes only)
+// the call's buffers, carved in one fixed order
 struct TiedBuffers {
   float *Pfw[3], *Pa1;                           // [N][128] W1v_l . h_V_enc, W1a_1 . h_V_enc + b1
   int32_t *gl, *gpos, *leader;                   // [N]
@@ -30,36 +21,8 @@ struct TiedBuffers {
   int32_t* header;                               // OUTPUT section: int32 [64], then
   float* unit_lp;                                // float [n_chunk][N], then
   float* member_lp;                              // float [n_chunk][N]
-  size_t in_off, out_off, bytes;
+  size_t in_off, out_off, bytes;                 // (all 0: the dims are refused)
 };
-
-TiedBuffers tied_carve(void* base, const TiedDims& d) {
-  TiedBuffers b;
-  size_t off = 0;
-  auto take = [&](size_t elems) {
-    void* p = base ? (void*)((char*)base + off) : nullptr;
-    off += (elems * 4 + 255) & ~size_t(255);
-    return p;
-  };
-  const size_t N = (size_t)d.N, R = (size_t)d.n_chunk * N, g128 = N * NAMP_HIDDEN, r128 = R * NAMP_HIDDEN + 4;
-  for (int l = 0; l < 3; ++l) b.Pfw[l] = (float*)take(g128);
-  b.Pa1 = (float*)take(g128);
-  b.gl = (int32_t*)take(N); b.gpos = (int32_t*)take(N); b.leader = (int32_t*)take(N); b.key = (uint32_t*)take(N);
-  b.tab.ctr = (int32_t*)take(R + 1); b.tab.msk = (int32_t*)take(R + 1); b.tab.tok = (int32_t*)take(R + 1);
-  for (int q = 0; q < 2; ++q) { b.tab.cen[q] = (int32_t*)take(R + 1); b.tab.esrc[q] = (int32_t*)take(R * d.K + 1); }
-  b.in_off = off;
-  b.in = (int32_t*)take(4 * N + 128 * (size_t)d.n_tables + R);
-  b.tokrows = (float*)take(r128);
-  for (int l = 0; l < 2; ++l) {
-    b.hO[l] = (float*)take(r128); b.PaO[l] = (float*)take(r128); b.bwO[l] = (float*)take(r128); b.nbO[l] = (float*)take(r128);
-  }
-  b.out_off = off;
-  b.header = (int32_t*)take(64);
-  b.unit_lp = (float*)take(R + 1);
-  b.member_lp = (float*)take(R + 1);
-  b.bytes = off;
-  return b;
-}
 
 bool tied_dims_ok(int N, int K, int n_dec, int n_tables, int n_classes, int n_chunk) {
   if (N < 1 || K < 1 || K > NAMP_MAX_K || K > N || n_dec != 3 || n_chunk < 0) return false;
@@ -68,44 +31,50 @@ bool tied_dims_ok(int N, int K, int n_dec, int n_tables, int n_classes, int n_ch
   return (long)(n_chunk > 0 ? n_chunk : 1) * N < (1L << LOO_ROW_BITS);
 }
 
-// what the calling thread's NEXT namp_decoder_fwd call scores: taken, and cleared, by that call
-struct TiedAttachment { bool on; int dims[3]; };
-thread_local TiedAttachment g_tied_attached = {};
+// validates, then carves (base == nullptr: sizes only); m: n_tables, n_classes, n_chunk
+TiedBuffers tied_layout(void* base, int N_, int K, int n_dec, const int* m) {
+  TiedBuffers b = {};
+  if (!tied_dims_ok(N_, K, n_dec, m[0], m[1], m[2])) return b;
+  WsCarver c(base);
+  const size_t N = (size_t)N_, R = (size_t)m[2] * N, g128 = N * NAMP_HIDDEN, r128 = R * NAMP_HIDDEN + 4;
+  for (int l = 0; l < 3; ++l) b.Pfw[l] = c.take<float>(g128);
+  b.Pa1 = c.take<float>(g128);
+  b.gl = c.take<int32_t>(N); b.gpos = c.take<int32_t>(N); b.leader = c.take<int32_t>(N); b.key = c.take<uint32_t>(N);
+  b.tab.ctr = c.take<int32_t>(R + 1); b.tab.msk = c.take<int32_t>(R + 1); b.tab.tok = c.take<int32_t>(R + 1);
+  for (int q = 0; q < 2; ++q) { b.tab.cen[q] = c.take<int32_t>(R + 1); b.tab.esrc[q] = c.take<int32_t>(R * K + 1); }
+  b.in_off = c.off;
+  b.in = c.take<int32_t>(4 * N + 128 * (size_t)m[0] + R);
+  b.tokrows = c.take<float>(r128);
+  for (int l = 0; l < 2; ++l) {
+    b.hO[l] = c.take<float>(r128); b.PaO[l] = c.take<float>(r128); b.bwO[l] = c.take<float>(r128); b.nbO[l] = c.take<float>(r128);
+  }
+  b.out_off = c.off;
+  b.header = c.take<int32_t>(64);
+  b.unit_lp = c.take<float>(R + 1);
+  b.member_lp = c.take<float>(R + 1);
+  b.bytes = c.off;
+  return b;
+}
 
 }  // namespace
 
-// (for namp_decoder_fwd, namp.hip) the attachment of the calling thread, cleared
-__attribute__((visibility("hidden"))) int namp_internal_tied_take(int* dims) {
-  const TiedAttachment a = g_tied_attached;
-  g_tied_attached = {};
-  if (!a.on) return 0;
-  for (int q = 0; q < 3; ++q) dims[q] = a.dims[q];
-  return 1;
-}
-
 // the carrier's body with an attachment; m: n_tables, n_classes, n_chunk
-__attribute__((visibility("hidden"))) int namp_internal_tied_run(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
-                                                                  const int32_t* S, const int32_t* mask, const int32_t* rank, float* log_probs,
-                                                                  const float* logits, const float* h_V_dec, void* ws, size_t ws_bytes,
-                                                                  int B_dec, int B_enc, int N, int K, const int* m, void* stream) {
-  if (!w || !h_V_enc || !h_E || !E_idx || !S || !mask || !rank || !log_probs || !ws)
-    return bfail(NAMP_EINVAL, "namp_decoder_fwd: null pointer argument (a tied score was attached; mask is required)");
-  if (logits || h_V_dec) return bfail(NAMP_EINVAL, "namp_decoder_fwd: logits / h_V_dec are not written with a tied score attached");
-  if (B_dec != 1 || B_enc != 1) return bfail(NAMP_EINVAL, "namp_decoder_fwd: a tied score runs on one complex (B_dec=%ld, B_enc=%ld)", B_dec, B_enc);
-  if ((((uintptr_t)h_V_enc | (uintptr_t)h_E | (uintptr_t)ws | (uintptr_t)log_probs) & 15u) != 0)
-    return bfail(NAMP_EINVAL, "namp_decoder_fwd: h_V_enc / h_E / log_probs / ws must be 16-byte aligned (a tied score was attached)");
+__attribute__((visibility("hidden"))) int namp_internal_tied_run(const AttachedCall& c, const int* m) {
+  const char* noun = ATTACH_NOUN[ATTACH_TIED];
   int prec = PREC_F32;
-  int rc = loo_check_weights(w, "namp_decoder_fwd (tied score attached)", &prec);
+  int rc = attached_prologue(c, noun, &prec);
   if (rc) return rc;
-  if (!tied_dims_ok(N, K, w->n_dec, m[0], m[1], m[2]) || m[1] < w->vocab)
-    return bfail(NAMP_EINVAL, "namp_decoder_fwd: bad dims for the attached tied score N=%ld K=%ld n_classes=%ld", N, K, m[1]);
-  const TiedDims d = {N, K, m[0], m[1], m[2]};
-  TiedBuffers b = tied_carve(ws, d);
-  if (b.bytes > ws_bytes)                                        // (the sections are part of the call's arguments: include/namp.h)
-    return bfail(NAMP_EINVAL, "namp_decoder_fwd: workspace too small for the attached tied score (%ld bytes, %ld needed)", (long)ws_bytes,
-                 (long)b.bytes);
-  const hipError_t ready = loo_items_ready();
-  if (ready != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(ready));
+  const NampModelW* w = c.w;
+  const float *h_V_enc = c.h_V_enc, *h_E = c.h_E;
+  const int32_t *E_idx = c.E_idx, *mask = c.mask, *rank = c.rank;
+  float* log_probs = c.log_probs;
+  void* stream = c.stream;
+  const int N = c.N, K = c.K;
+  struct { int n_tables, n_classes, n_chunk; } d = {m[0], m[1], m[2]};
+  TiedBuffers b = tied_layout(c.ws, N, K, w->n_dec, m);
+  if (!b.bytes || d.n_classes < w->vocab)
+    return namp_failf(NAMP_EINVAL, "namp_decoder_fwd: bad dims for the attached tied score N=%ld K=%ld n_classes=%ld", N, K, d.n_classes);
+  if ((rc = attached_ready(c, noun, b.bytes))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const NampDecLayerW *D0 = &w->dec[0], *D1 = &w->dec[1], *D2 = &w->dec[2];
   const long R = (long)d.n_chunk * N;
@@ -165,26 +134,27 @@ __attribute__((visibility("hidden"))) int namp_internal_tied_run(const NampModel
 extern "C" {
 
 size_t namp_tied_score_workspace_bytes(int N, int K, int n_dec, int n_tables, int n_classes, int n_chunk) {
-  if (!tied_dims_ok(N, K, n_dec, n_tables, n_classes, n_chunk)) return 0;
-  return tied_carve(nullptr, TiedDims{N, K, n_tables, n_classes, n_chunk}).bytes;
+  const int m[3] = {n_tables, n_classes, n_chunk};
+  return tied_layout(nullptr, N, K, n_dec, m).bytes;
 }
 
 size_t namp_tied_score_in_offset(int N, int K, int n_dec, int n_tables, int n_classes, int n_chunk) {
-  if (!tied_dims_ok(N, K, n_dec, n_tables, n_classes, n_chunk)) return 0;
-  return tied_carve(nullptr, TiedDims{N, K, n_tables, n_classes, n_chunk}).in_off;
+  const int m[3] = {n_tables, n_classes, n_chunk};
+  return tied_layout(nullptr, N, K, n_dec, m).in_off;
 }
 
 size_t namp_tied_score_out_offset(int N, int K, int n_dec, int n_tables, int n_classes, int n_chunk) {
-  if (!tied_dims_ok(N, K, n_dec, n_tables, n_classes, n_chunk)) return 0;
-  return tied_carve(nullptr, TiedDims{N, K, n_tables, n_classes, n_chunk}).out_off;
+  const int m[3] = {n_tables, n_classes, n_chunk};
+  return tied_layout(nullptr, N, K, n_dec, m).out_off;
 }
 
 int namp_tied_score(int n_tables, int n_classes, int n_chunk) {
-  g_tied_attached = {};
+  namp_internal_detach(ATTACH_TIED);
   if (n_tables < 1 || n_tables > 64 || n_classes < 1 || n_classes > 64 || n_chunk < 0)
-    return bfail(NAMP_EINVAL, "namp_tied_score: n_tables=%ld must be in [1, 64], n_classes=%ld in [1, 64] (the attached call refuses one below the vocabulary), n_chunk=%ld not negative", n_tables,
-                 n_classes, n_chunk);
-  g_tied_attached = {true, {n_tables, n_classes, n_chunk}};
+    return namp_failf(NAMP_EINVAL, "namp_tied_score: n_tables=%ld must be in [1, 64], n_classes=%ld in [1, 64] (the attached call refuses one below the vocabulary), n_chunk=%ld not negative", n_tables,
+                      n_classes, n_chunk);
+  const int m[3] = {n_tables, n_classes, n_chunk};
+  namp_internal_attach(ATTACH_TIED, m, 3);
   return NAMP_OK;
 }
 

@@ -81,6 +81,33 @@ def _require_device(t, what):
                            "(no CPU fallback — use the reference or oracle/cpu_ref.py for CPU checks)")
 
 
+def _section_bytes(elems):
+    """The bytes one array of elems (+ 1) four-byte entries takes in a workspace section: rounded to 256 (include/namp.h)."""
+    return (4 * (elems + 1) + 255) & ~255
+
+
+def _positions_argument(positions, L):
+    """The `positions` of score_sequences() / score_mutations(), checked -> a host list of ints."""
+    p = torch.as_tensor(positions)
+    if p.dim() != 1 or p.dtype.is_floating_point or p.dtype == torch.bool:
+        raise ValueError("positions must be a one-dimensional integer tensor")
+    pos = [int(v) for v in p.tolist()]
+    if any(v < 0 or v >= L for v in pos):
+        raise ValueError(f"positions must lie in [0, {L})")
+    if any(b <= a for a, b in zip(pos, pos[1:])):
+        raise ValueError("positions must be ascending and unique")
+    return pos
+
+
+def _require_one_complex(fd, who, states_note):
+    """One input complex; states_note: what state_weights would mean for `who`, where it does not take them (else None)."""
+    S = fd["S"]
+    if S.dim() != 2 or S.shape[0] != 1:
+        raise ValueError(f"{who} expects one input complex (B == 1); got S of shape {tuple(S.shape)}")
+    if states_note is not None and fd.get("state_weights") is not None:
+        raise NotImplementedError(f"{who} does not take state_weights ({states_note})")
+
+
 def level_work_lists(level, group_first, group_last, order0, E_idx0, split):
     """Work lists of the level-parallel sampler (include/namp.h: namp_decoder_sample_levels / _walk) from the per-visit levels.
 
@@ -967,6 +994,56 @@ class ProteinMPNN(nn.Module):
         zeros = torch.zeros_like(m, dtype=torch.int32)
         return {"log_probs": self.decode_graph(h_V, h_E, E_idx, zeros, m, zeros)}
 
+    # ---- shared by the calls that ride on a decoder call (conditional_probs, score_sequences, score_mutations, score_tied) ----------
+
+    def _item_routes_ok(self):
+        """What the item kernel of the cone conditionals evaluates: three decoder layers, split-bf16 or exact fp32."""
+        return len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+
+    def _state_arguments_of(self, fd):
+        """fd["state_weights"] checked as sample() checks them, for a call that draws nothing -> (state weights, M, L)."""
+        fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
+        fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
+        fd_chk.pop("S_forced", None)
+        return self._states_arguments(fd_chk)[:3]
+
+    def _encode_side_by_side(self, fd, order, state_w, M, L):
+        """The states (one without state_weights) side by side as the encoder batch, as _sample_states featurises them -> h_V, h_E, E_idx."""
+        fd_enc = fd
+        if state_w is not None:
+            fd_enc = dict(fd)
+            for k in self._STATE_SHARED:
+                fd_enc[k] = fd[k].expand(M, L)
+        V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=order)
+        h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
+        return h_V, h_E, E_idx
+
+    def _item_decoder_inputs(self, h_V, h_E, E_idx, S, mask, rank, M, L):
+        """What the ABI calls with item launches read -> (packed weights, h_V, h_E float32 contiguous, E_idx, S, mask, rank int32).  The M
+        states are ONE complex of M * L residues: the block-diagonal flattened graph; S, mask and rank repeat per block."""
+        W = self._weights()
+        E_f = E_idx if M == 1 else (E_idx + (torch.arange(M, dtype=torch.int32, device=h_V.device) * L)[:, None, None]).contiguous()
+        rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
+        E32, S32, m32, r32 = _i32(E_f), _i32(rep(self._as(S, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
+        return W, h_V.float().contiguous(), h_E.float().contiguous(), E32, S32, m32, r32
+
+    def _attached_decoder_call(self, family, dims, attach_args, fill, inputs, log_probs, N, K, what):
+        """One namp_decoder_fwd call that carries what namp_<family>(*attach_args) attaches: the workspace is sized
+        for dims (a size of 0: ValueError(what)), fill(section) writes the input section (a uint8 view from its offset on), then the
+        attach and the call -> (the workspace, the offset of its output section).  inputs: _item_decoder_inputs."""
+        Lb = hip.lib()
+        W, h_V, h_E, E32, S32, m32, r32 = inputs
+        need = getattr(Lb, f"namp_{family}_workspace_bytes")(*dims)
+        if need == 0:
+            raise ValueError(what)
+        ws = torch.empty(need, dtype=torch.uint8, device=h_V.device)
+        fill(ws[getattr(Lb, f"namp_{family}_in_offset")(*dims):])
+        hip.check(getattr(Lb, "namp_" + family)(*attach_args), family)
+        hip.check(Lb.namp_decoder_fwd(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
+                                      r32.data_ptr(), log_probs.data_ptr(), None, None, ws.data_ptr(), ws.numel(), 1, 1, N, K,
+                                      hip.current_stream()), f"decoder_fwd ({family})")
+        return ws, getattr(Lb, f"namp_{family}_out_offset")(*dims)
+
     # streams of the L-stream form of conditional_probs() per decoder call: chunk * L stays within the 64 x 1000 tokens of the B = 64 batches
     loo_dense_tokens = 65536
 
@@ -1026,12 +1103,9 @@ class ProteinMPNN(nn.Module):
         B, L = S_true.shape
         state_w, M = None, 1
         if tied and fd.get("state_weights") is not None:
-            fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
-            fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
-            fd_chk.pop("S_forced", None)
-            state_w, M, L, _, _ = self._states_arguments(fd_chk)
+            state_w, M, L = self._state_arguments_of(fd)
         ties = self._conditional_arguments(fd, B, L, state_w, tied, classes)
-        cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        cone_ok = self._item_routes_ok()
         if method == "cone" and not cone_ok:
             raise NotImplementedError("conditional_probs(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
                                       "use method='dense'")
@@ -1057,14 +1131,8 @@ class ProteinMPNN(nn.Module):
             index = ties["index"].to(dev, non_blocking=True)
             lead = index[:, 0] if index.numel() else index.reshape(-1)
         o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1] if state_w is not None else fd["randn"])
-        if tied and ties is not None:                      # the states (one without state_weights) side by side, as _sample_states featurises them
-            fd_enc = fd
-            if state_w is not None:
-                fd_enc = dict(fd)
-                for k in self._STATE_SHARED:
-                    fd_enc[k] = fd[k].expand(M, L)
-            V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
-            h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
+        if tied and ties is not None:
+            h_V, h_E, E_idx = self._encode_side_by_side(fd, o, state_w, M, L)
         else:
             h_V, h_E, E_idx = self.encode(fd, order=o)
         self._check_tokens(S_true)
@@ -1073,12 +1141,7 @@ class ProteinMPNN(nn.Module):
         out = {"S": S_true, "decoding_order": o.order[0]}
         dev = h_V.device
         if use_cone:
-            W = self._weights()
-            # the M states as ONE complex of M * L residues: the block-diagonal flattened graph; ranks repeat per block
-            E_f = E_idx if M == 1 else (E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).contiguous()
-            rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
-            E32, S32, m32, r32 = _i32(E_f), _i32(rep(self._as(S_true, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
-            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+            W, h_V, h_E, E32, S32, m32, r32 = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, rank, M, L)
             if ties is None:
                 ws = torch.empty(Lb.namp_loo_workspace_bytes(B, N, K, n_dec), dtype=torch.uint8, device=dev)
             elif classes:                                  # the NEXT namp_decoder_loo call reads the section
@@ -1134,23 +1197,13 @@ class ProteinMPNN(nn.Module):
     def _library_arguments(self, fd, S_lib, positions):
         """The checked arguments of score_sequences() (no device needed): -> positions int64 [n_var] as a host list, the tokens at the
         positions [n, n_var] and the full sequences [n, L] (int64, on S_lib's device)."""
+        _require_one_complex(fd, "score_sequences", "a library over several backbone states")
         S_true, mask = fd["S"], fd["mask"]
-        if S_true.dim() != 2 or S_true.shape[0] != 1:
-            raise ValueError(f"score_sequences expects one input complex (B == 1); got S of shape {tuple(S_true.shape)}")
-        if fd.get("state_weights") is not None:
-            raise NotImplementedError("score_sequences does not take state_weights (a library over several backbone states)")
         L = S_true.shape[1]
         if positions is None:
             pos = torch.nonzero((mask[0] * fd["chain_mask"][0]) != 0).reshape(-1).tolist()
         else:
-            p = torch.as_tensor(positions)
-            if p.dim() != 1 or p.dtype.is_floating_point or p.dtype == torch.bool:
-                raise ValueError("positions must be a one-dimensional integer tensor")
-            pos = [int(v) for v in p.tolist()]
-            if any(v < 0 or v >= L for v in pos):
-                raise ValueError(f"positions must lie in [0, {L})")
-            if any(b <= a for a, b in zip(pos, pos[1:])):
-                raise ValueError("positions must be ascending and unique")
+            pos = _positions_argument(positions, L)
         S_lib = torch.as_tensor(S_lib)
         n_var = len(pos)
         if S_lib.dim() != 2 or S_lib.dtype.is_floating_point or S_lib.shape[1] not in (L, n_var):
@@ -1204,7 +1257,7 @@ class ProteinMPNN(nn.Module):
         pos, tokens, S_full = self._library_arguments(fd, S_lib, positions)
         S_true, mask = fd["S"], fd["mask"]
         L, n, n_var = S_true.shape[1], S_full.shape[0], len(pos)
-        active_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        active_ok = self._item_routes_ok()
         if method == "active" and not active_ok:
             raise NotImplementedError("score_sequences(method='active') needs three decoder layers and message_precision 'x3' or 'fp32'; "
                                       "use method='dense'")
@@ -1221,29 +1274,21 @@ class ProteinMPNN(nn.Module):
         tlp = torch.empty(n, L, device=dev)
         chunks = 0
         if use_active:
-            W, Lb = self._weights(), hip.lib()
             K = E_idx.shape[2]
-            E32, S32, m32, r32 = _i32(E_idx), _i32(self._as(S_true, "i32")), _i32(self._as(mask, "i32")), _i32(rank)
-            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+            inputs = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, rank, 1, L)
             pos32 = torch.tensor(pos, dtype=torch.int32).to(dev)
             tok32 = tokens.to(torch.int32)
             base = torch.empty(1, L, self.num_letters, device=dev)
 
             def call(k0, k1, rows):
                 """One attached decoder call over sequences k0 .. k1 - 1 -> its workspace and the offset of its output section."""
-                dims = (L, K, 3, n_var, k1 - k0) + tuple(rows)
-                need = Lb.namp_library_workspace_bytes(*dims)
-                if need == 0:
-                    raise ValueError(f"score_sequences: no library workspace for L={L} K={K} n_var={n_var} sequences={k1 - k0}")
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
-                sec = ws[Lb.namp_library_in_offset(*dims):][:4 * (n_var + (k1 - k0) * n_var)].view(torch.int32)
-                sec[:n_var] = pos32
-                sec[n_var:] = tok32[k0:k1].reshape(-1)
-                hip.check(Lb.namp_library(n_var, k1 - k0, *rows), "library")
-                hip.check(Lb.namp_decoder_fwd(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
-                                              r32.data_ptr(), base.data_ptr(), None, None, ws.data_ptr(), ws.numel(), 1, 1, L, K,
-                                              hip.current_stream()), "decoder_fwd (library)")
-                return ws, Lb.namp_library_out_offset(*dims)
+                def fill(section):
+                    sec = section[:4 * (n_var + (k1 - k0) * n_var)].view(torch.int32)
+                    sec[:n_var] = pos32
+                    sec[n_var:] = tok32[k0:k1].reshape(-1)
+                return self._attached_decoder_call(
+                    "library", (L, K, 3, n_var, k1 - k0) + tuple(rows), (n_var, k1 - k0) + tuple(rows), fill, inputs, base, L, K,
+                    f"score_sequences: no library workspace for L={L} K={K} n_var={n_var} sequences={k1 - k0}")
 
             ws, ooff = call(0, 0, (0, 0, 0))                     # the plan alone: the counts, and base_log_probs
             counts = ws[ooff:ooff + 24].view(torch.int32).clone()
@@ -1272,12 +1317,8 @@ class ProteinMPNN(nn.Module):
         """The checked arguments of score_mutations() (no device needed) -> (sites int64 [n_sites, M] padded with -1, site_tokens int64
         [n, 1 + M] (0 in the padded columns), scan): both numpy; scan is None in the general form, else {"positions": the scanned
         residues (of a pair its first listed member), "tokens": the token axis, "valid": bool [P, T]}."""
-        S_true = fd["S"]
-        if S_true.dim() != 2 or S_true.shape[0] != 1:
-            raise ValueError(f"score_mutations expects one input complex (B == 1); got S of shape {tuple(S_true.shape)}")
-        if fd.get("state_weights") is not None:
-            raise NotImplementedError("score_mutations does not take state_weights (a scan over several backbone states)")
-        L = S_true.shape[1]
+        _require_one_complex(fd, "score_mutations", "a scan over several backbone states")
+        L = fd["S"].shape[1]
         general = sites is not None or site_tokens is not None
         if general and (positions is not None or tokens is not None):
             raise ValueError("score_mutations takes positions / tokens (the scan form) or sites / site_tokens (the general form), not both")
@@ -1312,14 +1353,7 @@ class ProteinMPNN(nn.Module):
         if positions is None:
             pos = [i for i in range(L) if w[i] != 0]
         else:
-            p = torch.as_tensor(positions)
-            if p.dim() != 1 or p.dtype.is_floating_point or p.dtype == torch.bool:
-                raise ValueError("positions must be a one-dimensional integer tensor")
-            pos = [int(v) for v in p.tolist()]
-            if any(v < 0 or v >= L for v in pos):
-                raise ValueError(f"positions must lie in [0, {L})")
-            if any(b <= a for a, b in zip(pos, pos[1:])):
-                raise ValueError("positions must be ascending and unique")
+            pos = _positions_argument(positions, L)
         S0, prot, dna, rna = host("S"), host("protein_mask"), host("dna_mask"), host("rna_mask")
         partner = {}
         if pairs:
@@ -1404,7 +1438,7 @@ class ProteinMPNN(nn.Module):
         st, tk, scan = self._mutation_arguments(fd, positions, tokens, sites, site_tokens, pairs)
         S_true, mask = fd["S"], fd["mask"]
         L, n, n_sites, M = S_true.shape[1], len(tk), st.shape[0], st.shape[1]
-        cone_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        cone_ok = self._item_routes_ok()
         if method == "cone" and not cone_ok:
             raise NotImplementedError("score_mutations(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
                                       "use method='dense'")
@@ -1419,10 +1453,8 @@ class ProteinMPNN(nn.Module):
             h_V, h_E, E_idx = self.encode(fd, order=o)
             self._check_tokens(S_true)
             o.wait()
-            W, Lb = self._weights(), hip.lib()
             K = E_idx.shape[2]
-            E32, S32, m32, r32 = _i32(E_idx), _i32(self._as(S_true, "i32")), _i32(self._as(mask, "i32")), _i32(o.rank[:1])
-            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
+            inputs = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, o.rank[:1], 1, L)
             base = torch.empty(1, L, self.num_letters, device=dev)
             sites8 = np.full((n_sites, MUT_MAX_EDITS), -1, np.int32)
             sites8[:, :M] = st
@@ -1433,29 +1465,22 @@ class ProteinMPNN(nn.Module):
                 """One attached decoder call over the listed sites and variants -> its workspace and the offset of its output section."""
                 ns, nv = len(site_ids), len(variant_ids)
                 dims = (L, K, 3, ns, nv) + tuple(lcap) + tuple(icap)
-                need = Lb.namp_mutations_workspace_bytes(*dims)
-                if need == 0:
-                    raise ValueError(f"score_mutations: no workspace for L={L} K={K} sites={ns} variants={nv}")
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
-                local = np.zeros(n_sites, np.int32)
-                local[site_ids] = np.arange(ns, dtype=np.int32)
-                var = tok9[variant_ids].copy()
-                var[:, 0] = local[var[:, 0]]
-                sec = torch.from_numpy(np.concatenate((sites8[site_ids].reshape(-1), var.reshape(-1))))
-                ioff = Lb.namp_mutations_in_offset(*dims)
-                ws[ioff:ioff + 4 * sec.numel()].view(torch.int32).copy_(sec)
-                ws[ioff + 4 * sec.numel():ioff + 4 * (sec.numel() + L)].view(torch.float32).copy_(w)     # (the weights never leave the device)
-                hip.check(Lb.namp_mutations(*dims[3:]), "mutations")
-                hip.check(Lb.namp_decoder_fwd(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
-                                              r32.data_ptr(), base.data_ptr(), None, None, ws.data_ptr(), ws.numel(), 1, 1, L, K,
-                                              hip.current_stream()), "decoder_fwd (mutations)")
-                return ws, Lb.namp_mutations_out_offset(*dims)
+
+                def fill(section):
+                    local = np.zeros(n_sites, np.int32)
+                    local[site_ids] = np.arange(ns, dtype=np.int32)
+                    var = tok9[variant_ids].copy()
+                    var[:, 0] = local[var[:, 0]]
+                    sec = torch.from_numpy(np.concatenate((sites8[site_ids].reshape(-1), var.reshape(-1))))
+                    section[:4 * sec.numel()].view(torch.int32).copy_(sec)
+                    section[4 * sec.numel():4 * (sec.numel() + L)].view(torch.float32).copy_(w)           # (the weights never leave the device)
+                return self._attached_decoder_call("mutations", dims, dims[3:], fill, inputs, base, L, K,
+                                                   f"score_mutations: no workspace for L={L} K={K} sites={ns} variants={nv}")
 
             ws, ooff = call(np.arange(n_sites), np.zeros(0, np.int64), (0, 0, 0), (0, 0, 0))      # the plan alone: the sizes, and base_log_probs
             out["site_rows"] = ws[ooff:ooff + 12 * n_sites].view(torch.int32).view(n_sites, 3).clone()
             rows_host = out["site_rows"].cpu().numpy().astype(np.int64)           # the call's ONE read-back: route and chunks hang on it
             use_cone = method == "cone" or int(rows_host[tk[:, 0]].sum()) <= 2 * L * n
-        pad = lambda elems: (4 * (elems + 1) + 255) & ~255                        # (the arrays of the output section, include/namp.h)
         if n == 0:
             one = dict(fd)
             one["batch_size"] = 1
@@ -1476,9 +1501,9 @@ class ProteinMPNN(nn.Module):
                 lcap = rows_host[sids].sum(0).tolist()
                 icap = rows_host[tk[vids, 0]].sum(0).tolist()
                 ws, ooff = call(sids, vids, lcap, icap)
-                a = ooff + pad(3 * len(sids))
-                b = a + pad(len(vids))
-                c = b + pad(icap[2])
+                a = ooff + _section_bytes(3 * len(sids))
+                b = a + _section_bytes(len(vids))
+                c = b + _section_bytes(icap[2])
                 d_l.append(ws[a:a + 4 * len(vids)].view(torch.float32).clone())
                 r_l.append(ws[b:b + 4 * icap[2]].view(torch.int32).clone())
                 e_l.append(ws[c:c + 4 * icap[2]].view(torch.float32).clone())
@@ -1608,16 +1633,12 @@ class ProteinMPNN(nn.Module):
         if method not in ("auto", "items", "stream", "sampler"):
             raise ValueError(f"method must be 'auto', 'items', 'stream' or 'sampler'; got {method!r}")
         fd = feature_dict
+        _require_one_complex(fd, "score_tied", None)
         S_true, mask = fd["S"], fd["mask"]
-        if S_true.dim() != 2 or S_true.shape[0] != 1:
-            raise ValueError(f"score_tied expects one input complex (B == 1); got S of shape {tuple(S_true.shape)}")
         L = S_true.shape[1]
         state_w, M = None, 1
         if fd.get("state_weights") is not None:
-            fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
-            fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
-            fd_chk.pop("S_forced", None)
-            state_w, M, L, _, _ = self._states_arguments(fd_chk)
+            state_w, M, L = self._state_arguments_of(fd)
         classes = self._wobble_arguments(fd)[2]
         ties = self._conditional_arguments(fd, 1, L, state_w, True, classes)
         if S_lib is None:
@@ -1630,7 +1651,7 @@ class ProteinMPNN(nn.Module):
             self._check_tokens(S_lib, "S_lib")
         pairs, sym = fd.get("paired_residues"), fd.get("symmetry_residues")
         listed = not (pairs is None or len(pairs) == 0) or not (sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0))
-        items_ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        items_ok = self._item_routes_ok()
         if method == "stream" and listed:
             raise ValueError("score_tied(method='stream') is defined with state_weights alone or no tie at all: two members of a listed "
                              "group can be graph neighbours; use method='items' or 'sampler'")
@@ -1692,13 +1713,7 @@ class ProteinMPNN(nn.Module):
                 chunks += 1
         else:
             o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1] if state_w is not None else fd["randn"])
-            fd_enc = fd
-            if state_w is not None:
-                fd_enc = dict(fd)
-                for k in self._STATE_SHARED:
-                    fd_enc[k] = fd[k].expand(M, L)
-            V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
-            h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
+            h_V, h_E, E_idx = self._encode_side_by_side(fd, o, state_w, M, L)
             self._check_tokens(S_true)
             o.wait()
             order0, rank = o.order[0], o.rank[:1]
@@ -1724,7 +1739,6 @@ class ProteinMPNN(nn.Module):
                 unit_lp[k0:k1], member_lp[k0:k1] = u.reshape(nk, N), own.reshape(nk, N)
                 chunks += 1
         elif method == "items":
-            W, Lb = self._weights(), hip.lib()
             K = E_idx.shape[2]
             n_cls = spec.N_CLASSES if classes else Vn
             if ties is None:                               # no tie at all: every residue a unit of one under the identity table
@@ -1738,29 +1752,21 @@ class ProteinMPNN(nn.Module):
                 if not classes:                            # (token maps come without a bias block: zeros)
                     section = torch.cat((section, torch.zeros(n_tab * spec.N_CLASS_LANES, dtype=torch.int32)))
             section = section.to(dev)
-            E_f = E_idx if M == 1 else (E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).contiguous()
-            rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
-            E32, S32, m32, r32 = _i32(E_f), _i32(rep(self._as(S_true, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
-            h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
-            seq32 = rep(S_lib).to(torch.int32)
+            inputs = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, rank, M, L)
+            seq32 = (S_lib if M == 1 else S_lib.repeat(1, M)).to(torch.int32)
             rows0 = torch.empty(1, N, Vn, device=dev)             # the carrier's log_probs (the first sequence's own rows): the call requires it
             for k0 in range(0, n, chunk):
                 k1 = min(n, k0 + chunk)
                 nk = k1 - k0
-                dims = (N, K, 3, n_tab, n_cls, nk)
-                need = Lb.namp_tied_score_workspace_bytes(*dims)
-                if need == 0:
-                    raise ValueError(f"score_tied: no workspace for N={N} K={K} tables={n_tab} sequences={nk}")
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
-                sec = ws[Lb.namp_tied_score_in_offset(*dims):][:4 * (section.numel() + nk * N)].view(torch.int32)
-                sec[:section.numel()] = section
-                sec[section.numel():] = seq32[k0:k1].reshape(-1)
-                hip.check(Lb.namp_tied_score(n_tab, n_cls, nk), "tied_score")
-                hip.check(Lb.namp_decoder_fwd(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
-                                              r32.data_ptr(), rows0.data_ptr(), None, None, ws.data_ptr(), ws.numel(), 1, 1, N, K,
-                                              hip.current_stream()), "decoder_fwd (tied score)")
-                ooff = Lb.namp_tied_score_out_offset(*dims) + 256
-                span = (4 * (nk * N + 1) + 255) & ~255
+
+                def fill(sec):
+                    sec = sec[:4 * (section.numel() + nk * N)].view(torch.int32)
+                    sec[:section.numel()] = section
+                    sec[section.numel():] = seq32[k0:k1].reshape(-1)
+                ws, ooff = self._attached_decoder_call("tied_score", (N, K, 3, n_tab, n_cls, nk), (n_tab, n_cls, nk), fill, inputs, rows0, N, K,
+                                                       f"score_tied: no workspace for N={N} K={K} tables={n_tab} sequences={nk}")
+                ooff += 256
+                span = _section_bytes(nk * N)
                 unit_lp[k0:k1] = ws[ooff:ooff + 4 * nk * N].view(torch.float32).view(nk, N)
                 member_lp[k0:k1] = ws[ooff + span:ooff + span + 4 * nk * N].view(torch.float32).view(nk, N)
                 chunks += 1

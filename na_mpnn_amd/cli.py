@@ -57,6 +57,9 @@ def build_parser():
     a("--multi_state", type=int, default=0, help="1 - the MODELs of --pdb_path are states of one molecule: ONE sequence is designed "
       "to fit all of them (ProteinMPNN.sample with state_weights)")
     a("--state_weights", type=str, default="", help="weights of the states in model order, e.g. '0.5,0.3,0.2' (default: 1/M each)")
+    a("--state_contexts", type=int, default=0, help="1 (with --multi_state 1) - the MODELs are context states: they may differ in the "
+      "names of FIXED residues and lack residues or whole chains (on-target against off-target partner, bound against unbound; signed "
+      "--state_weights such as '1,-0.5'); the residue list is the union of the models (ProteinMPNN.sample with state_S / state_mask)")
     a("--paired_residues", type=str, default="", help="base pairs, e.g. 'A5:B20,A6:B19' (residues named as in --fixed_residues): the "
       "second residue of a pair receives the Watson-Crick complement of the first (canonical pairs; G-U as well with --paired_wobble 1; "
       "a fixed residue decides)")
@@ -256,6 +259,12 @@ def main(argv=None):
                              args.conditional_probs_only):
         raise ValueError("--score_fasta scores given sequences on one structure: it does not go with --multi_state, --paired_residues, "
                          "--paired_strands, --paired_wobble or --conditional_probs_only")
+    if args.state_contexts not in (0, 1):
+        raise ValueError(f"--state_contexts is 0 or 1; got {args.state_contexts}")
+    if args.state_contexts and not args.multi_state:
+        raise ValueError("--state_contexts 1 reads the MODELs of the file as states: it needs --multi_state 1")
+    if args.state_contexts and args.conditional_probs_only:
+        raise ValueError("--state_contexts 1 does not go with --conditional_probs_only: conditional_probs() takes no context states")
     if args.mutation_scan not in (0, 1):
         raise ValueError(f"--mutation_scan is 0 or 1; got {args.mutation_scan}")
     if args.mutation_scan and (args.score_fasta or args.conditional_probs_only or args.multi_state or args.paired_wobble):
@@ -346,9 +355,10 @@ def main(argv=None):
 def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bias_AA, omit_AA, int_to_str, dna_to_rna, rti, base,
             pair_bias_AA=None):
     parse = pdbio.parse_states if args.multi_state else pdbio.parse_pdb
+    more = {"contexts": True} if args.state_contexts else {}
     P = parse(pdb, chains=list(args.parse_these_chains_only) or None, parse_na_only=bool(args.parse_na_only),
               na_shared_tokens=bool(args.na_shared_tokens),
-              load_residues_with_missing_atoms=bool(args.load_residues_with_missing_atoms))
+              load_residues_with_missing_atoms=bool(args.load_residues_with_missing_atoms), **more)
     state_w = None
     if args.multi_state:
         if args.conditional_probs_only and not args.conditional_tied:
@@ -397,6 +407,9 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
             fd["X"] = torch.as_tensor(X_states, dtype=torch.float32, device=device)
             fd["X_m"] = torch.as_tensor(X_m_states, dtype=torch.int32, device=device)
             fd["state_weights"] = state_w
+            if args.state_contexts:
+                fd["state_S"] = torch.as_tensor(P["state_S"], dtype=torch.int64, device=device)
+                fd["state_mask"] = torch.as_tensor(P["state_mask"], dtype=torch.int32, device=device)
             wn = torch.tensor(state_w, device=device)
             wn = wn / wn.sum() if float(wn.sum()) != 0 else torch.full_like(wn, 1.0 / len(state_w))
         if pair_bias_AA is not None:
@@ -440,7 +453,8 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
                          leader=out["leader"].cpu().numpy(), log_likelihood=out["log_likelihood"].cpu().numpy(),
                          member_log_probs=out["member_log_probs"].cpu().numpy(), consistent=out["consistent"].cpu().numpy(),
                          state_weights=np.asarray(state_w if state_w is not None else [1.0], np.float32), S=lib,
-                         decoding_order=out["decoding_order"].cpu().numpy(), chunks=out["chunks"])
+                         decoding_order=out["decoding_order"].cpu().numpy(), chunks=out["chunks"],
+                         **({"state_log_likelihood": out["state_log_likelihood"].cpu().numpy()} if "state_log_likelihood" in out else {}))
                 return
             out = model.score_sequences(fd, torch.from_numpy(lib).to(device))
             np.savez(os.path.join(base, "scores", name + ".npz"), token_log_probs=out["token_log_probs"].cpu().numpy(),
@@ -458,7 +472,7 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
                      base_loss=out["base_loss"].cpu().numpy(), wild_type_token=np.asarray(P["S"])[scanned],
                      site_rows=(out["site_rows"].cpu().numpy() if out["site_rows"] is not None else np.zeros((0, 3), np.int32)))
             return
-        S_l, lp_l, sp_l, loss_l, lpr_l = [], [], [], [], []
+        S_l, lp_l, sp_l, loss_l, lpr_l, Ss_l = [], [], [], [], [], []
         cmask = (fd["mask"] * fd["chain_mask"]).float()
         forced = np.load(args.forced_draws_npz) if args.forced_draws_npz else None
         model.sample_check_walk = True      # verify the persistent level walk's barriers per design call; falls back to per-level launches
@@ -477,6 +491,8 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
             lpr_l.append(lpr)
             loss_l.append((lpr * cmask).sum(-1) / (cmask.sum(-1) + 1e-8))
             S_l.append(out["S"]); lp_l.append(out["log_probs"]); sp_l.append(out["sampling_probs"])
+            if "S_states" in out:
+                Ss_l.append(out["S_states"])
         S_stack, sp_stack, loss_stack, lpr_stack = torch.cat(S_l), torch.cat(sp_l), torch.cat(loss_l), torch.cat(lpr_l)
         rec = ((fd["S"][:1] == S_stack) * cmask).sum(-1) / cmask.sum(-1)               # get_seq_rec, data_utils.py:18-30
 
@@ -508,9 +524,12 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
                  encoded_residues=encoded, encoded_residues_dict=encoded_dict, restype_to_int=rti)
     if args.save_stats:
         os.makedirs(base + "stats", exist_ok=True)
-        torch.save({"generated_sequences": S_stack.cpu(), "sampling_probs": sp_stack.cpu(), "log_probs": torch.cat(lp_l).cpu(),
-                    "native_sequence": fd["S"][0].cpu(), "mask": fd["mask"][0].cpu(), "chain_mask": fd["chain_mask"][0].cpu(),
-                    "seed": seed, "temperature": args.temperature}, base + "stats/" + name + ".pt")
+        stats = {"generated_sequences": S_stack.cpu(), "sampling_probs": sp_stack.cpu(), "log_probs": torch.cat(lp_l).cpu(),
+                 "native_sequence": fd["S"][0].cpu(), "mask": fd["mask"][0].cpu(), "chain_mask": fd["chain_mask"][0].cpu(),
+                 "seed": seed, "temperature": args.temperature}
+        if Ss_l:                                        # context states: the token every state's copy holds [n, M, L]
+            stats["S_states"] = torch.cat(Ss_l).cpu()
+        torch.save(stats, base + "stats/" + name + ".pt")
 
 
 if __name__ == "__main__":

@@ -1001,30 +1001,38 @@ class ProteinMPNN(nn.Module):
         return len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
 
     def _state_arguments_of(self, fd):
-        """fd["state_weights"] checked as sample() checks them, for a call that draws nothing -> (state weights, M, L)."""
+        """fd["state_weights"] checked as sample() checks them, for a call that draws nothing -> (state weights, M, L, the context
+        states of _state_contexts or None)."""
         fd_chk = dict(fd, batch_size=int(fd["randn"].shape[0]))
         fd_chk.setdefault("bias", torch.zeros(1, 1, self.num_letters))
         fd_chk.pop("S_forced", None)
-        return self._states_arguments(fd_chk)[:3]
+        got = self._states_arguments(fd_chk)
+        return got[:3] + got[5:]
 
-    def _encode_side_by_side(self, fd, order, state_w, M, L):
-        """The states (one without state_weights) side by side as the encoder batch, as _sample_states featurises them -> h_V, h_E, E_idx."""
+    def _encode_side_by_side(self, fd, order, state_w, M, L, ctx=None):
+        """The states (one without state_weights) side by side as the encoder batch, as _sample_states featurises them -> h_V, h_E, E_idx.
+        ctx: the context states (every state with its own tokens and presence) or None."""
         fd_enc = fd
         if state_w is not None:
             fd_enc = dict(fd)
             for k in self._STATE_SHARED:
                 fd_enc[k] = fd[k].expand(M, L)
+            if ctx is not None:
+                fd_enc["S"], fd_enc["mask"] = ctx[:2]
         V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=order)
         h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
         return h_V, h_E, E_idx
 
-    def _item_decoder_inputs(self, h_V, h_E, E_idx, S, mask, rank, M, L):
+    def _item_decoder_inputs(self, h_V, h_E, E_idx, S, mask, rank, M, L, ctx=None):
         """What the ABI calls with item launches read -> (packed weights, h_V, h_E float32 contiguous, E_idx, S, mask, rank int32).  The M
-        states are ONE complex of M * L residues: the block-diagonal flattened graph; S, mask and rank repeat per block."""
+        states are ONE complex of M * L residues: the block-diagonal flattened graph; S, mask and rank repeat per block
+        (with context states, ctx, S and mask are the states' own rows)."""
         W = self._weights()
         E_f = E_idx if M == 1 else (E_idx + (torch.arange(M, dtype=torch.int32, device=h_V.device) * L)[:, None, None]).contiguous()
         rep = (lambda t: t) if M == 1 else (lambda t: t.repeat(1, M))
         E32, S32, m32, r32 = _i32(E_f), _i32(rep(self._as(S, "i32"))), _i32(rep(self._as(mask, "i32"))), _i32(rep(_i32(rank)))
+        if ctx is not None:
+            S32, m32 = _i32(ctx[0].reshape(1, M * L)), _i32(ctx[1].reshape(1, M * L))
         return W, h_V.float().contiguous(), h_E.float().contiguous(), E32, S32, m32, r32
 
     def _attached_decoder_call(self, family, dims, attach_args, fill, inputs, log_probs, N, K, what):
@@ -1099,11 +1107,13 @@ class ProteinMPNN(nn.Module):
         if method not in ("auto", "dense", "cone"):
             raise ValueError(f"method must be 'auto', 'dense' or 'cone'; got {method!r}")
         fd, tied, classes = feature_dict, bool(tied), bool(classes)
+        if fd.get("state_S") is not None or fd.get("state_mask") is not None:
+            raise NotImplementedError("conditional_probs does not take context states (state_S / state_mask): score_tied() scores them")
         S_true, mask = fd["S"], fd["mask"]
         B, L = S_true.shape
         state_w, M = None, 1
         if tied and fd.get("state_weights") is not None:
-            state_w, M, L = self._state_arguments_of(fd)
+            state_w, M, L = self._state_arguments_of(fd)[:3]
         ties = self._conditional_arguments(fd, B, L, state_w, tied, classes)
         cone_ok = self._item_routes_ok()
         if method == "cone" and not cone_ok:
@@ -1603,6 +1613,11 @@ class ProteinMPNN(nn.Module):
         terms, special tokens kept: the conventions of conditional_probs().  One input complex (B != 1: ValueError); with state_weights
         X is [M, L, A, 3] and the shared entries [1, L], as in sample().  S_lib: int [n, L], None = feature_dict["S"] as the one
         sequence; ids outside [0, vocab) raise IndexError; n = 0 is legal.
+        Context states (state_S / state_mask beside state_weights): the tokens of S_lib at fixed positions are replaced
+        per state by state_S, a unit is the set of PRESENT copies, residue i reports through its first present copy, member_log_probs is
+        zero at absent copies, and "state_log_likelihood" [n, M] is added: the untied own-entry log-likelihood of the counted positions
+        present in state m.  A unit of one present copy whose state weight is not 1: stream and sampler only ("items":
+        NotImplementedError).
         Ties are read as conditional_probs(tied=True, classes=<paired_wobble asked>) reads them (mapped_groups(fixed=None), LISTED
         order; with states the union across the states in flat indices m * L + i, state-major, weights w_m * w_member; a group with a
         masked member is not tied: its residues are units of one; more than hip.loo_group_max() members, more than 64 distinct tables,
@@ -1636,11 +1651,17 @@ class ProteinMPNN(nn.Module):
         _require_one_complex(fd, "score_tied", None)
         S_true, mask = fd["S"], fd["mask"]
         L = S_true.shape[1]
-        state_w, M = None, 1
+        state_w, M, ctx, present = None, 1, None, None
         if fd.get("state_weights") is not None:
-            state_w, M, L = self._state_arguments_of(fd)
+            state_w, M, L, ctx = self._state_arguments_of(fd)
+        elif fd.get("state_S") is not None or fd.get("state_mask") is not None:
+            raise ValueError("score_tied: state_S / state_mask need state_weights")
+        if ctx is not None:
+            if "present" not in ctx[2]:                    # (one read-back per checked set of tensors)
+                ctx[2]["present"] = tuple(tuple(bool(v) for v in row) for row in ctx[1].tolist())
+            present = ctx[2]["present"]
         classes = self._wobble_arguments(fd)[2]
-        ties = self._conditional_arguments(fd, 1, L, state_w, True, classes)
+        ties = self._conditional_arguments(fd, 1, L, state_w, True, classes, present)
         if S_lib is None:
             S_lib = S_true
         S_lib = torch.as_tensor(S_lib)
@@ -1658,8 +1679,14 @@ class ProteinMPNN(nn.Module):
         if method == "items" and not items_ok:
             raise NotImplementedError("score_tied(method='items') needs three decoder layers and message_precision 'x3' or 'fp32'; "
                                       "use method='sampler'")
+        # (context states: a unit of ONE present copy still draws from softmax(w_m logits_m); the item kernel's unit of one is the own
+        #  entry of log_softmax(logits_m), so that route serves such units with weight 1 only)
+        weighted_singles = ctx is not None and any(wr != 1.0 for _, wr in ties["singles"])
+        if method == "items" and weighted_singles:
+            raise NotImplementedError("score_tied(method='items'): a residue present in one state only whose state weight is not 1; "
+                                      "use method='stream' or 'sampler'")
         if method == "auto":
-            method = "stream" if not listed else ("items" if items_ok else "sampler")
+            method = "stream" if not listed else ("items" if items_ok and not weighted_singles else "sampler")
         _require_device(fd["X"], "X")
         dev, N, Vn = fd["X"].device, M * L, self.num_letters
         S_lib = S_lib.to(dev).long().contiguous()
@@ -1668,6 +1695,22 @@ class ProteinMPNN(nn.Module):
             for r in flat:
                 if r < L:
                     leader[r] = flat[0]
+        seat = None
+        if ctx is not None:
+            # Context states: every state's copy holds the sequence's token where the design draws one and its own state_S elsewhere;
+            # residue i speaks through its first present copy (its seat), and its leader is the residue of the unit's listed-first member
+            state_S, state_mask = ctx[:2]
+            designable = ((mask * fd["chain_mask"])[0] != 0)
+            pres_t = state_mask != 0                                             # [M, L]
+            absent = ((mask != 0) & ~pres_t).reshape(N)
+            rows_of = lambda S_k: torch.where(designable[None, None, :], S_k[:, None, :], state_S[None])      # [n, M, L]
+            seat = [next((s_ * L + i for s_ in range(M) if present[s_][i]), i) for i in range(L)]
+            leader = list(range(L))
+            for flat, *_ in ties["tied"]:
+                for r in flat:
+                    if seat[r % L] == r:
+                        leader[r % L] = flat[0] % L
+            seat = torch.tensor(seat, dtype=torch.long, device=dev)
         leader = torch.tensor(leader, dtype=torch.long, device=dev)
         unit_lp, member_lp = torch.empty(n, N, device=dev), torch.empty(n, N, device=dev)
         chunk = max(1, min(self.score_library_tokens // N, ((1 << 28) - 1) // N))
@@ -1684,6 +1727,8 @@ class ProteinMPNN(nn.Module):
             randn = torch.where(mask[0] != 0, randn, randn * 1e4)              # (a masked residue's sort key is 1e-4 |randn|: its place again)
             ident = list(range(Vn))
             groups = [(flat[:len(gw)], gw, ft[:len(gw)]) for flat, _, ft, _, gw in (ties["tied"] if ties is not None else ()) if len(gw) > 1]
+            if ctx is not None:                            # (a state-0 copy may be absent: the groups in residue terms)
+                groups = ties["listed"]
             one = dict(keep, chain_mask=torch.ones_like(fd["chain_mask"]), temperature=1.0, bias=torch.zeros(1, L, Vn, device=dev))
             if groups:
                 one.update(symmetry_residues=[g for g, _, _ in groups], symmetry_weights=[gw for _, gw, _ in groups])
@@ -1704,16 +1749,25 @@ class ProteinMPNN(nn.Module):
             for k0 in range(0, n, chunk):
                 k1 = min(n, k0 + chunk)
                 S_k = S_lib[k0:k1]
-                got = self._sample(dict(one, randn=randn[None].expand(k1 - k0, L).contiguous(), batch_size=k1 - k0, S_forced=S_k),
-                                   self.sample_level_walk)
+                call = dict(one, randn=randn[None].expand(k1 - k0, L).contiguous(), batch_size=k1 - k0, S_forced=S_k)
+                if ctx is not None:
+                    call["S_forced_states"] = rows_of(S_k)
+                got = self._sample(call, self.sample_level_walk)
                 if not torch.equal(got["decoding_order"][0], visits):
                     raise RuntimeError("score_tied: the design call did not visit the residues in the order of the tied stream")
-                u, own = self._tied_combine(got["log_probs"].reshape(k1 - k0, N, Vn), S_k.repeat(1, M), plan)
+                lp_rows = got["log_probs"].reshape(k1 - k0, N, Vn)
+                if ctx is None:
+                    u, own = self._tied_combine(lp_rows, S_k.repeat(1, M), plan)
+                else:
+                    S_flat = rows_of(S_k).reshape(k1 - k0, N)
+                    u, own = self._tied_combine(lp_rows, S_flat, plan)
+                    for r, wr in ties["singles"]:                              # a unit of one present copy: softmax(w_m logits_m)
+                        u[:, r] = torch.log_softmax(wr * lp_rows[:, r], -1).gather(1, S_flat[:, r, None])[:, 0]
                 unit_lp[k0:k1], member_lp[k0:k1] = u, own
                 chunks += 1
         else:
             o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1] if state_w is not None else fd["randn"])
-            h_V, h_E, E_idx = self._encode_side_by_side(fd, o, state_w, M, L)
+            h_V, h_E, E_idx = self._encode_side_by_side(fd, o, state_w, M, L, ctx)
             self._check_tokens(S_true)
             o.wait()
             order0, rank = o.order[0], o.rank[:1]
@@ -1726,6 +1780,26 @@ class ProteinMPNN(nn.Module):
                 k1 = min(n, k0 + chunk)
                 nk = k1 - k0
                 S_k = S_lib[k0:k1]
+                if ctx is not None:
+                    # every state decodes its own token row under its own presence; the unit of a residue sums its present copies in
+                    # state order and has a value where they all hold one token (they can differ at fixed positions only)
+                    rows = rows_of(S_k)
+                    lp, lg = self.decode_graph(h_V, h_E, E_long, rows.reshape(nk * M, L), state_mask.repeat(nk, 1), rank.expand(nk * M, L),
+                                               want_logits=True)
+                    lp, lg = lp.view(nk, M, L, Vn), lg.view(nk, M, L, Vn)
+                    own = lp.gather(3, rows[..., None])[..., 0]                                # [nk, M, L]
+                    total = None
+                    for m_ in range(M):
+                        term = torch.where(pres_t[m_][None, :, None], sw[m_] * lg[:, m_], torch.zeros_like(lg[:, m_]))
+                        total = term if total is None else total + term
+                    tok = rows.reshape(nk, N)[:, seat]                                         # [nk, L]
+                    same = ((rows == tok[:, None, :]) | ~pres_t[None]).all(1)
+                    tied_lp = torch.log_softmax(total, -1).gather(2, tok[:, :, None])[:, :, 0]
+                    tied_lp = torch.where(same, tied_lp, torch.full_like(tied_lp, float("-inf")))
+                    u = torch.where((tied_res[None, :] & pres_t)[None], tied_lp[:, None, :].expand(nk, M, L), own)
+                    unit_lp[k0:k1], member_lp[k0:k1] = u.reshape(nk, N), own.reshape(nk, N)
+                    chunks += 1
+                    continue
                 S_dec = S_k[:, None, :].expand(nk, M, L).reshape(nk * M, L)
                 lp, lg = self.decode_graph(h_V, h_E, E_long, S_dec, mask.expand(nk * M, L), rank.expand(nk * M, L), want_logits=True)
                 lp, lg = lp.view(nk, M, L, Vn), lg.view(nk, M, L, Vn)
@@ -1752,8 +1826,10 @@ class ProteinMPNN(nn.Module):
                 if not classes:                            # (token maps come without a bias block: zeros)
                     section = torch.cat((section, torch.zeros(n_tab * spec.N_CLASS_LANES, dtype=torch.int32)))
             section = section.to(dev)
-            inputs = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, rank, M, L)
+            inputs = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, rank, M, L, ctx)
             seq32 = (S_lib if M == 1 else S_lib.repeat(1, M)).to(torch.int32)
+            if ctx is not None and n:
+                seq32 = rows_of(S_lib).reshape(n, N).to(torch.int32)
             rows0 = torch.empty(1, N, Vn, device=dev)             # the carrier's log_probs (the first sequence's own rows): the call requires it
             for k0 in range(0, n, chunk):
                 k1 = min(n, k0 + chunk)
@@ -1770,15 +1846,22 @@ class ProteinMPNN(nn.Module):
                 unit_lp[k0:k1] = ws[ooff:ooff + 4 * nk * N].view(torch.float32).view(nk, N)
                 member_lp[k0:k1] = ws[ooff + span:ooff + span + 4 * nk * N].view(torch.float32).view(nk, N)
                 chunks += 1
-        tlp = unit_lp[:, :L].contiguous()
+        tlp = (unit_lp[:, :L] if seat is None else unit_lp[:, seat]).contiguous()
         cm = (mask * fd["chain_mask"])[0] != 0
         counted = torch.zeros(L, dtype=torch.bool, device=dev)
         counted[leader] = True                                                 # one slot per distinct unit: its leader's
         counted &= cm
         picked = tlp[:, counted]
-        return {"S": S_lib, "token_log_probs": tlp, "leader": leader, "log_likelihood": picked.sum(-1), "units": counted.sum(),
-                "member_log_probs": member_lp.view(n, M, L), "consistent": torch.isfinite(picked).all(-1), "decoding_order": order0,
-                "chunks": chunks, "method": method}
+        out = {"S": S_lib, "token_log_probs": tlp, "leader": leader, "log_likelihood": picked.sum(-1), "units": counted.sum(),
+               "member_log_probs": member_lp.view(n, M, L), "consistent": torch.isfinite(picked).all(-1), "decoding_order": order0,
+               "chunks": chunks, "method": method}
+        if ctx is not None:
+            # an absent copy scores nothing; per state the untied own-entry log-likelihood of the designed positions present there:
+            # what ranks designs by their on-target / off-target gap
+            own = member_lp.masked_fill(absent[None, :], 0.0).view(n, M, L)
+            out["member_log_probs"] = own
+            out["state_log_likelihood"] = torch.where((cm[None, :] & pres_t)[None], own, torch.zeros_like(own)).sum(-1)
+        return out
 
     def _wobble_arguments(self, fd, n_pairs=None):
         """feature_dict["paired_wobble"] / ["paired_wobble_bias"] in one normal form -> (wobble, wobble_bias, asked): each None, a scalar
@@ -1805,7 +1888,7 @@ class ProteinMPNN(nn.Module):
                     polymer[r] = polymer[q]
         return polymer
 
-    def _conditional_arguments(self, fd, B, L, state_w=None, tied=False, classes=False):
+    def _conditional_arguments(self, fd, B, L, state_w=None, tied=False, classes=False, present=None):
         """The ties of a conditional_probs(tied, classes) call — base pairs alone with tied=False, every tie with tied=True; spoken in
         token maps, with classes=True in class tables — -> None with nothing to tie, else
         {"tied": [(members, weights, tables, class bias or None, listed weights)] what the device ties (no masked member): flat indices
@@ -1814,7 +1897,10 @@ class ProteinMPNN(nn.Module):
         "index": int64 [n, width] the members padded with -1 (tied=False: [n, 2]),
         "section": the int32 input section of the workspace (include/namp.h: next, first, table_idx, weight bits, tables [n_tables][64],
         with classes the bias bits [n_tables][64]; table 0 is the identity; tables are told apart by (table, bias)), "n_tables"}.
-        state_w: None or the M state weights."""
+        state_w: None or the M state weights.  present: None, or with context states a tuple of M tuples of L bools —
+        a group without a masked residue is tied over its PRESENT copies only; "singles": [(flat index, weight)] the groups one present
+        copy is left of (a unit of one whose logits still carry their weight), "listed": [(residues, weights, tables)] the tied groups in
+        residue terms, for the slow route's design call."""
         pairs, sym = fd.get("paired_residues"), fd.get("symmetry_residues")
         pairs = None if pairs is None or len(pairs) == 0 else pairs
         sym = None if sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0) else sym
@@ -1852,7 +1938,7 @@ class ProteinMPNN(nn.Module):
         listed = lambda v: None if v is None else [[as_list(x) for x in g] if hasattr(g, "__len__") else g for g in v]
         key = (None if pairs is None else [(int(a), int(b)) for a, b in pairs], as_list(fd.get("paired_weights")),
                None if sym is None else [[int(r) for r in g] for g in sym], listed(fd.get("symmetry_weights")) if sym is not None else None,
-               state_w, wobble if classes else None, wobble_bias if classes else None, fd.get("symmetry_token_maps") is None)
+               state_w, wobble if classes else None, wobble_bias if classes else None, present, fd.get("symmetry_token_maps") is None)
         last = self._tie_tables.get((tied, classes))
         if last is not None and key[-1] and last[0] == key and all(x is y for x, y in zip(last[1], (dna, rna, m))):
             return last[2]
@@ -1877,15 +1963,22 @@ class ProteinMPNN(nn.Module):
         N = M * L
         nxt, first, tidx, w = [-1] * N, [0] * N, [0] * N, [1.0] * N
         table, bias, index = [ident], [zero], {(tuple(ident), tuple(zero)): 0}
-        tied_specs = []
+        tied_specs, singles, listed_groups = [], [], []
         for g, gw, gt, gb in zip(groups, weights, gtabs, gbias):
             if len(g) * M > hip.loo_group_max():
                 raise ValueError(f"conditional_probs: the group of residue {g[0]} has {len(g) * M} members; at most {hip.loo_group_max()} are tied")
             if len(g) * M < 2:
                 continue
-            flat = [r + s_ * L for s_ in range(M) for r in g]                 # state-major, as _sample_states lists them
-            fw = [sw[s_] * float(v) for s_ in range(M) for v in gw]
-            ft = [C for s_ in range(M) for C in gt]
+            # (context states: the present copies; a group with a masked residue stays whole — the device's rule unties it below)
+            here = lambda s_, r: present is None or present[s_][r] or not all(m[q] for q in g)
+            flat = [r + s_ * L for s_ in range(M) for r in g if here(s_, r)]    # state-major, as _sample_states lists them
+            fw = [sw[s_] * float(v) for s_ in range(M) for r, v in zip(g, gw) if here(s_, r)]
+            ft = [C for s_ in range(M) for r, C in zip(g, gt) if here(s_, r)]
+            if len(g) > 1 and all(m[r] for r in g):
+                listed_groups.append(([int(r) for r in g], [float(v) for v in gw], [list(C) for C in gt]))
+            if len(flat) < 2:
+                singles += [(r, wr) for r, wr in zip(flat, fw)]
+                continue
             for t, (r, wr, C) in enumerate(zip(flat, fw, ft)):
                 row = (tuple(C) + tuple(range(len(C), lanes)), tuple(gb))
                 k = index.get(row)
@@ -1903,7 +1996,7 @@ class ProteinMPNN(nn.Module):
                  torch.tensor([t for C in table for t in C], dtype=torch.int32)]
         if classes:
             words.append(torch.tensor([v for row in bias for v in row], dtype=torch.float32).view(torch.int32))
-        out = {"tied": tied_specs, "section": torch.cat(words), "n_tables": len(table),
+        out = {"tied": tied_specs, "singles": singles, "listed": listed_groups, "section": torch.cat(words), "n_tables": len(table),
                "index": torch.tensor([t[0] + [-1] * (width - len(t[0])) for t in tied_specs], dtype=torch.int64).reshape(-1, width)}
         self._tie_tables[(tied, classes)] = (key, (dna, rna, m), out)
         return out
@@ -2018,6 +2111,8 @@ class ProteinMPNN(nn.Module):
         ``pair_bias``) as one persistent HIP launch.  ``feature_dict["pair_terms"]`` is the compact form of ``pair_bias`` —
         {"partner", "table": int [B, L, D], "tables": float [n, V, V], "members": "closing" | "all"}, see pair_terms_arguments — and,
         unlike the dense tensor, goes with every tie (symmetry_residues, paired_residues, paired_wobble, state_weights).
+        With ``state_weights`` one sequence is tied across backbone states, with ``state_S`` / ``state_mask`` beside it the states also
+        differ in their fixed tokens and in which residues they have (_sample_states).
         The categorical draw uses torch.rand on the device (seed with torch.manual_seed) through an inverse
         CDF instead of torch.multinomial; ``feature_dict["S_forced"]`` (optional, [batch,L]) teacher-forces."""
         return self._sample(feature_dict, self.sample_level_walk)
@@ -2273,7 +2368,8 @@ class ProteinMPNN(nn.Module):
     _STATE_SHARED = ("S", "mask", "chain_mask", "R_idx", "chain_labels", "protein_mask", "dna_mask", "rna_mask", "R_polymer_type")
 
     def _states_arguments(self, fd):
-        """The checks of the tied-states path (they need no device) -> (state weights as floats, M, L, batch_size, symmetric)."""
+        """The checks of the tied-states path (they need no device) -> (state weights as floats, M, L, batch_size, symmetric, the context
+        states of _state_contexts or None)."""
         w = fd["state_weights"]
         w = [float(v) for v in (w.detach().reshape(-1).tolist() if torch.is_tensor(w) else list(w))]
         M, bs = len(w), int(fd["batch_size"])
@@ -2297,8 +2393,47 @@ class ProteinMPNN(nn.Module):
             raise NotImplementedError("pair_bias is not supported together with state_weights")
         if M * L > 16000:
             raise ValueError(f"states x residues = {M * L} exceeds the level lists' limit of 16000")
+        ctx = self._state_contexts(fd, M, L)
         sym = fd.get("symmetry_residues", [[]])
-        return w, M, L, bs, not (len(sym) == 1 and len(sym[0]) == 0)
+        return w, M, L, bs, not (len(sym) == 1 and len(sym[0]) == 0), ctx
+
+    def _state_contexts(self, fd, M, L):
+        """Context states: feature_dict["state_S"] int [M, L], the token of every residue in every state, and
+        feature_dict["state_mask"] [M, L] in {0, 1}, its presence there; either alone, the other is the shared row repeated.  Checked
+        here — the tokens' range, the masks' values, mask == OR of state_mask over the states: ONE host read per new set of tensor
+        objects, as _check_tokens keeps it — -> None without the keys, else (state_S int64 [M, L], state_mask [M, L] in the dtype of
+        mask, a dict for what callers derive from the two and keep with them), on the device of S."""
+        sS, sm = fd.get("state_S"), fd.get("state_mask")
+        if sS is None and sm is None:
+            return None
+        S, mask = fd["S"], fd["mask"]
+        for k, t in (("state_S", sS), ("state_mask", sm)):
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (M, L)):
+                raise ValueError(f"'{k}' is given per state and must be a tensor [{M}, {L}]; got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if sS is not None and (sS.dtype.is_floating_point or sS.dtype == torch.bool):
+            raise ValueError(f"'state_S' must be an integer tensor; got {sS.dtype}")
+        given = tuple(t for t in (sS, sm, S, mask) if t is not None)
+        cached = not any(t.is_inference() for t in given)
+        slot = self._tokens_ok.get("state_contexts")
+        if cached and slot is not None and len(slot[0]) == len(given) and all(r() is t and v == t._version for (r, v), t in zip(slot[0], given)) \
+                and slot[1] == (sS is None, sm is None):
+            return slot[2]
+        sS = (S.expand(M, L) if sS is None else sS.to(S.device)).long().contiguous()
+        sm = (mask.expand(M, L) if sm is None else sm.to(device=mask.device)).to(mask.dtype).contiguous()
+        lo, hi = torch.aminmax(sS)
+        lo, hi, bad_value, bad_or = torch.stack((lo, hi, ((sm != 0) & (sm != 1)).any().long().to(lo.device),
+                                                 ((sm != 0).any(0) != (mask[0] != 0)).any().long().to(lo.device))).tolist()
+        if lo < 0 or hi >= self.vocab:
+            raise IndexError(f"na_mpnn_amd: token ids in 'state_S' must lie in [0, {self.vocab}); got [{lo}, {hi}]")
+        if bad_value:
+            raise ValueError("'state_mask' must hold 0 (absent) or 1 (present)")
+        if bad_or:
+            raise ValueError("'mask' must equal the OR of 'state_mask' over the states: a residue is there iff some state has it")
+        if cached:
+            self._tokens_ok["state_contexts"] = ([(weakref.ref(t), t._version) for t in given], (fd.get("state_S") is None, fd.get("state_mask") is None),
+                                                 (sS, sm, {}))
+            return self._tokens_ok["state_contexts"][2]
+        return sS, sm, {}
 
     def _sample_states(self, fd, walk, uniform=None):
         """sample() of ONE sequence tied across M backbone states (feature_dict["state_weights"], X [M, L, A, 3]): at every step of the one
@@ -2306,8 +2441,11 @@ class ProteinMPNN(nn.Module):
         drawn from softmax((sum_m w_m logits_m + bias_i) / T) and written to all states.  The states are encoded as a batch and decoded as
         a symmetric design on the block-diagonal flattened graph of M * L residues (flat residue m * L + i, neighbours E_idx[m] + m * L,
         groups {i, L + i, ...} with the state weights): the decoder sees the graph through E_idx only.  Returns S [bs, L], sampling_probs
-        [bs, L, V], log_probs [bs, M, L, V], decoding_order [bs, L], uniform [bs, L] (by step), levels, work_items."""
-        w, M, L, bs, symmetric = self._states_arguments(fd)
+        [bs, L, V], log_probs [bs, M, L, V], decoding_order [bs, L], uniform [bs, L] (by step), levels, work_items.
+        Context states (feature_dict["state_S"] / ["state_mask"] [M, L]): every state's copy of a fixed residue holds its
+        own state_S[m, i]; a residue absent in a state (state_mask 0) has a zero context there, adds nothing to the sum and still takes
+        the drawn token.  Then also S_states int64 [bs, M, L], the token every copy holds; the log_probs rows of absent copies are zeros."""
+        w, M, L, bs, symmetric, ctx = self._states_arguments(fd)
         sym_groups, sym_weights = fd.get("symmetry_residues", [[]]), fd.get("symmetry_weights", [[]])
         tok_maps, n_maps, cls_bias = None, 0, None
         mapped = self._mapped_arguments(fd, 1, L)                                   # base pairs beside the states: the host route
@@ -2337,6 +2475,8 @@ class ProteinMPNN(nn.Module):
         fd_enc = dict(fd)
         for k in self._STATE_SHARED:
             fd_enc[k] = fd[k].expand(M, L)
+        if ctx is not None:                                                         # every state is encoded with its own tokens and presence
+            fd_enc["S"], fd_enc["mask"] = ctx[:2]
         V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
         K = E_idx.shape[-1]
         Lb = hip.lib()
@@ -2409,9 +2549,23 @@ class ProteinMPNN(nn.Module):
         W = self._weights()
         flat_i32 = lambda t: _i32(t.repeat(1, M))
         m_f, cm_f, S_f = flat_i32(mask), flat_i32(mask * fd["chain_mask"]), flat_i32(S_true)
+        forced = flat_i32(fd["S_forced"]) if fd.get("S_forced") is not None else None
+        if ctx is not None:
+            # Context states: the flat arrays are the kernel's interface, and here their rows differ.  Presence gates a copy's context
+            # (mask_true, the residue tail's mask) and its tokens are its own; cm_f stays the SHARED mask * chain_mask — a fixed member
+            # passes its own token on to the members behind it, so an absent copy of a designable residue must not be one: it takes
+            # the group's token as every free member does, and its logits enter the group's sum with weight zero.
+            state_S, state_mask, kept = ctx
+            if "flat" not in kept:                                             # (kept with the checked tensors: a resident feature_dict)
+                kept["flat"] = (((mask != 0) & (state_mask == 0)).reshape(N), _i32(state_mask.reshape(1, N)), _i32(state_S.reshape(1, N)))
+            absent, m_f, S_f = kept["flat"]
+            sym_w = torch.where(absent, torch.zeros_like(sym_w), sym_w)
+            if fd.get("S_forced_states") is not None:                          # (score_tied's slow route: the forced tokens per state)
+                if tuple(fd["S_forced_states"].shape) != (bs, M, L):
+                    raise ValueError(f"S_forced_states must be [{bs}, {M}, {L}]; got {tuple(fd['S_forced_states'].shape)}")
+                forced = _i32(fd["S_forced_states"].reshape(bs, N))
         md_f = m_f if bs == 1 else m_f.repeat(bs, 1)
         bias_f = fd["bias"].float().expand(1, L, Vn).repeat(1, M, 1).contiguous()
-        forced = flat_i32(fd["S_forced"]) if fd.get("S_forced") is not None else None
         S_out, probs = i32e(bs, N), torch.empty(bs, N, Vn, device=dev)
         logp = torch.empty_like(probs)
         if close is not None:
@@ -2440,8 +2594,12 @@ class ProteinMPNN(nn.Module):
             if code != 0:
                 warnings.warn(f"persistent level walk timed out (code {code:#x}); re-running with per-level launches")
                 return self._sample_states(fd, walk=False, uniform=uniform)
-        return {"S": S_out[:, :L].long(), "sampling_probs": probs[:, :L], "log_probs": logp.view(bs, M, L, Vn),
-                "decoding_order": o.order[0].expand(bs, L), "uniform": uniform, "levels": levels, "work_items": nwork}
+        out = {"S": S_out[:, :L].long(), "sampling_probs": probs[:, :L], "log_probs": logp.view(bs, M, L, Vn),
+               "decoding_order": o.order[0].expand(bs, L), "uniform": uniform, "levels": levels, "work_items": nwork}
+        if ctx is not None:                                                    # (an absent copy scores nothing: its rows are zeros)
+            out["log_probs"] = logp.view(bs, N, Vn).masked_fill(absent[None, :, None], 0.0).view(bs, M, L, Vn)
+            out["S_states"] = S_out.view(bs, M, L).long()
+        return out
 
     def sample_walk_status(self):
         """Barrier state of the last persistent level walk (synchronises): 0 = every grid barrier completed; otherwise the code of the barrier

@@ -230,12 +230,21 @@ def parse_pdb(path, chains=None, parse_na_only=False, na_shared_tokens=True, loa
 
 
 def parse_states(path, chains=None, parse_na_only=False, na_shared_tokens=True, load_residues_with_missing_atoms=False,
-                 normalize_legacy_names=False):
+                 normalize_legacy_names=False, contexts=False):
     """Every model of a structure file as the states of ONE molecule (an NMR ensemble, the folds of a riboswitch): the first
     model's parse_pdb dict with 'X' [M, L, 16, 3] and 'X_m' [M, L, 16] stacked over the models, and 'model_ids'.  Raises ValueError
-    unless all models give the same residues — chain, number, insertion code, residue name and `mask`."""
+    unless all models give the same residues — chain, number, insertion code, residue name and `mask`.
+    contexts=True: the models are CONTEXT states — they may differ in residue names and lack residues or whole
+    chains (a fixed partner with another sequence, the unbound form).  The residue list is the union: chains in order of first
+    appearance over the models, inside a chain the order of the model with the most residues of it (the first such model), of which
+    every other model's residues of that chain must be a subsequence (ValueError names the model otherwise); a residue's polymer type
+    must agree across the models that have it.  Also returns 'state_S' int32 [M, L] (an absent residue: the token of the first model
+    that has it) and 'state_mask' int32 [M, L] (the model's own `mask`; 0 where it lacks the residue); 'S' and the other per-residue
+    entries come from the first model that has the residue, `mask` is the OR of state_mask, X / X_m of an absent residue are zero."""
     ids = model_ids(path)
     parsed = [_parse(path, chains, parse_na_only, na_shared_tokens, load_residues_with_missing_atoms, normalize_legacy_names, i) for i in ids]
+    if contexts:
+        return _union_of_states(path, ids, parsed)
     key = lambda P, names: (P["chain_letters"], P["R_idx"].tolist(), P["icodes"], names, P["mask"].tolist())
     first = key(*parsed[0])
     for i, pn in zip(ids[1:], parsed[1:]):
@@ -248,6 +257,71 @@ def parse_states(path, chains=None, parse_na_only=False, na_shared_tokens=True, 
     out["X"] = np.stack([P["X"] for P, _ in parsed])
     out["X_m"] = np.stack([P["X_m"] for P, _ in parsed])
     out["model_ids"] = ids
+    return out
+
+
+def _union_of_states(path, ids, parsed):
+    """parse_states(contexts=True): the models' parses merged over the union of their residues."""
+    keys = [list(zip(P["chain_letters"], P["R_idx"].tolist(), P["icodes"])) for P, _ in parsed]
+    chain_order = []
+    for ks in keys:
+        for k in ks:
+            if k[0] not in chain_order:
+                chain_order.append(k[0])
+    union = []
+    for c in chain_order:
+        per_model = [[k for k in ks if k[0] == c] for ks in keys]
+        longest = max(per_model, key=len)                                    # (max returns the first of equals)
+        for i, mine in zip(ids, per_model):
+            it = iter(longest)
+            if not all(k in it for k in mine):                               # (consumes `it`: a subsequence test)
+                raise ValueError(f"{path}: the residues of chain {c} in model {i} are not a subsequence of the chain's longest model: "
+                                 "context states list one molecule's residues in one order")
+        union += longest
+    L, M = len(union), len(parsed)
+    at = {k: i for i, k in enumerate(union)}
+    rows = [np.array([at[k] for k in ks], np.int64) for ks in keys]
+    X = np.zeros((M, L) + parsed[0][0]["X"].shape[1:], np.float32)
+    X_m = np.zeros((M, L) + parsed[0][0]["X_m"].shape[1:], np.int32)
+    state_mask, has = np.zeros((M, L), np.int32), np.zeros((M, L), bool)
+    state_S = np.zeros((M, L), np.int32)
+    for m, ((P, _), r) in enumerate(zip(parsed, rows)):
+        X[m, r], X_m[m, r], state_mask[m, r], state_S[m, r], has[m, r] = P["X"], P["X_m"], P["mask"], P["S"], True
+    if not has.any(0).all():
+        raise ValueError(f"{path}: internal error: a residue of the union is in no model")
+    first = has.argmax(0)                                                    # the first model that has the residue
+    shared = ("S", "R_idx", "protein_mask", "dna_mask", "rna_mask", "rna_mask_for_token_conversion", "R_polymer_type")
+    out = dict(parsed[0][0])
+    for k in shared:
+        out[k] = np.zeros(L, parsed[0][0][k].dtype)
+    for m, ((P, _), r) in enumerate(zip(parsed, rows)):
+        sel = first[r] == m
+        for k in shared:
+            out[k][r[sel]] = P[k][sel]
+    # the polymer type of a residue: the same in every model that resolves it (mask 1; an unresolved residue has none)
+    ptype = np.full((M, L), -1, np.int64)
+    for m, ((P, _), r) in enumerate(zip(parsed, rows)):
+        ptype[m, r] = P["R_polymer_type"]
+    resolved = state_mask != 0
+    ref = ptype[resolved.argmax(0), np.arange(L)]                            # ... of the first model that resolves it
+    clash = resolved & (ptype != ref[None, :])
+    if clash.any():
+        m, i = (int(v[0]) for v in np.nonzero(clash))
+        c, n, ic = union[i]
+        raise ValueError(f"{path}: residue {c}{n}{ic} is another polymer type in model {ids[m]} than in model {ids[int(resolved[:, i].argmax())]}")
+    state_S = np.where(has, state_S, out["S"][None, :]).astype(np.int32)
+    # chain labels: the first model's that has the chain, moved aside where two chains of different models would share one
+    label = {}
+    for c in chain_order:
+        P = next(P for (P, _), ks in zip(parsed, keys) if any(k[0] == c for k in ks))
+        v = int(P["chain_labels"][P["chain_letters"].index(c)])
+        while v in label.values():
+            v = max(label.values()) + 1
+        label[c] = v
+    letters = [k[0] for k in union]
+    out.update({"X": X, "X_m": X_m, "state_S": state_S, "state_mask": state_mask, "mask": state_mask.max(0).astype(np.int32),
+                "chain_labels": np.array([label[c] for c in letters], np.int32), "chain_letters": letters, "icodes": [k[2] for k in union],
+                "na_chain_letters": [c for i, c in enumerate(letters) if out["dna_mask"][i] or out["rna_mask"][i]], "model_ids": ids})
     return out
 
 

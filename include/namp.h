@@ -519,6 +519,23 @@ long namp_train_feat_wgrad_ws_ints(long edges);       /* int32 elements of tile_
 long namp_train_g16_elems(long rows);
 int namp_train_feat_wgrad(const float* X18, const float* M18, const int32_t* E_idx, const float* E_pos, const float* g_pre, const void* g16,
                           float* dW_part, int32_t* tile_ws, int x3, int B, int L, int K, void* stream);
+/* Coordinate gradients, carried by namp_train_feat_wgrad (attach and carry): dX18 [B*L][18][3] = dL/dX18 from the same
+ * g_pre, the same atoms and the same neighbour lists — the transpose of the weight gradient's contraction through the regenerated RBFs
+ * (neighbour lists are constants; a masked atom gets exactly 0).  namp_train_feat_xgrad(ws_ints) records for the calling thread that its NEXT
+ * namp_train_feat_wgrad call carries it and that the call's tile_ws holds ws_ints int32 elements (>= namp_train_feat_xgrad_ws_ints, 256-byte
+ * aligned), laid out as: the plain call's presence words; at namp_train_feat_xgrad_in_offset the INPUT section, the caller's copy of the
+ * embedding weight as plain fp32 [128][5200] (the 18-atom column layout; never written); scratch (clamped neighbour lists, their reverse
+ * adjacency, two rows [18][3] per edge); at namp_train_feat_xgrad_out_offset the OUTPUT section dX18.  Sizes and offsets in int32 elements of
+ * tile_ws, multiples of 64 (256 bytes); 0 where edges != B*L*K, a dim is < 1, K > L or the edges do not fit int32:
+ *   ws_ints = sum of ceil256(4 * n) / 4 over n = 2 T, 665600, E, 2 T, G + 1, E, 2 G + E, 108 E, 54 G   (E edges, G = B*L, T = ceil(E / 64)).
+ * The entry point clears its own record first (ws_ints < 1: NAMP_EINVAL, nothing attached); the carrier takes and clears the record whatever
+ * becomes of the call; a tile_ws declared too small is NAMP_EINVAL before any launch.  E_idx values outside [0, L) are clamped for dX18
+ * (dW_part is the plain call's).  Without a record the carrier is the plain call; dW_part is bit-identical with and without the attachment.
+ * One form for every precision code and both atom forms: fp32 MFMA on the fp32 g_pre rows; no atomics, one summation order. */
+long namp_train_feat_xgrad_ws_ints(long edges, int B, int L, int K);
+long namp_train_feat_xgrad_in_offset(long edges, int B, int L, int K);
+long namp_train_feat_xgrad_out_offset(long edges, int B, int L, int K);
+int namp_train_feat_xgrad(long ws_ints);
 
 /* ---- training: loss and optimiser step (round 3) ----------------------------------------------
  * namp_train_loss_smoothed: the per-residue label-smoothed loss of na_model_utils.py:111-146 in fp64 (backward = 0: loss[G]) and its

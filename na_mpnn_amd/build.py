@@ -22,7 +22,7 @@ UNITS = {"namp.hip": ["namp.hip", "namp_kernels.h", "namp_bf16s32.h", "namp_bf16
          "namp_tied.hip": ["namp_tied.hip", "namp_tied.h", "namp_attach.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_states.hip": ["namp_states.hip", "namp_states.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_pairs.hip": ["namp_pairs.hip", "namp_pairs.h", INC],
-         "namp_train.hip": ["namp_train.hip", "namp_train.h", "namp_train_dw.h", "namp_metrics.h", "namp_device.h", INC],
+         "namp_train.hip": ["namp_train.hip", "namp_train.h", "namp_train_dw.h", "namp_train_dx.h", "namp_attach.h", "namp_metrics.h", "namp_device.h", INC],
          "namp_train_eu.hip": ["namp_train_eu.hip", "namp_train_eu.h", "namp_train_dw.h", "namp_train.h", "namp_device.h", INC]}
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 OBJ_DIR = os.path.join(HERE, "lib", "obj")

@@ -100,6 +100,10 @@ def build_parser():
       "scored with ProteinMPNN.score_mutations as the change of the structure's joint log-likelihood; with --paired_residues / "
       "--paired_strands a paired residue is mutated together with its partner (canonical duplexes, pairs=True); writes "
       "mutations/<name>.npz (residues, tokens, delta [P, T], base_loss, wild_type_token, site_rows)")
+    a("--coordinate_gradients", type=int, default=0, help="1: no sampling: the gradient of the structure's negative log-likelihood, "
+      "sum of -log p(s_i) over the residues the usual flags make designable (fixed residues decoded first, as score does), with respect to "
+      "every atom coordinate (ProteinMPNN.coordinate_gradients); writes gradients/<name>.npz (dX [L, 16, 3], residue_norm [L], loss, "
+      "encoded_residues, mask, chain_mask, decoding_randn)")
     a("--load_residues_with_missing_atoms", type=int, default=0)
     a("--mode", type=str, default=None)
     a("--device", type=str, default="cuda:0")
@@ -270,6 +274,11 @@ def main(argv=None):
     if args.mutation_scan and (args.score_fasta or args.conditional_probs_only or args.multi_state or args.paired_wobble):
         raise ValueError("--mutation_scan 1 scans one structure: it does not go with --score_fasta, --conditional_probs_only, "
                          "--multi_state or --paired_wobble")
+    if args.coordinate_gradients not in (0, 1):
+        raise ValueError(f"--coordinate_gradients is 0 or 1; got {args.coordinate_gradients}")
+    if args.coordinate_gradients and (args.score_fasta or args.conditional_probs_only or args.multi_state or args.mutation_scan):
+        raise ValueError("--coordinate_gradients 1 differentiates one structure's likelihood: it does not go with --score_fasta, "
+                         "--conditional_probs_only, --multi_state or --mutation_scan")
     if args.model_type != "na_mpnn":
         print("Choose --model_type flag from currently available models")
         sys.exit()
@@ -323,6 +332,9 @@ def main(argv=None):
         args.output_pdbs = args.output_sequences = args.output_specificity = 0
     elif args.mutation_scan:
         os.makedirs(base + "mutations", exist_ok=True)
+        args.output_pdbs = args.output_sequences = args.output_specificity = 0
+    elif args.coordinate_gradients:
+        os.makedirs(base + "gradients", exist_ok=True)
         args.output_pdbs = args.output_sequences = args.output_specificity = 0
     else:
         os.makedirs(base + "seqs", exist_ok=True)
@@ -471,6 +483,16 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
                      tokens=np.array([int_to_str.get(int(t), "?") for t in out["tokens"].tolist()]), delta=out["delta"].cpu().numpy(),
                      base_loss=out["base_loss"].cpu().numpy(), wild_type_token=np.asarray(P["S"])[scanned],
                      site_rows=(out["site_rows"].cpu().numpy() if out["site_rows"] is not None else np.zeros((0, 3), np.int32)))
+            return
+        if args.coordinate_gradients:
+            # per-atom saliency of the structure's own sequence under one decoding order (its noise is the only random input)
+            if args.multi_state:
+                raise ValueError("--coordinate_gradients differentiates one structure: it does not go with --multi_state")
+            fd["randn"] = torch.randn(1, L, device=device)
+            out = model.coordinate_gradients(fd)
+            np.savez(os.path.join(base, "gradients", name + ".npz"), dX=out["dX"][0].cpu().numpy(),
+                     residue_norm=out["residue_norm"][0].cpu().numpy(), loss=float(out["loss"]), encoded_residues=encoded,
+                     mask=P["mask"], chain_mask=chain_mask, decoding_randn=fd["randn"][0].cpu().numpy())
             return
         S_l, lp_l, sp_l, loss_l, lpr_l, Ss_l = [], [], [], [], [], []
         cmask = (fd["mask"] * fd["chain_mask"]).float()

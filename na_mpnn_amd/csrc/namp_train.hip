@@ -2,7 +2,9 @@
 #include "../../include/namp.h"
 #include "namp_train.h"
 #include "namp_train_dw.h"
+#include "namp_train_dx.h"
 #include "namp_metrics.h"
+#include "namp_attach.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -69,6 +71,41 @@ int ensure_attributes() {
   if (g_attr_err != hipSuccess)
     return fail(NAMP_ELAUNCH, "hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(g_attr_err));
   return NAMP_OK;
+}
+
+// ---- the coordinate gradient carried by namp_train_feat_wgrad (include/namp.h "namp_train_feat_xgrad")
+// What the calling thread's NEXT namp_train_feat_wgrad call carries: the size in int32 elements its tile_ws was declared with.
+struct XgradRecord { bool on; long ws_ints; };
+thread_local XgradRecord g_xgrad = {};
+
+// tile_ws of an attached call, carved in one fixed order; base == nullptr: offsets only.  false: invalid dims.
+struct XgradWs {
+  int32_t* pres;                                   // the plain call's presence words: first and unchanged
+  float* W;                                        // input section: Wedge [128][5200]
+  int32_t *eidx, *pres2, *roff, *redge, *rws;      // scratch: clamped E_idx, its presence words, the reverse adjacency and its scratch
+  float* rows;                                     // scratch: per-edge rows [E][XG_ROW]
+  float* dX;                                       // output section: dX18 [B*L][18][3]
+  long in_off, out_off, total;                     // int32 elements
+};
+bool xgrad_carve(void* base, long edges, int B, int L, int K, XgradWs* w) {
+  if (B < 1 || L < 1 || K < 1 || K > L) return false;
+  const long G = (long)B * L, E = G * K;
+  if (edges != E || E >= (1L << 31)) return false;
+  const long ntile = (E + FEATW_TILE - 1) / FEATW_TILE;
+  WsCarver c(base);
+  w->pres = c.take<int32_t>((size_t)(2 * ntile));
+  w->in_off = (long)(c.off / 4);
+  w->W = c.take<float>((size_t)NAMP_H * FEATW_COLS);
+  w->eidx = c.take<int32_t>((size_t)E);
+  w->pres2 = c.take<int32_t>((size_t)(2 * ntile));
+  w->roff = c.take<int32_t>((size_t)(G + 1));
+  w->redge = c.take<int32_t>((size_t)E);
+  w->rws = c.take<int32_t>((size_t)(2 * G + E));
+  w->rows = c.take<float>((size_t)E * XG_ROW);
+  w->out_off = (long)(c.off / 4);
+  w->dX = c.take<float>((size_t)G * (XG_ROW / 2));
+  w->total = (long)(c.off / 4);
+  return true;
 }
 
 }  // namespace
@@ -573,6 +610,15 @@ long namp_train_feat_wgrad_ws_ints(long edges) { return edges <= 0 ? 0 : 2 * ((e
 
 int namp_train_feat_wgrad(const float* X18, const float* M18, const int32_t* E_idx, const float* E_pos, const float* g_pre, const void* g16,
                           float* dW_part, int32_t* tile_ws, int x3, int B, int L, int K, void* stream) {
+  const XgradRecord carried = g_xgrad;             // taken and cleared, whatever becomes of this call
+  g_xgrad = {};
+  XgradWs xw = {};
+  if (carried.on) {                                // the declared size first: integers only, so the answer does not depend on the pointers
+    REQUIRE(B >= 1 && L >= 1 && K >= 1 && K <= L, "namp_train_feat_wgrad: bad dims B=%d L=%d K=%d (a coordinate gradient was attached)", B, L, K);
+    REQUIRE(xgrad_carve(nullptr, (long)B * L * K, B, L, K, &xw), "namp_train_feat_wgrad: B=%d L=%d K=%d: the edges do not fit int32 (a coordinate gradient was attached)", B, L, K);
+    REQUIRE(carried.ws_ints >= xw.total, "namp_train_feat_wgrad: tile_ws too small for the attached coordinate gradient (%ld int32, %ld needed)",
+            carried.ws_ints, xw.total);
+  }
   if (!tile_ws) return fail(NAMP_EINVAL, "namp_train_feat_wgrad: null tile workspace (namp_train_feat_wgrad_ws_ints int32s)");
   REQUIRE_PTR(X18); REQUIRE_PTR(E_pos); REQUIRE_PTR(g_pre); REQUIRE_PTR(dW_part);
   const bool packed = (M18 == nullptr);            // X18 = [G][18][4] (x, y, z, mask): split-bf16 / bf16 launches only
@@ -582,6 +628,7 @@ int namp_train_feat_wgrad(const float* X18, const float* M18, const int32_t* E_i
   REQUIRE(B >= 1 && L >= 1 && K >= 1 && K <= L, "namp_train_feat_wgrad: bad dims B=%d L=%d K=%d", B, L, K);
   REQUIRE(!g16 || (packed && x3 != 0 && aligned16(g16)), "namp_train_feat_wgrad: g16 (bf16 tiles of g_pre) goes with the packed atoms and precision code 1 / 2");
   const long E = (long)B * L * K;
+  if (carried.on) xgrad_carve(tile_ws, E, B, L, K, &xw);
   const int nchunk = namp_train_feat_wgrad_chunks(E);
   long per = (E + nchunk - 1) / nchunk;
   per = (per + FEATW_TILE - 1) / FEATW_TILE * FEATW_TILE;
@@ -601,6 +648,42 @@ int namp_train_feat_wgrad(const float* X18, const float* M18, const int32_t* E_i
     hipLaunchKernelGGL(feat_wgrad_kernel, dim3(41, nchunk), dim3(256), 0, (hipStream_t)stream, X18, M18, E_idx, E_pos, g_pre,
                        tile_ws, E, per, L, K, dW_part);
   CHECK_LAUNCH();
+  if (!carried.on) return NAMP_OK;
+  // the carried coordinate gradient: clamped neighbour lists -> their presence words and reverse adjacency -> per-edge rows -> dX18
+  hipStream_t s = (hipStream_t)stream;
+  long cb = (E + 255) / 256;
+  if (cb > 8192) cb = 8192;
+  hipLaunchKernelGGL(xgrad_clamp_kernel, dim3((unsigned)cb), dim3(256), 0, s, E_idx, xw.eidx, E, L);
+  hipLaunchKernelGGL(tile_presence_kernel, dim3((unsigned)((ntile + 3) / 4)), dim3(256), 0, s, packed ? X18 + 3 : M18, packed ? 4 : 1, xw.eidx, E, L, K,
+                     xw.pres2);
+  CHECK_LAUNCH();
+  const int rc = namp_train_reverse_adjacency(xw.eidx, xw.roff, xw.redge, xw.rws, B, L, K, stream);
+  if (rc != NAMP_OK) return rc;
+  if (packed) hipLaunchKernelGGL(feat_xgrad_kernel<true>, dim3((unsigned)ntile), dim3(256), 0, s, X18, M18, xw.eidx, g_pre, xw.W, xw.pres2, E, L, K, xw.rows);
+  else hipLaunchKernelGGL(feat_xgrad_kernel<false>, dim3((unsigned)ntile), dim3(256), 0, s, X18, M18, xw.eidx, g_pre, xw.W, xw.pres2, E, L, K, xw.rows);
+  const long G = (long)B * L;
+  hipLaunchKernelGGL(xgrad_reduce_kernel, dim3((unsigned)((G * (XG_ROW / 2) + 255) / 256)), dim3(256), 0, s, xw.rows, xw.roff, xw.redge, G, K, xw.dX);
+  CHECK_LAUNCH();
+  return NAMP_OK;
+}
+
+long namp_train_feat_xgrad_ws_ints(long edges, int B, int L, int K) {
+  XgradWs w = {};
+  return xgrad_carve(nullptr, edges, B, L, K, &w) ? w.total : 0;
+}
+long namp_train_feat_xgrad_in_offset(long edges, int B, int L, int K) {
+  XgradWs w = {};
+  return xgrad_carve(nullptr, edges, B, L, K, &w) ? w.in_off : 0;
+}
+long namp_train_feat_xgrad_out_offset(long edges, int B, int L, int K) {
+  XgradWs w = {};
+  return xgrad_carve(nullptr, edges, B, L, K, &w) ? w.out_off : 0;
+}
+
+int namp_train_feat_xgrad(long ws_ints) {
+  g_xgrad = {};
+  REQUIRE(ws_ints >= 1, "namp_train_feat_xgrad: ws_ints=%ld (the int32 elements of the next namp_train_feat_wgrad call's tile_ws)", ws_ints);
+  g_xgrad = {true, ws_ints};
   return NAMP_OK;
 }
 

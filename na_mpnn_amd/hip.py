@@ -174,6 +174,10 @@ _PROTOTYPES = {
     "namp_train_feat_wgrad_chunks": (i32, [C.c_long]),
     "namp_train_feat_wgrad_ws_ints": (C.c_long, [C.c_long]),
     "namp_train_feat_wgrad": (i32, [c_fp, c_fp, c_ip, c_fp, c_fp, vp, c_fp, c_ip, i32, i32, i32, i32, vp]),
+    "namp_train_feat_xgrad_ws_ints": (C.c_long, [C.c_long, i32, i32, i32]),
+    "namp_train_feat_xgrad_in_offset": (C.c_long, [C.c_long, i32, i32, i32]),
+    "namp_train_feat_xgrad_out_offset": (C.c_long, [C.c_long, i32, i32, i32]),
+    "namp_train_feat_xgrad": (i32, [C.c_long]),
     "namp_train_g16_elems": (C.c_long, [C.c_long]),
     "namp_train_loss_smoothed": (i32, [i32, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.POINTER(C.c_float), C.c_double, c_ip, vp,
                                        vp, vp, c_fp, C.c_long, i32, vp]),

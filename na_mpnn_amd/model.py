@@ -983,6 +983,29 @@ class ProteinMPNN(nn.Module):
         log_probs = self.decode_graph(h_V, h_E, E_idx, rep(S_true), rep(mask), rep(rank))
         return {"S": rep(S_true), "log_probs": log_probs, "decoding_order": o.order[0]}
 
+    def coordinate_gradients(self, feature_dict, decoding_randn=None, weights=None):
+        """dL/dX of L = sum_i w_i (-log p(S_i)) under score()'s decoding order (sorted on mask * chain_mask: fixed residues first), through
+        the differentiable training forward (train.forward_train) and the featuriser's coordinate gradient.  decoding_randn
+        [B, L] (default: feature_dict["randn"], else drawn); weights [B, L] (default mask * chain_mask).  The neighbour lists are constants.
+        -> {"loss" scalar, "dX" [B, L, 16, 3] (virtual Cb / N_na folded back onto their parents by autograd), "residue_norm" [B, L] =
+        the Euclidean norm of a residue's 16 x 3 block}.  The model's mode decides dropout and coordinate noise: call it in eval().
+        Parameter gradients are not touched."""
+        from . import train
+        fd = dict(feature_dict)
+        mask = fd["mask"]
+        B, L = mask.shape
+        X = fd["X"].detach().float().clone().requires_grad_(True)
+        fd["X"] = X
+        order_mask = mask * fd["chain_mask"] if fd.get("chain_mask") is not None else mask
+        if decoding_randn is None:
+            decoding_randn = fd["randn"][:B] if fd.get("randn") is not None else torch.randn(B, L, device=mask.device)
+        w = (order_mask if weights is None else weights).to(torch.float32)
+        with torch.enable_grad():
+            log_probs, _ = train.forward_train(self, fd, decoding_randn, order_mask=order_mask)
+            loss = -(w * torch.gather(log_probs, -1, fd["S"].long().unsqueeze(-1)).squeeze(-1)).sum()
+            dX, = torch.autograd.grad(loss, X)
+        return {"loss": loss.detach(), "dX": dX, "residue_norm": dX.reshape(B, L, -1).norm(dim=-1)}
+
     @torch.no_grad()
     def unconditional_probs(self, feature_dict):
         """ProteinMPNN.unconditional_probs (model_utils.py:329-364): nothing is decoded 'before'."""

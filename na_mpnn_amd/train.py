@@ -683,7 +683,10 @@ def _edge_embedding_fwd(fp, W18, X, ints, top_k, ref_atom):
 class _EdgeEmbeddingGrad(torch.autograd.Function):
     """Identity on y that routes dL/dy into edge_embedding.weight and the positional embedding (embeddings.linear weight / bias): the weight
     gradient of the 5200 -> 128 embedding (namp_train_feat_wgrad) and the positional table gradient (namp_train_pos_grad: the data gradient
-    g . Wedge[:, :16] contracted per relative-position class on chip — no [E,16] tensors, no library GEMM, no one-hot products)."""
+    g . Wedge[:, :16] contracted per relative-position class on chip — no [E,16] tensors, no library GEMM, no one-hot products).
+    Where X18 needs a gradient, the same namp_train_feat_wgrad call also carries dL/dX18 (namp_train_feat_xgrad): a larger
+    tile_ws with the weight copied into its input section; _atom_frames and _noised_X are torch ops, so autograd takes it on to fd["X"].
+    The scratch is 108 floats per edge for the whole batch at once (no slices: slicing the carrier would regroup dW's partial sums)."""
 
     @staticmethod
     def forward(ctx, y, Wedge, pos_w, pos_b, E_pos, d32, X18, M18, E_idx):
@@ -700,7 +703,17 @@ class _EdgeEmbeddingGrad(torch.autograd.Function):
         g = g_y.contiguous()
         n = L.namp_train_feat_wgrad_chunks(E)
         part = torch.empty(n, H, Wedge.shape[1], device=g.device)
-        tws = torch.empty(L.namp_train_feat_wgrad_ws_ints(E), dtype=torch.int32, device=g.device)
+        want_x = ctx.needs_input_grad[6]
+        if want_x:
+            dims = (E, B, Lr, K)
+            ws_ints = L.namp_train_feat_xgrad_ws_ints(*dims)
+            if ws_ints == 0 or tuple(Wedge.shape) != (H, 5200):
+                raise ValueError(f"coordinate gradients: B={B} L={Lr} K={K} ({E} edges; they must fit int32), weight {tuple(Wedge.shape)}")
+            tws = torch.empty(ws_ints, dtype=torch.int32, device=g.device)
+            o_in = L.namp_train_feat_xgrad_in_offset(*dims)
+            tws[o_in:o_in + H * 5200].view(torch.float32).view(H, 5200).copy_(Wedge.detach())
+        else:
+            tws = torch.empty(L.namp_train_feat_wgrad_ws_ints(E), dtype=torch.int32, device=g.device)
         if int(ctx.x3):                                   # packed atoms (x, y, z, mask): one 16-byte request per gathered atom
             XM = torch.cat((X18, M18.unsqueeze(-1)), -1).contiguous()
             xp, mp = XM.data_ptr(), None
@@ -711,6 +724,8 @@ class _EdgeEmbeddingGrad(torch.autograd.Function):
         # tiles would then describe the old values while pos_grad below reads the new ones — fall back to the fp32 rows)
         if g16 is not None and (g16[1] != E or g16[2] != int(ctx.x3) or g16[3] != g._version):
             g16 = None
+        if want_x:
+            hip.check(L.namp_train_feat_xgrad(ws_ints), "train_feat_xgrad")       # this thread's next call, the one below, carries dL/dX18
         hip.check(L.namp_train_feat_wgrad(xp, mp, E_idx.data_ptr(), E_pos.data_ptr(), g.data_ptr(), g16[0].data_ptr() if g16 else None,
                                           part.data_ptr(), tws.data_ptr(), int(ctx.x3), B, Lr, K, hip.current_stream()),
                   "train_feat_wgrad")
@@ -722,8 +737,12 @@ class _EdgeEmbeddingGrad(torch.autograd.Function):
                   "train_pos_grad")
         dW, tab = _reduce(_seg0(part), _seg0(part2))
         tab = tab.view(spec.NUM_POS_CLASSES + 1, spec.NUM_POS)
+        gX = None
+        if want_x:
+            o_out = L.namp_train_feat_xgrad_out_offset(*dims)
+            gX = tws[o_out:o_out + B * Lr * 54].view(torch.float32).view(B, Lr, 18, 3).clone()
         return (None, dW.view(part.shape[1:]), tab[:spec.NUM_POS_CLASSES].t().contiguous(), tab[spec.NUM_POS_CLASSES].contiguous(),
-                None, None, None, None, None)
+                None, None, gX, None, None)
 
 
 def edge_embedding(model, fd):
@@ -1021,8 +1040,10 @@ def _ffn(x, dense):
     return dense.W_out(F.gelu(dense.W_in(x)))
 
 
-def forward_train(model, fd, decoding_randn=None):
-    """Differentiable ProteinMPNN.forward of the training copy (na_model_utils.py:589-646) -> (log_probs, probs)."""
+def forward_train(model, fd, decoding_randn=None, order_mask=None):
+    """Differentiable ProteinMPNN.forward of the training copy (na_model_utils.py:589-646) -> (log_probs, probs); differentiable in fd["X"]
+    too where that tensor requires a gradient.  order_mask (default None: the training order, on mask): the [B, L] factor the
+    decoding order is sorted on instead, e.g. mask * chain_mask for score()'s order."""
     global X3, _STEP, _CACHE_STEP
     X3 = PREC_CODE[getattr(model, "message_precision", "x3")]
     _STEP = _CACHE_STEP = object()                           # a new step: its own (empty) image cache
@@ -1031,12 +1052,12 @@ def forward_train(model, fd, decoding_randn=None):
     if X3 and fd["mask"].is_cuda and torch.is_grad_enabled():
         _PLAN.begin_step(_STEP, fd["mask"].device)            # every image the previous step asked for, from one launch
     try:
-        return _forward_train(model, fd, decoding_randn)
+        return _forward_train(model, fd, decoding_randn, order_mask)
     finally:
         _STEP = None
 
 
-def _forward_train(model, fd, decoding_randn):
+def _forward_train(model, fd, decoding_randn, order_mask=None):
     mask = fd["mask"]
     if not mask.is_cuda:
         raise RuntimeError("na_mpnn_amd.train: tensors must be on a HIP device (no CPU fallback)")
@@ -1066,7 +1087,9 @@ def _forward_train(model, fd, decoding_randn):
         h_E = _EdgeUpdate.apply(h_E, Pa, Pc, W11b, p.W12.weight, p.W12.bias, p.W13.weight, p.W13.bias,
                                 p.norm3.weight, p.norm3.bias, E_idx, drop_p, seed, rev)
     chain_M = mask
-    if model.decode_protein_first:
+    if order_mask is not None:
+        chain_M = order_mask.to(mask.dtype)
+    elif model.decode_protein_first:
         chain_M = chain_M.masked_fill(fd["protein_mask"].to(torch.bool), 0.0)
     if decoding_randn is None:
         decoding_randn = torch.randn(chain_M.shape, device=mask.device)

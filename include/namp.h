@@ -979,6 +979,40 @@ size_t namp_mutations_out_offset(int N, int K, int n_dec, int n_sites, int n_var
                                  int items2, int items3);
 int namp_mutations(int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3);
 
+/* ---- specificity scan: the mutational scan under tied backbone states, riding on namp_decoder_fwd -------------------------------
+ * The scan above on the FLATTENED graph of n_states (1 to NAMP_MUT_MAX_EDITS) backbone states of L residues, N = n_states * L (flat
+ * residue m * L + i; block-diagonal E_idx, so no edge joins two copies of a residue; rank = the one order repeated per block; S and
+ * mask the states' own rows).  A copy is PRESENT where mask != 0.  The caller lists a mutation of shared residue i as a site of its
+ * n_states copies; plan, lists and items are those of namp_mutations, unchanged.  Behind layer 3, with row_j the log_softmax row of
+ * flat residue j (the variant's row where j is in U_3(site), else the base row),
+ *     unit[i]  = log_softmax(sum over the present copies j = m L + i, m ascending, of unit_w[j] * row_j)[token of i]
+ * every product and sum rounded once in fp32.  A layer-3 row LEADS shared residue i if it is present and no present copy of a lower
+ * state lies in U_3(site); the leader stores unit_v (its own token in the variant) and w * (unit_v - unit).  Then
+ *     delta[v]          = the fp32 recursive sum, in list order, of the leader terms of v
+ *     state_delta[v][m] = the sum, in list order, over the rows j of v in block m of w[j] * (own entry - base own entry)
+ * No entry point takes a pointer.  With the twelve ints (N, K, n_dec, n_states, n_sites, n_variants, list1..3, items1..3),
+ *     namp_state_mutations_workspace_bytes(...)  0 where namp_mutations_workspace_bytes is 0, n_states is outside [1, 8] or does
+ *                                                not divide N
+ *     namp_state_mutations_in_offset(...)        the INPUT SECTION: that of namp_mutations (sites, variants, w[N]: counted and
+ *                                                present), then unit_w[N] float (the state's weight where the copy is present, else 0)
+ *     namp_state_mutations_out_offset(...)       the OUTPUT SECTION, each array padded as above
+ *                                                    int32 [n_sites][3]          |U_1..3(site)|
+ *                                                    float [n_variants]          delta
+ *                                                    float [n_variants][n_states] state_delta
+ *                                                    int32 [items3], float [items3]   flat residue (-1: no item) and own entry per row
+ *                                                    int32 [items3], float [items3]   shared residue the row leads (-1: none), its unit
+ *                                                    float [L]                   the units of S (written by every attached call)
+ * and namp_state_mutations(n_states, L, n_sites, n_variants, list1..3, items1..3) attaches them to the calling thread's NEXT
+ * namp_decoder_fwd call under the rules of namp_mutations (its own attach kind: together with another kind neither runs; the call
+ * must have N == n_states * L, else NAMP_EINVAL).  Clamping, capacities, equal bits and the untouched input section: as above. */
+size_t namp_state_mutations_workspace_bytes(int N, int K, int n_dec, int n_states, int n_sites, int n_variants, int list1, int list2, int list3,
+                                            int items1, int items2, int items3);
+size_t namp_state_mutations_in_offset(int N, int K, int n_dec, int n_states, int n_sites, int n_variants, int list1, int list2, int list3,
+                                      int items1, int items2, int items3);
+size_t namp_state_mutations_out_offset(int N, int K, int n_dec, int n_states, int n_sites, int n_variants, int list1, int list2, int list3,
+                                       int items1, int items2, int items3);
+int namp_state_mutations(int n_states, int L, int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3);
+
 /* ---- tied score: the joint log-likelihood of tie-consistent sequences, riding on namp_decoder_fwd ----------------------------
  * What the tied branch of the sampler computes when every token is forced, evaluated in parallel (T = 1, no bias, special tokens
  * kept).  The carrier runs on the FLATTENED graph of N residues (M backbone states of L residues side by side, block-diagonal E_idx)

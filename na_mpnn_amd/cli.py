@@ -99,7 +99,9 @@ def build_parser():
       "(--chains_to_design, --fixed_residues, --redesigned_residues, --design_na_only), over the letters of the residue's own polymer, "
       "scored with ProteinMPNN.score_mutations as the change of the structure's joint log-likelihood; with --paired_residues / "
       "--paired_strands a paired residue is mutated together with its partner (canonical duplexes, pairs=True); writes "
-      "mutations/<name>.npz (residues, tokens, delta [P, T], base_loss, wild_type_token, site_rows)")
+      "mutations/<name>.npz (residues, tokens, delta [P, T], base_loss, wild_type_token, site_rows); with --multi_state 1 "
+      "[--state_contexts 1] the scan is the specificity scan under --state_weights (no pair or symmetry flags beside it) and "
+      "state_delta [n, M], state_weights and base_state_log_likelihood are added")
     a("--coordinate_gradients", type=int, default=0, help="1: no sampling: the gradient of the structure's negative log-likelihood, "
       "sum of -log p(s_i) over the residues the usual flags make designable (fixed residues decoded first, as score does), with respect to "
       "every atom coordinate (ProteinMPNN.coordinate_gradients); writes gradients/<name>.npz (dX [L, 16, 3], residue_norm [L], loss, "
@@ -271,9 +273,12 @@ def main(argv=None):
         raise ValueError("--state_contexts 1 does not go with --conditional_probs_only: conditional_probs() takes no context states")
     if args.mutation_scan not in (0, 1):
         raise ValueError(f"--mutation_scan is 0 or 1; got {args.mutation_scan}")
-    if args.mutation_scan and (args.score_fasta or args.conditional_probs_only or args.multi_state or args.paired_wobble):
-        raise ValueError("--mutation_scan 1 scans one structure: it does not go with --score_fasta, --conditional_probs_only, "
-                         "--multi_state or --paired_wobble")
+    if args.mutation_scan and (args.score_fasta or args.conditional_probs_only or args.paired_wobble):
+        raise ValueError("--mutation_scan 1 scans one structure: it does not go with --score_fasta, --conditional_probs_only "
+                         "or --paired_wobble")
+    if args.mutation_scan and args.multi_state and (args.paired_residues or args.paired_strands or args.symmetry_residues or args.pair_bias_AA):
+        raise ValueError("--mutation_scan 1 with --multi_state 1 scans backbone states alone: it does not go with --paired_residues, "
+                         "--paired_strands, --symmetry_residues or --pair_bias_AA")
     if args.coordinate_gradients not in (0, 1):
         raise ValueError(f"--coordinate_gradients is 0 or 1; got {args.coordinate_gradients}")
     if args.coordinate_gradients and (args.score_fasta or args.conditional_probs_only or args.multi_state or args.mutation_scan):
@@ -479,10 +484,11 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
             fd["randn"] = torch.randn(1, L, device=device)
             out = model.score_mutations(fd, pairs=bool(pairs))
             scanned = out["positions"].cpu().numpy()
+            states = {k: out[k].cpu().numpy() for k in ("state_delta", "state_weights", "base_state_log_likelihood") if k in out}
             np.savez(os.path.join(base, "mutations", name + ".npz"), residues=np.array([encoded[i] for i in scanned]),
                      tokens=np.array([int_to_str.get(int(t), "?") for t in out["tokens"].tolist()]), delta=out["delta"].cpu().numpy(),
                      base_loss=out["base_loss"].cpu().numpy(), wild_type_token=np.asarray(P["S"])[scanned],
-                     site_rows=(out["site_rows"].cpu().numpy() if out["site_rows"] is not None else np.zeros((0, 3), np.int32)))
+                     site_rows=(out["site_rows"].cpu().numpy() if out["site_rows"] is not None else np.zeros((0, 3), np.int32)), **states)
             return
         if args.coordinate_gradients:
             # per-atom saliency of the structure's own sequence under one decoding order (its noise is the only random input)

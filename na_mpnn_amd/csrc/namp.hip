@@ -2175,11 +2175,11 @@ int namp_decoder_fwd(const NampModelW* w, const float* h_V_enc, const float* h_E
                      float* h_V_dec, void* ws, size_t ws_bytes, int B_dec, int B_enc, int N, int K, void* stream) {
   {     // what the thread attached (namp_attach.h): this call carries it, and every attachment is gone whatever becomes of the call
     static int (*const run[ATTACH_KINDS])(const AttachedCall&, const int*) = {namp_internal_library_run, namp_internal_mutations_run,
-                                                                              namp_internal_tied_run};
+                                                                              namp_internal_tied_run, namp_internal_state_mutations_run};
     Attachment att[ATTACH_KINDS];
     const unsigned on = namp_internal_take_attached(att);
     if (on & (on - 1)) {                                        // more than one kind: none is run, before any pointer is looked at
-      char names[96] = "";
+      char names[128] = "";
       for (int k = 0; k < ATTACH_KINDS; ++k)
         if (on >> k & 1) snprintf(names + strlen(names), sizeof(names) - strlen(names), "%s%s", names[0] ? " and " : "", ATTACH_NOUN[k]);
       return fail(NAMP_EINVAL, "namp_decoder_fwd: %s were attached together; none is run", names);

@@ -34,8 +34,8 @@ struct WsCarver {
 };
 
 // ---- (c) what the calling thread's NEXT namp_decoder_fwd call carries, per kind; dims: the integers of the kind's entry point
-enum AttachKind { ATTACH_LIBRARY, ATTACH_MUTATIONS, ATTACH_TIED, ATTACH_KINDS };
-constexpr int ATTACH_MAX_DIMS = 8;
+enum AttachKind { ATTACH_LIBRARY, ATTACH_MUTATIONS, ATTACH_TIED, ATTACH_STATE_MUTATIONS, ATTACH_KINDS };
+constexpr int ATTACH_MAX_DIMS = 10;
 struct Attachment { bool on; int dims[ATTACH_MAX_DIMS]; };
 __attribute__((visibility("hidden"))) inline thread_local Attachment g_attached[ATTACH_KINDS] = {};
 
@@ -58,7 +58,7 @@ static inline unsigned namp_internal_take_attached(Attachment out[ATTACH_KINDS])
   return on;
 }
 // what the messages call a kind
-static const char* const ATTACH_NOUN[ATTACH_KINDS] = {"a library", "a mutational scan", "a tied score"};
+static const char* const ATTACH_NOUN[ATTACH_KINDS] = {"a library", "a mutational scan", "a tied score", "a state scan"};
 
 // ---- (d) namp_decoder_fwd's arguments as a rider's body gets them; the bodies, one per kind
 struct AttachedCall {
@@ -75,6 +75,7 @@ struct AttachedCall {
 __attribute__((visibility("hidden"))) int namp_internal_library_run(const AttachedCall& c, const int* dims);       // n_var, n_chunk, row capacities [3]
 __attribute__((visibility("hidden"))) int namp_internal_mutations_run(const AttachedCall& c, const int* dims);     // n_sites, n_variants, list [3] and item [3] capacities
 __attribute__((visibility("hidden"))) int namp_internal_tied_run(const AttachedCall& c, const int* dims);          // n_tables, n_classes, n_chunk
+__attribute__((visibility("hidden"))) int namp_internal_state_mutations_run(const AttachedCall& c, const int* dims);   // the scan's eight, n_states, L
 
 #ifdef LOO_ROW_BITS      // (behind namp_loo.h: the units that launch dec_items_kernel)
 // The checks every body starts with, in the order that decides which error a doubly-wrong call gets; noun: "a library", ...

@@ -2,9 +2,10 @@
 // namp_mutations_out_offset of include/namp.h, and the body namp_decoder_fwd runs when the calling thread has attached a scan.
 // Host code only validates, carves the caller's workspace and enqueues launches on the caller's stream: the base stream as
 // namp_library.hip runs it, the per-site plan, and per layer the index tables and one dec_items_kernel launch over
-// (variant, row of U_l(site)) items.
+// (variant, row of U_l(site)) items.  The specificity scan (namp_state_mutations, namp_state_scan.h) is the same call on the flattened graph
+// of n_states backbone states with another output side: its buffers are carved behind the scan's own, its launches follow layer 3.
 #include "../../include/namp.h"
-#include "namp_mutations.h"
+#include "namp_state_scan.h"
 #include "namp_attach.h"
 
 namespace {
@@ -14,12 +15,17 @@ struct MutBuffers : LooBaseStream, LooItemRows {                                
   uint8_t* level;                                                                      // the plan
   int32_t *loff[3], *list[3], *ioff[3];
   int32_t* in;                                   // INPUT section: sites[n_sites][8], variants[n_var][9], w[N] (float bits)
+                                                 // (states: unit_w[N] (float bits) behind them)
                                                  // (LooItemRows: [n_var * 8], [icap_l] rows)
   MutItemTables tab[3];
   int32_t* sizes;                                // OUTPUT section: int32 [n_sites][3], then
   float* delta;                                  // float [n_var], then
   int32_t* row_res;                              // int32 [icap_3], then
   float* row_lp;                                 // float [icap_3]
+  float *rows, *term;                            // states only: the variants' whole rows [icap_3][64] and the leader terms [icap_3]
+  float* state_delta;                            // states only, OUTPUT section behind delta: float [n_var][n_states]
+  int32_t* unit_res;                             // ... behind row_lp: int32 [icap_3], then
+  float *unit_lp, *base_unit;                    // float [icap_3], float [L]
   size_t in_off, out_off, bytes;                 // (all 0: the dims are refused)
 };
 
@@ -33,10 +39,13 @@ bool mut_dims_ok(int N, int K, int n_dec, const int* m) {
   return true;
 }
 
-// validates, then carves (base == nullptr: sizes only); m: n_sites, n_variants, list capacities [3], item capacities [3]
-MutBuffers mut_layout(void* base, int N_, int K, int n_dec, const int* m) {
+// validates, then carves (base == nullptr: sizes only); m: n_sites, n_variants, list capacities [3], item capacities [3];
+// n_states: 0 = the plain scan, else the specificity scan on N = n_states * L flat residues
+MutBuffers mut_layout(void* base, int N_, int K, int n_dec, const int* m, int n_states = 0) {
   MutBuffers b = {};
   if (!mut_dims_ok(N_, K, n_dec, m)) return b;
+  if (n_states < 0 || n_states > MUT_E || (n_states && N_ % n_states != 0)) return b;
+  const size_t st = (size_t)n_states;
   WsCarver c(base);
   const int *lcap = m + 2, *icap = m + 5;
   const size_t N = (size_t)N_, g128 = N * NAMP_HIDDEN, tpn = (K + 15) / 16, ns = (size_t)m[0], nv = (size_t)m[1];
@@ -48,7 +57,7 @@ MutBuffers mut_layout(void* base, int N_, int K, int n_dec, const int* m) {
     b.loff[l] = c.take<int32_t>(ns + 1); b.list[l] = c.take<int32_t>((size_t)lcap[l] + 1); b.ioff[l] = c.take<int32_t>(nv + 1);
   }
   b.in_off = c.off;
-  b.in = c.take<int32_t>(ns * MUT_E + nv * (1 + MUT_E) + N);
+  b.in = c.take<int32_t>(ns * MUT_E + nv * (1 + MUT_E) + N + (st ? N : 0));
   b.ov1 = c.take<float>(nv * MUT_E * NAMP_HIDDEN + 4);
   for (int l = 0; l < 3; ++l) {
     const size_t R = (size_t)icap[l];
@@ -58,36 +67,57 @@ MutBuffers mut_layout(void* base, int N_, int K, int n_dec, const int* m) {
     t.act = c.take<int32_t>(R + 1); t.ctr = c.take<int32_t>(R + 1); t.cen = c.take<int32_t>(R + 1); t.msk = c.take<int32_t>(R + 1);
     t.tok = c.take<int32_t>(R + 1); t.esrc = c.take<int32_t>(R * K + 1);
   }
+  if (st) { b.rows = c.take<float>((size_t)icap[2] * 64 + 4); b.term = c.take<float>((size_t)icap[2] + 1); }
   b.out_off = c.off;
   b.sizes = c.take<int32_t>(ns * 3 + 1);
   b.delta = c.take<float>(nv + 1);
+  if (st) b.state_delta = c.take<float>(nv * st + 1);
   b.row_res = c.take<int32_t>((size_t)icap[2] + 1);
   b.row_lp = c.take<float>((size_t)icap[2] + 1);
+  if (st) {
+    b.unit_res = c.take<int32_t>((size_t)icap[2] + 1);
+    b.unit_lp = c.take<float>((size_t)icap[2] + 1);
+    b.base_unit = c.take<float>(N / st + 1);
+  }
   b.bytes = c.off;
   return b;
 }
 
-}  // namespace
-
 // the carrier's body with an attachment: base stream -> log_probs, the per-site plan -> sizes, the items -> sparse entries and deltas
-__attribute__((visibility("hidden"))) int namp_internal_mutations_run(const AttachedCall& c, const int* m) {
-  const char* noun = ATTACH_NOUN[ATTACH_MUTATIONS];
+// (n_states != 0: the units and the deltas of the specificity scan instead of mut_head_kernel / mut_delta_kernel)
+int mut_run(const AttachedCall& c, const int* m, int kind, int n_states) {
+  const char* noun = ATTACH_NOUN[kind];
   int prec = PREC_F32;
   int rc = attached_prologue(c, noun, &prec);
   if (rc) return rc;
   const NampModelW* w = c.w;
   const int N = c.N, K = c.K, n_sites = m[0], n_var = m[1], *lcap = m + 2, *icap = m + 5;
-  MutBuffers b = mut_layout(c.ws, N, K, w->n_dec, m);
-  if (!b.bytes) return namp_failf(NAMP_EINVAL, "namp_decoder_fwd: bad dims for the attached mutational scan N=%ld K=%ld n_sites=%ld", N, K, n_sites);
+  if (n_states && (n_states < 1 || m[9] < 1 || (long)n_states * m[9] != N))
+    return namp_failf(NAMP_EINVAL, "namp_decoder_fwd: bad dims for the attached state scan N=%ld n_states=%ld L=%ld", N, n_states, m[9]);
+  MutBuffers b = mut_layout(c.ws, N, K, w->n_dec, m, n_states);
+  if (!b.bytes)
+    return namp_failf(NAMP_EINVAL, n_states ? "namp_decoder_fwd: bad dims for the attached state scan N=%ld K=%ld n_sites=%ld"
+                                            : "namp_decoder_fwd: bad dims for the attached mutational scan N=%ld K=%ld n_sites=%ld", N, K, n_sites);
   if ((rc = attached_ready(c, noun, b.bytes))) return rc;
   hipStream_t s = (hipStream_t)c.stream;
 
   // ---- base stream (namp_loo.h: the launches of namp_library.hip's, one summation order for every call that rides on this carrier)
   if ((rc = loo_base_stream(w, b, c.h_V_enc, c.h_E, c.E_idx, c.S, c.mask, c.rank, c.log_probs, N, K, c.stream))) return rc;
+  MutPlanArgs pa = {};
+  StateScanArgs sa = {};
+  if (n_states) {                                                // the units of S: every call leaves them, whatever its sites
+    pa.mask = c.mask; pa.S = c.S; pa.N = N; pa.vocab = w->vocab;
+    sa.base_lp = c.log_probs; sa.unit_w = (const float*)(b.in + (size_t)n_sites * MUT_E + (size_t)n_var * (1 + MUT_E) + N);
+    sa.rows = b.rows; sa.term = b.term; sa.row_res = b.row_res; sa.row_lp = b.row_lp; sa.unit_res = b.unit_res; sa.unit_lp = b.unit_lp;
+    sa.base_unit = b.base_unit; sa.delta = b.delta; sa.state_delta = b.state_delta; sa.ctr = b.tab[2].ctr; sa.tok = b.tab[2].tok;
+    sa.n_states = n_states; sa.L = N / n_states;
+    hipLaunchKernelGGL(state_base_unit_kernel, dim3((unsigned)((sa.L + 3) / 4)), dim3(256), 0, s, pa, sa);
+    const hipError_t eb = hipGetLastError();
+    if (eb != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(eb));
+  }
   if (n_sites == 0) return NAMP_OK;
 
   // ---- the plan: levels and sizes per site, the prefix sums, the lists
-  MutPlanArgs pa = {};
   pa.E_idx = c.E_idx; pa.rank = c.rank; pa.mask = c.mask; pa.S = c.S;
   pa.sites = b.in; pa.variants = b.in + (size_t)n_sites * MUT_E; pa.w = (const float*)(pa.variants + (size_t)n_var * (1 + MUT_E));
   pa.level = b.level; pa.sizes = b.sizes;
@@ -109,12 +139,30 @@ __attribute__((visibility("hidden"))) int namp_internal_mutations_run(const Atta
     hipLaunchKernelGGL(mut_items_kernel, dim3((unsigned)((Rl * K + 255) / 256)), dim3(256), 0, s, pa, b.tab[l], l);
   });
   if (rc) return rc;
+  if (n_states) {
+    if (icap[2] > 0) {
+      hipLaunchKernelGGL(state_head_kernel, dim3((unsigned)((icap[2] + 3) / 4)), dim3(256), 0, s, pa, sa, b.hO[2], w->Wout_w, w->Wout_b);
+      hipLaunchKernelGGL(state_unit_kernel, dim3((unsigned)((icap[2] + 3) / 4)), dim3(256), 0, s, pa, sa);
+    }
+    hipLaunchKernelGGL(state_delta_kernel, dim3((unsigned)((n_var + 255) / 256)), dim3(256), 0, s, pa, sa);
+    hipLaunchKernelGGL(state_block_delta_kernel, dim3((unsigned)(((long)n_var * n_states + 255) / 256)), dim3(256), 0, s, pa, sa);
+    if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+    return NAMP_OK;
+  }
   if (icap[2] > 0)
     hipLaunchKernelGGL(mut_head_kernel, dim3((unsigned)((icap[2] + 3) / 4)), dim3(256), 0, s, pa, b.tab[2].ctr, b.tab[2].tok, b.hO[2], w->Wout_w,
                        w->Wout_b, b.row_res, b.row_lp);
   hipLaunchKernelGGL(mut_delta_kernel, dim3((unsigned)((n_var + 255) / 256)), dim3(256), 0, s, pa, b.row_res, b.row_lp, c.log_probs, b.delta);
   if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
   return NAMP_OK;
+}
+
+}  // namespace
+
+__attribute__((visibility("hidden"))) int namp_internal_mutations_run(const AttachedCall& c, const int* m) { return mut_run(c, m, ATTACH_MUTATIONS, 0); }
+// dims: the scan's eight, then n_states and L
+__attribute__((visibility("hidden"))) int namp_internal_state_mutations_run(const AttachedCall& c, const int* m) {
+  return mut_run(c, m, ATTACH_STATE_MUTATIONS, m[8]);
 }
 
 extern "C" {
@@ -143,6 +191,36 @@ int namp_mutations(int n_sites, int n_variants, int list1, int list2, int list3,
   for (int v : m)
     if (v < 0) return namp_failf(NAMP_EINVAL, "namp_mutations: n_sites=%ld, n_variants=%ld and the capacities must not be negative", n_sites, n_variants);
   namp_internal_attach(ATTACH_MUTATIONS, m, 8);
+  return NAMP_OK;
+}
+
+size_t namp_state_mutations_workspace_bytes(int N, int K, int n_dec, int n_states, int n_sites, int n_variants, int list1, int list2, int list3,
+                                            int items1, int items2, int items3) {
+  const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
+  return n_states < 1 ? 0 : mut_layout(nullptr, N, K, n_dec, m, n_states).bytes;
+}
+
+size_t namp_state_mutations_in_offset(int N, int K, int n_dec, int n_states, int n_sites, int n_variants, int list1, int list2, int list3,
+                                      int items1, int items2, int items3) {
+  const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
+  return n_states < 1 ? 0 : mut_layout(nullptr, N, K, n_dec, m, n_states).in_off;
+}
+
+size_t namp_state_mutations_out_offset(int N, int K, int n_dec, int n_states, int n_sites, int n_variants, int list1, int list2, int list3,
+                                       int items1, int items2, int items3) {
+  const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
+  return n_states < 1 ? 0 : mut_layout(nullptr, N, K, n_dec, m, n_states).out_off;
+}
+
+int namp_state_mutations(int n_states, int L, int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3) {
+  namp_internal_detach(ATTACH_STATE_MUTATIONS);
+  const int m[10] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3, n_states, L};
+  for (int q = 0; q < 8; ++q)
+    if (m[q] < 0)
+      return namp_failf(NAMP_EINVAL, "namp_state_mutations: n_sites=%ld, n_variants=%ld and the capacities must not be negative", n_sites, n_variants);
+  if (n_states < 1 || n_states > MUT_E || L < 1)
+    return namp_failf(NAMP_EINVAL, "namp_state_mutations: n_states=%ld must lie in [1, %ld] and L=%ld be positive", n_states, MUT_E, L);
+  namp_internal_attach(ATTACH_STATE_MUTATIONS, m, 10);
   return NAMP_OK;
 }
 

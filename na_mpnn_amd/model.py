@@ -1350,7 +1350,7 @@ class ProteinMPNN(nn.Module):
         """The checked arguments of score_mutations() (no device needed) -> (sites int64 [n_sites, M] padded with -1, site_tokens int64
         [n, 1 + M] (0 in the padded columns), scan): both numpy; scan is None in the general form, else {"positions": the scanned
         residues (of a pair its first listed member), "tokens": the token axis, "valid": bool [P, T]}."""
-        _require_one_complex(fd, "score_mutations", "a scan over several backbone states")
+        _require_one_complex(fd, "score_mutations", "several state weights need X [M, L, atoms, 3], one backbone per state")
         L = fd["S"].shape[1]
         general = sites is not None or site_tokens is not None
         if general and (positions is not None or tokens is not None):
@@ -1439,8 +1439,9 @@ class ProteinMPNN(nn.Module):
         """A mutational scan: for every VARIANT — a SITE of 1 to 8 distinct residues with one token per residue, every other residue
         keeping feature_dict["S"] — the change of the joint log-likelihood score() reports, delta = sum_i w_i (log p_v(S_v[i]) -
         log p(S[i])) with w = mask * chain_mask, under score()'s own decoding order (the same randn, batch_size = 1: the definition
-        of score_sequences()).  One input complex (B != 1: ValueError); state_weights: NotImplementedError; ties other than
-        paired_residues with pairs=True are not read.
+        of score_sequences()).  One input complex (B != 1: ValueError); with state_weights and X [M, L, atoms, 3] the call is the
+        specificity scan of _score_state_mutations (several weights beside one backbone: NotImplementedError); ties
+        other than paired_residues with pairs=True are not read.
         The scan form: positions int [P], ascending and unique (default: mask * chain_mask != 0) x tokens int [T] (default: every
         letter of the residue's own polymer alphabet — 0..19, 21..24, 26..29 — and the token axis is their union; a given `tokens`
         is applied to every position as it stands).  pairs=True with feature_dict["paired_residues"]: scanning a paired residue
@@ -1468,6 +1469,11 @@ class ProteinMPNN(nn.Module):
         if method not in ("auto", "cone", "dense"):
             raise ValueError(f"method must be 'auto', 'cone' or 'dense'; got {method!r}")
         fd = feature_dict
+        sw = fd.get("state_weights")
+        if sw is not None:
+            # (several weights beside ONE backbone stay the refusal they were: _mutation_arguments raises NotImplementedError)
+            if not (fd["X"].dim() == 4 and fd["X"].shape[0] == 1 and (sw.numel() if torch.is_tensor(sw) else len(sw)) != 1):
+                return self._score_state_mutations(fd, positions, tokens, sites, site_tokens, pairs, method)
         st, tk, scan = self._mutation_arguments(fd, positions, tokens, sites, site_tokens, pairs)
         S_true, mask = fd["S"], fd["mask"]
         L, n, n_sites, M = S_true.shape[1], len(tk), st.shape[0], st.shape[1]
@@ -1575,6 +1581,205 @@ class ProteinMPNN(nn.Module):
         base_loss = (-btlp * w).sum() / denom
         out.update({"delta_log_likelihood": delta, "loss": base_loss - delta / denom, "base_loss": base_loss, "base_token_log_probs": btlp,
                     "base_log_probs": base, "decoding_order": order, "row_offsets": offs, "row_residue": rres, "row_token_log_prob": rlp,
+                    "chunks": chunks, "method": "cone" if use_cone else "dense"})
+        if scan is not None:
+            grid = torch.full((len(scan["positions"]), len(scan["tokens"])), float("nan"), device=dev)
+            grid[torch.from_numpy(scan["valid"]).to(dev)] = delta
+            out.update({"positions": torch.tensor(scan["positions"], dtype=torch.long, device=dev),
+                        "tokens": torch.tensor(scan["tokens"], dtype=torch.long, device=dev), "delta": grid})
+        return out
+
+    def _state_scan_arguments(self, fd, positions, tokens, sites, site_tokens, pairs):
+        """The checked arguments of the specificity scan (no device needed) -> (state weights, M, L, ctx, sites [n_sites, s], site_tokens
+        [n, 1 + s], scan: _mutation_arguments over SHARED residues; flat sites int32 [n_sites, 8] and flat variants int32 [n, 9]: the
+        edit of shared residue r goes to all M copies m * L + r, absent ones too)."""
+        listed = lambda v: v is not None and len(v) > 0 and not (len(v) == 1 and hasattr(v[0], "__len__") and len(v[0]) == 0)
+        if pairs or any(listed(fd.get(k)) for k in ("symmetry_residues", "paired_residues")) or fd.get("pair_terms") is not None \
+                or self._wobble_arguments(fd)[2]:
+            raise NotImplementedError("score_mutations with state_weights scans backbone states alone: pairs=True, symmetry_residues, "
+                                      "paired_residues, paired_wobble and pair_terms are not supported beside them")
+        _require_one_complex(fd, "score_mutations", None)
+        state_w, M, L, ctx = self._state_arguments_of(fd)
+        shared = {k: v for k, v in fd.items() if k != "state_weights"}
+        st, tk, scan = self._mutation_arguments(shared, positions, tokens, sites, site_tokens, False)
+        s = int((st >= 0).sum(1).max()) if len(st) else 1
+        if s * M > MUT_MAX_EDITS:
+            raise ValueError(f"a site of {s} residues in {M} states is {s * M} edits on the flattened graph; at most {MUT_MAX_EDITS} fit")
+        w = [a * b for a, b in zip(fd["mask"][0].reshape(-1).tolist(), fd["chain_mask"][0].reshape(-1).tolist())]
+        for r in sorted({int(r) for r in st.reshape(-1) if r >= 0}):
+            if w[r] == 0:
+                raise ValueError(f"residue {r} has mask * chain_mask == 0: score_tied would not apply an edit there")
+        sites8 = np.full((len(st), MUT_MAX_EDITS), -1, np.int32)
+        tok9 = np.zeros((len(tk), 1 + MUT_MAX_EDITS), np.int32)
+        tok9[:, 0] = tk[:, 0]
+        for q, row in enumerate(st):
+            cols = [c for c, r in enumerate(row) if r >= 0]
+            pick = np.nonzero(tk[:, 0] == q)[0]
+            for e, c in enumerate(cols):
+                for m_ in range(M):
+                    sites8[q, e * M + m_] = m_ * L + row[c]
+                    tok9[pick, 1 + e * M + m_] = tk[pick, 1 + c]
+        return state_w, M, L, ctx, st, tk, scan, sites8, tok9
+
+    def _score_state_mutations(self, fd, positions, tokens, sites, site_tokens, pairs, method):
+        """score_mutations() with feature_dict["state_weights"] — the specificity scan: which point mutations widen the
+        gap between backbone states.  The states arguments and conventions are score_tied()'s (state_weights of M entries, optionally
+        state_S / state_mask, shared [1, L] rows, X [M, L, A, 3]; T = 1, no bias, special tokens kept, score()'s order from the shared
+        mask * chain_mask and row 0 of randn).  positions / sites are SHARED residue indices with mask * chain_mask != 0 (else ValueError);
+        the edit goes to all M copies, so a site of s residues is s * M <= 8 edits on the flattened graph (else ValueError).
+        delta_log_likelihood[v] = score_tied(fd, S_v)["log_likelihood"] - score_tied(fd, S)["log_likelihood"], the sum over the counted
+        residues of unit_v[i] - unit[i], unit[i] = log_softmax(sum over the states in which i is present of w_m lp_m[i])[S[i]] (M = 1:
+        the own entry, as score_tied has it); "state_delta" [n, M] the difference of score_tied's state_log_likelihood.  Returns what
+        score_mutations returns, "loss" / "base_loss" / "base_token_log_probs" [L] on units (-inf where the present copies of a fixed
+        residue hold different tokens, as in score_tied), "base_log_probs" [1, M * L, vocab] and the sparse rows in FLAT residues, and
+        adds "state_delta", "base_state_log_likelihood" [M], "state_weights" [M] and the sparse units "unit_offsets" int64 [n + 1],
+        "unit_residue" int32 (shared, ascending per variant), "unit_log_prob" float32: one entry per shared residue with a copy in
+        U_3(site).  method: "cone" — namp_state_mutations (include/namp.h) carried by one decoder call per chunk on the flattened
+        graph; "dense" — the explicit library through score_tied(method="stream"); "auto" — the cone where it applies and the mean of
+        sum_l |U_l(site)| over the variants is at most 2 * M * L."""
+        state_w, M, L, ctx, st, tk, scan, sites8, tok9 = self._state_scan_arguments(fd, positions, tokens, sites, site_tokens, pairs)
+        S_true, mask = fd["S"], fd["mask"]
+        n, n_sites, N, Vn = len(tk), len(st), M * L, self.num_letters
+        cone_ok = self._item_routes_ok()
+        if method == "cone" and not cone_ok:
+            raise NotImplementedError("score_mutations(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
+                                      "use method='dense'")
+        _require_device(fd["X"], "X")
+        dev = fd["X"].device
+        counted = (mask * fd["chain_mask"])[0] != 0                                        # [L]
+        present = (mask.expand(M, L) if ctx is None else ctx[1]) != 0                       # [M, L]
+        sw = torch.tensor(state_w if M > 1 else [1.0], dtype=torch.float32, device=dev)     # (M = 1: the own entry, as score_tied has it)
+        w_flat = (counted[None] & present).reshape(N).float()
+        unit_w = (sw[:, None] * present).reshape(N).float()
+        out = {"site_index": torch.from_numpy(tk[:, 0].copy()).to(dev), "sites": torch.from_numpy(st).to(dev),
+               "site_tokens": torch.from_numpy(tk).to(dev), "site_rows": None,
+               "state_weights": torch.tensor(state_w, dtype=torch.float32, device=dev)}
+        o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1])
+        h_V, h_E, E_idx = self._encode_side_by_side(fd, o, state_w, M, L, ctx)
+        self._check_tokens(S_true)
+        o.wait()
+        K = E_idx.shape[2]
+        inputs = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, o.rank[:1], M, L, ctx)
+        S_flat = inputs[4][0].long()
+        use_cone, rows_host, base, btlp = False, None, None, None
+        if cone_ok and method != "dense" and n_sites:
+            base = torch.empty(1, N, Vn, device=dev)
+
+            def call(site_ids, variant_ids, lcap, icap):
+                """One attached decoder call over the listed sites and variants -> its workspace and the offset of its output section."""
+                ns, nv = len(site_ids), len(variant_ids)
+                dims = (N, K, 3, M, ns, nv) + tuple(lcap) + tuple(icap)
+
+                def fill(section):
+                    local = np.zeros(n_sites, np.int32)
+                    local[site_ids] = np.arange(ns, dtype=np.int32)
+                    var = tok9[variant_ids].copy()
+                    var[:, 0] = local[var[:, 0]]
+                    sec = torch.from_numpy(np.concatenate((sites8[site_ids].reshape(-1), var.reshape(-1))))
+                    section[:4 * sec.numel()].view(torch.int32).copy_(sec)
+                    section[4 * sec.numel():4 * (sec.numel() + 2 * N)].view(torch.float32).copy_(torch.cat((w_flat, unit_w)))
+                return self._attached_decoder_call("state_mutations", dims, (M, L) + dims[4:], fill, inputs, base, N, K,
+                                                   f"score_mutations: no workspace for {M} states x L={L} K={K} sites={ns} variants={nv}")
+
+            def sections(ws, ooff, ns, nv, rows3):
+                """The arrays of the output section, in its order."""
+                got = []
+                for elems, dt in ((3 * ns, torch.int32), (nv, torch.float32), (nv * M, torch.float32), (rows3, torch.int32),
+                                  (rows3, torch.float32), (rows3, torch.int32), (rows3, torch.float32), (L, torch.float32)):
+                    got.append(ws[ooff:ooff + 4 * elems].view(dt))
+                    ooff += _section_bytes(elems)
+                return got
+
+            ws, ooff = call(np.arange(n_sites), np.zeros(0, np.int64), (0, 0, 0), (0, 0, 0))      # the plan alone: sizes, base rows, base units
+            first = sections(ws, ooff, n_sites, 0, 0)
+            out["site_rows"] = first[0].view(n_sites, 3).clone()
+            btlp = first[7].clone()
+            rows_host = out["site_rows"].cpu().numpy().astype(np.int64)           # the call's ONE read-back: route and chunks hang on it
+            use_cone = method == "cone" or int(rows_host[tk[:, 0]].sum()) <= 2 * N * n
+        if use_cone and n:
+            perm, cuts = mutation_chunks(tk[:, 0].tolist(), rows_host.tolist(), 3 * self.score_library_tokens)
+            perm = np.asarray(perm, np.int64)
+            parts = [[] for _ in range(6)]
+            for q0, q1 in cuts:
+                vids = perm[q0:q1]
+                sids = np.unique(tk[vids, 0])                                     # (perm is ordered by site: the order of appearance)
+                lcap = rows_host[sids].sum(0).tolist()
+                icap = rows_host[tk[vids, 0]].sum(0).tolist()
+                ws, ooff = call(sids, vids, lcap, icap)
+                got = sections(ws, ooff, len(sids), len(vids), icap[2])
+                for p, g in zip(parts, got[1:7]):
+                    p.append(g.clone())
+            delta_s, sdelta_s, rres, rlp, ures, ulp = (torch.cat(p) for p in parts)
+            counts = torch.from_numpy(rows_host[tk[:, 0], 2])
+            offs = torch.cat((torch.zeros(1, dtype=torch.int64), counts.cumsum(0)))
+            pt = torch.from_numpy(perm)
+            delta = torch.empty_like(delta_s)
+            delta[pt.to(dev)] = delta_s
+            sdelta = torch.empty(n, M, device=dev)
+            sdelta[pt.to(dev)] = sdelta_s.view(n, M)
+            if not np.array_equal(perm, np.arange(n)):                                          # the rows back into the order the variants were given in
+                start_sorted = torch.cat((torch.zeros(1, dtype=torch.int64), counts[pt].cumsum(0)))[:-1]
+                start = torch.empty(n, dtype=torch.int64)
+                start[pt] = start_sorted
+                idx = (torch.repeat_interleave(start - offs[:-1], counts) + torch.arange(int(offs[-1]))).to(dev)
+                rres, rlp, ures, ulp = rres[idx], rlp[idx], ures[idx], ulp[idx]
+            # the sparse units: the leader rows, per variant ascending in the shared residue
+            vid = torch.repeat_interleave(torch.arange(n), counts).to(dev)
+            lead = ures >= 0
+            key = vid[lead] * L + ures[lead].long()
+            srt = torch.argsort(key, stable=True)
+            ures, ulp = ures[lead][srt], ulp[lead][srt]
+            uoffs = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.bincount(vid[lead], minlength=n).cumsum(0)))
+            offs = offs.to(dev)
+            chunks = len(cuts)
+        elif n == 0:
+            use_cone = False
+            delta, sdelta = torch.zeros(0, device=dev), torch.zeros(0, M, device=dev)
+            rres, rlp = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev)
+            ures, ulp = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev)
+            offs = uoffs = torch.zeros(1, dtype=torch.int64, device=dev)
+            chunks = 0
+        else:
+            use_cone = False
+            S_full = S_true.long().expand(n + 1, L).clone()                       # the variants, and S itself as the last row
+            s_w = st.shape[1]
+            res = st[tk[:, 0]].reshape(-1)
+            keep = res >= 0
+            vi = torch.from_numpy(np.repeat(np.arange(n), s_w)[keep]).to(dev)
+            S_full[vi, torch.from_numpy(res[keep]).to(dev)] = torch.from_numpy(tk[:, 1:].reshape(-1)[keep]).to(dev)
+            lib = self.score_tied(fd, S_full, method="stream")
+            own = lib["member_log_probs"]                                          # [n + 1, M, L]
+            state_ll = torch.where((counted[None] & present)[None], own, torch.zeros_like(own)).sum(-1)
+            delta = lib["log_likelihood"][:n] - lib["log_likelihood"][n]
+            sdelta = state_ll[:n] - state_ll[n:]
+            offs = torch.arange(n + 1, dtype=torch.int64, device=dev) * N
+            rres = torch.arange(N, dtype=torch.int32, device=dev).repeat(n)
+            rlp = own[:n].reshape(-1)
+            uoffs = torch.arange(n + 1, dtype=torch.int64, device=dev) * L
+            ures = torch.arange(L, dtype=torch.int32, device=dev).repeat(n)
+            ulp = lib["token_log_probs"][:n].reshape(-1)
+            btlp = lib["token_log_probs"][n].clone()
+            chunks = lib["chunks"]
+        if base is None:                                                           # the flat base rows of the routes that ran no attached call
+            rows = S_flat.view(M, L)
+            base = self.decode_graph(h_V, h_E, E_idx.long(), rows, present.to(mask.dtype), o.rank[:1].expand(M, L)).reshape(1, N, Vn)
+        if btlp is None:
+            btlp = self.score_tied(fd, method="stream")["token_log_probs"][0]
+        else:
+            # (the device reports every unit at its first present copy's token; where the present copies of a fixed residue hold
+            #  different tokens score_tied has -inf)
+            tok = S_flat.view(M, L)
+            seat = torch.where(present.any(0), present.float().argmax(0), torch.zeros(L, dtype=torch.long, device=dev))
+            same = ((tok == tok.gather(0, seat[None])) | ~present).all(0)
+            btlp = torch.where(same, btlp, torch.full_like(btlp, float("-inf")))
+        own0 = base[0].gather(1, S_flat[:, None])[:, 0]
+        wl = counted.float()
+        denom = wl.sum() + 1e-8
+        base_loss = -torch.where(counted, btlp, torch.zeros_like(btlp)).sum() / denom
+        out.update({"delta_log_likelihood": delta, "loss": base_loss - delta / denom, "base_loss": base_loss, "base_token_log_probs": btlp,
+                    "base_log_probs": base, "decoding_order": o.order[0], "row_offsets": offs, "row_residue": rres, "row_token_log_prob": rlp,
+                    "state_delta": sdelta, "base_state_log_likelihood": (own0 * w_flat).view(M, L).sum(-1),
+                    "unit_offsets": uoffs, "unit_residue": ures, "unit_log_prob": ulp,
                     "chunks": chunks, "method": "cone" if use_cone else "dense"})
         if scan is not None:
             grid = torch.full((len(scan["positions"]), len(scan["tokens"])), float("nan"), device=dev)
@@ -2020,7 +2225,7 @@ class ProteinMPNN(nn.Module):
         if classes:
             words.append(torch.tensor([v for row in bias for v in row], dtype=torch.float32).view(torch.int32))
         out = {"tied": tied_specs, "singles": singles, "listed": listed_groups, "section": torch.cat(words), "n_tables": len(table),
-               "index": torch.tensor([t[0] + [-1] * (width - len(t[0])) for t in tied_specs], dtype=torch.int64).reshape(-1, width)}
+               "index": torch.tensor([t[0] + [-1] * (width - len(t[0])) for t in tied_specs], dtype=torch.int64).reshape(len(tied_specs), width)}
         self._tie_tables[(tied, classes)] = (key, (dna, rna, m), out)
         return out
 

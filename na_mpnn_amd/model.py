@@ -13,6 +13,7 @@ otherwise a RuntimeError is raised.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import sys
 import warnings
@@ -84,6 +85,37 @@ def _require_device(t, what):
 def _section_bytes(elems):
     """The bytes one array of elems (+ 1) four-byte entries takes in a workspace section: rounded to 256 (include/namp.h)."""
     return (4 * (elems + 1) + 255) & ~255
+
+
+def output_section_layout(family, dims):
+    """The arrays of the OUTPUT SECTION of an attached namp_decoder_fwd call, in the order include/namp.h lists (and the library
+    carves) them -> [(name, elems, dtype), ...]; needs no device.  family: "library", "mutations", "state_mutations" or "tied_score";
+    dims: the ints of the family's size functions.  The 64-word header of "library" / "tied_score" is carved as it stands: 63 (+ 1)."""
+    i32, f32 = torch.int32, torch.float32
+    if family == "library":
+        N, n_chunk = dims[0], dims[4]
+        return [("counts", 63, i32), ("token_log_probs", n_chunk * N, f32)]
+    if family == "tied_score":
+        N, n_chunk = dims[0], dims[5]
+        return [("header", 63, i32), ("unit_log_probs", n_chunk * N, f32), ("member_log_probs", n_chunk * N, f32)]
+    if family == "mutations":
+        ns, nv, rows3 = dims[3], dims[4], dims[10]
+        return [("site_rows", 3 * ns, i32), ("delta", nv, f32), ("row_residue", rows3, i32), ("row_token_log_prob", rows3, f32)]
+    if family == "state_mutations":
+        N, M, ns, nv, rows3 = dims[0], dims[3], dims[4], dims[5], dims[11]
+        return [("site_rows", 3 * ns, i32), ("delta", nv, f32), ("state_delta", nv * M, f32), ("row_residue", rows3, i32),
+                ("row_token_log_prob", rows3, f32), ("unit_residue", rows3, i32), ("unit_log_prob", rows3, f32), ("base_units", N // M, f32)]
+    raise ValueError(f"no output section is described for {family!r}")
+
+
+def _read_sections(ws, out_offset, layout):
+    """The arrays of output_section_layout as views of the workspace -> {name: view [elems]} (clone what must outlive the workspace's
+    next use)."""
+    views = {}
+    for name, elems, dtype in layout:
+        views[name] = ws[out_offset:out_offset + 4 * elems].view(dtype)
+        out_offset += _section_bytes(elems)
+    return views
 
 
 def _positions_argument(positions, L):
@@ -409,6 +441,12 @@ def pair_terms_dense(pair_terms, L):
 
 MUT_MAX_EDITS = 8     # NAMP_MUT_MAX_EDITS of include/namp.h: residues per site of score_mutations()
 
+# A scan on the per-site cones as ProteinMPNN._cone_scan drives it: the family riding on namp_decoder_fwd; the carrier's N, K; what
+# comes before (n_sites, n_variants, list1..3, items1..3) in the ints of the size functions (dims) and of the attach; the start of the
+# "no workspace" message; the padded sites / variants (flat_sites_and_variants); the float tail of the input section (on the device);
+# the output arrays (output_section_layout) with one entry per variant {name: trailing shape} and those with one per row of U_3.
+_ConeRoute = collections.namedtuple("_ConeRoute", "family N K dims attach what sites8 tok9 weights per_variant per_row")
+
 
 def mutation_chunks(site_index, site_rows, budget):
     """The chunk cutter of score_mutations(method="cone"); needs no device.  site_index [n]: the site of every variant; site_rows
@@ -428,6 +466,37 @@ def mutation_chunks(site_index, site_rows, budget):
     if len(perm) > q0:
         cuts.append((q0, len(perm)))
     return perm, cuts
+
+
+def variant_row_order(perm, counts):
+    """The sparse rows of score_mutations(method="cone") back into the order the variants were given in; needs no device.  perm [n]:
+    the order the variants ran in (mutation_chunks), counts int64 [n]: rows per variant, in the GIVEN order.  -> (offsets int64
+    [n + 1] of the given order, idx int64 [sum(counts)] with restored = ran[idx], or None where perm is the identity)."""
+    offs = torch.cat((torch.zeros(1, dtype=torch.int64), counts.cumsum(0)))
+    if np.array_equal(perm, np.arange(len(perm))):
+        return offs, None
+    pt = torch.as_tensor(np.asarray(perm, np.int64))
+    start_sorted = torch.cat((torch.zeros(1, dtype=torch.int64), counts[pt].cumsum(0)))[:-1]
+    start = torch.empty(len(pt), dtype=torch.int64)
+    start[pt] = start_sorted
+    return offs, torch.repeat_interleave(start - offs[:-1], counts) + torch.arange(int(offs[-1]))
+
+
+def flat_sites_and_variants(st, tk, M, L):
+    """The sites and variants of the input section of namp_mutations / namp_state_mutations; needs no device.  st int [n_sites, s]
+    padded with -1, tk int [n, 1 + s] (a site index, then one token per column of st), M states of L residues (M = 1: the plain scan)
+    -> sites8 int32 [n_sites, 8], tok9 int32 [n, 9]: with e counting the residues a site lists, copy m * L + r of edit e sits at column
+    e * M + m and its token at 1 + e * M + m; padded columns hold -1 / 0.  (The callers have checked that s * M <= 8 edits are listed.)"""
+    sites8 = np.full((len(st), MUT_MAX_EDITS), -1, np.int32)
+    tok9 = np.zeros((len(tk), 1 + MUT_MAX_EDITS), np.int32)
+    tok9[:, 0] = tk[:, 0]
+    s = min(st.shape[1], MUT_MAX_EDITS // M)
+    first = np.argsort(st < 0, axis=1, kind="stable")                               # the listed residues first, in their order
+    res = np.take_along_axis(st, first, 1)[:, :s]
+    tok = np.take_along_axis(tk[:, 1:], first[tk[:, 0]], 1)[:, :s]
+    sites8[:, :s * M] = np.where(res[:, :, None] >= 0, res[:, :, None] + L * np.arange(M), -1).reshape(len(st), s * M)
+    tok9[:, 1:1 + s * M] = np.repeat(np.where(res[tk[:, 0]] >= 0, tok, 0), M, axis=1)
+    return sites8, tok9
 
 
 def mutations_dense(out, L):
@@ -1019,9 +1088,14 @@ class ProteinMPNN(nn.Module):
 
     # ---- shared by the calls that ride on a decoder call (conditional_probs, score_sequences, score_mutations, score_tied) ----------
 
-    def _item_routes_ok(self):
-        """What the item kernel of the cone conditionals evaluates: three decoder layers, split-bf16 or exact fp32."""
-        return len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+    def _item_routes_ok(self, who, method, fallback):
+        """What the item kernel of the cone conditionals evaluates: three decoder layers, split-bf16 or exact fp32 -> whether this
+        model has them; `who` asked for an item route by name (method "cone", "active" or "items") without them: NotImplementedError."""
+        ok = len(self.decoder_layers) == 3 and self.message_precision in ("x3", "fp32")
+        if method in ("cone", "active", "items") and not ok:
+            raise NotImplementedError(f"{who}(method='{method}') needs three decoder layers and message_precision 'x3' or 'fp32'; "
+                                      f"use method='{fallback}'")
+        return ok
 
     def _state_arguments_of(self, fd):
         """fd["state_weights"] checked as sample() checks them, for a call that draws nothing -> (state weights, M, L, the context
@@ -1061,7 +1135,8 @@ class ProteinMPNN(nn.Module):
     def _attached_decoder_call(self, family, dims, attach_args, fill, inputs, log_probs, N, K, what):
         """One namp_decoder_fwd call that carries what namp_<family>(*attach_args) attaches: the workspace is sized
         for dims (a size of 0: ValueError(what)), fill(section) writes the input section (a uint8 view from its offset on), then the
-        attach and the call -> (the workspace, the offset of its output section).  inputs: _item_decoder_inputs."""
+        attach and the call -> the arrays of its output section by name (output_section_layout: views of the call's workspace).
+        inputs: _item_decoder_inputs."""
         Lb = hip.lib()
         W, h_V, h_E, E32, S32, m32, r32 = inputs
         need = getattr(Lb, f"namp_{family}_workspace_bytes")(*dims)
@@ -1073,7 +1148,7 @@ class ProteinMPNN(nn.Module):
         hip.check(Lb.namp_decoder_fwd(W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), S32.data_ptr(), m32.data_ptr(),
                                       r32.data_ptr(), log_probs.data_ptr(), None, None, ws.data_ptr(), ws.numel(), 1, 1, N, K,
                                       hip.current_stream()), f"decoder_fwd ({family})")
-        return ws, getattr(Lb, f"namp_{family}_out_offset")(*dims)
+        return _read_sections(ws, getattr(Lb, f"namp_{family}_out_offset")(*dims), output_section_layout(family, dims))
 
     # streams of the L-stream form of conditional_probs() per decoder call: chunk * L stays within the 64 x 1000 tokens of the B = 64 batches
     loo_dense_tokens = 65536
@@ -1138,10 +1213,7 @@ class ProteinMPNN(nn.Module):
         if tied and fd.get("state_weights") is not None:
             state_w, M, L = self._state_arguments_of(fd)[:3]
         ties = self._conditional_arguments(fd, B, L, state_w, tied, classes)
-        cone_ok = self._item_routes_ok()
-        if method == "cone" and not cone_ok:
-            raise NotImplementedError("conditional_probs(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
-                                      "use method='dense'")
+        cone_ok = self._item_routes_ok("conditional_probs", method, "dense")
         use_cone = method == "cone" or (method == "auto" and cone_ok)
         Lb, n_dec, N = hip.lib(), len(self.decoder_layers), M * L
         K = int(min(self.k_neighbors, L))
@@ -1290,10 +1362,7 @@ class ProteinMPNN(nn.Module):
         pos, tokens, S_full = self._library_arguments(fd, S_lib, positions)
         S_true, mask = fd["S"], fd["mask"]
         L, n, n_var = S_true.shape[1], S_full.shape[0], len(pos)
-        active_ok = self._item_routes_ok()
-        if method == "active" and not active_ok:
-            raise NotImplementedError("score_sequences(method='active') needs three decoder layers and message_precision 'x3' or 'fp32'; "
-                                      "use method='dense'")
+        active_ok = self._item_routes_ok("score_sequences", method, "dense")
         use_active = method == "active" or (method == "auto" and active_ok and self._library_auto(n_var, L, n))
         _require_device(fd["X"], "X")
         dev = fd["X"].device
@@ -1314,7 +1383,7 @@ class ProteinMPNN(nn.Module):
             base = torch.empty(1, L, self.num_letters, device=dev)
 
             def call(k0, k1, rows):
-                """One attached decoder call over sequences k0 .. k1 - 1 -> its workspace and the offset of its output section."""
+                """One attached decoder call over sequences k0 .. k1 - 1 -> the arrays of its output section."""
                 def fill(section):
                     sec = section[:4 * (n_var + (k1 - k0) * n_var)].view(torch.int32)
                     sec[:n_var] = pos32
@@ -1323,15 +1392,13 @@ class ProteinMPNN(nn.Module):
                     "library", (L, K, 3, n_var, k1 - k0) + tuple(rows), (n_var, k1 - k0) + tuple(rows), fill, inputs, base, L, K,
                     f"score_sequences: no library workspace for L={L} K={K} n_var={n_var} sequences={k1 - k0}")
 
-            ws, ooff = call(0, 0, (0, 0, 0))                     # the plan alone: the counts, and base_log_probs
-            counts = ws[ooff:ooff + 24].view(torch.int32).clone()
+            counts = call(0, 0, (0, 0, 0))["counts"][:6].clone()    # the plan alone: the counts, and base_log_probs
             out["active_rows"] = counts[:3]
             rows = [int(v) for v in counts[3:6].tolist()]        # the call's ONE read-back: the chunks are sized by it
             chunk = max(1, min(3 * self.score_library_tokens // max(1, sum(rows)), ((1 << 28) - 1) // L))
             for k0 in range(0, n, chunk):
                 k1 = min(n, k0 + chunk)
-                ws, ooff = call(k0, k1, rows)
-                tlp[k0:k1] = ws[ooff + 256:ooff + 256 + 4 * (k1 - k0) * L].view(torch.float32).view(k1 - k0, L)
+                tlp[k0:k1] = call(k0, k1, rows)["token_log_probs"].view(k1 - k0, L)
                 chunks += 1
         else:
             base = self.decode_graph(h_V, h_E, E_idx, S_true, mask, rank)
@@ -1477,16 +1544,13 @@ class ProteinMPNN(nn.Module):
         st, tk, scan = self._mutation_arguments(fd, positions, tokens, sites, site_tokens, pairs)
         S_true, mask = fd["S"], fd["mask"]
         L, n, n_sites, M = S_true.shape[1], len(tk), st.shape[0], st.shape[1]
-        cone_ok = self._item_routes_ok()
-        if method == "cone" and not cone_ok:
-            raise NotImplementedError("score_mutations(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
-                                      "use method='dense'")
+        cone_ok = self._item_routes_ok("score_mutations", method, "dense")
         _require_device(fd["X"], "X")
         dev = fd["X"].device
         w = (mask * fd["chain_mask"])[0].float()
         out = {"site_index": torch.from_numpy(tk[:, 0].copy()).to(dev), "sites": torch.from_numpy(st).to(dev),
                "site_tokens": torch.from_numpy(tk).to(dev), "site_rows": None}
-        use_cone, rows_host, base = False, None, None
+        use_cone, base = False, None
         if cone_ok and method != "dense" and n_sites:
             o = self._decoding_order(mask, fd["chain_mask"], fd["randn"])
             h_V, h_E, E_idx = self.encode(fd, order=o)
@@ -1495,35 +1559,12 @@ class ProteinMPNN(nn.Module):
             K = E_idx.shape[2]
             inputs = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, o.rank[:1], 1, L)
             base = torch.empty(1, L, self.num_letters, device=dev)
-            sites8 = np.full((n_sites, MUT_MAX_EDITS), -1, np.int32)
-            sites8[:, :M] = st
-            tok9 = np.zeros((n, 1 + MUT_MAX_EDITS), np.int32)
-            tok9[:, :1 + M] = tk
-
-            def call(site_ids, variant_ids, lcap, icap):
-                """One attached decoder call over the listed sites and variants -> its workspace and the offset of its output section."""
-                ns, nv = len(site_ids), len(variant_ids)
-                dims = (L, K, 3, ns, nv) + tuple(lcap) + tuple(icap)
-
-                def fill(section):
-                    local = np.zeros(n_sites, np.int32)
-                    local[site_ids] = np.arange(ns, dtype=np.int32)
-                    var = tok9[variant_ids].copy()
-                    var[:, 0] = local[var[:, 0]]
-                    sec = torch.from_numpy(np.concatenate((sites8[site_ids].reshape(-1), var.reshape(-1))))
-                    section[:4 * sec.numel()].view(torch.int32).copy_(sec)
-                    section[4 * sec.numel():4 * (sec.numel() + L)].view(torch.float32).copy_(w)           # (the weights never leave the device)
-                return self._attached_decoder_call("mutations", dims, dims[3:], fill, inputs, base, L, K,
-                                                   f"score_mutations: no workspace for L={L} K={K} sites={ns} variants={nv}")
-
-            ws, ooff = call(np.arange(n_sites), np.zeros(0, np.int64), (0, 0, 0), (0, 0, 0))      # the plan alone: the sizes, and base_log_probs
-            out["site_rows"] = ws[ooff:ooff + 12 * n_sites].view(torch.int32).view(n_sites, 3).clone()
-            rows_host = out["site_rows"].cpu().numpy().astype(np.int64)           # the call's ONE read-back: route and chunks hang on it
-            use_cone = method == "cone" or int(rows_host[tk[:, 0]].sum()) <= 2 * L * n
+            route = _ConeRoute("mutations", L, K, (L, K, 3), (), f"score_mutations: no workspace for L={L} K={K}",
+                               *flat_sites_and_variants(st, tk, 1, L), w, {"delta": ()}, ("row_residue", "row_token_log_prob"))
+            got = self._cone_scan(route, inputs, base, tk[:, 0], method)
+            out["site_rows"], use_cone = got["site_rows"], got["use_cone"]
         if n == 0:
-            one = dict(fd)
-            one["batch_size"] = 1
-            sc = self.score(one)
+            sc = self.score(dict(fd, batch_size=1))
             base, order = sc["log_probs"], sc["decoding_order"]
             delta = torch.zeros(0, device=dev)
             rres, rlp = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev)
@@ -1531,35 +1572,7 @@ class ProteinMPNN(nn.Module):
             chunks = 0
         elif use_cone:
             order = o.order[0]
-            perm, cuts = mutation_chunks(tk[:, 0].tolist(), rows_host.tolist(), 3 * self.score_library_tokens)
-            perm = np.asarray(perm, np.int64)
-            d_l, r_l, e_l = [], [], []
-            for q0, q1 in cuts:
-                vids = perm[q0:q1]
-                sids = np.unique(tk[vids, 0])                                     # (perm is ordered by site: the order of appearance)
-                lcap = rows_host[sids].sum(0).tolist()
-                icap = rows_host[tk[vids, 0]].sum(0).tolist()
-                ws, ooff = call(sids, vids, lcap, icap)
-                a = ooff + _section_bytes(3 * len(sids))
-                b = a + _section_bytes(len(vids))
-                c = b + _section_bytes(icap[2])
-                d_l.append(ws[a:a + 4 * len(vids)].view(torch.float32).clone())
-                r_l.append(ws[b:b + 4 * icap[2]].view(torch.int32).clone())
-                e_l.append(ws[c:c + 4 * icap[2]].view(torch.float32).clone())
-            delta_s, rres, rlp = torch.cat(d_l), torch.cat(r_l), torch.cat(e_l)
-            counts = torch.from_numpy(rows_host[tk[:, 0], 2])
-            offs = torch.cat((torch.zeros(1, dtype=torch.int64), counts.cumsum(0)))
-            pt = torch.from_numpy(perm)
-            delta = torch.empty_like(delta_s)
-            delta[pt.to(dev)] = delta_s
-            if not np.array_equal(perm, np.arange(n)):                                          # the rows back into the order the variants were given in
-                start_sorted = torch.cat((torch.zeros(1, dtype=torch.int64), counts[pt].cumsum(0)))[:-1]
-                start = torch.empty(n, dtype=torch.int64)
-                start[pt] = start_sorted
-                idx = (torch.repeat_interleave(start - offs[:-1], counts) + torch.arange(int(offs[-1]))).to(dev)
-                rres, rlp = rres[idx], rlp[idx]
-            offs = offs.to(dev)
-            chunks = len(cuts)
+            delta, offs, rres, rlp, chunks = (got[k] for k in ("delta", "row_offsets", "row_residue", "row_token_log_prob", "chunks"))
         else:
             S_full = S_true.long().expand(n, L).clone()
             vi = torch.from_numpy(np.repeat(np.arange(n), M)[(st[tk[:, 0]] >= 0).reshape(-1)]).to(dev)
@@ -1579,15 +1592,80 @@ class ProteinMPNN(nn.Module):
         btlp = base[0].gather(1, S_true[0].long()[:, None])[:, 0]
         denom = w.sum() + 1e-8
         base_loss = (-btlp * w).sum() / denom
+        return self._scan_result(out, scan, delta, base_loss, denom, btlp, base, order, (offs, rres, rlp), {}, chunks, use_cone)
+
+    @staticmethod
+    def _scan_result(out, scan, delta, base_loss, denom, btlp, base, order, rows, extra, chunks, use_cone):
+        """What both forms of score_mutations() return alike, added to out: the deltas and losses, the sparse rows (offsets, residues,
+        entries), `extra` (the form's own keys), "chunks", "method" and, in the scan form, the [P, T] grid."""
+        dev = delta.device
         out.update({"delta_log_likelihood": delta, "loss": base_loss - delta / denom, "base_loss": base_loss, "base_token_log_probs": btlp,
-                    "base_log_probs": base, "decoding_order": order, "row_offsets": offs, "row_residue": rres, "row_token_log_prob": rlp,
-                    "chunks": chunks, "method": "cone" if use_cone else "dense"})
+                    "base_log_probs": base, "decoding_order": order, "row_offsets": rows[0], "row_residue": rows[1],
+                    "row_token_log_prob": rows[2], **extra, "chunks": chunks, "method": "cone" if use_cone else "dense"})
         if scan is not None:
             grid = torch.full((len(scan["positions"]), len(scan["tokens"])), float("nan"), device=dev)
             grid[torch.from_numpy(scan["valid"]).to(dev)] = delta
             out.update({"positions": torch.tensor(scan["positions"], dtype=torch.long, device=dev),
                         "tokens": torch.tensor(scan["tokens"], dtype=torch.long, device=dev), "delta": grid})
         return out
+
+    def _cone_scan(self, route, inputs, base, site_index, method):
+        """The cone route of both forms of score_mutations() (DESIGN.md 5.14, 5.19).  route: a _ConeRoute; inputs: _item_decoder_inputs;
+        base: the carrier's log_probs; site_index int64 [n] (numpy): the site of every variant.  One attached call with zero variants
+        gives the sizes (and base); they are read back ONCE, "auto" is decided, the variants are cut by mutation_chunks and every chunk
+        is one attached call with its own sites, renumbered.  -> {"site_rows" int32 [n_sites, 3], "use_cone", "chunks", the plan call's
+        arrays that are neither per variant nor per row} and, where the cone is taken and there are variants, the route's per-variant and
+        per-row arrays by name in the order the variants were GIVEN in, "row_offsets" int64 [n + 1] and "row_counts" (on the host).
+        Every array is a clone: the next call reuses the workspace."""
+        r, n_sites, n, dev = route, len(route.sites8), len(site_index), base.device
+
+        def call(site_ids, variant_ids, lcap, icap):
+            """One attached decoder call over the listed sites and variants -> the arrays of its output section."""
+            ns, nv = len(site_ids), len(variant_ids)
+            tail = (ns, nv) + tuple(lcap) + tuple(icap)
+
+            def fill(section):
+                local = np.zeros(n_sites, np.int32)
+                local[site_ids] = np.arange(ns, dtype=np.int32)
+                var = r.tok9[variant_ids].copy()
+                var[:, 0] = local[var[:, 0]]
+                sec = torch.from_numpy(np.concatenate((r.sites8[site_ids].reshape(-1), var.reshape(-1))))
+                section[:4 * sec.numel()].view(torch.int32).copy_(sec)
+                section[4 * sec.numel():4 * (sec.numel() + r.weights.numel())].view(torch.float32).copy_(r.weights)   # (they never leave the device)
+            return self._attached_decoder_call(r.family, r.dims + tail, r.attach + tail, fill, inputs, base, r.N, r.K,
+                                               f"{r.what} sites={ns} variants={nv}")
+
+        first = call(np.arange(n_sites), np.zeros(0, np.int64), (0, 0, 0), (0, 0, 0))         # the plan alone: the sizes, and base_log_probs
+        got = {"site_rows": first.pop("site_rows").view(n_sites, 3).clone(), "chunks": 0}
+        got.update({k: v.clone() for k, v in first.items() if k not in r.per_variant and k not in r.per_row})
+        rows_host = got["site_rows"].cpu().numpy().astype(np.int64)               # the call's ONE read-back: route and chunks hang on it
+        got["use_cone"] = method == "cone" or int(rows_host[site_index].sum()) <= 2 * r.N * n
+        if not (got["use_cone"] and n):
+            return got
+        perm, cuts = mutation_chunks(site_index.tolist(), rows_host.tolist(), 3 * self.score_library_tokens)
+        perm = np.asarray(perm, np.int64)
+        names = tuple(r.per_variant) + tuple(r.per_row)
+        parts = {k: [] for k in names}
+        for q0, q1 in cuts:
+            vids = perm[q0:q1]
+            sids = np.unique(site_index[vids])                                    # (perm is ordered by site: the order of appearance)
+            lcap = rows_host[sids].sum(0).tolist()
+            icap = rows_host[site_index[vids]].sum(0).tolist()
+            sec = call(sids, vids, lcap, icap)
+            for k in names:
+                parts[k].append(sec[k].clone())
+        counts = torch.from_numpy(rows_host[site_index, 2])
+        offs, idx = variant_row_order(perm, counts)
+        pt = torch.from_numpy(perm).to(dev)
+        for k, shape in r.per_variant.items():
+            ran = torch.cat(parts[k]).view((n,) + shape)
+            got[k] = torch.empty_like(ran)
+            got[k][pt] = ran
+        idx = None if idx is None else idx.to(dev)
+        for k in r.per_row:
+            got[k] = torch.cat(parts[k]) if idx is None else torch.cat(parts[k])[idx]
+        got.update({"row_offsets": offs.to(dev), "row_counts": counts, "chunks": len(cuts)})
+        return got
 
     def _state_scan_arguments(self, fd, positions, tokens, sites, site_tokens, pairs):
         """The checked arguments of the specificity scan (no device needed) -> (state weights, M, L, ctx, sites [n_sites, s], site_tokens
@@ -1609,17 +1687,7 @@ class ProteinMPNN(nn.Module):
         for r in sorted({int(r) for r in st.reshape(-1) if r >= 0}):
             if w[r] == 0:
                 raise ValueError(f"residue {r} has mask * chain_mask == 0: score_tied would not apply an edit there")
-        sites8 = np.full((len(st), MUT_MAX_EDITS), -1, np.int32)
-        tok9 = np.zeros((len(tk), 1 + MUT_MAX_EDITS), np.int32)
-        tok9[:, 0] = tk[:, 0]
-        for q, row in enumerate(st):
-            cols = [c for c, r in enumerate(row) if r >= 0]
-            pick = np.nonzero(tk[:, 0] == q)[0]
-            for e, c in enumerate(cols):
-                for m_ in range(M):
-                    sites8[q, e * M + m_] = m_ * L + row[c]
-                    tok9[pick, 1 + e * M + m_] = tk[pick, 1 + c]
-        return state_w, M, L, ctx, st, tk, scan, sites8, tok9
+        return (state_w, M, L, ctx, st, tk, scan) + flat_sites_and_variants(st, tk, M, L)
 
     def _score_state_mutations(self, fd, positions, tokens, sites, site_tokens, pairs, method):
         """score_mutations() with feature_dict["state_weights"] — the specificity scan: which point mutations widen the
@@ -1640,10 +1708,7 @@ class ProteinMPNN(nn.Module):
         state_w, M, L, ctx, st, tk, scan, sites8, tok9 = self._state_scan_arguments(fd, positions, tokens, sites, site_tokens, pairs)
         S_true, mask = fd["S"], fd["mask"]
         n, n_sites, N, Vn = len(tk), len(st), M * L, self.num_letters
-        cone_ok = self._item_routes_ok()
-        if method == "cone" and not cone_ok:
-            raise NotImplementedError("score_mutations(method='cone') needs three decoder layers and message_precision 'x3' or 'fp32'; "
-                                      "use method='dense'")
+        cone_ok = self._item_routes_ok("score_mutations", method, "dense")
         _require_device(fd["X"], "X")
         dev = fd["X"].device
         counted = (mask * fd["chain_mask"])[0] != 0                                        # [L]
@@ -1661,87 +1726,32 @@ class ProteinMPNN(nn.Module):
         K = E_idx.shape[2]
         inputs = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, o.rank[:1], M, L, ctx)
         S_flat = inputs[4][0].long()
-        use_cone, rows_host, base, btlp = False, None, None, None
+        use_cone, base, btlp = False, None, None
         if cone_ok and method != "dense" and n_sites:
             base = torch.empty(1, N, Vn, device=dev)
-
-            def call(site_ids, variant_ids, lcap, icap):
-                """One attached decoder call over the listed sites and variants -> its workspace and the offset of its output section."""
-                ns, nv = len(site_ids), len(variant_ids)
-                dims = (N, K, 3, M, ns, nv) + tuple(lcap) + tuple(icap)
-
-                def fill(section):
-                    local = np.zeros(n_sites, np.int32)
-                    local[site_ids] = np.arange(ns, dtype=np.int32)
-                    var = tok9[variant_ids].copy()
-                    var[:, 0] = local[var[:, 0]]
-                    sec = torch.from_numpy(np.concatenate((sites8[site_ids].reshape(-1), var.reshape(-1))))
-                    section[:4 * sec.numel()].view(torch.int32).copy_(sec)
-                    section[4 * sec.numel():4 * (sec.numel() + 2 * N)].view(torch.float32).copy_(torch.cat((w_flat, unit_w)))
-                return self._attached_decoder_call("state_mutations", dims, (M, L) + dims[4:], fill, inputs, base, N, K,
-                                                   f"score_mutations: no workspace for {M} states x L={L} K={K} sites={ns} variants={nv}")
-
-            def sections(ws, ooff, ns, nv, rows3):
-                """The arrays of the output section, in its order."""
-                got = []
-                for elems, dt in ((3 * ns, torch.int32), (nv, torch.float32), (nv * M, torch.float32), (rows3, torch.int32),
-                                  (rows3, torch.float32), (rows3, torch.int32), (rows3, torch.float32), (L, torch.float32)):
-                    got.append(ws[ooff:ooff + 4 * elems].view(dt))
-                    ooff += _section_bytes(elems)
-                return got
-
-            ws, ooff = call(np.arange(n_sites), np.zeros(0, np.int64), (0, 0, 0), (0, 0, 0))      # the plan alone: sizes, base rows, base units
-            first = sections(ws, ooff, n_sites, 0, 0)
-            out["site_rows"] = first[0].view(n_sites, 3).clone()
-            btlp = first[7].clone()
-            rows_host = out["site_rows"].cpu().numpy().astype(np.int64)           # the call's ONE read-back: route and chunks hang on it
-            use_cone = method == "cone" or int(rows_host[tk[:, 0]].sum()) <= 2 * N * n
-        if use_cone and n:
-            perm, cuts = mutation_chunks(tk[:, 0].tolist(), rows_host.tolist(), 3 * self.score_library_tokens)
-            perm = np.asarray(perm, np.int64)
-            parts = [[] for _ in range(6)]
-            for q0, q1 in cuts:
-                vids = perm[q0:q1]
-                sids = np.unique(tk[vids, 0])                                     # (perm is ordered by site: the order of appearance)
-                lcap = rows_host[sids].sum(0).tolist()
-                icap = rows_host[tk[vids, 0]].sum(0).tolist()
-                ws, ooff = call(sids, vids, lcap, icap)
-                got = sections(ws, ooff, len(sids), len(vids), icap[2])
-                for p, g in zip(parts, got[1:7]):
-                    p.append(g.clone())
-            delta_s, sdelta_s, rres, rlp, ures, ulp = (torch.cat(p) for p in parts)
-            counts = torch.from_numpy(rows_host[tk[:, 0], 2])
-            offs = torch.cat((torch.zeros(1, dtype=torch.int64), counts.cumsum(0)))
-            pt = torch.from_numpy(perm)
-            delta = torch.empty_like(delta_s)
-            delta[pt.to(dev)] = delta_s
-            sdelta = torch.empty(n, M, device=dev)
-            sdelta[pt.to(dev)] = sdelta_s.view(n, M)
-            if not np.array_equal(perm, np.arange(n)):                                          # the rows back into the order the variants were given in
-                start_sorted = torch.cat((torch.zeros(1, dtype=torch.int64), counts[pt].cumsum(0)))[:-1]
-                start = torch.empty(n, dtype=torch.int64)
-                start[pt] = start_sorted
-                idx = (torch.repeat_interleave(start - offs[:-1], counts) + torch.arange(int(offs[-1]))).to(dev)
-                rres, rlp, ures, ulp = rres[idx], rlp[idx], ures[idx], ulp[idx]
+            route = _ConeRoute("state_mutations", N, K, (N, K, 3, M), (M, L), f"score_mutations: no workspace for {M} states x L={L} K={K}",
+                               sites8, tok9, torch.cat((w_flat, unit_w)), {"delta": (), "state_delta": (M,)},
+                               ("row_residue", "row_token_log_prob", "unit_residue", "unit_log_prob"))
+            got = self._cone_scan(route, inputs, base, tk[:, 0], method)         # (the plan call: sizes, base rows, base units)
+            out["site_rows"], btlp, use_cone = got["site_rows"], got["base_units"], got["use_cone"] and n > 0
+        if use_cone:
+            delta, sdelta, offs, rres, rlp, ures, ulp, chunks = (got[k] for k in (
+                "delta", "state_delta", "row_offsets", "row_residue", "row_token_log_prob", "unit_residue", "unit_log_prob", "chunks"))
             # the sparse units: the leader rows, per variant ascending in the shared residue
-            vid = torch.repeat_interleave(torch.arange(n), counts).to(dev)
+            vid = torch.repeat_interleave(torch.arange(n), got["row_counts"]).to(dev)
             lead = ures >= 0
             key = vid[lead] * L + ures[lead].long()
             srt = torch.argsort(key, stable=True)
             ures, ulp = ures[lead][srt], ulp[lead][srt]
             uoffs = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.bincount(vid[lead], minlength=n).cumsum(0)))
-            offs = offs.to(dev)
-            chunks = len(cuts)
         elif n == 0:
-            use_cone = False
             delta, sdelta = torch.zeros(0, device=dev), torch.zeros(0, M, device=dev)
             rres, rlp = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev)
             ures, ulp = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev)
             offs = uoffs = torch.zeros(1, dtype=torch.int64, device=dev)
             chunks = 0
         else:
-            use_cone = False
-            S_full = S_true.long().expand(n + 1, L).clone()                       # the variants, and S itself as the last row
+            S_full = S_true.long().expand(n + 1, L).clone()                      # the variants, and S itself as the last row
             s_w = st.shape[1]
             res = st[tk[:, 0]].reshape(-1)
             keep = res >= 0
@@ -1776,17 +1786,9 @@ class ProteinMPNN(nn.Module):
         wl = counted.float()
         denom = wl.sum() + 1e-8
         base_loss = -torch.where(counted, btlp, torch.zeros_like(btlp)).sum() / denom
-        out.update({"delta_log_likelihood": delta, "loss": base_loss - delta / denom, "base_loss": base_loss, "base_token_log_probs": btlp,
-                    "base_log_probs": base, "decoding_order": o.order[0], "row_offsets": offs, "row_residue": rres, "row_token_log_prob": rlp,
-                    "state_delta": sdelta, "base_state_log_likelihood": (own0 * w_flat).view(M, L).sum(-1),
-                    "unit_offsets": uoffs, "unit_residue": ures, "unit_log_prob": ulp,
-                    "chunks": chunks, "method": "cone" if use_cone else "dense"})
-        if scan is not None:
-            grid = torch.full((len(scan["positions"]), len(scan["tokens"])), float("nan"), device=dev)
-            grid[torch.from_numpy(scan["valid"]).to(dev)] = delta
-            out.update({"positions": torch.tensor(scan["positions"], dtype=torch.long, device=dev),
-                        "tokens": torch.tensor(scan["tokens"], dtype=torch.long, device=dev), "delta": grid})
-        return out
+        extra = {"state_delta": sdelta, "base_state_log_likelihood": (own0 * w_flat).view(M, L).sum(-1),
+                 "unit_offsets": uoffs, "unit_residue": ures, "unit_log_prob": ulp}
+        return self._scan_result(out, scan, delta, base_loss, denom, btlp, base, o.order[0], (offs, rres, rlp), extra, chunks, use_cone)
 
     @staticmethod
     def _tied_combine_plan(ties, classes, dev):
@@ -1900,13 +1902,10 @@ class ProteinMPNN(nn.Module):
             self._check_tokens(S_lib, "S_lib")
         pairs, sym = fd.get("paired_residues"), fd.get("symmetry_residues")
         listed = not (pairs is None or len(pairs) == 0) or not (sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0))
-        items_ok = self._item_routes_ok()
         if method == "stream" and listed:
             raise ValueError("score_tied(method='stream') is defined with state_weights alone or no tie at all: two members of a listed "
                              "group can be graph neighbours; use method='items' or 'sampler'")
-        if method == "items" and not items_ok:
-            raise NotImplementedError("score_tied(method='items') needs three decoder layers and message_precision 'x3' or 'fp32'; "
-                                      "use method='sampler'")
+        items_ok = self._item_routes_ok("score_tied", method, "sampler")
         # (context states: a unit of ONE present copy still draws from softmax(w_m logits_m); the item kernel's unit of one is the own
         #  entry of log_softmax(logits_m), so that route serves such units with weight 1 only)
         weighted_singles = ctx is not None and any(wr != 1.0 for _, wr in ties["singles"])
@@ -2067,12 +2066,10 @@ class ProteinMPNN(nn.Module):
                     sec = sec[:4 * (section.numel() + nk * N)].view(torch.int32)
                     sec[:section.numel()] = section
                     sec[section.numel():] = seq32[k0:k1].reshape(-1)
-                ws, ooff = self._attached_decoder_call("tied_score", (N, K, 3, n_tab, n_cls, nk), (n_tab, n_cls, nk), fill, inputs, rows0, N, K,
-                                                       f"score_tied: no workspace for N={N} K={K} tables={n_tab} sequences={nk}")
-                ooff += 256
-                span = _section_bytes(nk * N)
-                unit_lp[k0:k1] = ws[ooff:ooff + 4 * nk * N].view(torch.float32).view(nk, N)
-                member_lp[k0:k1] = ws[ooff + span:ooff + span + 4 * nk * N].view(torch.float32).view(nk, N)
+                got = self._attached_decoder_call("tied_score", (N, K, 3, n_tab, n_cls, nk), (n_tab, n_cls, nk), fill, inputs, rows0, N, K,
+                                                  f"score_tied: no workspace for N={N} K={K} tables={n_tab} sequences={nk}")
+                unit_lp[k0:k1] = got["unit_log_probs"].view(nk, N)
+                member_lp[k0:k1] = got["member_log_probs"].view(nk, N)
                 chunks += 1
         tlp = (unit_lp[:, :L] if seat is None else unit_lp[:, seat]).contiguous()
         cm = (mask * fd["chain_mask"])[0] != 0

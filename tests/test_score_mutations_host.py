@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from na_mpnn_amd import spec, synth
-from na_mpnn_amd.model import ProteinMPNN, mutation_chunks
+from na_mpnn_amd.model import ProteinMPNN, mutation_chunks, variant_row_order
 from oracle import cpu_ref
 import library_ref as LR
 import mutation_ref as MR
@@ -171,3 +171,29 @@ def test_chunk_cutter():
             assert total + sum(site_rows[site_index[perm[b0]]]) > budget
     assert mutation_chunks([], [[1, 1, 1]], 10) == ([], [])
     assert mutation_chunks([0, 0, 0], [[50, 50, 50]], 10)[1] == [(0, 1), (1, 2), (2, 3)]
+
+
+@pytest.mark.parametrize("name,site_index,rows3", [
+    ("three sites interleaved", [2, 0, 1, 0, 2, 1, 1, 0], [3, 1, 5]),
+    ("a site without rows", [1, 0, 2, 1, 0, 2], [4, 0, 2]),
+    ("one variant", [0], [3]),
+    ("the identity", [0, 0, 1, 2, 2], [2, 3, 1])])
+def test_rows_return_to_the_order_the_variants_were_given_in(name, site_index, rows3):
+    """variant_row_order against a loop: the variants run grouped by site (mutation_chunks' perm), each leaving rows3[site] rows; the
+    restored rows are every variant's own, in the order given, and row_offsets are their prefix sums.  The identity order takes the
+    fast path: the rows stay untouched."""
+    n = len(site_index)
+    perm = mutation_chunks(site_index, [[0, 0, r] for r in rows3], 10 ** 6)[0]
+    counts = [rows3[s] for s in site_index]
+    ran = [(v, k) for v in perm for k in range(counts[v])]                              # what the calls leave: (variant, its k-th row)
+    offs, idx = variant_row_order(np.asarray(perm, np.int64), torch.tensor(counts, dtype=torch.int64))
+    assert offs.dtype == torch.int64 and offs.tolist() == [sum(counts[:v]) for v in range(n + 1)]
+    want = [(v, k) for v in range(n) for k in range(counts[v])]
+    if name == "the identity":
+        assert perm == list(range(n)) and idx is None and ran == want
+    else:
+        assert perm != list(range(n)) or n == 1
+        got = ran if idx is None else [ran[q] for q in idx.tolist()]
+        assert got == want and (idx is None or (idx.dtype == torch.int64 and sorted(idx.tolist()) == list(range(len(ran)))))
+    if name == "a site without rows":
+        assert 0 in counts

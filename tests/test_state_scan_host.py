@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from na_mpnn_amd import hip, spec
-from na_mpnn_amd.model import MUT_MAX_EDITS, ProteinMPNN
+from na_mpnn_amd.model import MUT_MAX_EDITS, ProteinMPNN, _read_sections, _section_bytes, flat_sites_and_variants, output_section_layout
 from oracle import cpu_ref
 import context_states_ref as CR
 import mutation_ref as MR
@@ -117,6 +117,84 @@ def test_sections_are_aligned_ordered_and_hold_what_the_header_lists(dims):
     add_in = _round(ns * 8 + nv * 9 + 2 * N) - _round(ns * 8 + nv * 9 + N)
     add = add_in + _round(i3 * 64 + 4) + _round(i3 + 1) + _round(nv * M + 1) + 2 * _round(i3 + 1) + _round(N // M + 1)
     assert size == plain[0] + add
+
+
+def _section_total(family, dims):
+    return sum(_section_bytes(elems) for _, elems, _ in output_section_layout(family, dims))
+
+
+@pytest.mark.parametrize("dims", LEGAL)
+def test_the_python_layout_is_the_output_section_of_both_scans(dims):
+    """output_section_layout against the library's own sizes, and against the arrays include/namp.h lists, in its order."""
+    N, K, n_dec, M, ns, nv, l1, l2, l3, i1, i2, i3 = dims
+    i32, f32 = torch.int32, torch.float32
+    size, _, o_off = _sizes(dims)
+    assert _section_total("state_mutations", dims) == size - o_off
+    assert [(e, t) for _, e, t in output_section_layout("state_mutations", dims)] == [
+        (3 * ns, i32), (nv, f32), (nv * M, f32), (i3, i32), (i3, f32), (i3, i32), (i3, f32), (N // M, f32)]
+    plain = dims[:3] + dims[4:]
+    Lb = hip.lib()
+    assert _section_total("mutations", plain) == int(Lb.namp_mutations_workspace_bytes(*plain)) - int(Lb.namp_mutations_out_offset(*plain))
+    assert [(e, t) for _, e, t in output_section_layout("mutations", plain)] == [(3 * ns, i32), (nv, f32), (i3, i32), (i3, f32)]
+    # the reader walks the same bytes: every view starts 256-aligned, holds its elems, and the last one ends inside the section
+    ws = torch.zeros(size - o_off + 256, dtype=torch.uint8)
+    views = _read_sections(ws, 256, output_section_layout("state_mutations", dims))
+    assert list(views) == ["site_rows", "delta", "state_delta", "row_residue", "row_token_log_prob", "unit_residue", "unit_log_prob",
+                           "base_units"]
+    for (name, elems, dtype), v in zip(output_section_layout("state_mutations", dims), views.values()):
+        assert v.dtype == dtype and v.numel() == elems and 4 * v.storage_offset() % 256 == 0
+    last = views["base_units"]
+    assert 4 * last.storage_offset() + _section_bytes(last.numel()) == ws.numel()
+
+
+# small and large shapes of tests/test_workspace_layout_host.py: (N, K, n_dec, n_var, n_chunk, rows_1..3) / (N, K, n_dec, n_tables, n_classes, n_chunk)
+@pytest.mark.parametrize("family,dims,want", [
+    ("library", (1, 1, 3, 1, 1, 1, 1, 1), [(63, torch.int32), (1, torch.float32)]),
+    ("library", (1000, 48, 3, 40, 64, 60, 150, 400), [(63, torch.int32), (64000, torch.float32)]),
+    ("tied_score", (1, 1, 3, 1, 33, 1), [(63, torch.int32), (1, torch.float32), (1, torch.float32)]),
+    ("tied_score", (1000, 48, 3, 64, 64, 65), [(63, torch.int32), (65000, torch.float32), (65000, torch.float32)])])
+def test_the_python_layout_of_the_library_and_the_tied_score(family, dims, want):
+    """A 64-word header (carved as it stands: 63 + 1), then float [n_chunk][N] once / twice, as include/namp.h lists them."""
+    Lb = hip.lib()
+    size, o_off = (int(getattr(Lb, f"namp_{family}{f}")(*dims)) for f in ("_workspace_bytes", "_out_offset"))
+    assert 0 < o_off < size and _section_total(family, dims) == size - o_off
+    assert [(e, t) for _, e, t in output_section_layout(family, dims)] == want
+    assert _section_bytes(63) == 256
+
+
+def _flat_by_loops(st, tk, M, L):
+    """The arrays of flat_sites_and_variants spelled out: per site, per listed residue, per state."""
+    sites8 = np.full((len(st), MUT_MAX_EDITS), -1, np.int32)
+    tok9 = np.zeros((len(tk), 1 + MUT_MAX_EDITS), np.int32)
+    tok9[:, 0] = tk[:, 0]
+    for q, row in enumerate(st):
+        cols = [c for c, r in enumerate(row) if r >= 0]
+        pick = np.nonzero(tk[:, 0] == q)[0]
+        for e, c in enumerate(cols):
+            for m_ in range(M):
+                sites8[q, e * M + m_] = m_ * L + row[c]
+                tok9[pick, 1 + e * M + m_] = tk[pick, 1 + c]
+    return sites8, tok9
+
+
+@pytest.mark.parametrize("name,st,tk,M,L", [
+    ("M=1", [[3, 5, 7], [9, 11, 2]], [[1, 4, 5, 6], [0, 1, 2, 3], [1, 7, 8, 9], [0, 20, 21, 22]], 1, 12),
+    ("M=1, eight residues", [list(range(8, 0, -1))], [[0] + list(range(10, 18))], 1, 9),
+    ("M=4 at the cap", [[3, 5], [0, 11]], [[1, 4, 5], [0, 1, 2], [1, 7, 8]], 4, 12),
+    ("a padded site row", [[3, -1], [4, 6], [8, -1]], [[2, 9, 0], [0, 1, 0], [1, 2, 3], [0, 5, 0]], 3, 10),
+    ("a padded row of three columns in four states", [[3, -1, -1], [4, 6, -1]], [[1, 2, 3, 0], [0, 1, 0, 0]], 4, 10),
+    ("n=0", [[3, 5], [0, 11]], np.zeros((0, 3), np.int64), 4, 12),
+    ("no site", np.zeros((0, 1), np.int64), np.zeros((0, 2), np.int64), 2, 12)])
+def test_the_padding_of_sites_and_variants_against_loops(name, st, tk, M, L):
+    st, tk = np.asarray(st, np.int64), np.asarray(tk, np.int64)
+    sites8, tok9 = flat_sites_and_variants(st, tk, M, L)
+    want8, want9 = _flat_by_loops(st, tk, M, L)
+    assert sites8.dtype == tok9.dtype == np.int32 and sites8.shape == (len(st), 8) and tok9.shape == (len(tk), 9)
+    assert np.array_equal(sites8, want8) and np.array_equal(tok9, want9)
+    if M == 1 and (st >= 0).all():                                # the plain scan: the arrays as they are, padded
+        assert np.array_equal(sites8[:, :st.shape[1]], st) and np.array_equal(tok9[:, :tk.shape[1]], tk)
+    if name == "M=4 at the cap":
+        assert (sites8 >= 0).all() and sites8[0].tolist() == [3, 15, 27, 39, 5, 17, 29, 41] and tok9[0].tolist() == [1, 4, 4, 4, 4, 5, 5, 5, 5]
 
 
 @pytest.mark.parametrize("dims", REFUSED)

@@ -14,7 +14,6 @@ otherwise a RuntimeError is raised.
 from __future__ import annotations
 
 import collections
-import ctypes as C
 import sys
 import warnings
 import weakref
@@ -23,8 +22,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import hip, spec
+from . import hip, sampling, spec
 from .pack import PackedWeights
+from .sampling import _i32, level_work_lists, symmetry_visits          # (the two host routines: imported from here by tests and tools)
 
 H = spec.H
 
@@ -70,10 +70,6 @@ class _FeatureParams(nn.Module):
         self.norm_nodes = nn.LayerNorm(node_features)
         self.edge_embedding = nn.Linear(spec.NUM_POS + spec.NUM_RBF * n_atoms_aug * n_atoms_aug, edge_features, bias=False)
         self.norm_edges = nn.LayerNorm(edge_features)
-
-
-def _i32(t):
-    return t.to(torch.int32).contiguous()
 
 
 def _require_device(t, what):
@@ -138,80 +134,6 @@ def _require_one_complex(fd, who, states_note):
         raise ValueError(f"{who} expects one input complex (B == 1); got S of shape {tuple(S.shape)}")
     if states_note is not None and fd.get("state_weights") is not None:
         raise NotImplementedError(f"{who} does not take state_weights ({states_note})")
-
-
-def level_work_lists(level, group_first, group_last, order0, E_idx0, split):
-    """Work lists of the level-parallel sampler (include/namp.h: namp_decoder_sample_levels / _walk) from the per-visit levels.
-
-    level [B_dec, L] int32 by visit (namp_sample_levels_dep); group_first / group_last [B_dec, L] int32 by visit, or None without
-    symmetry groups (every stream has the same groups); order0 [L] the residues in visit order, E_idx0 [L, K] the neighbour lists.
-    Returns (sel, flat, work_n, close, close_off): sel = stream * L + first visit of every work item, sorted by level (flat = those
-    levels); work_n = visits per item (None without groups); close / close_off = the deferred-draw lists when `split`, else None.
-    split: a group none of whose members has another member among its graph neighbours becomes single-member items (decoded in
-    parallel, one deferred draw per group); a group with internal edges stays ONE item whose members run one after the other."""
-    B_dec, L = level.shape
-    dev = level.device
-    if group_first is None:
-        flat = level.reshape(-1).long()
-        perm = torch.argsort(flat, stable=True)
-        return perm, flat[perm], None, None, None
-    ar = torch.arange(L, dtype=torch.int32, device=dev)
-    gf0 = group_first[0].to(torch.int32)
-    gsize = torch.bincount(gf0.long(), minlength=L).to(torch.int32)                       # by first visit
-    whole = torch.ones(L, dtype=torch.bool, device=dev)                                    # visit v belongs to a group run as ONE item
-    close = close_off = None
-    if split:
-        ord0 = order0.long()
-        gid_res = torch.empty(L, dtype=torch.int32, device=dev).scatter_(0, ord0, gf0)    # residue -> its group's first visit
-        nb = E_idx0.long()
-        intra = ((gid_res[nb] == gid_res[:, None]) & (nb != ar[:, None].long())).any(1)   # residue has a neighbour in its own group
-        gdep = torch.zeros(L, dtype=torch.int32, device=dev).scatter_reduce_(0, gf0.long(), intra[ord0].to(torch.int32), "amax")
-        whole = gdep[gf0.long()] > 0
-        lastv = (group_last[0] != 0).nonzero().view(-1)                                    # one closing entry per group and stream
-        cl_v = lastv.repeat(B_dec)
-        cl_b = torch.arange(B_dec, device=dev).repeat_interleave(lastv.numel())
-        cl_lv = level[cl_b, cl_v].long()
-        cperm = torch.argsort(cl_lv, stable=True)
-        close = torch.stack((cl_b[cperm], cl_v[cperm]), 1).to(torch.int32).contiguous()
-        chist = torch.zeros(L + 1, dtype=torch.int64, device=dev).scatter_add_(0, cl_lv, torch.ones_like(cl_lv))
-        close_off = torch.cat((chist.new_zeros(1), chist.cumsum(0))).to(torch.int32).contiguous()
-    heads0 = (~whole) | (gf0 == ar)                                                        # an item starts at this visit
-    n0 = torch.where(whole, gsize[gf0.long()], torch.ones_like(gsize))
-    head_pos0 = heads0.nonzero().view(-1)
-    head_pos = (torch.arange(B_dec, device=dev)[:, None] * L + head_pos0[None, :]).view(-1)   # stream-major
-    sizes = n0[head_pos0].repeat(B_dec)
-    flat = level.reshape(-1)[head_pos].long()
-    perm = torch.argsort(flat, stable=True)
-    return head_pos[perm], flat[perm], sizes[perm].contiguous(), close, close_off
-
-
-def symmetry_visits(groups, weights, order0, L):
-    """Visit plan of symmetry-tied sampling (model_utils.py:220-235): tied residues are visited together, in the order stream 0's
-    decoding order `order0` (a list of the L residues) reaches their first member; every stream then uses that one order.  A residue
-    listed in several groups belongs to the FIRST listed one (as in the reference).  groups / weights: the feature_dict's
-    symmetry_residues / symmetry_weights.  Returns lists of L: (visits, group_first, group_last, w) = the residues in visit order, the
-    first visit of each visit's group, 1 on a group's last visit (else 0), and the weight of each residue (1 outside the groups)."""
-    w = [1.0] * L
-    for i1, group in enumerate(groups):
-        for i2, item in enumerate(group):
-            w[item] = float(weights[i1][i2])
-    group_of = {}
-    for g in groups:
-        for item in g:
-            group_of.setdefault(int(item), g)
-    seen, visit_groups = set(), []
-    for t in order0:
-        if t in seen:
-            continue
-        visit_groups.append(list(group_of.get(t, (t,))))
-        seen.update(visit_groups[-1])
-    visits = [t for g in visit_groups for t in g]
-    if sorted(visits) != list(range(L)):
-        raise ValueError("symmetry_residues groups must be disjoint")
-    gf, gl, v = [], [], 0
-    for g in visit_groups:
-        gf += [v] * len(g); gl += [0] * (len(g) - 1) + [1]; v += len(g)
-    return visits, gf, gl, w
 
 
 def tied_stream_keys(rank0, groups):
@@ -2344,7 +2266,8 @@ class ProteinMPNN(nn.Module):
 
     def _sample(self, fd, walk, uniform=None, plan_out=None):
         """sample() with the persistent level walk on or off (`walk`) and the uniforms of the draws given (None: torch.rand).
-        plan_out: a dict that receives the plan arrays of a symmetry-tied call (tests compare the routes array for array)."""
+        plan_out: a dict that receives the plan arrays of a symmetry-tied call (tests compare the routes array for array).  The plan and the
+        launch are sampling.py's."""
         if fd.get("state_weights") is not None:
             return self._sample_states(fd, walk, uniform)
         bs = fd["batch_size"]
@@ -2371,224 +2294,85 @@ class ProteinMPNN(nn.Module):
         V, _, h_E, E_idx = self._featurize_hip(fd, want_E=False, want_hE=True, order=o)   # (E_idx stays int32: the kernels' dtype)
         K = E_idx.shape[-1]
         B_dec = B * bs
+        dims, Lb = (B_dec, B, L, K), hip.lib()
+        # (dep_idx, n_dep) of the levels beside the graph's — the pair terms section's partner block IS one; None: the sequential walk
+        deps = (None, 0) if pterms is None else (pterms["dep"], pterms["D"])
+        on_device = (self.sample_level_parallel and walk and o.order32 is not None and order.shape[0] == B_dec
+                     and E_idx.dtype == torch.int32 and E_idx.is_contiguous())
+        plan = start = None
         # Plain branch: the dependency levels and the walk's work lists need the neighbour lists and the decoding order only — enqueued on
-        # the side stream behind the featuriser launch, beside the encoder launches (sample_levels_kernel is a serial walk of one wave per
-        # stream: 62 us at 97 residues in front of the walk otherwise).
-        early = None
-        # (pair terms add dependencies to the levels: the early levels receive the section's partner block — uploaded and sorted on this
-        # stream in front of the event —, the device plan of the pairs below stands aside)
-        if (not symmetric and "pair_bias" not in fd and self.sample_level_parallel and walk and not o.pending and o.order32 is not None
-                and order.shape[0] == B_dec and L <= 16000 and E_idx.dtype == torch.int32 and E_idx.is_contiguous()
-                and hip.lib().namp_decoder_sample_walk_grid(B_dec, L, K) > 0):
-            Lb_ = hip.lib()
-            main_, side_ = torch.cuda.current_stream(dev), self._side_stream(dev)
-            level = torch.empty(B_dec, L, dtype=torch.int32, device=dev)
-            work = torch.empty(B_dec * L, 2, dtype=torch.int32, device=dev)
-            level_off = torch.empty(L + 2, dtype=torch.int32, device=dev)
-            n_levels = torch.empty(1, dtype=torch.int32, device=dev)
-            ev_ = torch.cuda.Event(); ev_.record(main_)                              # the neighbour lists and the order are out
-            side_.wait_event(ev_)
-            dep_, n_dep_ = (None, 0) if pterms is None else (pterms["dep"], pterms["D"])
-            hip.check(Lb_.namp_sample_levels_dep(E_idx.data_ptr(), o.order32.data_ptr(), rank.data_ptr(), hip.ptr(dep_), n_dep_, None, None,
-                                                 level.data_ptr(), B_dec, B, L, K, side_.cuda_stream), "sample_levels")
-            hip.check(Lb_.namp_sample_work_lists(level.data_ptr(), work.data_ptr(), level_off.data_ptr(), n_levels.data_ptr(), B_dec, L,
-                                                 side_.cuda_stream), "sample_work_lists")
-            o.event = torch.cuda.Event(); o.event.record(side_)                      # o.wait() orders the decoder behind both launches
-            for t_ in (E_idx, o.order32, rank, level, work, level_off, n_levels) + (() if pterms is None else (pterms["ws"],)):
-                t_.record_stream(side_)                                              # (not recycled before the side stream is done)
-            early = (level, work, level_off, n_levels)
-        # Base pairs only: the visit plan, the levels and the work lists are built on the device, beside the encoder, with nothing read back
-        plan = None
-        if (pair_list and pterms is None and self.sample_pairs_device_plan and self.sample_level_parallel and walk and o.order32 is not None
-                and order.shape[0] == B_dec and L <= 8192 and E_idx.dtype == torch.int32 and E_idx.is_contiguous()
-                and hip.lib().namp_decoder_sample_walk_grid(B_dec, L, K) > 0):
+        # the side stream behind the featuriser launch, beside the encoder launches (with pair terms too: the pairs' device plan stands aside)
+        if (not symmetric and "pair_bias" not in fd and on_device and not o.pending and L <= 16000
+                and Lb.namp_decoder_sample_walk_grid(B_dec, L, K) > 0):
+            plan = sampling.plain_plan(self, E_idx, o.order32, rank, deps, dims, o)
+        # Base pairs only: the visit plan, the levels and the work lists are built on the device, beside the encoder, with nothing read
+        # back — buffers and uploads in front of the encoder's launches, the plan's own launches behind them: they are running by then
+        if (pair_list and pterms is None and self.sample_pairs_device_plan and on_device and L <= 8192
+                and Lb.namp_decoder_sample_walk_grid(B_dec, L, K) > 0):
             o.wait()                                                                 # (the sort, if the featuriser launch did not take it)
-            # The plan's buffers are allocated HERE, in front of the event: the side stream writes them behind `ev_` only, and a block the
-            # allocator hands out later could still be a temporary of the encoder launches enqueued below.
-            plan = self._pairs_plan_buffers(pair_list, B_dec, L, dev)
-            ev_ = torch.cuda.Event(); ev_.record(torch.cuda.current_stream(dev))     # the neighbour lists, the order and the uploads are out
+            plan, start = sampling.pairs_plan(self, pair_list, o, E_idx, dims)
         h_V, h_E = self.encode_graph(V, None, E_idx, mask, h_E_embedded=h_E)
-        if plan is not None:                                                         # (enqueued behind the encoder's launches: they are running by now)
-            self._pairs_plan_launch(plan, o, E_idx, ev_, B_dec, L, K)
+        if start is not None:
+            start()
         o.wait()
-        chain_mask = mask * fd["chain_mask"]
-        group_first = group_last = sym_w = None
-        if plan is not None:
-            order, rank, group_first, group_last, sym_w = (plan[k] for k in ("order", "rank", "group_first", "group_last", "sym_w"))
-        elif symmetric:
-            if B != 1:
-                raise ValueError("symmetry-tied sampling expects one input complex (B == 1)")
-            visits, gf, gl, wl = symmetry_visits(sym, sym_weights, order[0].tolist(), L)
-            order = torch.tensor(visits, device=dev).unsqueeze(0).repeat(B_dec, 1)
-            group_first = torch.tensor(gf, dtype=torch.int32, device=dev).repeat(B_dec, 1).contiguous()
-            group_last = torch.tensor(gl, dtype=torch.int32, device=dev).repeat(B_dec, 1).contiguous()
-            sym_w = torch.tensor(wl, dtype=torch.float32).to(dev).contiguous()
-            rank = self.ranks_of(order)
-        if order.shape[0] != B_dec:
+        if symmetric and plan is None and B != 1:
+            raise ValueError("symmetry-tied sampling expects one input complex (B == 1)")
+        if not symmetric and order.shape[0] != B_dec:
             raise ValueError(f"randn has {fd['randn'].shape[0]} rows; expected batch_size*B = {B_dec}")
-        mask_dec = mask if bs == 1 else mask.repeat(bs, 1)
-        if self.reference_sample_mask_quirk and B == 1 and bs > 1 and not symmetric:   # :186 vs :292
-            m0 = mask[0][order[0]]                                             # stream 0's mask along the steps
-            mask_dec = torch.empty_like(mask_dec).scatter_(1, order, m0.expand(B_dec, L).contiguous())
         pair_bias = fd["pair_bias"].float().contiguous() if "pair_bias" in fd else None
-        if uniform is None:
-            uniform = torch.rand(B_dec, L, device=dev)
-        special = 0
-        for name in ("UNK", "DX", "RX", "MAS", "PAD"):                        # model_utils.py:199-203
-            special |= 1 << int(self.restype_to_int[name])
-        W = self._weights()
-        Lb = hip.lib()
-        S_out = torch.empty(B_dec, L, dtype=torch.int32, device=dev)
-        probs = torch.empty(B_dec, L, self.num_letters, device=dev)
-        logp = torch.empty_like(probs)
-        ws_bytes = Lb.namp_sample_workspace_bytes_n(B, B_dec, L, K, len(self.decoder_layers))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if pterms is None else pterms["ws"]      # (the section behind the carve)
-        E32, cm32, St32 = _i32(E_idx), _i32(chain_mask), self._as(S_true, "i32")
-        m32 = self._as(mask, "i32")
-        md32, o32, r32 = (m32 if mask_dec is mask else _i32(mask_dec)), (o.order32 if early is not None else _i32(order)), _i32(rank)
-        if plan is not None:
-            order = order.long()                                               # (decoding_order of the result: int64 as on every route)
-        bias_f = bias.float().expand(B, L, self.num_letters).contiguous()
-        forced = _i32(fd["S_forced"]) if fd.get("S_forced") is not None else None
-        h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
-        deps = (None, 0) if pair_bias is None else None                       # (dep_idx, n_dep) of the levels; None: sequential walk
         if pair_bias is not None and self.sample_level_parallel:
             if tuple(pair_bias.shape) != (B, L, self.num_letters, L, self.num_letters):
                 raise ValueError(f"pair_bias must be [B, L, {self.num_letters}, L, {self.num_letters}]; got {tuple(pair_bias.shape)}")
             deps = pair_bias_dependencies(pair_bias)
-        if pterms is not None:                                                # the section's partner block IS the levels' dep_idx
-            deps = (pterms["dep"], pterms["D"])
-        common = (W.model(), h_V.data_ptr(), h_E.data_ptr(), E32.data_ptr(), m32.data_ptr(), md32.data_ptr(), cm32.data_ptr(),
-                  St32.data_ptr(), bias_f.data_ptr(), o32.data_ptr(), r32.data_ptr(), uniform.data_ptr(), hip.ptr(forced),
-                  hip.ptr(group_first), hip.ptr(group_last), hip.ptr(sym_w), hip.ptr(pair_bias))
-        tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
-                B_dec, B, L, K, hip.current_stream())
-
-        def attach():       # the token maps go to the NEXT sampler call of this thread (namp_sample_token_maps / namp_sample_class_tables)
-            self._attach_maps(tok_maps, n_maps, cls_bias is not None)
-            if pterms is not None:                                             # ... and the pair terms (namp_sample_pair_terms)
-                hip.check(Lb.namp_sample_pair_terms(pterms["D"], pterms["n_tables"], pterms["members"]), "sample_pair_terms")
-        out = {"S": None, "sampling_probs": probs, "log_probs": logp, "decoding_order": order, "uniform": uniform}   # (S: after the launch)
-        if not (self.sample_level_parallel and deps is not None):
-            attach()
-            hip.check(Lb.namp_decoder_sample(*common, *tail), "decoder_sample")
-            # (no host sync needed: temporaries are stream-ordered allocations, see _featurize_hip)
-            out["S"] = S_out.long()
-            return out
-        # residue i depends only on the neighbours decoded before it -> decode by dependency level (one launch per level over all
-        # streams, ~64 levels at L = 1000 instead of 1000 sequential steps).  Symmetry-tied: the unit of work is a GROUP (its members
-        # run one after the other in the group's workgroup slot and share one draw); its level follows its members' dependencies
-        dep_idx, n_dep = deps
-        if early is not None:
-            level = early[0]
-        elif plan is not None:
-            level = plan["level"]
-        else:
-            level = torch.empty(B_dec, L, dtype=torch.int32, device=dev)
-            hip.check(Lb.namp_sample_levels_dep(E32.data_ptr(), o32.data_ptr(), r32.data_ptr(), hip.ptr(dep_idx), n_dep,
-                                                hip.ptr(group_first), hip.ptr(group_last), level.data_ptr(),
-                                                B_dec, B, L, K, hip.current_stream()), "sample_levels")
-        walk = walk and Lb.namp_decoder_sample_walk_grid(B_dec, L, K) > 0
-        work_n = close = close_off = zbuf = hist = None
-        if walk and not symmetric and L <= 16000:
-            # plain branch: the walk's work lists are built on the device as well (one launch instead of a stable argsort, gathers,
-            # divisions, a histogram and its prefix sums) — the whole design is enqueued with ~a dozen launches
-            nwork = B_dec * L
-            if early is not None:
-                _, work, level_off, n_levels = early
-            else:
-                work = torch.empty(nwork, 2, dtype=torch.int32, device=dev)
-                level_off = torch.empty(L + 2, dtype=torch.int32, device=dev)
-                n_levels = torch.empty(1, dtype=torch.int32, device=dev)
-                hip.check(Lb.namp_sample_work_lists(level.data_ptr(), work.data_ptr(), level_off.data_ptr(), n_levels.data_ptr(), B_dec, L,
-                                                    hip.current_stream()), "sample_work_lists")
-        elif plan is not None:
-            work, work_n, level_off, n_levels, nwork = (plan[k] for k in ("work", "work_n", "level_off", "n_levels", "nwork"))
-        else:
-            sel, flat, work_n, close, close_off = level_work_lists(level, group_first, group_last, order[0], E_idx[0].long(),
-                                                                   split=bool(symmetric and walk and self.sample_split_groups))
-            if close is not None:
-                zbuf = torch.empty(B_dec, L, self.num_letters, device=dev)
-            nwork = int(sel.numel())
-            work = torch.stack((sel // L, sel % L), 1).to(torch.int32).contiguous()
-            if not walk:
-                counts = torch.bincount(flat).cpu().tolist()                   # per-level launches: the one host sync of the sampler
-                counts_c = (C.c_int32 * len(counts))(*counts)
-                attach()
-                hip.check(Lb.namp_decoder_sample_levels(*common, work.data_ptr(), hip.ptr(work_n), counts_c, len(counts), *tail),
-                          "decoder_sample_levels")
-                out.update(S=S_out.long(), levels=len(counts))
-                return out
-            # the level histogram stays on the device (levels < L, so L + 2 offsets; everything behind the last level equals nwork)
-            hist = torch.zeros(L + 1, dtype=torch.int64, device=dev).scatter_add_(0, flat, torch.ones_like(flat))
-            level_off = torch.cat((hist.new_zeros(1), hist.cumsum(0))).to(torch.int32).contiguous()
-        if plan_out is not None and symmetric:
-            plan_out.update(order=o32, rank=r32, group_first=group_first, group_last=group_last, sym_w=sym_w, map_idx=tok_maps,
-                            work=work[:nwork], work_n=work_n[:nwork], level_off=level_off,
-                            n_levels=n_levels[0] if hist is None else (hist > 0).sum())
-        # one persistent launch walking the levels: nothing is read back, the call returns with the whole design enqueued
-        attach()
-        hip.check(Lb.namp_decoder_sample_walk(*common, work.data_ptr(), hip.ptr(work_n), nwork, level_off.data_ptr(), hip.ptr(close),
-                                              hip.ptr(close_off), hip.ptr(zbuf), *tail), "decoder_sample_walk")
-        # the 64 barrier words, copied out of the per-call workspace (a view would keep the whole workspace alive on the model)
-        self._walk_sync = ws[ws_bytes - 4096:][:256].view(torch.int32).clone()
-        out.update(S=S_out.long(), levels=n_levels[0] if hist is None else (hist > 0).sum(), work_items=nwork)   # (levels: a device scalar)
-        code = self.sample_walk_status() if self.sample_check_walk else 0
+        if not self.sample_level_parallel:
+            deps = None
+        walk = bool(walk and deps is not None and Lb.namp_decoder_sample_walk_grid(B_dec, L, K) > 0)
+        if plan is None and walk and not symmetric and L <= 16000:
+            plan = sampling.plain_plan(self, _i32(E_idx), _i32(order), _i32(rank), deps, dims)
+        elif plan is None:
+            plan = sampling.host_plan(self, sym if symmetric else None, sym_weights, order, rank, _i32(E_idx), dims, deps, walk,
+                                      split=bool(symmetric and walk and self.sample_split_groups))
+        chain_mask = mask * fd["chain_mask"]
+        mask_dec = mask if bs == 1 else mask.repeat(bs, 1)
+        if self.reference_sample_mask_quirk and B == 1 and bs > 1 and not symmetric:   # :186 vs :292
+            m0 = mask[0][order[0]]                                             # stream 0's mask along the steps
+            mask_dec = torch.empty_like(mask_dec).scatter_(1, order, m0.expand(B_dec, L).contiguous())
+        if uniform is None:
+            uniform = torch.rand(B_dec, L, device=dev)
+        m32 = self._as(mask, "i32")
+        arrays = sampling.SamplerArrays(
+            h_V.float().contiguous(), h_E.float().contiguous(), m32, m32 if mask_dec is mask else _i32(mask_dec), _i32(chain_mask),
+            self._as(S_true, "i32"), bias.float().expand(B, L, self.num_letters).contiguous(), uniform,
+            _i32(fd["S_forced"]) if fd.get("S_forced") is not None else None, pair_bias)
+        if plan_out is not None and symmetric and walk:
+            plan_out.update(order=plan.order, rank=plan.rank, group_first=plan.group_first, group_last=plan.group_last, sym_w=plan.sym_w,
+                            map_idx=tok_maps, work=plan.work[:plan.nwork], work_n=plan.work_n[:plan.nwork], level_off=plan.level_off,
+                            n_levels=plan.levels)
+        maps = (tok_maps, n_maps, cls_bias is not None)
+        (S_out, probs, logp, levels), code = sampling.launch(self, plan, arrays, maps, pterms, fd["temperature"], dims, walk)
         if code != 0:
             # the walk's grid barriers gave up (its workgroups were not all resident: a shared or partitioned device) — that call's
             # outputs are poisoned; decode again with one launch per level, which needs no co-residency
             warnings.warn(f"persistent level walk timed out (code {code:#x}); re-running with per-level launches")
             return self._sample(fd, walk=False, uniform=uniform)
+        out = {"S": S_out.long(), "sampling_probs": probs, "log_probs": logp, "uniform": uniform,
+               "decoding_order": plan.order.long() if symmetric else order}       # (int64 on every route)
+        if levels is not None:                                                 # (an int of the per-level launches; the walk's: a device scalar)
+            out["levels"] = levels
+        if walk:
+            out["work_items"] = plan.nwork
         return out
 
-    # build the plan of a design whose groups are all base pairs on the device (namp_pairs_plan, namp_sample_levels_dep,
-    # namp_pairs_work_lists: nothing is read back); False: the host route through symmetry_visits and level_work_lists (same results; also
-    # what symmetry_residues or states beside the pairs and walk=False take)
+    # build the plan of a design whose groups are all base pairs on the device (sampling.pairs_plan: namp_pairs_plan,
+    # namp_sample_levels_dep, namp_pairs_work_lists, nothing is read back); False: the host route (sampling.host_plan: symmetry_visits and
+    # level_work_lists; same results; also what symmetry_residues or states beside the pairs and walk=False take)
     sample_pairs_device_plan = True
-
-    def _pairs_plan_buffers(self, pair_list, B_dec, L, dev):
-        """The arrays of the plan of a base-paired design (every group a pair, one complex): the host's part uploaded (partner, listed-first
-        flag, weights), the device's part allocated — ONE allocation: visit order, rank, group_first / group_last, levels, work lists."""
-        partner, first, w = [-1] * L, [0] * L, [1.0] * L
-        for i, j, wi, wj, _ in pair_list:
-            partner[i], partner[j], first[i], w[i], w[j] = j, i, 1, wi, wj
-        pf = torch.tensor([partner, first], dtype=torch.int32).to(dev)
-        sym_w = torch.tensor(w, dtype=torch.float32).to(dev)
-        n = B_dec * L
-        sizes = (n, n, n, n, n, 2 * n, n, L + 2, 1)
-        offs = np.concatenate(([0], np.cumsum([(q + 3) & ~3 for q in sizes]))).tolist()          # (16-byte aligned pieces of ONE allocation)
-        buf = torch.empty(offs[-1], dtype=torch.int32, device=dev)
-        order, rank, group_first, group_last, level, work, work_n, level_off, n_levels = (buf[a:a + q] for a, q in zip(offs, sizes))
-        v2 = lambda t: t.view(B_dec, L)
-        return {"order": v2(order), "rank": v2(rank), "group_first": v2(group_first), "group_last": v2(group_last), "sym_w": sym_w,
-                "level": v2(level), "work": work.view(n, 2), "work_n": work_n, "level_off": level_off, "n_levels": n_levels,
-                "nwork": B_dec * (L - len(pair_list)), "pf": pf, "buf": buf}
-
-    def _pairs_plan_launch(self, plan, o, E_idx, ev, B_dec, L, K):
-        """Enqueues the plan on the side stream behind `ev`: the visit order of every stream (namp_pairs_plan), the levels of the groups
-        (namp_sample_levels_dep) and the level-sorted work lists with the pairs kept as whole items (namp_pairs_work_lists).  Sets o.event."""
-        Lb = hip.lib()
-        pf, buf = plan["pf"], plan["buf"]
-        order, rank, group_first, group_last, level, work, work_n, level_off, n_levels = (
-            plan[k] for k in ("order", "rank", "group_first", "group_last", "level", "work", "work_n", "level_off", "n_levels"))
-        side = self._side_stream(E_idx.device)
-        side.wait_event(ev)
-        s_ = side.cuda_stream
-        hip.check(Lb.namp_pairs_plan(pf[0].data_ptr(), pf[1].data_ptr(), o.order32.data_ptr(), o.rank.data_ptr(), order.data_ptr(),
-                                     rank.data_ptr(), group_first.data_ptr(), group_last.data_ptr(), B_dec, L, s_), "pairs_plan")
-        hip.check(Lb.namp_sample_levels_dep(E_idx.data_ptr(), order.data_ptr(), rank.data_ptr(), None, 0, group_first.data_ptr(),
-                                            group_last.data_ptr(), level.data_ptr(), B_dec, 1, L, K, s_), "sample_levels")
-        hip.check(Lb.namp_pairs_work_lists(level.data_ptr(), group_first.data_ptr(), work.data_ptr(), work_n.data_ptr(),
-                                           level_off.data_ptr(), n_levels.data_ptr(), B_dec, L, s_), "pairs_work_lists")
-        o.event = torch.cuda.Event(); o.event.record(side)                         # o.wait() orders the decoder behind the plan
-        for t_ in (E_idx, o.order32, o.rank, pf, buf):                             # (not recycled before the side stream is done)
-            t_.record_stream(side)
 
     # ---------------------------------------------------------------------------------------
     # tied states: one sequence over M backbone states of the same molecule
     # ---------------------------------------------------------------------------------------
-    # build the plan of the flattened problem in one HIP launch (namp_states_plan); False: the host route through symmetry_visits,
-    # namp_sample_levels_dep and level_work_lists (same results; also what `symmetry_residues` with states and walk=False take)
+    # build the plan of the flattened problem in one HIP launch (sampling.states_plan: namp_states_plan); False: the host route
+    # (sampling.host_plan; same results; also what `symmetry_residues` with states and walk=False take)
     sample_states_device_plan = True
     _STATE_SHARED = ("S", "mask", "chain_mask", "R_idx", "chain_labels", "protein_mask", "dna_mask", "rna_mask", "R_polymer_type")
 
@@ -2704,74 +2488,32 @@ class ProteinMPNN(nn.Module):
             fd_enc["S"], fd_enc["mask"] = ctx[:2]
         V, _, h_E, E_idx = self._featurize_hip(fd_enc, want_E=False, want_hE=True, order=o)
         K = E_idx.shape[-1]
-        Lb = hip.lib()
-        i32e = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-        walk = bool(walk and self.sample_level_parallel and Lb.namp_decoder_sample_walk_grid(bs, N, K) > 0)
-        close = close_off = zbuf = None
-        device_plan = (self.sample_states_device_plan and walk and self.sample_split_groups and not symmetric and o.order32 is not None
-                       and L <= 8192 and pterms is None)                           # (pair terms add dependencies: the host route)
-        if device_plan:
-            # one launch writes the flattened neighbour lists, the visit plan of every stream, the levels and the level-sorted lists.  It
-            # needs the neighbour lists and the decoding order only: enqueued on the side stream behind the featuriser launch, beside
-            # the encoder launches (its walk over the L steps is serial), as the plain branch does with its levels
+        dims = (bs, 1, N, K)
+        walk = bool(walk and self.sample_level_parallel and hip.lib().namp_decoder_sample_walk_grid(bs, N, K) > 0)
+        plan = start = None
+        if (self.sample_states_device_plan and walk and self.sample_split_groups and not symmetric and o.order32 is not None
+                and L <= 8192 and pterms is None):                                 # (pair terms add dependencies: the host route)
+            # (needs the neighbour lists and the decoding order only: on the side stream, beside the encoder, as the plain branch's levels)
             o.wait()                                                                   # (the sort, if the featuriser launch did not take it)
-            sizes = (N * K, N, bs * N, L, bs * N, bs * N, bs * N, bs * N, 2 * bs * N, N + 2, 1, 2 * bs * L, N + 2)
-            offs = np.concatenate(([0], np.cumsum([(n + 3) & ~3 for n in sizes]))).tolist()      # (16-byte aligned pieces of ONE allocation)
-            buf = i32e(offs[-1])
-            (E_f, sym_w, work_n, level, order_f, rank_f, group_first, group_last, work, level_off, n_levels, close,
-             close_off) = (buf[o_:o_ + n] for o_, n in zip(offs, sizes))
-            sym_w = sym_w.view(torch.float32)
-            wt = torch.tensor(w, dtype=torch.float32).to(dev)
-            main_, side_ = torch.cuda.current_stream(dev), self._side_stream(dev)
-            ev_ = torch.cuda.Event(); ev_.record(main_)                                # the neighbour lists and the order are out
+            plan, start = sampling.states_plan(self, w, o, E_idx, (bs, M, L, K))
         h_V, h_E = self.encode_graph(V, None, E_idx, fd_enc["mask"], h_E_embedded=h_E)
-        if device_plan:                                                                # (enqueued behind the encoder's launches: they are running by now)
-            side_.wait_event(ev_)
-            hip.check(Lb.namp_states_plan(E_idx.data_ptr(), o.order32.data_ptr(), o.rank.data_ptr(), wt.data_ptr(), E_f.data_ptr(),
-                                          order_f.data_ptr(), rank_f.data_ptr(), group_first.data_ptr(), group_last.data_ptr(),
-                                          sym_w.data_ptr(), work_n.data_ptr(), level.data_ptr(), work.data_ptr(), level_off.data_ptr(),
-                                          n_levels.data_ptr(), close.data_ptr(), close_off.data_ptr(), bs, M, L, K, side_.cuda_stream),
-                      "states_plan")
-            o.event = torch.cuda.Event(); o.event.record(side_)                        # o.wait() orders the decoder behind the plan
-            for t_ in (E_idx, o.order32, o.rank, wt, buf):                             # (not recycled before the side stream is done)
-                t_.record_stream(side_)
+        if start is not None:                                                          # (enqueued behind the encoder's launches: they are running by now)
+            start()
         o.wait()
-        if device_plan:
-            nwork, levels, step_of = bs * N, n_levels[0], None
-        else:
+        if plan is None:
             groups = [[int(i) + m * L for m in range(M) for i in g] for g in sym_groups] if symmetric else []
             weights = [[w[m] * float(ws) for m in range(M) for ws in gw] for gw in sym_weights] if symmetric else []
             tied = {int(i) for g in (sym_groups if symmetric else []) for i in g}
             for i in range(L):
                 if i not in tied:
                     groups.append([i + m * L for m in range(M)]); weights.append(list(w))
-            visits, gf, gl, wl = symmetry_visits(groups, weights, o.order[0].tolist(), N)
-            order_f = torch.tensor(visits, dtype=torch.int32, device=dev).repeat(bs, 1)
-            group_first = torch.tensor(gf, dtype=torch.int32, device=dev).repeat(bs, 1).contiguous()
-            group_last = torch.tensor(gl, dtype=torch.int32, device=dev).repeat(bs, 1).contiguous()
-            sym_w = torch.tensor(wl, dtype=torch.float32).to(dev)
-            rank_f = _i32(self.ranks_of(order_f.long()))
-            step_of = torch.tensor(np.cumsum([int(v == f) for v, f in enumerate(gf)]) - 1, device=dev)     # visit -> its group's step
             E_f = _i32(E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).view(N, K)
-            level = i32e(bs, N)
-            dep, n_dep = (None, 0) if pterms is None else (pterms["dep"], pterms["D"])
-            hip.check(Lb.namp_sample_levels_dep(E_f.data_ptr(), order_f.data_ptr(), rank_f.data_ptr(), hip.ptr(dep), n_dep, group_first.data_ptr(),
-                                                group_last.data_ptr(), level.data_ptr(), bs, 1, N, K, hip.current_stream()), "sample_levels")
-            sel, flat, work_n, close, close_off = level_work_lists(level, group_first, group_last, order_f[0], E_f.long(),
-                                                                   split=bool(walk and self.sample_split_groups))
-            nwork = int(sel.numel())
-            work = torch.stack((sel // N, sel % N), 1).to(torch.int32).contiguous()
-            hist = torch.zeros(N + 1, dtype=torch.int64, device=dev).scatter_add_(0, flat, torch.ones_like(flat))
-            level_off = torch.cat((hist.new_zeros(1), hist.cumsum(0))).to(torch.int32).contiguous()
-            levels = (hist > 0).sum()
+            plan = sampling.host_plan(self, groups, weights, o.order, o.rank, E_f, dims, (None, 0) if pterms is None else (pterms["dep"], pterms["D"]),
+                                      walk, split=bool(walk and self.sample_split_groups), steps=True)
         if uniform is None:
             uniform = torch.rand(bs, L, device=dev)
         # the walk reads a group's uniform at its LAST visit; `uniform` is by step (group)
-        u_f = (uniform.repeat_interleave(M, dim=1) if step_of is None else uniform[:, step_of]).contiguous()
-        special = 0
-        for name in ("UNK", "DX", "RX", "MAS", "PAD"):                        # model_utils.py:199-203
-            special |= 1 << int(self.restype_to_int[name])
-        W = self._weights()
+        u_f = (uniform.repeat_interleave(M, dim=1) if plan.step_of is None else uniform[:, plan.step_of]).contiguous()
         flat_i32 = lambda t: _i32(t.repeat(1, M))
         m_f, cm_f, S_f = flat_i32(mask), flat_i32(mask * fd["chain_mask"]), flat_i32(S_true)
         forced = flat_i32(fd["S_forced"]) if fd.get("S_forced") is not None else None
@@ -2784,43 +2526,21 @@ class ProteinMPNN(nn.Module):
             if "flat" not in kept:                                             # (kept with the checked tensors: a resident feature_dict)
                 kept["flat"] = (((mask != 0) & (state_mask == 0)).reshape(N), _i32(state_mask.reshape(1, N)), _i32(state_S.reshape(1, N)))
             absent, m_f, S_f = kept["flat"]
-            sym_w = torch.where(absent, torch.zeros_like(sym_w), sym_w)
+            plan = plan._replace(sym_w=torch.where(absent, torch.zeros_like(plan.sym_w), plan.sym_w))
             if fd.get("S_forced_states") is not None:                          # (score_tied's slow route: the forced tokens per state)
                 if tuple(fd["S_forced_states"].shape) != (bs, M, L):
                     raise ValueError(f"S_forced_states must be [{bs}, {M}, {L}]; got {tuple(fd['S_forced_states'].shape)}")
                 forced = _i32(fd["S_forced_states"].reshape(bs, N))
-        md_f = m_f if bs == 1 else m_f.repeat(bs, 1)
-        bias_f = fd["bias"].float().expand(1, L, Vn).repeat(1, M, 1).contiguous()
-        S_out, probs = i32e(bs, N), torch.empty(bs, N, Vn, device=dev)
-        logp = torch.empty_like(probs)
-        if close is not None:
-            zbuf = torch.empty(bs, N, Vn, device=dev)
-        ws_bytes = Lb.namp_sample_workspace_bytes_n(1, bs, N, K, len(self.decoder_layers))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if pterms is None else pterms["ws"]
-        h_V, h_E = h_V.float().contiguous(), h_E.float().contiguous()
-        common = (W.model(), h_V.data_ptr(), h_E.data_ptr(), E_f.data_ptr(), m_f.data_ptr(), md_f.data_ptr(), cm_f.data_ptr(),
-                  S_f.data_ptr(), bias_f.data_ptr(), order_f.data_ptr(), rank_f.data_ptr(), u_f.data_ptr(), hip.ptr(forced),
-                  group_first.data_ptr(), group_last.data_ptr(), sym_w.data_ptr(), None)
-        tail = (float(fd["temperature"]), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
-                bs, 1, N, K, hip.current_stream())
-        self._attach_maps(tok_maps, n_maps, cls_bias is not None)
-        if pterms is not None:
-            hip.check(Lb.namp_sample_pair_terms(pterms["D"], pterms["n_tables"], pterms["members"]), "sample_pair_terms")
-        if not walk:
-            counts = torch.bincount(flat).cpu().tolist()                       # per-level launches: one host sync
-            hip.check(Lb.namp_decoder_sample_levels(*common, work.data_ptr(), work_n.data_ptr(), (C.c_int32 * len(counts))(*counts),
-                                                    len(counts), *tail), "decoder_sample_levels")
-            levels = len(counts)
-        else:
-            hip.check(Lb.namp_decoder_sample_walk(*common, work.data_ptr(), work_n.data_ptr(), nwork, level_off.data_ptr(), hip.ptr(close),
-                                                  hip.ptr(close_off), hip.ptr(zbuf), *tail), "decoder_sample_walk")
-            self._walk_sync = ws[ws_bytes - 4096:][:256].view(torch.int32).clone()
-            code = self.sample_walk_status() if self.sample_check_walk else 0
-            if code != 0:
-                warnings.warn(f"persistent level walk timed out (code {code:#x}); re-running with per-level launches")
-                return self._sample_states(fd, walk=False, uniform=uniform)
+        arrays = sampling.SamplerArrays(
+            h_V.float().contiguous(), h_E.float().contiguous(), m_f, m_f if bs == 1 else m_f.repeat(bs, 1), cm_f, S_f,
+            fd["bias"].float().expand(1, L, Vn).repeat(1, M, 1).contiguous(), u_f, forced)
+        maps = (tok_maps, n_maps, cls_bias is not None)
+        (S_out, probs, logp, levels), code = sampling.launch(self, plan, arrays, maps, pterms, fd["temperature"], dims, walk)
+        if code != 0:
+            warnings.warn(f"persistent level walk timed out (code {code:#x}); re-running with per-level launches")
+            return self._sample_states(fd, walk=False, uniform=uniform)
         out = {"S": S_out[:, :L].long(), "sampling_probs": probs[:, :L], "log_probs": logp.view(bs, M, L, Vn),
-               "decoding_order": o.order[0].expand(bs, L), "uniform": uniform, "levels": levels, "work_items": nwork}
+               "decoding_order": o.order[0].expand(bs, L), "uniform": uniform, "levels": levels, "work_items": plan.nwork}
         if ctx is not None:                                                    # (an absent copy scores nothing: its rows are zeros)
             out["log_probs"] = logp.view(bs, N, Vn).masked_fill(absent[None, :, None], 0.0).view(bs, M, L, Vn)
             out["S_states"] = S_out.view(bs, M, L).long()

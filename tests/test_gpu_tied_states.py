@@ -138,6 +138,41 @@ def test_tied_states_routes_are_bit_identical(weights_np, L, K, M, bs, T, mf):
     assert outs["host_whole"]["work_items"] == bs * L
 
 
+@pytest.mark.parametrize("contexts", [False, True])
+def test_walk_fallback_equals_the_per_level_sampler(weights_np, contexts):
+    """With `sample_check_walk`, a tied-states walk whose grid barrier gave up (reported here by a patched `sample_walk_status`; no
+    real timeout is provoked) is decoded again with one launch per level and the same uniforms: the result is the per-level
+    sampler's, with a warning, and the model's switches are left as they were — as test_gpu_model's test of the plain path.
+    contexts: state_S (state 1 holds other tokens at the fixed residues) and state_mask (state 1 lacks three residues) beside."""
+    dev = torch.device("cuda:0")
+    L, K, M, bs = 30, 16, 2, 2
+    _, fd_cpu = case_fd(L, M, bs, 0.5)
+    if contexts:
+        fixed = (fd_cpu["chain_mask"][0] == 0).nonzero().view(-1)
+        fd_cpu["state_S"] = fd_cpu["S"].long().repeat(M, 1)
+        fd_cpu["state_S"][1, fixed] = (fd_cpu["state_S"][1, fixed] + 1) % 20
+        fd_cpu["state_mask"] = fd_cpu["mask"].repeat(M, 1)
+        fd_cpu["state_mask"][1, [5, 12, 18]] = 0                           # (a fixed one among them; state 0 has all: mask stays the OR)
+        assert (fd_cpu["mask"][0, [5, 12, 18]] != 0).all()
+        fd_cpu["X"] = fd_cpu["X"] * fd_cpu["state_mask"][:, :, None, None].to(fd_cpu["X"].dtype)
+        fd_cpu["X_m"] = fd_cpu["X_m"] * fd_cpu["state_mask"][:, :, None].to(fd_cpu["X_m"].dtype)
+    fd = to_dev(fd_cpu, dev)
+    m = make_model(weights_np, K, dev)
+    m.sample_level_walk = False
+    torch.manual_seed(8)
+    ref = m.sample(fd)
+    m.sample_level_walk, m.sample_check_walk = True, True
+    codes, real_status = [0x102], m.sample_walk_status
+    m.sample_walk_status = lambda: codes.pop() if codes else real_status()
+    torch.manual_seed(8)
+    with pytest.warns(UserWarning, match="timed out"):
+        out = m.sample(fd)
+    assert not codes and m.sample_level_walk and out["levels"] == ref["levels"]
+    assert ("S_states" in ref) == contexts
+    for key in ("uniform", "decoding_order", "S", "sampling_probs", "log_probs") + (("S_states",) if contexts else ()):
+        assert torch.equal(out[key], ref[key]), key
+
+
 def test_one_state_equals_plain_sample(weights_np):
     """M = 1 with weight 1.0 is plain sample() given the same repeated randn row and the same uniforms: same S, log-probs within 1e-5
     (the same kernels on the same graph; the group sum 1.0 * z and the deferred draw may reorder nothing but are other code paths)."""

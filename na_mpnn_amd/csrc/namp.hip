@@ -407,6 +407,18 @@ int launch_node_linear(const float* X, const int32_t* S, int G_out, int G_src, i
     else hipLaunchKernelGGL(node_linear_w_kernel<1>, dim3((G_out + NODEW_ROWS - 1) / NODEW_ROWS), dim3(NODEW_THREADS), NODEW_LDS, s, a);
     return NAMP_OK;
   }
+  const int ntiles = (G_out + 15) / 16;
+  if (nproj >= 1 && nproj <= NODE_LINEAR_TILE_MAXPROJ && ntiles <= device_cus()) {
+    // one or two blocks, at most a tile per CU: a wave per (tile, projection) leaves most SIMDs without work and every wave a chain of up to
+    // 512 dependent MFMAs; one workgroup per tile, a channel tile per wave (node_linear_tile_kernel), same arithmetic.  Measured per call,
+    // fp32, old -> new: 7.9 -> 7.0 us (12.8 -> 8.8 with `pre`) at 250 rows, 8.3 -> 7.7 (13.7 -> 9.7) at 4,096.  With 8 blocks a wave of the
+    // tile kernel walks 8 units in a row and the old grid already has 8 waves per tile: 8.0 -> 17.1 us at 250 rows, 9.4 -> 18.6 at 2,048;
+    // 3 .. 7 blocks were not measured and keep the old kernel.
+    if (x3 && g_residue_x1) hipLaunchKernelGGL(node_linear_tile_kernel<2>, dim3(ntiles), dim3(512), 0, s, a);
+    else if (x3) hipLaunchKernelGGL(node_linear_tile_kernel<1>, dim3(ntiles), dim3(512), 0, s, a);
+    else hipLaunchKernelGGL(node_linear_tile_kernel<0>, dim3(ntiles), dim3(512), 0, s, a);
+    return NAMP_OK;
+  }
   if (x3 && g_residue_x1) hipLaunchKernelGGL(node_linear_kernel<2>, dim3((units + 3) / 4), dim3(256), 0, s, a);
   else if (x3) hipLaunchKernelGGL(node_linear_kernel<1>, dim3((units + 3) / 4), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(node_linear_kernel<0>, dim3((units + 3) / 4), dim3(256), 0, s, a);

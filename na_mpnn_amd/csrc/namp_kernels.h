@@ -214,6 +214,13 @@ struct NodeTail {
   ProjDesc p[8];
 };
 
+// The tail-operand block (fp32-class stages with the 4- / 8-row tail): the small vectors the residue tail and the message GEMM 2 apply,
+// 128 floats each, copied to LDS when the stage starts.  At the 168 registers of a 768-thread workgroup the compiler fetches such operands
+// at the point of use and waits for each (s_waitcnt vmcnt(0)): behind the tail's fragment requests the vector-memory counter retires in
+// order, so LayerNorm 1 waited for all 24 W_in fragments and then for eight round trips of its own, one by one, with eleven waves at the
+// barrier; the biases and LayerNorm 2 likewise.  LDS reads count on the other counter.
+enum { TOP_LN1G = 0, TOP_LN1B = 1, TOP_BIN = 2, TOP_BOUT = 6, TOP_LN2G = 7, TOP_LN2B = 8, TOP_M3B = 9, TOP_B2 = 10, TOP_PBIAS = 11, TOP_N = 19 };
+
 // log_softmax head for one residue: y[c] = ybase[c * sc] lives in LDS; lane t < vocab owns logit t.
 __device__ __forceinline__ void tail_head_row(const NodeTail& a, const float* ybase, const int sc, const int orow,
                                               const int lane) {
@@ -586,10 +593,19 @@ __device__ __forceinline__ void tail4_phase(f4 (&wf)[TAIL4_AHEAD][8], const int 
   tail_units<false>(u0 + TAIL4_AHEAD * step, total, step, lane, frag, body);
 }
 
-template <int R, typename RowFn, bool SC1, bool M3, bool PF, bool AH>
+// OPS: the small operands (LayerNorm weights, biases, m3_b, the projections' bias rows) are read from the tail-operand block `ops` in LDS
+// (the fused edge stages: EDGE_OPS_OFF, TOP_*) instead of global memory; every other caller passes none and reads what it always read.
+template <int R, typename RowFn, bool SC1, bool M3, bool PF, bool AH, bool OPS = false>
 __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], const float wsum_m, const RowFn orow, float* lds,
-                                                const int tid, const int wave, const int nwaves, const int lane) {
+                                                const int tid, const int wave, const int nwaves, const int lane, const float* ops = nullptr) {
   static_assert(R == 4 || R == 8, "node_tail_mfma4: 4 or 8 rows");
+  const float* const ln1_g = OPS ? ops + TOP_LN1G * 128 : a.ln1_g;
+  const float* const ln1_b = OPS ? ops + TOP_LN1B * 128 : a.ln1_b;
+  const float* const b_in = OPS ? ops + TOP_BIN * 128 : a.b_in;
+  const float* const b_out = OPS ? ops + TOP_BOUT * 128 : a.b_out;
+  const float* const ln2_g = OPS ? ops + TOP_LN2G * 128 : a.ln2_g;
+  const float* const ln2_b = OPS ? ops + TOP_LN2B * 128 : a.ln2_b;
+  const float* const m3_b = OPS ? ops + TOP_M3B * 128 : a.m3_b;
   constexpr int NB = R / 4;
   // AH (the fused launches at 4 rows): a phase's fragments requested ahead of it.  PF (the sampler's lone workgroups): two units in flight
   // per wave, as node_tail_rows.  Neither: one unit at a time.
@@ -613,7 +629,7 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
 #pragma unroll
     for (int t = 0; t < TAIL4_AHEAD; ++t) {
       const int u = wave + t * nwaves;
-      bin_a[t] = a.b_in[16 * (u < 32 ? u : wave) + 4 * cb + g];
+      bin_a[t] = b_in[16 * (u < 32 ? u : wave) + 4 * cb + g];
     }
   }
   if (M3 && a.m3_img) {
@@ -632,7 +648,7 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
                        f4 o[NB];
                        tail4_unit<NB>(o, wf, xr);
                        if (st_lane) {
-                         const f4 b = *(const f4*)(a.m3_b + 16 * u + 4 * cb);
+                         const f4 b = *(const f4*)(m3_b + 16 * u + 4 * cb);
 #pragma unroll
                          for (int nb = 0; nb < NB; ++nb) *(f4*)(oP + (4 * nb + j) * NAMP_H + 16 * u + 4 * cb) = o[nb] + b * red[4 * nb + j];
                        }
@@ -647,7 +663,7 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
     for (int t = 0; t < 8; ++t) x[t] = *(const f4*)(hsrc + 16 * t) + *(const f4*)(oP + mr * NAMP_H + 16 * t + 4 * g);
   }
 
-  layernorm_row_T(x, a.ln1_g, a.ln1_b, g);
+  layernorm_row_T(x, ln1_g, ln1_b, g);
   if (wave == 0 && m < R) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) *(f4*)(xB + (m >> 2) * 512 + t * 64 + g * 16 + (m & 3) * 4) = x[t];
@@ -661,7 +677,7 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
       f4 o[NB];
       tail4_unit<NB>(o, wf, xr);
       const int t_ = AHEAD ? (u - wave) / nwaves : 0;
-      const float b = (AHEAD && t_ < TAIL4_AHEAD) ? (t_ == 0 ? bin_a[0] : t_ == 1 ? bin_a[1] : bin_a[2]) : a.b_in[16 * u + 4 * cb + g];
+      const float b = (AHEAD && t_ < TAIL4_AHEAD) ? (t_ == 0 ? bin_a[0] : t_ == 1 ? bin_a[1] : bin_a[2]) : b_in[16 * u + 4 * cb + g];
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const float v = g == 0 ? o[nb].x : g == 1 ? o[nb].y : g == 2 ? o[nb].z : o[nb].w;
@@ -708,7 +724,7 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
   const int boff = ln_thr ? (n_ >> 2) * 512 + tail4_off(c_, n_ & 3) : 0;
   float v = 0.f;
   if (ln_thr) {
-    v = xB[boff] + a.b_out[c_];
+    v = xB[boff] + b_out[c_];
 #pragma unroll
     for (int q = 0; q < 4; ++q) v += oP[(q * R + n_) * NAMP_H + c_];
     float s = v;
@@ -731,7 +747,7 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
     const float rstd = rsqrtf((red[32 + 2 * n_] + red[32 + 2 * n_ + 1]) * (1.0f / 128.0f) + 1e-5f);
     const int orw = orow(n_);
     const float mk = (a.mask && orw >= 0) ? (float)a.mask[orw] : 1.0f;
-    const float y = (d * rstd * a.ln2_g[c_] + a.ln2_b[c_]) * mk;
+    const float y = (d * rstd * ln2_g[c_] + ln2_b[c_]) * mk;
     yT[c_ * R + n_] = y;
     yB[boff] = y;
     if (orw >= 0) st_out<SC1>(a.hV_out + (long)orw * NAMP_H + c_, y);
@@ -793,17 +809,17 @@ __device__ __forceinline__ void node_tail_mfma4(const NodeTail& a, f4 (&x)[8], c
         tail4_unit<NB>(o, wf, xr);
       }
       first = false;
-      proj_out(o, pd.bias, pd.tok, pd.out, tn);
+      proj_out(o, (OPS && pd.bias) ? ops + (TOP_PBIAS + pi) * 128 : pd.bias, pd.tok, pd.out, tn);
     }
   }
 }
 
 // M3 = false: the caller has already applied the hoisted message layer 3 (x = h_V + message), whatever a.m3_img says
-template <int R, typename RowFn, bool SC1 = false, bool M3 = true, bool PF = false, bool AH = false>
+template <int R, typename RowFn, bool SC1 = false, bool M3 = true, bool PF = false, bool AH = false, bool OPS = false>
 __device__ __forceinline__ void node_tail_rows(const NodeTail& a, f4 (&x)[8], const float wsum_m, const RowFn orow, float* lds,
-                                               const int tid, const int wave, const int nwaves, const int lane) {
+                                               const int tid, const int wave, const int nwaves, const int lane, const float* ops = nullptr) {
 #ifndef NAMP_TAIL_VALU
-  node_tail_mfma4<R, RowFn, SC1, M3, PF, AH>(a, x, wsum_m, orow, lds, tid, wave, nwaves, lane);
+  node_tail_mfma4<R, RowFn, SC1, M3, PF, AH, OPS>(a, x, wsum_m, orow, lds, tid, wave, nwaves, lane, ops);
   return;
 #endif
   float* xT = lds;                    // [128][R]    x = LN1(...)          (k-major, residue-minor)
@@ -1221,8 +1237,30 @@ struct EdgeArgs {
 // TAIL (message modes only): the workgroup goes on to update its own residues (node_tail) instead of
 // writing partial sums — one launch per layer half instead of two, worth it while the whole batch is
 // a single wave of workgroups (every workgroup re-streams the 768 KiB of FFN / projection weights).
-#define EDGE_TAIL_LDS (2 * NAMP_IMG_BYTES + 12 * NAMP_H * 4 + 64 + 2048)   // ring + per-wave K-sums + their weight sums + the fused
-                                                                          // edge update's constant vectors (eb2 | eb3 | LN3 weight | bias)
+#define EDGE_CST_OFF (2 * NAMP_IMG_BYTES + 12 * NAMP_H * 4 + 64)           // ring + per-wave K-sums + their weight sums, then the fused
+#define EDGE_OPS_OFF (EDGE_CST_OFF + 2048)                                // edge update's constant vectors (eb2 | eb3 | LN3 weight | bias)
+#define EDGE_TAIL_LDS (EDGE_OPS_OFF + TOP_N * NAMP_H * 4)
+static_assert(EDGE_TAIL_LDS <= 160 * 1024, "the fused edge stages need more LDS than a CU has");
+static_assert(TOP_PBIAS + 8 == TOP_N, "one bias row per projection descriptor (NodeTail.p[8])");
+#define TOP_ROUNDS 3                                                      // vectors per wave: a workgroup has >= 7 waves (edge_geom)
+static_assert(TOP_ROUNDS * 7 >= TOP_N, "every vector of the tail-operand block needs a wave");
+
+// vector v of the tail-operand block in global memory, or null (absent: zeros are staged).  v is wave-uniform: a scalar select.
+template <class Args>
+__device__ __forceinline__ const float* tail_operand_vector(const Args& a, const int v) {
+  const float* p = nullptr;
+  if (v == TOP_LN1G) p = a.tail.ln1_g;
+  if (v == TOP_LN1B) p = a.tail.ln1_b;
+  if (v >= TOP_BIN && v < TOP_BIN + 4 && a.tail.b_in) p = a.tail.b_in + (v - TOP_BIN) * NAMP_H;
+  if (v == TOP_BOUT) p = a.tail.b_out;
+  if (v == TOP_LN2G) p = a.tail.ln2_g;
+  if (v == TOP_LN2B) p = a.tail.ln2_b;
+  if (v == TOP_M3B) p = a.tail.m3_b;
+  if (v == TOP_B2) p = a.b2;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) if (v == TOP_PBIAS + q && q < a.tail.nproj) p = a.tail.p[q].bias;
+  return p;
+}
 
 // TAIL: 0 = write partial sums; 4 / 8 = node_tail_rows<4/8> (the workgroup owns <= 4 / <= 6 residues);
 // 16 = node_tail (16-row MFMA tile).  Chosen by the host from 12/TPN so that only one variant is inlined.
@@ -1334,6 +1372,43 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
   const f4* w0 = (const f4*)buf0 + lane;
   const f4* w1 = (const f4*)buf1 + lane;
 
+  // ---- tail-operand block (EDGE_OPS_OFF): requested here, with the per-row operands and in front of the ring's LDS-DMA (in-order
+  // counter), one 128-float vector per wave and round; written to LDS behind the wait the stage performs before its first GEMM
+  constexpr bool OPS = !BF16 && (TAIL == 4 || TAIL == 8);
+  float* ops = (float*)(smem + EDGE_OPS_OFF);
+  f2 opv[TOP_ROUNDS];
+  if constexpr (OPS) {
+#pragma unroll
+    for (int r = 0; r < TOP_ROUNDS; ++r) {
+      const float* p = tail_operand_vector(a, wave + r * nwaves);
+      opv[r] = p ? *(const f2*)(p + 2 * lane) : (f2){0.f, 0.f};
+    }
+  }
+  // eb2 | eb3 | LayerNorm-3 weight | bias of the fused edge update (cstf, EDGE_CST_OFF): as 32 16-byte loads per wave they were 32 KiB x 12
+  // waves through the CU's 64 B/clk vector-memory path per launch (profiles/r02k_bf16s_ablation.md, last table).  One vector per wave
+  // (waves 0-3), requested here too: a select per LANE among the four argument pointers became a vector load of the pointer and then of
+  // the value, two dependent round trips behind the drain of both ring images.
+  float* cstf = (float*)(smem + EDGE_CST_OFF);
+  f2 cv = (f2){0.f, 0.f};
+  if constexpr (FUSE) {
+    if (wave < 4) cv = *(const f2*)((wave == 0 ? a.eb2 : wave == 1 ? a.eb3 : wave == 2 ? a.ln_g : a.ln_b) + 2 * lane);
+  }
+  // the first wait of the stage: everything requested so far has landed; the staged vectors go to LDS in front of the barrier
+  const auto wait_dma_ops_and_sync = [&]() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (OPS) {
+#pragma unroll
+      for (int r = 0; r < TOP_ROUNDS; ++r) {
+        const int v = wave + r * nwaves;
+        if (v < TOP_N) *(f2*)(ops + v * NAMP_H + 2 * lane) = opv[r];
+      }
+    }
+    if constexpr (FUSE) {
+      if (wave < 4) *(f2*)(cstf + wave * NAMP_H + 2 * lane) = cv;
+    }
+    __syncthreads();
+  };
+
   if (BF16) {
     const bf8* bw = (const bf8*)smem + lane;               // image l at smem + l * 32 KiB
     dma_to_lds(smem, a.W1_img, 32, wave, nwaves, lane);
@@ -1355,19 +1430,12 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
       }
     }
   } else {
-  float* cstf = (float*)(smem + 2 * NAMP_IMG_BYTES + 12 * NAMP_H * 4 + 64);
   if (FUSE) {
     // ---- fused edge update of the previous layer: images eW1 -> buf1, eW2 -> buf0, eW3 -> buf1, so that the
     // message images land in their usual slots (W1 buf0, W2 buf1, W3 buf0) one GEMM ahead of their use
     dma_to_lds(buf1, a.eW1_img, 64, wave, nwaves, lane);
     dma_to_lds(buf0, a.eW2_img, 64, wave, nwaves, lane);
-    // eb2 | eb3 | LayerNorm-3 weight | bias -> LDS: as 32 16-byte loads per wave they were 32 KiB x 12 waves through the CU's
-    // 64 B/clk vector-memory path per launch (profiles/r02k_bf16s_ablation.md, last table)
-    for (int i = tid; i < 512; i += (int)blockDim.x) {      // (a workgroup has 7 .. 12 waves)
-      const float* srcv = i < 128 ? a.eb2 : i < 256 ? a.eb3 : i < 384 ? a.ln_g : a.ln_b;
-      cstf[i] = srcv[i & 127];
-    }
-    wait_dma_and_sync();
+    wait_dma_ops_and_sync();
     gemm128<X3, false, false>(acc, x, w1);
 #pragma unroll
     for (int t = 0; t < 8; ++t) acc[t] += pjv[t];
@@ -1397,7 +1465,7 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
       dma_to_lds(buf0, a.W1_img, 64, wave, nwaves, lane);
 #pragma unroll
       for (int t = 0; t < 8; ++t) acc[t] = *(const f4*)(a.eb2 + 16 * t + 4 * g);
-      wait_dma_and_sync();
+      wait_dma_ops_and_sync();
       gemm128<X3, false, false>(acc, x, w1);
 #pragma unroll
       for (int t = 0; t < 8; ++t) x[t] = acc[t];
@@ -1437,7 +1505,7 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
   // above (the VM counter retires in order: loads queued behind a bulk DMA could not be consumed before it).
   dma_to_lds(buf0, a.W1_img, 64, wave, nwaves, lane);
   if (MODE != MODE_EMBED) dma_to_lds(buf1, a.W2_img, 64, wave, nwaves, lane);
-  wait_dma_and_sync();
+  wait_dma_ops_and_sync();
   }
   // ---- layer 1 (T): acc = Pa + W1b . h_E (+ Pj afterwards)
   gemm128<X3, false, false>(acc, x, w0);
@@ -1466,8 +1534,9 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
       }
       l2pf0 = p0[lane]; l2pf1 = p1[lane];
     }
+    const float* b2v = OPS ? ops + TOP_B2 * NAMP_H : a.b2;
 #pragma unroll
-    for (int t = 0; t < 8; ++t) { const float b = a.b2[16 * t + m]; y[t] = (f4){b, b, b, b}; }
+    for (int t = 0; t < 8; ++t) { const float b = b2v[16 * t + m]; y[t] = (f4){b, b, b, b}; }
     gemm128<X3, true, true>(y, acc, w1);
   } else {
   if (PRE != PRE_NONE) wait_dma_and_sync();               // W2 (issued one GEMM ago) landed; buf0 (W1) is free
@@ -1577,7 +1646,7 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
           // the K-sum area (8 rows x 128 floats <= 12 x 128)
           __syncthreads();                                      // every wave has read dpart / dws
           for (int tn = wave; tn < 8; tn += nwaves) {          // (a workgroup may have fewer than 8 waves: K > 96)
-            const f4 o = tile_gemm1<X3>(*(const f4*)(a.tail.m3_b + 16 * tn + 4 * g) * wsum_m, y, w0, tn);
+            const f4 o = tile_gemm1<X3>(*(const f4*)((OPS ? ops + TOP_M3B * NAMP_H : a.tail.m3_b) + 16 * tn + 4 * g) * wsum_m, y, w0, tn);
             if (m < 8) *(f4*)(dpart + m * NAMP_H + 16 * tn + 4 * g) = o;
           }
           __syncthreads();
@@ -1585,9 +1654,9 @@ __device__ __forceinline__ void edge_stage(const Args& a, f4 (&x)[8], char* smem
           const float* dsrc = dpart + (mm & 7) * NAMP_H + 4 * g;
 #pragma unroll
           for (int t = 0; t < 8; ++t) y[t] = *(const f4*)(hsrc + 16 * t) + *(const f4*)(dsrc + 16 * t);
-          node_tail_rows<R, ConsecutiveRows, (PERSIST != 0), false, false, !BF16>(a.tail, y, 0.f, orow, (float*)smem, tid, wave, nwaves, lane);
+          node_tail_rows<R, ConsecutiveRows, (PERSIST != 0), false, false, !BF16, OPS>(a.tail, y, 0.f, orow, (float*)smem, tid, wave, nwaves, lane, ops);
         } else {
-          node_tail_rows<R, ConsecutiveRows, (PERSIST != 0), true, false, !BF16>(a.tail, y, wsum_m, orow, (float*)smem, tid, wave, nwaves, lane);
+          node_tail_rows<R, ConsecutiveRows, (PERSIST != 0), true, false, !BF16, OPS>(a.tail, y, wsum_m, orow, (float*)smem, tid, wave, nwaves, lane, ops);
         }
       } else {
         node_tail<false>(a.tail, y, wsum_m, row0, npw, a.G, (float*)smem, tid, wave, nwaves, lane);
@@ -2888,6 +2957,131 @@ __global__ __launch_bounds__(256) void node_linear_kernel(const NodeLinearArgs a
     __bf16* dst = o16 + (long)row * NAMP_H;
 #pragma unroll
     for (int t = 0; t < 8; ++t) st_frag4(dst, t, g, acc[t]);
+  }
+}
+
+// One 16-channel output tile (tn) of a 128 x 128 product with the image streamed from global memory: all fragments of the tile (8 of
+// the fp32 image; 4 hi + 4 mid of an x3 image, hi only for X3 = 2) are requested at once and the MFMAs run behind them.  Per tile the
+// products accumulate in chain_gemm_global's / chain_gemm_global_x3's order (k ascending), so a tile computed alone is bit-identical
+// to the same tile computed beside the other seven.
+template <int X3>
+__device__ __forceinline__ void tile_frags_request(f4 (&wf)[8], const float* img, const int tn, const int lane) {
+  if constexpr (X3) {
+    const f4* w = (const f4*)img + lane;                     // a bf8 fragment is 16 bytes, as an f4
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      wf[s] = w[(s * 8 + tn) * 64];
+      wf[4 + s] = X3 == 2 ? wf[s] : w[NAMP_BIMG_BYTES / 16 + (s * 8 + tn) * 64];
+    }
+  } else {
+    const f4* w = (const f4*)img + lane;
+#pragma unroll
+    for (int tk = 0; tk < 8; ++tk) wf[tk] = w[(tk * 8 + tn) * 64];
+  }
+}
+template <int X3>
+__device__ __forceinline__ f4 tile_frags_gemm(f4 acc, const f4 (&x)[8], const f4 (&wf)[8]) {
+  if constexpr (X3) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      bf8 hi, mid;
+      if constexpr (X3 == 2) { hi = pack_bf16<false>(x[2 * s], x[2 * s + 1]); mid = hi; }
+      else split_x3(x[2 * s], x[2 * s + 1], hi, mid);
+      acc = mfma_xs<X3 == 2>(__builtin_bit_cast(bf8, wf[s]), __builtin_bit_cast(bf8, wf[4 + s]), hi, mid, acc);
+    }
+  } else {
+#pragma unroll
+    for (int tk = 0; tk < 8; ++tk) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc = mfma4(wf[tk][r], x[tk][r], acc);
+    }
+  }
+  return acc;
+}
+
+// ------------------------------------------------------------------------------------------
+// node_linear_tile_kernel — node_linear_kernel for small G: one WORKGROUP per 16-residue tile, wave w owns channel tile w.
+// node_linear_kernel gives every (tile, projection) pair one wave that runs the whole 128 x 128 product (and the `pre` product in
+// front of it, once per projection) alone: 2 x 256 dependent fp32 MFMAs, 6.9 us of matrix issue at B = 1, N = 1000, where the grid
+// is 126 waves on 1,024 SIMDs.  Here the eight channel tiles of a product run on eight waves (32 MFMAs each), the `pre` product runs
+// once per tile and is handed on through LDS in the register-chain layout (result layout = operand layout: no permutation), and the
+// nproj x 8 (projection, channel tile) units follow on the same waves with the next unit's fragments, bias and token row in flight
+// under this unit's MFMAs.  Bit-identical to node_linear_kernel (tile_frags_gemm).  For launches of at most NODE_LINEAR_TILE_MAXPROJ
+// blocks: with more, a wave here walks that many units in a row while node_linear_kernel's grid has that many waves per tile already
+// (8 blocks at 250 .. 2,048 rows: 8-9 us there, 17-19 us here).
+// ------------------------------------------------------------------------------------------
+#define NODE_LINEAR_TILE_MAXPROJ 2
+template <int X3>
+__global__ __launch_bounds__(512) void node_linear_tile_kernel(const NodeLinearArgs a) {
+  __shared__ __attribute__((aligned(16))) float hs[16 * FFN_LD];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (a.zero && blockIdx.x == 0 && threadIdx.x < 64) a.zero[threadIdx.x] = 0u;
+  const int m = lane & 15, g = lane >> 4;
+  const int row = blockIdx.x * 16 + m;
+  const bool valid = row < a.G_out;
+  const int rr = valid ? row : 0;
+  const int b = rr / a.N;
+  const int src_row = (b % (a.G_src / a.N)) * a.N + (rr - b * a.N);
+  const int col = 16 * wave + 4 * g;                          // this lane's four channels of the wave's tile
+  const f4 zero4 = (f4){0.f, 0.f, 0.f, 0.f};
+
+  f4 x[8];
+  const float* src = a.X + (long)src_row * NAMP_H + 4 * g;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) x[t] = *(const f4*)(src + 16 * t);
+  bool any_tok = false;
+#pragma unroll
+  for (int q = 0; q < NODE_LINEAR_TILE_MAXPROJ; ++q) any_tok |= q < a.nproj && a.p[q].tok != nullptr;
+  const int tok_row = any_tok ? a.S[rr] : 0;                  // an input of the call: requested here, first needed behind unit 0's fragments
+
+  // the operands of unit q (q static after unrolling): fragments, bias, token row — requested together, no load behind another
+  auto request = [&](const int q, f4 (&wf)[8], f4& bias, f4& tk) {
+    tile_frags_request<X3>(wf, a.p[q].img, wave, lane);
+    bias = a.p[q].bias ? *(const f4*)(a.p[q].bias + col) : zero4;
+    tk = a.p[q].tok ? *(const f4*)(a.p[q].tok + (long)tok_row * NAMP_H + col) : zero4;
+  };
+  auto store = [&](const int q, const f4 acc) {
+    if (valid && a.p[q].out) *(f4*)(a.p[q].out + (long)row * NAMP_H + col) = acc;
+    if (valid && a.out16[q]) st_frag4(a.out16[q] + (long)row * NAMP_H, wave, g, acc);     // fragment order B
+  };
+
+  f4 cur[8], nxt[8], cb, nb, ct, nt, h = zero4;
+  if (a.pre.img) {
+    f4 pf[8];
+    tile_frags_request<X3>(pf, a.pre.img, wave, lane);
+    h = a.pre.bias ? *(const f4*)(a.pre.bias + col) : zero4;
+    request(0, cur, cb, ct);                                  // unit 0's operands do not depend on h: they travel under the pre product
+    __builtin_amdgcn_sched_barrier(0);
+    h = tile_frags_gemm<X3>(h, x, pf);
+    *(f4*)(hs + m * FFN_LD + col) = h;
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 8; ++t) x[t] = *(const f4*)(hs + m * FFN_LD + 16 * t + 4 * g);
+  } else {
+    request(0, cur, cb, ct);
+  }
+  // A unit's stores are issued behind the NEXT unit's requests and its wait for its own operands: stores retire on the same in-order
+  // counter as loads, and a store in front of that wait would be waited out in full.
+  f4 prev = zero4;
+#pragma unroll
+  for (int pi = 0; pi < NODE_LINEAR_TILE_MAXPROJ; ++pi) {     // static indices into the argument block
+    if (pi >= a.nproj) break;
+    const bool more = pi + 1 < NODE_LINEAR_TILE_MAXPROJ && pi + 1 < a.nproj;
+    if (more) request(pi + 1 < NODE_LINEAR_TILE_MAXPROJ ? pi + 1 : 0, nxt, nb, nt);
+    if (pi == 0) { if (a.pre.img && valid && a.pre.out) *(f4*)(a.pre.out + (long)row * NAMP_H + col) = h; }
+    else store(pi - 1, prev);
+    __builtin_amdgcn_sched_barrier(0);                        // keep the requests ahead of this unit's MFMAs
+    f4 acc = tile_frags_gemm<X3>(cb, x, cur);
+    if (a.p[pi].tok) acc += ct;
+    if (!more) store(pi, acc);
+    prev = acc;
+    __builtin_amdgcn_sched_barrier(0);
+    if (more) {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) cur[t] = nxt[t];
+      cb = nb; ct = nt;
+    }
   }
 }
 

@@ -1013,6 +1013,48 @@ size_t namp_state_mutations_out_offset(int N, int K, int n_dec, int n_states, in
                                        int items1, int items2, int items3);
 int namp_state_mutations(int n_states, int L, int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3);
 
+/* ---- group scan: the mutational scan under symmetry groups on one backbone, riding on namp_decoder_fwd ---------------------------
+ * The scan of namp_mutations under the TIED stream of namp_tied_score (below) with identity token maps.  The caller lists a point
+ * mutation of a tied group as a site of ALL its members with one token.  The base stream is the tied stream of S: keys, and forward /
+ * backward / hidden-backward edges as namp_tied_score has them, run as items over all N residues with every layer's tables kept.
+ * The plan, lists and capacities are those of namp_mutations with key(i) in the place of rank[i]: a row is in U_l(site) if it is in
+ * the site or has a neighbour j with key(j) < key(i) that is in the site or in U_{l-1}(site) — hidden-backward edges count, which
+ * lists a superset of the rows that can differ.  An item reads a backward neighbour's row WITH its token (the variant's where it has
+ * one, else the base stream's) and a hidden-backward neighbour's row WITHOUT it (layer 1: the encoder state).  Behind layer 3, with
+ * row_j the log_softmax row of residue j (the variant's where j has a row in U_3(site), else the base row),
+ *     unit[u]  = log_softmax(sum over the members t of u, in listed order, of weight_t * row_t)[token of u]      (a unit of one: its
+ *                own entry), every product and sum rounded once in fp32
+ * A layer-3 row LEADS its unit if it is unmasked and no earlier-listed member of its group has a row in U_3(site) (within the
+ * capacity); the leader stores the unit's listed-first member, unit_v, and the term w[first member] * (unit_v - unit).
+ *     delta[v] = the fp32 recursive sum, in list order, of the leader terms of v
+ * No entry point takes a pointer.  With the eleven ints of namp_mutations' size functions,
+ *     namp_group_mutations_workspace_bytes(...)  0 where namp_mutations_workspace_bytes is 0, N >= 2^27 or items1 / items2 >= 2^27
+ *     namp_group_mutations_in_offset(...)        the INPUT SECTION: that of namp_mutations (sites [n_sites][8] in flat residues,
+ *                                                variants [n_variants][9], w[N] float), then next[N], first[N] int32 and weight[N]
+ *                                                float: the successor cycles in listed order, as namp_loo_groups takes them
+ *     namp_group_mutations_out_offset(...)       the OUTPUT SECTION, each array padded as above
+ *                                                    int32 [n_sites][3]          |U_1..3(site)|
+ *                                                    float [n_variants]          delta
+ *                                                    int32 [items3], float [items3]   residue (-1: no item) and own entry per row
+ *                                                    int32 [items3], float [items3]   listed-first member of the unit the row leads
+ *                                                                                (-1: none), its unit
+ *                                                    float [N]                   the units of S at every member (every attached call)
+ *                                                    int32 [64]                  namp_tied_score's header: grouped residues,
+ *                                                                                hidden-backward edges
+ * and namp_group_mutations(n_sites, n_variants, list1..3, items1..3) attaches them to the calling thread's NEXT namp_decoder_fwd
+ * call under the rules of namp_mutations, whose attach kind it SHARES: of namp_mutations and namp_group_mutations the later call holds
+ * (a refused one leaves neither), and together with a library, a tied score or a state scan neither runs.  log_probs receives the
+ * base stream's rows [N][vocab].  A group is tied as namp_loo_groups validates it (a cycle that closes within NAMP_LOO_GROUP_MAX
+ * steps, one `first`, no masked member), else its residues are units of one.  Clamping, capacities, equal bits and the untouched
+ * input section: as above. */
+size_t namp_group_mutations_workspace_bytes(int N, int K, int n_dec, int n_sites, int n_variants, int list1, int list2, int list3, int items1,
+                                            int items2, int items3);
+size_t namp_group_mutations_in_offset(int N, int K, int n_dec, int n_sites, int n_variants, int list1, int list2, int list3, int items1,
+                                      int items2, int items3);
+size_t namp_group_mutations_out_offset(int N, int K, int n_dec, int n_sites, int n_variants, int list1, int list2, int list3, int items1,
+                                       int items2, int items3);
+int namp_group_mutations(int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3);
+
 /* ---- tied score: the joint log-likelihood of tie-consistent sequences, riding on namp_decoder_fwd ----------------------------
  * What the tied branch of the sampler computes when every token is forced, evaluated in parallel (T = 1, no bias, special tokens
  * kept).  The carrier runs on the FLATTENED graph of N residues (M backbone states of L residues side by side, block-diagonal E_idx)

@@ -102,6 +102,10 @@ def build_parser():
       "mutations/<name>.npz (residues, tokens, delta [P, T], base_loss, wild_type_token, site_rows); with --multi_state 1 "
       "[--state_contexts 1] the scan is the specificity scan under --state_weights (no pair or symmetry flags beside it) and "
       "state_delta [n, M], state_weights and base_state_log_likelihood are added")
+    a("--mutation_tied", type=int, default=0, help="1, with --mutation_scan 1 and --symmetry_residues: the symmetric scan "
+      "(score_mutations(tied=True)): a scanned residue stands for its whole symmetry group, every member gets the token and delta is the "
+      "change of score_tied's log-likelihood; mutations/<name>.npz then also holds leader [L] and the sparse units unit_offsets, "
+      "unit_residue, unit_log_prob (no pair flags, --multi_state or --pair_bias_AA beside it)")
     a("--coordinate_gradients", type=int, default=0, help="1: no sampling: the gradient of the structure's negative log-likelihood, "
       "sum of -log p(s_i) over the residues the usual flags make designable (fixed residues decoded first, as score does), with respect to "
       "every atom coordinate (ProteinMPNN.coordinate_gradients); writes gradients/<name>.npz (dX [L, 16, 3], residue_norm [L], loss, "
@@ -279,6 +283,13 @@ def main(argv=None):
     if args.mutation_scan and args.multi_state and (args.paired_residues or args.paired_strands or args.symmetry_residues or args.pair_bias_AA):
         raise ValueError("--mutation_scan 1 with --multi_state 1 scans backbone states alone: it does not go with --paired_residues, "
                          "--paired_strands, --symmetry_residues or --pair_bias_AA")
+    if args.mutation_tied not in (0, 1):
+        raise ValueError(f"--mutation_tied is 0 or 1; got {args.mutation_tied}")
+    if args.mutation_tied and not (args.mutation_scan and args.symmetry_residues):
+        raise ValueError("--mutation_tied 1 needs --mutation_scan 1 and --symmetry_residues")
+    if args.mutation_tied and (args.multi_state or args.paired_residues or args.paired_strands or args.pair_bias_AA):
+        raise ValueError("--mutation_tied 1 scans symmetry groups on one backbone: it does not go with --multi_state, --paired_residues, "
+                         "--paired_strands or --pair_bias_AA")
     if args.coordinate_gradients not in (0, 1):
         raise ValueError(f"--coordinate_gradients is 0 or 1; got {args.coordinate_gradients}")
     if args.coordinate_gradients and (args.score_fasta or args.conditional_probs_only or args.multi_state or args.mutation_scan):
@@ -482,9 +493,10 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
             # the saturation scan of the designable residues under one decoding order (its noise is the only random input); a paired
             # residue is mutated with its partner and listed once, under the pair's first member
             fd["randn"] = torch.randn(1, L, device=device)
-            out = model.score_mutations(fd, pairs=bool(pairs))
+            out = model.score_mutations(fd, pairs=bool(pairs), tied=bool(args.mutation_tied))
             scanned = out["positions"].cpu().numpy()
-            states = {k: out[k].cpu().numpy() for k in ("state_delta", "state_weights", "base_state_log_likelihood") if k in out}
+            states = {k: out[k].cpu().numpy() for k in ("state_delta", "state_weights", "base_state_log_likelihood", "leader", "unit_offsets",
+                                                        "unit_residue", "unit_log_prob") if k in out and (args.mutation_tied or k.startswith(("state", "base")))}
             np.savez(os.path.join(base, "mutations", name + ".npz"), residues=np.array([encoded[i] for i in scanned]),
                      tokens=np.array([int_to_str.get(int(t), "?") for t in out["tokens"].tolist()]), delta=out["delta"].cpu().numpy(),
                      base_loss=out["base_loss"].cpu().numpy(), wild_type_token=np.asarray(P["S"])[scanned],

@@ -620,10 +620,11 @@ struct LooItemRows {
 };
 
 // tables(l, R): enqueues the launch that fills tab[l] for R items.  An empty layer ends the walk (stop_at_empty) or is stepped over.
+// both_rows: ovO[l] holds 2 R rows, the next layer's rows WITHOUT the token behind those with it (the group scan, namp_group_scan.h).
 template <class Tables, class LaunchTables>
 static inline int loo_item_layers(const NampModelW* w, int prec, const float* h_V_enc, const float* h_E, int K, const LooBaseStream& b,
                                   const LooItemRows& o, const Tables* tab, const long* R, bool stop_at_empty, hipStream_t s,
-                                  LaunchTables tables) {
+                                  LaunchTables tables, bool both_rows = false) {
   const float* Pa[3] = {b.Pa1, b.Pa2, b.Pa3};
   const float* Pbw[3] = {b.Pbw1, b.Pbw2, b.Pbw3};
   const float* hin[3] = {h_V_enc, b.h1, b.h2};
@@ -646,6 +647,7 @@ static inline int loo_item_layers(const NampModelW* w, int prec, const float* h_
       const NampDecLayerW* Dn = &w->dec[l + 1];
       loo_proj(a.tail, Dn->W1a_img, Dn->b1, nullptr, o.PaO[l]);
       loo_proj(a.tail, Dn->W1v_img, nullptr, Dn->tok, o.ovO[l]);
+      if (both_rows) loo_proj(a.tail, Dn->W1v_img, nullptr, nullptr, o.ovO[l] + R[l] * NAMP_HIDDEN);
     }
     const int rc = launch_items(a, prec, s);
     if (rc) return rc;

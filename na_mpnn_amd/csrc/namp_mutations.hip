@@ -4,8 +4,10 @@
 // namp_library.hip runs it, the per-site plan, and per layer the index tables and one dec_items_kernel launch over
 // (variant, row of U_l(site)) items.  The specificity scan (namp_state_mutations, namp_state_scan.h) is the same call on the flattened graph
 // of n_states backbone states with another output side: its buffers are carved behind the scan's own, its launches follow layer 3.
+// The group scan (namp_group_mutations, namp_group_scan.h) runs the same plan on the keys of the tied stream over a tied base stream
+// (gmut_run); its buffers come from the same layout function.
 #include "../../include/namp.h"
-#include "namp_state_scan.h"
+#include "namp_group_scan.h"
 #include "namp_attach.h"
 
 namespace {
@@ -26,6 +28,12 @@ struct MutBuffers : LooBaseStream, LooItemRows {                                
   float* state_delta;                            // states only, OUTPUT section behind delta: float [n_var][n_states]
   int32_t* unit_res;                             // ... behind row_lp: int32 [icap_3], then
   float *unit_lp, *base_unit;                    // float [icap_3], float [L]
+  // the group scan (namp_group_scan.h) only.  Pbw2 / Pbw3 hold 2 N rows (without the token at N + j), ovO[l] 2 icap_l rows; the
+  // input section carries next, first, weight bits [N] each behind w; rows / term / unit_res / unit_lp as with states, base_unit [N]
+  int32_t *gl, *gpos, *leader;                   // [N]
+  uint32_t* key;                                 // [N]
+  TiedItemTables ttab;                           // the base stream's item tables (R = N)
+  int32_t* header;                               // OUTPUT section behind base_unit: int32 [64], namp_tied_score's
   size_t in_off, out_off, bytes;                 // (all 0: the dims are refused)
 };
 
@@ -40,45 +48,55 @@ bool mut_dims_ok(int N, int K, int n_dec, const int* m) {
 }
 
 // validates, then carves (base == nullptr: sizes only); m: n_sites, n_variants, list capacities [3], item capacities [3];
-// n_states: 0 = the plain scan, else the specificity scan on N = n_states * L flat residues
-MutBuffers mut_layout(void* base, int N_, int K, int n_dec, const int* m, int n_states = 0) {
+// n_states: 0 = the plain scan, else the specificity scan on N = n_states * L flat residues; groups: the group scan (n_states = 0)
+MutBuffers mut_layout(void* base, int N_, int K, int n_dec, const int* m, int n_states = 0, bool groups = false) {
   MutBuffers b = {};
   if (!mut_dims_ok(N_, K, n_dec, m)) return b;
-  if (n_states < 0 || n_states > MUT_E || (n_states && N_ % n_states != 0)) return b;
-  const size_t st = (size_t)n_states;
+  if (n_states < 0 || n_states > MUT_E || (n_states && N_ % n_states != 0) || (groups && n_states)) return b;
+  if (groups) {                                                  // two-part tables (codes N + j, R + r) and the keys as int32 ranks
+    const long lim = 1L << (LOO_ROW_BITS - 1);
+    if (N_ >= (1 << 27) || m[5] >= lim || m[6] >= lim) return b;
+  }
+  const size_t st = (size_t)n_states, two = groups ? 2 : 1;
   WsCarver c(base);
   const int *lcap = m + 2, *icap = m + 5;
   const size_t N = (size_t)N_, g128 = N * NAMP_HIDDEN, tpn = (K + 15) / 16, ns = (size_t)m[0], nv = (size_t)m[1];
   float** gs[] = {&b.Pa1, &b.Pbw1, &b.Pfw[0], &b.Pfw[1], &b.Pfw[2], &b.h1, &b.Pa2, &b.Pbw2, &b.h2, &b.Pa3, &b.Pbw3, &b.h3};
-  for (float** p : gs) *p = c.take<float>(g128);
+  for (float** p : gs) *p = c.take<float>((p == &b.Pbw2 || p == &b.Pbw3) ? two * g128 : g128);
+  if (groups) {
+    b.gl = c.take<int32_t>(N); b.gpos = c.take<int32_t>(N); b.leader = c.take<int32_t>(N); b.key = c.take<uint32_t>(N);
+    b.ttab.ctr = c.take<int32_t>(N + 1); b.ttab.msk = c.take<int32_t>(N + 1); b.ttab.tok = c.take<int32_t>(N + 1);
+    for (int q = 0; q < 2; ++q) { b.ttab.cen[q] = c.take<int32_t>(N + 1); b.ttab.esrc[q] = c.take<int32_t>(N * K + 1); }
+  }
   b.partial = c.take<float>(N * tpn * (NAMP_HIDDEN + 1) + 3);
   b.level = c.take<uint8_t>((ns * N + 3) / 4 + 1);
   for (int l = 0; l < 3; ++l) {
     b.loff[l] = c.take<int32_t>(ns + 1); b.list[l] = c.take<int32_t>((size_t)lcap[l] + 1); b.ioff[l] = c.take<int32_t>(nv + 1);
   }
   b.in_off = c.off;
-  b.in = c.take<int32_t>(ns * MUT_E + nv * (1 + MUT_E) + N + (st ? N : 0));
+  b.in = c.take<int32_t>(ns * MUT_E + nv * (1 + MUT_E) + N + (st ? N : 0) + (groups ? 3 * N : 0));
   b.ov1 = c.take<float>(nv * MUT_E * NAMP_HIDDEN + 4);
   for (int l = 0; l < 3; ++l) {
     const size_t R = (size_t)icap[l];
     b.hO[l] = c.take<float>(R * NAMP_HIDDEN + 4);
-    if (l < 2) { b.PaO[l] = c.take<float>(R * NAMP_HIDDEN + 4); b.ovO[l] = c.take<float>(R * NAMP_HIDDEN + 4); }
+    if (l < 2) { b.PaO[l] = c.take<float>(R * NAMP_HIDDEN + 4); b.ovO[l] = c.take<float>(two * R * NAMP_HIDDEN + 4); }
     MutItemTables& t = b.tab[l];
     t.act = c.take<int32_t>(R + 1); t.ctr = c.take<int32_t>(R + 1); t.cen = c.take<int32_t>(R + 1); t.msk = c.take<int32_t>(R + 1);
     t.tok = c.take<int32_t>(R + 1); t.esrc = c.take<int32_t>(R * K + 1);
   }
-  if (st) { b.rows = c.take<float>((size_t)icap[2] * 64 + 4); b.term = c.take<float>((size_t)icap[2] + 1); }
+  if (st || groups) { b.rows = c.take<float>((size_t)icap[2] * 64 + 4); b.term = c.take<float>((size_t)icap[2] + 1); }
   b.out_off = c.off;
   b.sizes = c.take<int32_t>(ns * 3 + 1);
   b.delta = c.take<float>(nv + 1);
   if (st) b.state_delta = c.take<float>(nv * st + 1);
   b.row_res = c.take<int32_t>((size_t)icap[2] + 1);
   b.row_lp = c.take<float>((size_t)icap[2] + 1);
-  if (st) {
+  if (st || groups) {
     b.unit_res = c.take<int32_t>((size_t)icap[2] + 1);
     b.unit_lp = c.take<float>((size_t)icap[2] + 1);
-    b.base_unit = c.take<float>(N / st + 1);
+    b.base_unit = c.take<float>((st ? N / st : N) + 1);
   }
+  if (groups) b.header = c.take<int32_t>(64);
   b.bytes = c.off;
   return b;
 }
@@ -157,9 +175,94 @@ int mut_run(const AttachedCall& c, const int* m, int kind, int n_states) {
   return NAMP_OK;
 }
 
+// the carrier's body with a group scan attached (namp_group_scan.h): groups and keys, the TIED base stream of S as items over all N
+// residues -> log_probs and the base units, the plan on the keys -> sizes, the items with edge kinds -> sparse rows, units and deltas
+// (the group scan rides on the attach kind of the mutational scan, marked by a ninth dim: the carrier and its table of kinds are
+// unchanged; the messages of this body name it)
+int gmut_run(const AttachedCall& c, const int* m) {
+  const char* noun = "a group scan";
+  int prec = PREC_F32;
+  int rc = attached_prologue(c, noun, &prec);
+  if (rc) return rc;
+  const NampModelW* w = c.w;
+  const int N = c.N, K = c.K, n_sites = m[0], n_var = m[1], *lcap = m + 2, *icap = m + 5;
+  MutBuffers b = mut_layout(c.ws, N, K, w->n_dec, m, 0, true);
+  if (!b.bytes) return namp_failf(NAMP_EINVAL, "namp_decoder_fwd: bad dims for the attached group scan N=%ld K=%ld n_sites=%ld", N, K, n_sites);
+  if ((rc = attached_ready(c, noun, b.bytes))) return rc;
+  hipStream_t s = (hipStream_t)c.stream;
+  const NampDecLayerW* D0 = &w->dec[0];
+
+  // ---- groups and keys (the kernels of the tied score as they stand, on the one sequence S), the header
+  const int32_t* wsec = b.in + (size_t)n_sites * MUT_E + (size_t)n_var * (1 + MUT_E);
+  TiedArgs ta = {};
+  ta.E_idx = c.E_idx; ta.rank = c.rank; ta.mask = c.mask;
+  ta.next = wsec + N; ta.weight = (const float*)(wsec + 3 * (size_t)N); ta.seq = c.S;
+  ta.gl = b.gl; ta.gpos = b.gpos; ta.key = b.key; ta.leader = b.leader; ta.header = b.header;
+  ta.N = N; ta.K = K; ta.n_tables = 1; ta.n_classes = w->vocab; ta.n_chunk = 1; ta.vocab = w->vocab;
+  const unsigned gN = (unsigned)((N + 255) / 256);
+  hipLaunchKernelGGL(loo_groups_kernel, dim3(gN), dim3(256), 0, s, ta.next, wsec + 2 * (size_t)N, c.mask, b.gl, b.gpos, N, N);
+  hipLaunchKernelGGL(tied_keys_kernel, dim3(gN), dim3(256), 0, s, ta);
+  hipLaunchKernelGGL(tied_count_kernel, dim3(1), dim3(256), 0, s, ta);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+
+  // ---- the base stream: the tied stream of S, every layer's tables kept (with the token at j, without it at N + j)
+  NampProj pf[4] = {{D0->W1v_img, nullptr, nullptr, b.Pfw[0]}, {w->dec[1].W1v_img, nullptr, nullptr, b.Pfw[1]},
+                    {w->dec[2].W1v_img, nullptr, nullptr, b.Pfw[2]}, {D0->W1a_img, D0->b1, nullptr, b.Pa1}};
+  if ((rc = namp_node_linear(c.h_V_enc, nullptr, 1, 1, N, pf, 4, nullptr, c.stream))) return rc;
+  hipLaunchKernelGGL(tied_items_kernel, dim3((unsigned)(((long)N * K + 255) / 256)), dim3(256), 0, s, ta, b.ttab);
+  hipLaunchKernelGGL(tied_token_rows_kernel, dim3((unsigned)(((long)N * (NAMP_H / 4) + 255) / 256)), dim3(256), 0, s, ta, b.Pfw[0], D0->tok, b.Pbw1);
+  if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+  const size_t g128 = (size_t)N * NAMP_HIDDEN;
+  const TiedStreamRows rows = {b.Pa1, {b.Pfw[0], b.Pfw[1], b.Pfw[2]}, b.Pbw1, {b.h1, b.h2, b.h3},
+                               {b.Pa2, b.Pa3}, {b.Pbw2, b.Pbw3}, {b.Pbw2 + g128, b.Pbw3 + g128}};
+  if ((rc = tied_item_stream(w, prec, c.h_V_enc, c.h_E, K, N, b.ttab, rows, s))) return rc;
+  MutPlanArgs pa = {};
+  pa.E_idx = c.E_idx; pa.rank = (const int32_t*)b.key; pa.mask = c.mask; pa.S = c.S;
+  pa.sites = b.in; pa.variants = b.in + (size_t)n_sites * MUT_E; pa.w = (const float*)wsec;
+  pa.level = b.level; pa.sizes = b.sizes;
+  for (int l = 0; l < 3; ++l) { pa.loff[l] = b.loff[l]; pa.list[l] = b.list[l]; pa.ioff[l] = b.ioff[l]; pa.lcap[l] = lcap[l]; pa.icap[l] = icap[l]; }
+  pa.N = N; pa.K = K; pa.n_sites = n_sites; pa.n_var = n_var; pa.vocab = w->vocab;
+  GroupScanArgs ga = {ta.next, ta.weight, b.gl, b.key, b.leader, b.base_unit};
+  hipLaunchKernelGGL(group_base_head_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, b.h3, w->Wout_w, w->Wout_b, c.log_probs, N, w->vocab);
+  hipLaunchKernelGGL(group_base_unit_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, pa, ga, c.log_probs);
+  if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+  if (n_sites == 0) return NAMP_OK;
+
+  // ---- the plan (namp_mutations.h, unchanged): the keys are its ranks
+  hipLaunchKernelGGL(mut_plan_kernel, dim3((unsigned)n_sites), dim3(256), 0, s, pa);
+  if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+  if (n_var == 0) return NAMP_OK;
+  hipLaunchKernelGGL(mut_offsets_kernel, dim3(1), dim3(256), 0, s, pa);
+  hipLaunchKernelGGL(mut_lists_kernel, dim3((unsigned)n_sites), dim3(256), 0, s, pa);
+  hipLaunchKernelGGL(mut_token_rows_kernel, dim3((unsigned)(((long)n_var * MUT_E * (NAMP_H / 4) + 255) / 256)), dim3(256), 0, s, pa, b.Pfw[0],
+                     D0->tok, b.ov1);
+  if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+
+  // ---- the items, layer by layer, then the head, the units and the deltas
+  const long R[3] = {icap[0], icap[1], icap[2]};
+  rc = loo_item_layers(w, prec, c.h_V_enc, c.h_E, K, b, b, b.tab, R, false, s, [&](int l, long Rl) {
+    hipLaunchKernelGGL(gmut_items_kernel, dim3((unsigned)((Rl * K + 255) / 256)), dim3(256), 0, s, pa, ga, b.tab[l], l);
+  }, true);
+  if (rc) return rc;
+  StateScanArgs sa = {};
+  sa.base_lp = c.log_probs; sa.rows = b.rows; sa.term = b.term; sa.row_res = b.row_res; sa.row_lp = b.row_lp; sa.unit_res = b.unit_res;
+  sa.unit_lp = b.unit_lp; sa.delta = b.delta; sa.ctr = b.tab[2].ctr; sa.tok = b.tab[2].tok; sa.n_states = 1; sa.L = N;
+  if (icap[2] > 0) {
+    hipLaunchKernelGGL(state_head_kernel, dim3((unsigned)((icap[2] + 3) / 4)), dim3(256), 0, s, pa, sa, b.hO[2], w->Wout_w, w->Wout_b);
+    hipLaunchKernelGGL(group_unit_kernel, dim3((unsigned)((icap[2] + 3) / 4)), dim3(256), 0, s, pa, sa, ga);
+  }
+  hipLaunchKernelGGL(state_delta_kernel, dim3((unsigned)((n_var + 255) / 256)), dim3(256), 0, s, pa, sa);
+  if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
+  return NAMP_OK;
+}
+
 }  // namespace
 
-__attribute__((visibility("hidden"))) int namp_internal_mutations_run(const AttachedCall& c, const int* m) { return mut_run(c, m, ATTACH_MUTATIONS, 0); }
+// dims: the scan's eight, then 1 where namp_group_mutations attached them (namp_mutations leaves 0)
+__attribute__((visibility("hidden"))) int namp_internal_mutations_run(const AttachedCall& c, const int* m) {
+  return m[8] == 1 ? gmut_run(c, m) : mut_run(c, m, ATTACH_MUTATIONS, 0);
+}
 // dims: the scan's eight, then n_states and L
 __attribute__((visibility("hidden"))) int namp_internal_state_mutations_run(const AttachedCall& c, const int* m) {
   return mut_run(c, m, ATTACH_STATE_MUTATIONS, m[8]);
@@ -210,6 +313,34 @@ size_t namp_state_mutations_out_offset(int N, int K, int n_dec, int n_states, in
                                        int items1, int items2, int items3) {
   const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
   return n_states < 1 ? 0 : mut_layout(nullptr, N, K, n_dec, m, n_states).out_off;
+}
+
+size_t namp_group_mutations_workspace_bytes(int N, int K, int n_dec, int n_sites, int n_variants, int list1, int list2, int list3, int items1,
+                                            int items2, int items3) {
+  const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
+  return mut_layout(nullptr, N, K, n_dec, m, 0, true).bytes;
+}
+
+size_t namp_group_mutations_in_offset(int N, int K, int n_dec, int n_sites, int n_variants, int list1, int list2, int list3, int items1,
+                                      int items2, int items3) {
+  const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
+  return mut_layout(nullptr, N, K, n_dec, m, 0, true).in_off;
+}
+
+size_t namp_group_mutations_out_offset(int N, int K, int n_dec, int n_sites, int n_variants, int list1, int list2, int list3, int items1,
+                                       int items2, int items3) {
+  const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
+  return mut_layout(nullptr, N, K, n_dec, m, 0, true).out_off;
+}
+
+int namp_group_mutations(int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3) {
+  namp_internal_detach(ATTACH_MUTATIONS);
+  const int m[9] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3, 1};
+  for (int v : m)
+    if (v < 0)
+      return namp_failf(NAMP_EINVAL, "namp_group_mutations: n_sites=%ld, n_variants=%ld and the capacities must not be negative", n_sites, n_variants);
+  namp_internal_attach(ATTACH_MUTATIONS, m, 9);
+  return NAMP_OK;
 }
 
 int namp_state_mutations(int n_states, int L, int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3) {

@@ -65,20 +65,11 @@ static __global__ __launch_bounds__(256) void state_base_unit_kernel(const MutPl
   if (lane == tk) s.base_unit[i] = row;
 }
 
-// one wave per layer-3 item row: mut_head_kernel's sums, the whole log_softmax row kept beside the own entry
-static __global__ __launch_bounds__(256) void state_head_kernel(const MutPlanArgs a, const StateScanArgs s, const float* __restrict__ h3,
-                                                                 const float* __restrict__ head_w, const float* __restrict__ head_b) {
-  const int lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= a.icap[2]) return;                                 // (wave-uniform)
-  if (a.n_var == 0 || r >= a.ioff[2][a.n_var]) {              // (wave-uniform)
-    s.rows[r * 64 + lane] = 0.f;
-    if (lane == 0) { s.row_res[r] = -1; s.row_lp[r] = 0.f; }
-    return;
-  }
-  const float* y = h3 + r * NAMP_H;
+// lane = token: log_softmax(W_out . y + b) of one state row y [128] (mut_head_kernel's sums); lanes >= vocab hold -inf
+__device__ __forceinline__ float state_head_row(const float* __restrict__ y, const float* __restrict__ head_w, const float* __restrict__ head_b,
+                                                const int vocab, const int lane) {
   float z = -INFINITY;
-  if (lane < a.vocab) {
+  if (lane < vocab) {
     const float* w = head_w + (long)lane * NAMP_H;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll 8
@@ -92,10 +83,24 @@ static __global__ __launch_bounds__(256) void state_head_kernel(const MutPlanArg
   float mx = z;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  float ex = (lane < a.vocab) ? expf(z - mx) : 0.f;
+  float ex = (lane < vocab) ? expf(z - mx) : 0.f;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) ex += __shfl_xor(ex, o);
-  const float lp = (z - mx) - logf(ex);
+  return (z - mx) - logf(ex);
+}
+
+// one wave per layer-3 item row: mut_head_kernel's sums, the whole log_softmax row kept beside the own entry
+static __global__ __launch_bounds__(256) void state_head_kernel(const MutPlanArgs a, const StateScanArgs s, const float* __restrict__ h3,
+                                                                 const float* __restrict__ head_w, const float* __restrict__ head_b) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= a.icap[2]) return;                                 // (wave-uniform)
+  if (a.n_var == 0 || r >= a.ioff[2][a.n_var]) {              // (wave-uniform)
+    s.rows[r * 64 + lane] = 0.f;
+    if (lane == 0) { s.row_res[r] = -1; s.row_lp[r] = 0.f; }
+    return;
+  }
+  const float lp = state_head_row(h3 + r * NAMP_H, head_w, head_b, a.vocab, lane);
   s.rows[r * 64 + lane] = lane < a.vocab ? lp : 0.f;
   if (lane == loo_clamp(s.tok[r], a.vocab)) s.row_lp[r] = lp;
   if (lane == 0) s.row_res[r] = s.ctr[r];

@@ -147,6 +147,43 @@ static __global__ __launch_bounds__(256) void tied_head_kernel(const TiedArgs a,
   logits[r * a.vocab + lane] = (s0 + s1) + (s2 + s3) + head_b[lane];
 }
 
+// ---- host: the three item launches of a forced tied stream over R = n_chunk * N item rows (namp_tied.hip, and the base stream of the
+// group scan, namp_group_scan.h, at n_chunk = 1).  T0 = the rows of the layer in front projected WITH the token (layer 1: tokrows),
+// T1 = Pfw of the layer, T2 = the same rows projected WITHOUT the token (layer 1: Pfw_1).  The caller says where every layer's
+// outputs go: hO[l] the states, PaO / bwO / nbO [l] the next layer's centres and its rows with and without token (l = 0, 1).  One
+// sequence of launches, hence one summation order, for every caller.
+struct TiedStreamRows {
+  const float* Pa1;                  // [N][128] layer 1's centres
+  const float* Pfw[3];               // [N][128]
+  const float* tokrows;              // [R][128] layer 1's rows with token
+  float* hO[3];                      // [R][128]
+  float *PaO[2], *bwO[2], *nbO[2];   // [R][128]
+};
+
+static inline int tied_item_stream(const NampModelW* w, const int prec, const float* h_V_enc, const float* h_E, const int K, const long R,
+                                   const TiedItemTables& tab, const TiedStreamRows& b, hipStream_t s) {
+  const float* cenPa[3] = {b.Pa1, b.PaO[0], b.PaO[1]};
+  const float* cenH[3] = {h_V_enc, b.hO[0], b.hO[1]};
+  const float* T0[3] = {b.tokrows, b.bwO[0], b.bwO[1]};
+  const float* T2[3] = {b.Pfw[0], b.nbO[0], b.nbO[1]};
+  for (int l = 0; l < 3; ++l) {
+    const NampDecLayerW* D = &w->dec[l];
+    const int q = l ? 1 : 0;
+    LooItemArgs it = loo_items(D, prec, h_E, K, R, nullptr, tab.ctr, tab.cen[q], tab.esrc[q], b.Pa1, cenPa[l], h_V_enc, cenH[l], T0[l], b.Pfw[l],
+                               T2[l]);
+    loo_tail(it.tail, D, tab.msk, tab.tok, b.hO[l]);
+    if (l < 2) {
+      const NampDecLayerW* Dn = &w->dec[l + 1];
+      loo_proj(it.tail, Dn->W1a_img, Dn->b1, nullptr, b.PaO[l]);
+      loo_proj(it.tail, Dn->W1v_img, nullptr, Dn->tok, b.bwO[l]);
+      loo_proj(it.tail, Dn->W1v_img, nullptr, nullptr, b.nbO[l]);
+    }
+    const int rc = launch_items(it, prec, s);
+    if (rc) return rc;
+  }
+  return NAMP_OK;
+}
+
 __device__ __forceinline__ float tied_wave_max(float v) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));

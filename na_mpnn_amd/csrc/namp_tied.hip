@@ -105,27 +105,11 @@ __attribute__((visibility("hidden"))) int namp_internal_tied_run(const AttachedC
   if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
 
   // ---- the items, layer by layer: T0 rows with token, T1 the layer's forward table, T2 rows without token
-  float* hO[3] = {b.hO[0], b.hO[1], b.tokrows};                  // (layer 1 alone reads tokrows)
-  const float* cenPa[3] = {b.Pa1, b.PaO[0], b.PaO[1]};
-  const float* cenH[3] = {h_V_enc, b.hO[0], b.hO[1]};
-  const float* T0[3] = {b.tokrows, b.bwO[0], b.bwO[1]};
-  const float* T2[3] = {b.Pfw[0], b.nbO[0], b.nbO[1]};
-  for (int l = 0; l < 3; ++l) {
-    const NampDecLayerW* D = &w->dec[l];
-    const int q = l ? 1 : 0;
-    LooItemArgs it = loo_items(D, prec, h_E, K, R, nullptr, b.tab.ctr, b.tab.cen[q], b.tab.esrc[q], b.Pa1, cenPa[l], h_V_enc, cenH[l], T0[l],
-                               b.Pfw[l], T2[l]);
-    loo_tail(it.tail, D, b.tab.msk, b.tab.tok, hO[l]);
-    if (l < 2) {
-      const NampDecLayerW* Dn = &w->dec[l + 1];
-      loo_proj(it.tail, Dn->W1a_img, Dn->b1, nullptr, b.PaO[l]);
-      loo_proj(it.tail, Dn->W1v_img, nullptr, Dn->tok, b.bwO[l]);
-      loo_proj(it.tail, Dn->W1v_img, nullptr, nullptr, b.nbO[l]);
-    }
-    if ((rc = launch_items(it, prec, s))) return rc;
-  }
+  const TiedStreamRows rows = {b.Pa1, {b.Pfw[0], b.Pfw[1], b.Pfw[2]}, b.tokrows, {b.hO[0], b.hO[1], b.tokrows},   // (layer 1 alone reads tokrows)
+                               {b.PaO[0], b.PaO[1]}, {b.bwO[0], b.bwO[1]}, {b.nbO[0], b.nbO[1]}};
+  if ((rc = tied_item_stream(w, prec, h_V_enc, h_E, K, R, b.tab, rows, s))) return rc;
   float* lg = b.hO[0];                                           // (layer 1's states are read by layer 2 alone: [R][vocab <= 64] fits)
-  hipLaunchKernelGGL(tied_head_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, a, hO[2], w->Wout_w, w->Wout_b, lg);
+  hipLaunchKernelGGL(tied_head_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, a, b.tokrows, w->Wout_w, w->Wout_b, lg);
   hipLaunchKernelGGL(tied_combine_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, a, lg, b.unit_lp, b.member_lp, log_probs);
   if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
   return NAMP_OK;

@@ -85,7 +85,7 @@ def _section_bytes(elems):
 
 def output_section_layout(family, dims):
     """The arrays of the OUTPUT SECTION of an attached namp_decoder_fwd call, in the order include/namp.h lists (and the library
-    carves) them -> [(name, elems, dtype), ...]; needs no device.  family: "library", "mutations", "state_mutations" or "tied_score";
+    carves) them -> [(name, elems, dtype), ...]; needs no device.  family: "library", "mutations", "state_mutations", "group_mutations" or "tied_score";
     dims: the ints of the family's size functions.  The 64-word header of "library" / "tied_score" is carved as it stands: 63 (+ 1)."""
     i32, f32 = torch.int32, torch.float32
     if family == "library":
@@ -101,6 +101,10 @@ def output_section_layout(family, dims):
         N, M, ns, nv, rows3 = dims[0], dims[3], dims[4], dims[5], dims[11]
         return [("site_rows", 3 * ns, i32), ("delta", nv, f32), ("state_delta", nv * M, f32), ("row_residue", rows3, i32),
                 ("row_token_log_prob", rows3, f32), ("unit_residue", rows3, i32), ("unit_log_prob", rows3, f32), ("base_units", N // M, f32)]
+    if family == "group_mutations":
+        N, ns, nv, rows3 = dims[0], dims[3], dims[4], dims[10]
+        return [("site_rows", 3 * ns, i32), ("delta", nv, f32), ("row_residue", rows3, i32), ("row_token_log_prob", rows3, f32),
+                ("unit_residue", rows3, i32), ("unit_log_prob", rows3, f32), ("base_units", N, f32), ("header", 63, i32)]
     raise ValueError(f"no output section is described for {family!r}")
 
 
@@ -419,6 +423,47 @@ def flat_sites_and_variants(st, tk, M, L):
     sites8[:, :s * M] = np.where(res[:, :, None] >= 0, res[:, :, None] + L * np.arange(M), -1).reshape(len(st), s * M)
     tok9[:, 1:1 + s * M] = np.repeat(np.where(res[tk[:, 0]] >= 0, tok, 0), M, axis=1)
     return sites8, tok9
+
+
+def expand_group_sites(st, tk, groups, L):
+    """The sites of score_mutations(tied=True) on the device; needs no device.  st int [n_sites, s] padded with -1, tk
+    int [n, 1 + s], groups: the tied groups (lists of residues in LISTED order, disjoint).  Every named residue stands for its whole
+    unit: the edit goes to all members of its group with the same token -> (st_x int64 [n_sites, s_x], tk_x int64 [n, 1 + s_x]), the
+    members in listed order, unit by unit in the order the site names them.  Two named residues of one site in one unit, or more than
+    MUT_MAX_EDITS flat residues in one expanded site: ValueError."""
+    unit = {}
+    for g in groups:
+        for r in g:
+            unit[int(r)] = [int(q) for q in g]
+    rows, cols = [], []
+    for s, row in enumerate(st):
+        flat, col, seen = [], [], set()
+        for c, r in enumerate(row):
+            if r < 0:
+                continue
+            members = unit.get(int(r), [int(r)])
+            if members[0] in seen:
+                raise ValueError(f"sites[{s}] names two residues of one tied unit (the unit of residue {members[0]}): a named residue "
+                                 "stands for its whole unit")
+            seen.add(members[0])
+            flat += members
+            col += [c] * len(members)
+        if len(flat) > MUT_MAX_EDITS:
+            raise ValueError(f"sites[{s}] expands to {len(flat)} flat residues (every member of every named unit); at most "
+                             f"{MUT_MAX_EDITS} fit")
+        rows.append(flat)
+        cols.append(col)
+    width = max([len(f) for f in rows], default=1) or 1
+    st_x = np.full((len(st), width), -1, np.int64)
+    src = np.zeros((len(st), width), np.int64)
+    for s, (flat, col) in enumerate(zip(rows, cols)):
+        st_x[s, :len(flat)] = flat
+        src[s, :len(col)] = col
+    tk_x = np.zeros((len(tk), 1 + width), np.int64)
+    if len(tk):
+        tk_x[:, 0] = tk[:, 0]
+        tk_x[:, 1:] = np.where(st_x[tk[:, 0]] >= 0, np.take_along_axis(tk[:, 1:], src[tk[:, 0]], 1), 0)
+    return st_x, tk_x
 
 
 def mutations_dense(out, L):
@@ -1424,7 +1469,7 @@ class ProteinMPNN(nn.Module):
         return st, tk, {"positions": [m[0] for m in site_list], "tokens": T, "valid": valid}
 
     @torch.no_grad()
-    def score_mutations(self, feature_dict, positions=None, tokens=None, sites=None, site_tokens=None, pairs=False, method="auto"):
+    def score_mutations(self, feature_dict, positions=None, tokens=None, sites=None, site_tokens=None, pairs=False, method="auto", tied=False):
         """A mutational scan: for every VARIANT — a SITE of 1 to 8 distinct residues with one token per residue, every other residue
         keeping feature_dict["S"] — the change of the joint log-likelihood score() reports, delta = sum_i w_i (log p_v(S_v[i]) -
         log p(S[i])) with w = mask * chain_mask, under score()'s own decoding order (the same randn, batch_size = 1: the definition
@@ -1454,11 +1499,22 @@ class ProteinMPNN(nn.Module):
         message_precision "x3" or "fp32" (NotImplementedError otherwise).  "dense" — the explicit library through
         score_sequences(method="dense"), reduced in torch (every row is listed): every layer count and precision mode.  "auto" —
         decided after the read-back: the cone where it applies and the mean of sum_l |U_l(site)| over the variants is at most 2 L
-        (two thirds of the dense route's 3 L rows: the break-even measured for the item route, score_sequences()), else dense."""
+        (two thirds of the dense route's 3 L rows: the break-even measured for the item route, score_sequences()), else dense.
+        tied=True: the symmetric scan of _score_group_mutations — feature_dict["symmetry_residues"] are read as
+        score_tied() reads them, a named residue stands for its whole unit and the deltas are differences of score_tied()'s
+        log_likelihood; with state_weights and no listed group the call is the specificity scan as it stands (with both:
+        NotImplementedError).  tied=False reads no symmetry group."""
         if method not in ("auto", "cone", "dense"):
             raise ValueError(f"method must be 'auto', 'cone' or 'dense'; got {method!r}")
         fd = feature_dict
         sw = fd.get("state_weights")
+        if tied:
+            sym = fd.get("symmetry_residues")
+            listed = not (sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0))
+            if sw is not None and listed:
+                raise NotImplementedError("score_mutations(tied=True): symmetry_residues joined with state_weights are not supported")
+            if sw is None:
+                return self._score_group_mutations(fd, positions, tokens, sites, site_tokens, pairs, method)
         if sw is not None:
             # (several weights beside ONE backbone stay the refusal they were: _mutation_arguments raises NotImplementedError)
             if not (fd["X"].dim() == 4 and fd["X"].shape[0] == 1 and (sw.numel() if torch.is_tensor(sw) else len(sw)) != 1):
@@ -1711,6 +1767,126 @@ class ProteinMPNN(nn.Module):
         extra = {"state_delta": sdelta, "base_state_log_likelihood": (own0 * w_flat).view(M, L).sum(-1),
                  "unit_offsets": uoffs, "unit_residue": ures, "unit_log_prob": ulp}
         return self._scan_result(out, scan, delta, base_loss, denom, btlp, base, o.order[0], (offs, rres, rlp), extra, chunks, use_cone)
+
+    def _group_scan_arguments(self, fd, positions, tokens, sites, site_tokens, pairs):
+        """The checked arguments of the symmetric scan (no device needed) -> (ties: _conditional_arguments(tied=True) or None, groups:
+        the validly tied groups in listed order, leader [L] as a list, st [n_sites, s] and tk [n, 1 + s] as NAMED, scan, st_x / tk_x:
+        expand_group_sites, sites8 int32 [n_sites, 8], tok9 int32 [n, 9])."""
+        listed = lambda v: v is not None and len(v) > 0 and not (len(v) == 1 and hasattr(v[0], "__len__") and len(v[0]) == 0)
+        if pairs or fd.get("symmetry_token_maps") is not None or listed(fd.get("paired_residues")) or fd.get("pair_terms") is not None \
+                or self._wobble_arguments(fd)[2]:
+            raise NotImplementedError("score_mutations(tied=True) scans symmetry groups with identity token maps: symmetry_token_maps, "
+                                      "paired_residues, pairs=True, paired_wobble and pair_terms are not supported")
+        _require_one_complex(fd, "score_mutations", None)
+        L = fd["S"].shape[1]
+        ties = self._conditional_arguments(fd, 1, L, None, True, False)
+        groups = [list(flat) for flat, *_ in (ties["tied"] if ties is not None else ())]
+        S0 = [int(v) for v in fd["S"][0].reshape(-1).tolist()]
+        leader = list(range(L))
+        for g in groups:
+            if len({S0[r] for r in g}) != 1:
+                raise ValueError(f"feature_dict['S'] is not tie-consistent on the group of residue {g[0]}: a tied scan has no base there")
+            for r in g:
+                leader[r] = g[0]
+        w = [a * b for a, b in zip(fd["mask"][0].reshape(-1).tolist(), fd["chain_mask"][0].reshape(-1).tolist())]
+        if positions is None and sites is None and site_tokens is None:
+            positions = torch.tensor([i for i in range(L) if leader[i] == i and w[i] != 0], dtype=torch.long)
+        plain = {k: v for k, v in fd.items() if k not in ("symmetry_residues", "symmetry_weights")}
+        st, tk, scan = self._mutation_arguments(plain, positions, tokens, sites, site_tokens, False)
+        for r in sorted({int(r) for r in st.reshape(-1) if r >= 0}):
+            if w[r] == 0:
+                raise ValueError(f"residue {r} has mask * chain_mask == 0: score_tied would not apply an edit there")
+        st_x, tk_x = expand_group_sites(st, tk, groups, L)
+        return (ties, groups, leader, st, tk, scan, st_x, tk_x) + flat_sites_and_variants(st_x, tk_x, 1, L)
+
+    def _score_group_mutations(self, fd, positions, tokens, sites, site_tokens, pairs, method):
+        """score_mutations(tied=True) — the symmetric scan: which point mutations of a tied design change its likelihood
+        under the distribution tied sample() draws from.  One complex; feature_dict["symmetry_residues"] / ["symmetry_weights"] are read
+        as score_tied() reads them (listed order, a group with a masked member is not tied, the caps of conditional_probs(tied=True));
+        T = 1, no bias, special tokens kept, score()'s order as rank0.  A site names 1 to s residues and every named residue stands for
+        its whole unit: the edit goes to ALL members of its group with the same token (identity maps), so the device site is the
+        expanded list of flat residues (more than 8: ValueError; two named residues of one unit in a site: ValueError; a named residue
+        with mask * chain_mask == 0: ValueError; feature_dict["S"] not tie-consistent on a tied group: ValueError).  The scan form's
+        default positions are the listed-first members of the units whose leader has mask * chain_mask != 0.  symmetry_token_maps,
+        paired_residues, pairs=True, paired_wobble, pair_terms: NotImplementedError.  Without any tie every unit is a unit of one.
+        delta_log_likelihood[v] = score_tied(fd, S_v)["log_likelihood"] - score_tied(fd, S)["log_likelihood"] = the sum over the counted
+        units u of w_u (unit_v[u] - unit[u]), unit[u] = log_softmax(sum over the members t of u, listed order, of weight_t row_t)[token],
+        row_t the member's log-softmax row of the tied stream (keys; forward / backward / hidden-backward edges).  Returns what
+        score_mutations returns — "sites" / "site_tokens" as named, "loss" / "base_loss" / "base_token_log_probs" [L] on units (the
+        unit's value at every member), the sparse own-entry rows as today ("base_log_probs" is None where no attached call ran) — and adds
+        "leader" int64 [L] and the sparse units "unit_offsets" int64 [n + 1], "unit_residue" int32 (the unit's listed-first member,
+        ascending per variant), "unit_log_prob" float32: one entry per unit with a member in U_3(site).
+        method: "cone" — namp_group_mutations (include/namp.h) carried by one decoder call per chunk; "dense" — the explicit library
+        [S; S_v ...] through score_tied(method="auto"): every layer count and precision mode; "auto" — the cone where it applies and
+        the mean of sum_l |U_l(site)| over the variants is at most 2 L."""
+        ties, groups, leader_l, st, tk, scan, st_x, tk_x, sites8, tok9 = self._group_scan_arguments(fd, positions, tokens, sites, site_tokens,
+                                                                                                     pairs)
+        S_true, mask = fd["S"], fd["mask"]
+        L, n, n_sites, Vn = S_true.shape[1], len(tk), len(st), self.num_letters
+        cone_ok = self._item_routes_ok("score_mutations", method, "dense")
+        _require_device(fd["X"], "X")
+        dev = fd["X"].device
+        cm = (mask * fd["chain_mask"])[0] != 0
+        leader = torch.tensor(leader_l, dtype=torch.long, device=dev)
+        counted = torch.zeros(L, dtype=torch.bool, device=dev)
+        counted[leader] = True
+        counted &= cm
+        out = {"site_index": torch.from_numpy(tk[:, 0].copy()).to(dev), "sites": torch.from_numpy(st).to(dev),
+               "site_tokens": torch.from_numpy(tk).to(dev), "site_rows": None, "leader": leader}
+        use_cone, base, btlp, order = False, None, None, None
+        if cone_ok and method != "dense" and n_sites:
+            o = self._decoding_order(mask, fd["chain_mask"], fd["randn"])
+            h_V, h_E, E_idx = self.encode(fd, order=o)
+            self._check_tokens(S_true)
+            o.wait()
+            order = o.order[0]
+            K = E_idx.shape[2]
+            inputs = self._item_decoder_inputs(h_V, h_E, E_idx, S_true, mask, o.rank[:1], 1, L)
+            if ties is None:
+                nxt = torch.full((L,), -1, dtype=torch.int32)
+                first, gw = torch.zeros(L, dtype=torch.int32), torch.ones(L, dtype=torch.float32)
+            else:
+                sec = ties["section"]
+                nxt, first, gw = sec[:L], sec[L:2 * L], sec[3 * L:4 * L].view(torch.float32)
+            tail = torch.cat((cm.float(), torch.cat((nxt, first)).view(torch.float32).to(dev), gw.to(dev)))
+            base = torch.empty(1, L, Vn, device=dev)
+            route = _ConeRoute("group_mutations", L, K, (L, K, 3), (), f"score_mutations: no workspace for the group scan L={L} K={K}",
+                               sites8, tok9, tail, {"delta": ()}, ("row_residue", "row_token_log_prob", "unit_residue", "unit_log_prob"))
+            got = self._cone_scan(route, inputs, base, tk[:, 0], method)         # (the plan call: sizes, base rows, base units)
+            out["site_rows"], btlp, use_cone = got["site_rows"], got["base_units"], got["use_cone"] and n > 0
+        if use_cone:
+            delta, offs, rres, rlp, ures, ulp, chunks = (got[k] for k in (
+                "delta", "row_offsets", "row_residue", "row_token_log_prob", "unit_residue", "unit_log_prob", "chunks"))
+            # the sparse units: the leader rows, per variant ascending in the unit's listed-first member
+            vid = torch.repeat_interleave(torch.arange(n), got["row_counts"]).to(dev)
+            lead = ures >= 0
+            srt = torch.argsort(vid[lead] * L + ures[lead].long(), stable=True)
+            ures, ulp = ures[lead][srt], ulp[lead][srt]
+            uoffs = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.bincount(vid[lead], minlength=n).cumsum(0)))
+        else:
+            S_full = S_true.long().expand(n + 1, L).clone()                      # S itself, then the variants
+            res = st_x[tk_x[:, 0]].reshape(-1)
+            keep = res >= 0
+            vi = torch.from_numpy(1 + np.repeat(np.arange(n), st_x.shape[1])[keep]).to(dev)
+            S_full[vi, torch.from_numpy(res[keep]).to(dev)] = torch.from_numpy(tk_x[:, 1:].reshape(-1)[keep]).to(dev)
+            lib = self.score_tied(fd, S_full, method="auto")
+            tlp, own = lib["token_log_probs"], lib["member_log_probs"][:, 0]
+            if not torch.equal(lib["leader"], leader):
+                raise RuntimeError("score_mutations(tied=True): score_tied reads other units than the scan")
+            delta = lib["log_likelihood"][1:] - lib["log_likelihood"][0]
+            btlp, order = tlp[0].clone(), lib["decoding_order"]
+            units = torch.nonzero(leader == torch.arange(L, device=dev))[:, 0]
+            offs = torch.arange(n + 1, dtype=torch.int64, device=dev) * L
+            rres = torch.arange(L, dtype=torch.int32, device=dev).repeat(n)
+            rlp = own[1:].reshape(-1)
+            uoffs = torch.arange(n + 1, dtype=torch.int64, device=dev) * units.numel()
+            ures = units.to(torch.int32).repeat(n)
+            ulp = tlp[1:][:, units].reshape(-1)
+            chunks = lib["chunks"]
+        denom = counted.float().sum() + 1e-8
+        base_loss = -torch.where(counted, btlp, torch.zeros_like(btlp)).sum() / denom
+        extra = {"unit_offsets": uoffs, "unit_residue": ures, "unit_log_prob": ulp}
+        return self._scan_result(out, scan, delta, base_loss, denom, btlp, base, order, (offs, rres, rlp), extra, chunks, use_cone)
 
     @staticmethod
     def _tied_combine_plan(ties, classes, dev):

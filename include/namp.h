@@ -1055,6 +1055,39 @@ size_t namp_group_mutations_out_offset(int N, int K, int n_dec, int n_sites, int
                                        int items2, int items3);
 int namp_group_mutations(int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2, int items3);
 
+/* ---- class scan: the mutational scan under every tie of one backbone, riding on namp_decoder_fwd ----------------------------------
+ * The group scan above with the combine of namp_tied_score (below): the members of a unit speak through CLASS TABLES, so a unit may
+ * be a base pair, a wobble pair, a group with token maps or a pair joined with symmetry groups.  The caller lists a variant as a site
+ * of ALL members of every edited unit, each with the token its table holds for the unit's class.  The base stream, the keys, the plan,
+ * the edge kinds and the leader rule are the group scan's.  Behind layer 3, with row_t the log_softmax row of member t (the variant's
+ * where t has a row in U_3(site), else the base row), C_t its table and close = the LAST listed member,
+ *     total[c] = sum over the members t, listed order, of weight_t * row_t[C_t[c]]  +  bias[ti_close][c]    for the classes
+ *                c < n_classes every member has a token for, else -inf; every product and sum rounded once in fp32, from 0
+ *     clp = log_softmax(total);  unit = logsumexp of clp[c] over { c : C_t[c] == token of member t, for every t }, -inf if there is none
+ * where a member's token is the variant's where the site lists it, else S (a unit of one: its own entry).  With identity tables and a
+ * zero bias every output has the bits of namp_group_mutations.  No entry point takes a pointer.  With the ints (N, K, n_dec, n_tables,
+ * n_classes, n_sites, n_variants, list1..3, items1..3),
+ *     namp_class_mutations_workspace_bytes(...)  0 where namp_group_mutations_workspace_bytes is 0 or n_tables / n_classes lies
+ *                                                outside [1, 64]
+ *     namp_class_mutations_in_offset(...)        the INPUT SECTION: that of namp_mutations (sites, variants, w[N] float), then the group
+ *                                                section of namp_tied_score: next[N], first[N], table_idx[N] int32, weight[N] float,
+ *                                                tables [n_tables][64] int32, bias [n_tables][64] float
+ *     namp_class_mutations_out_offset(...)       the OUTPUT SECTION: exactly that of namp_group_mutations
+ * and namp_class_mutations(n_tables, n_classes, n_sites, n_variants, list1..3, items1..3) attaches them to the calling thread's NEXT
+ * namp_decoder_fwd call (n_classes below the vocabulary: that call is refused).  It SHARES the attach kind of namp_mutations: of
+ * namp_mutations, namp_group_mutations and namp_class_mutations the later call holds (a refused one leaves none), and together with a
+ * library, a tied score or a state scan none runs.  Table indices, table entries and tokens are clamped, an entry below 0 is "absent";
+ * a malformed section gives a defined result and nothing outside ws and log_probs is written.  Capacities, equal bits and the untouched
+ * input section: as above. */
+size_t namp_class_mutations_workspace_bytes(int N, int K, int n_dec, int n_tables, int n_classes, int n_sites, int n_variants, int list1, int list2,
+                                            int list3, int items1, int items2, int items3);
+size_t namp_class_mutations_in_offset(int N, int K, int n_dec, int n_tables, int n_classes, int n_sites, int n_variants, int list1, int list2,
+                                      int list3, int items1, int items2, int items3);
+size_t namp_class_mutations_out_offset(int N, int K, int n_dec, int n_tables, int n_classes, int n_sites, int n_variants, int list1, int list2,
+                                       int list3, int items1, int items2, int items3);
+int namp_class_mutations(int n_tables, int n_classes, int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2,
+                         int items3);
+
 /* ---- tied score: the joint log-likelihood of tie-consistent sequences, riding on namp_decoder_fwd ----------------------------
  * What the tied branch of the sampler computes when every token is forced, evaluated in parallel (T = 1, no bias, special tokens
  * kept).  The carrier runs on the FLATTENED graph of N residues (M backbone states of L residues side by side, block-diagonal E_idx)

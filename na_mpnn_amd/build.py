@@ -18,7 +18,7 @@ UNITS = {"namp.hip": ["namp.hip", "namp_kernels.h", "namp_bf16s32.h", "namp_bf16
          "namp_persist.hip": ["namp_persist.hip", "namp_kernels.h", "namp_device.h"],
          "namp_loo.hip": ["namp_loo.hip", "namp_loo.h", "namp_attach.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_library.hip": ["namp_library.hip", "namp_library.h", "namp_attach.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
-         "namp_mutations.hip": ["namp_mutations.hip", "namp_mutations.h", "namp_state_scan.h", "namp_group_scan.h", "namp_tied.h", "namp_attach.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
+         "namp_mutations.hip": ["namp_mutations.hip", "namp_mutations.h", "namp_state_scan.h", "namp_group_scan.h", "namp_class_scan.h", "namp_tied.h", "namp_attach.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_tied.hip": ["namp_tied.hip", "namp_tied.h", "namp_attach.h", "namp_loo.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_states.hip": ["namp_states.hip", "namp_states.h", "namp_kernels.h", "namp_device.h", INC],
          "namp_pairs.hip": ["namp_pairs.hip", "namp_pairs.h", INC],

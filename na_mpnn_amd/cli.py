@@ -106,6 +106,11 @@ def build_parser():
       "(score_mutations(tied=True)): a scanned residue stands for its whole symmetry group, every member gets the token and delta is the "
       "change of score_tied's log-likelihood; mutations/<name>.npz then also holds leader [L] and the sparse units unit_offsets, "
       "unit_residue, unit_log_prob (no pair flags, --multi_state or --pair_bias_AA beside it)")
+    a("--mutation_classes", type=int, default=0, help="1, with --mutation_scan 1 --mutation_tied 1 and --paired_residues / "
+      "--paired_strands [--paired_wobble 1 --paired_wobble_bias B] and/or --symmetry_residues: the paired scan "
+      "(score_mutations(tied=True, classes=True)): the ties are read through pair classes as score_tied reads them; with pair flags every "
+      "pair is scanned once over its classes (4 canonical, 6 with wobble on an RNA-containing pair) and mutations/<name>.npz also holds "
+      "classes [T], class_tokens [P, T, 2] and the unit arrays (no --multi_state or --pair_bias_AA beside it)")
     a("--coordinate_gradients", type=int, default=0, help="1: no sampling: the gradient of the structure's negative log-likelihood, "
       "sum of -log p(s_i) over the residues the usual flags make designable (fixed residues decoded first, as score does), with respect to "
       "every atom coordinate (ProteinMPNN.coordinate_gradients); writes gradients/<name>.npz (dX [L, 16, 3], residue_norm [L], loss, "
@@ -277,7 +282,15 @@ def main(argv=None):
         raise ValueError("--state_contexts 1 does not go with --conditional_probs_only: conditional_probs() takes no context states")
     if args.mutation_scan not in (0, 1):
         raise ValueError(f"--mutation_scan is 0 or 1; got {args.mutation_scan}")
-    if args.mutation_scan and (args.score_fasta or args.conditional_probs_only or args.paired_wobble):
+    if args.mutation_classes not in (0, 1):
+        raise ValueError(f"--mutation_classes is 0 or 1; got {args.mutation_classes}")
+    if args.mutation_classes and not (args.mutation_scan and args.mutation_tied):
+        raise ValueError("--mutation_classes 1 needs --mutation_scan 1 --mutation_tied 1")
+    if args.mutation_classes and not (args.paired_residues or args.paired_strands or args.symmetry_residues):
+        raise ValueError("--mutation_classes 1 needs --paired_residues, --paired_strands or --symmetry_residues")
+    if args.mutation_classes and (args.multi_state or args.pair_bias_AA):
+        raise ValueError("--mutation_classes 1 scans the ties of one backbone: it does not go with --multi_state or --pair_bias_AA")
+    if args.mutation_scan and (args.score_fasta or args.conditional_probs_only or (args.paired_wobble and not args.mutation_classes)):
         raise ValueError("--mutation_scan 1 scans one structure: it does not go with --score_fasta, --conditional_probs_only "
                          "or --paired_wobble")
     if args.mutation_scan and args.multi_state and (args.paired_residues or args.paired_strands or args.symmetry_residues or args.pair_bias_AA):
@@ -285,9 +298,9 @@ def main(argv=None):
                          "--paired_strands, --symmetry_residues or --pair_bias_AA")
     if args.mutation_tied not in (0, 1):
         raise ValueError(f"--mutation_tied is 0 or 1; got {args.mutation_tied}")
-    if args.mutation_tied and not (args.mutation_scan and args.symmetry_residues):
+    if args.mutation_tied and not args.mutation_classes and not (args.mutation_scan and args.symmetry_residues):
         raise ValueError("--mutation_tied 1 needs --mutation_scan 1 and --symmetry_residues")
-    if args.mutation_tied and (args.multi_state or args.paired_residues or args.paired_strands or args.pair_bias_AA):
+    if args.mutation_tied and not args.mutation_classes and (args.multi_state or args.paired_residues or args.paired_strands or args.pair_bias_AA):
         raise ValueError("--mutation_tied 1 scans symmetry groups on one backbone: it does not go with --multi_state, --paired_residues, "
                          "--paired_strands or --pair_bias_AA")
     if args.coordinate_gradients not in (0, 1):
@@ -493,10 +506,14 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
             # the saturation scan of the designable residues under one decoding order (its noise is the only random input); a paired
             # residue is mutated with its partner and listed once, under the pair's first member
             fd["randn"] = torch.randn(1, L, device=device)
-            out = model.score_mutations(fd, pairs=bool(pairs), tied=bool(args.mutation_tied))
+            if args.mutation_classes:
+                out = model.score_mutations(fd, pairs=bool(pairs), tied=True, classes=True)
+            else:
+                out = model.score_mutations(fd, pairs=bool(pairs), tied=bool(args.mutation_tied))
             scanned = out["positions"].cpu().numpy()
             states = {k: out[k].cpu().numpy() for k in ("state_delta", "state_weights", "base_state_log_likelihood", "leader", "unit_offsets",
-                                                        "unit_residue", "unit_log_prob") if k in out and (args.mutation_tied or k.startswith(("state", "base")))}
+                                                        "unit_residue", "unit_log_prob", "classes", "class_tokens")
+                      if k in out and (args.mutation_tied or k.startswith(("state", "base")))}
             np.savez(os.path.join(base, "mutations", name + ".npz"), residues=np.array([encoded[i] for i in scanned]),
                      tokens=np.array([int_to_str.get(int(t), "?") for t in out["tokens"].tolist()]), delta=out["delta"].cpu().numpy(),
                      base_loss=out["base_loss"].cpu().numpy(), wild_type_token=np.asarray(P["S"])[scanned],

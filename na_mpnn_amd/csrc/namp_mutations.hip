@@ -5,9 +5,10 @@
 // (variant, row of U_l(site)) items.  The specificity scan (namp_state_mutations, namp_state_scan.h) is the same call on the flattened graph
 // of n_states backbone states with another output side: its buffers are carved behind the scan's own, its launches follow layer 3.
 // The group scan (namp_group_mutations, namp_group_scan.h) runs the same plan on the keys of the tied stream over a tied base stream
-// (gmut_run); its buffers come from the same layout function.
+// (gmut_run); its buffers come from the same layout function.  The class scan (namp_class_mutations, namp_class_scan.h) is the group
+// scan with class tables behind its input section and another combine: the same body.
 #include "../../include/namp.h"
-#include "namp_group_scan.h"
+#include "namp_class_scan.h"
 #include "namp_attach.h"
 
 namespace {
@@ -29,7 +30,8 @@ struct MutBuffers : LooBaseStream, LooItemRows {                                
   int32_t* unit_res;                             // ... behind row_lp: int32 [icap_3], then
   float *unit_lp, *base_unit;                    // float [icap_3], float [L]
   // the group scan (namp_group_scan.h) only.  Pbw2 / Pbw3 hold 2 N rows (without the token at N + j), ovO[l] 2 icap_l rows; the
-  // input section carries next, first, weight bits [N] each behind w; rows / term / unit_res / unit_lp as with states, base_unit [N]
+  // input section carries next, first, weight bits [N] each behind w (the class scan: next, first, table_idx, weight bits [N] each,
+  // tables and bias bits [n_tables][64] each); rows / term / unit_res / unit_lp as with states, base_unit [N]
   int32_t *gl, *gpos, *leader;                   // [N]
   uint32_t* key;                                 // [N]
   TiedItemTables ttab;                           // the base stream's item tables (R = N)
@@ -48,11 +50,13 @@ bool mut_dims_ok(int N, int K, int n_dec, const int* m) {
 }
 
 // validates, then carves (base == nullptr: sizes only); m: n_sites, n_variants, list capacities [3], item capacities [3];
-// n_states: 0 = the plain scan, else the specificity scan on N = n_states * L flat residues; groups: the group scan (n_states = 0)
-MutBuffers mut_layout(void* base, int N_, int K, int n_dec, const int* m, int n_states = 0, bool groups = false) {
+// n_states: 0 = the plain scan, else the specificity scan on N = n_states * L flat residues; groups: the group scan (n_states = 0);
+// n_tables != 0: the class scan, the group scan's buffers with a longer input section
+MutBuffers mut_layout(void* base, int N_, int K, int n_dec, const int* m, int n_states = 0, bool groups = false, int n_tables = 0) {
   MutBuffers b = {};
   if (!mut_dims_ok(N_, K, n_dec, m)) return b;
   if (n_states < 0 || n_states > MUT_E || (n_states && N_ % n_states != 0) || (groups && n_states)) return b;
+  if (n_tables < 0 || n_tables > 64 || (n_tables && !groups)) return b;
   if (groups) {                                                  // two-part tables (codes N + j, R + r) and the keys as int32 ranks
     const long lim = 1L << (LOO_ROW_BITS - 1);
     if (N_ >= (1 << 27) || m[5] >= lim || m[6] >= lim) return b;
@@ -74,7 +78,7 @@ MutBuffers mut_layout(void* base, int N_, int K, int n_dec, const int* m, int n_
     b.loff[l] = c.take<int32_t>(ns + 1); b.list[l] = c.take<int32_t>((size_t)lcap[l] + 1); b.ioff[l] = c.take<int32_t>(nv + 1);
   }
   b.in_off = c.off;
-  b.in = c.take<int32_t>(ns * MUT_E + nv * (1 + MUT_E) + N + (st ? N : 0) + (groups ? 3 * N : 0));
+  b.in = c.take<int32_t>(ns * MUT_E + nv * (1 + MUT_E) + N + (st ? N : 0) + (groups ? 3 * N : 0) + (n_tables ? N + 128 * (size_t)n_tables : 0));
   b.ov1 = c.take<float>(nv * MUT_E * NAMP_HIDDEN + 4);
   for (int l = 0; l < 3; ++l) {
     const size_t R = (size_t)icap[l];
@@ -178,16 +182,20 @@ int mut_run(const AttachedCall& c, const int* m, int kind, int n_states) {
 // the carrier's body with a group scan attached (namp_group_scan.h): groups and keys, the TIED base stream of S as items over all N
 // residues -> log_probs and the base units, the plan on the keys -> sizes, the items with edge kinds -> sparse rows, units and deltas
 // (the group scan rides on the attach kind of the mutational scan, marked by a ninth dim: the carrier and its table of kinds are
-// unchanged; the messages of this body name it)
-int gmut_run(const AttachedCall& c, const int* m) {
-  const char* noun = "a group scan";
+// unchanged; the messages of this body name it).  cls: nullptr, or n_tables and n_classes of a class scan (namp_class_scan.h): the
+// section then carries table_idx, tables and bias as namp_tied_score's does, and the units come from class_unit_row
+int gmut_run(const AttachedCall& c, const int* m, const int* cls) {
+  const char* noun = cls ? "a class scan" : "a group scan";
   int prec = PREC_F32;
   int rc = attached_prologue(c, noun, &prec);
   if (rc) return rc;
   const NampModelW* w = c.w;
   const int N = c.N, K = c.K, n_sites = m[0], n_var = m[1], *lcap = m + 2, *icap = m + 5;
-  MutBuffers b = mut_layout(c.ws, N, K, w->n_dec, m, 0, true);
-  if (!b.bytes) return namp_failf(NAMP_EINVAL, "namp_decoder_fwd: bad dims for the attached group scan N=%ld K=%ld n_sites=%ld", N, K, n_sites);
+  const bool cls_ok = !cls || (cls[0] >= 1 && cls[0] <= 64 && cls[1] >= w->vocab && cls[1] <= 64);
+  MutBuffers b = cls_ok ? mut_layout(c.ws, N, K, w->n_dec, m, 0, true, cls ? cls[0] : 0) : MutBuffers{};
+  if (!b.bytes)
+    return namp_failf(NAMP_EINVAL, cls ? "namp_decoder_fwd: bad dims for the attached class scan N=%ld K=%ld n_sites=%ld"
+                                       : "namp_decoder_fwd: bad dims for the attached group scan N=%ld K=%ld n_sites=%ld", N, K, n_sites);
   if ((rc = attached_ready(c, noun, b.bytes))) return rc;
   hipStream_t s = (hipStream_t)c.stream;
   const NampDecLayerW* D0 = &w->dec[0];
@@ -196,7 +204,12 @@ int gmut_run(const AttachedCall& c, const int* m) {
   const int32_t* wsec = b.in + (size_t)n_sites * MUT_E + (size_t)n_var * (1 + MUT_E);
   TiedArgs ta = {};
   ta.E_idx = c.E_idx; ta.rank = c.rank; ta.mask = c.mask;
-  ta.next = wsec + N; ta.weight = (const float*)(wsec + 3 * (size_t)N); ta.seq = c.S;
+  ta.next = wsec + N; ta.weight = (const float*)(wsec + (cls ? 4 : 3) * (size_t)N); ta.seq = c.S;
+  ClassScanArgs ca = {};
+  if (cls) {
+    ca.table_idx = wsec + 3 * (size_t)N; ca.tables = wsec + 5 * (size_t)N; ca.bias = (const float*)(ca.tables + 64 * (size_t)cls[0]);
+    ca.n_tables = cls[0]; ca.n_classes = cls[1];
+  }
   ta.gl = b.gl; ta.gpos = b.gpos; ta.key = b.key; ta.leader = b.leader; ta.header = b.header;
   ta.N = N; ta.K = K; ta.n_tables = 1; ta.n_classes = w->vocab; ta.n_chunk = 1; ta.vocab = w->vocab;
   const unsigned gN = (unsigned)((N + 255) / 256);
@@ -225,7 +238,8 @@ int gmut_run(const AttachedCall& c, const int* m) {
   pa.N = N; pa.K = K; pa.n_sites = n_sites; pa.n_var = n_var; pa.vocab = w->vocab;
   GroupScanArgs ga = {ta.next, ta.weight, b.gl, b.key, b.leader, b.base_unit};
   hipLaunchKernelGGL(group_base_head_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, b.h3, w->Wout_w, w->Wout_b, c.log_probs, N, w->vocab);
-  hipLaunchKernelGGL(group_base_unit_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, pa, ga, c.log_probs);
+  if (cls) hipLaunchKernelGGL(class_base_unit_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, pa, ga, ca, c.log_probs);
+  else hipLaunchKernelGGL(group_base_unit_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, pa, ga, c.log_probs);
   if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
   if (n_sites == 0) return NAMP_OK;
 
@@ -250,7 +264,8 @@ int gmut_run(const AttachedCall& c, const int* m) {
   sa.unit_lp = b.unit_lp; sa.delta = b.delta; sa.ctr = b.tab[2].ctr; sa.tok = b.tab[2].tok; sa.n_states = 1; sa.L = N;
   if (icap[2] > 0) {
     hipLaunchKernelGGL(state_head_kernel, dim3((unsigned)((icap[2] + 3) / 4)), dim3(256), 0, s, pa, sa, b.hO[2], w->Wout_w, w->Wout_b);
-    hipLaunchKernelGGL(group_unit_kernel, dim3((unsigned)((icap[2] + 3) / 4)), dim3(256), 0, s, pa, sa, ga);
+    if (cls) hipLaunchKernelGGL(class_unit_kernel, dim3((unsigned)((icap[2] + 3) / 4)), dim3(256), 0, s, pa, sa, ga, ca);
+    else hipLaunchKernelGGL(group_unit_kernel, dim3((unsigned)((icap[2] + 3) / 4)), dim3(256), 0, s, pa, sa, ga);
   }
   hipLaunchKernelGGL(state_delta_kernel, dim3((unsigned)((n_var + 255) / 256)), dim3(256), 0, s, pa, sa);
   if ((e = hipGetLastError()) != hipSuccess) return namp_internal_fail(NAMP_ELAUNCH, hipGetErrorString(e));
@@ -259,9 +274,14 @@ int gmut_run(const AttachedCall& c, const int* m) {
 
 }  // namespace
 
-// dims: the scan's eight, then 1 where namp_group_mutations attached them (namp_mutations leaves 0)
+// dims: the scan's eight, then 1 where namp_group_mutations attached them, 2 where namp_class_mutations did (namp_mutations leaves 0);
+// behind a 2: n_tables | n_classes << 8
 __attribute__((visibility("hidden"))) int namp_internal_mutations_run(const AttachedCall& c, const int* m) {
-  return m[8] == 1 ? gmut_run(c, m) : mut_run(c, m, ATTACH_MUTATIONS, 0);
+  if (m[8] == 2) {
+    const int cls[2] = {m[9] & 0xff, (m[9] >> 8) & 0xff};
+    return gmut_run(c, m, cls);
+  }
+  return m[8] == 1 ? gmut_run(c, m, nullptr) : mut_run(c, m, ATTACH_MUTATIONS, 0);
 }
 // dims: the scan's eight, then n_states and L
 __attribute__((visibility("hidden"))) int namp_internal_state_mutations_run(const AttachedCall& c, const int* m) {
@@ -340,6 +360,40 @@ int namp_group_mutations(int n_sites, int n_variants, int list1, int list2, int 
     if (v < 0)
       return namp_failf(NAMP_EINVAL, "namp_group_mutations: n_sites=%ld, n_variants=%ld and the capacities must not be negative", n_sites, n_variants);
   namp_internal_attach(ATTACH_MUTATIONS, m, 9);
+  return NAMP_OK;
+}
+
+static bool class_dims_ok(int n_tables, int n_classes) { return n_tables >= 1 && n_tables <= 64 && n_classes >= 1 && n_classes <= 64; }
+
+size_t namp_class_mutations_workspace_bytes(int N, int K, int n_dec, int n_tables, int n_classes, int n_sites, int n_variants, int list1, int list2,
+                                            int list3, int items1, int items2, int items3) {
+  const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
+  return class_dims_ok(n_tables, n_classes) ? mut_layout(nullptr, N, K, n_dec, m, 0, true, n_tables).bytes : 0;
+}
+
+size_t namp_class_mutations_in_offset(int N, int K, int n_dec, int n_tables, int n_classes, int n_sites, int n_variants, int list1, int list2,
+                                      int list3, int items1, int items2, int items3) {
+  const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
+  return class_dims_ok(n_tables, n_classes) ? mut_layout(nullptr, N, K, n_dec, m, 0, true, n_tables).in_off : 0;
+}
+
+size_t namp_class_mutations_out_offset(int N, int K, int n_dec, int n_tables, int n_classes, int n_sites, int n_variants, int list1, int list2,
+                                       int list3, int items1, int items2, int items3) {
+  const int m[8] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3};
+  return class_dims_ok(n_tables, n_classes) ? mut_layout(nullptr, N, K, n_dec, m, 0, true, n_tables).out_off : 0;
+}
+
+int namp_class_mutations(int n_tables, int n_classes, int n_sites, int n_variants, int list1, int list2, int list3, int items1, int items2,
+                         int items3) {
+  namp_internal_detach(ATTACH_MUTATIONS);
+  const int m[10] = {n_sites, n_variants, list1, list2, list3, items1, items2, items3, 2, (n_tables & 0xff) | ((n_classes & 0xff) << 8)};
+  for (int q = 0; q < 8; ++q)
+    if (m[q] < 0)
+      return namp_failf(NAMP_EINVAL, "namp_class_mutations: n_sites=%ld, n_variants=%ld and the capacities must not be negative", n_sites, n_variants);
+  if (!class_dims_ok(n_tables, n_classes))
+    return namp_failf(NAMP_EINVAL, "namp_class_mutations: n_tables=%ld must be in [1, 64], n_classes=%ld in [1, 64] (the attached call refuses one below the vocabulary)",
+                      n_tables, n_classes);
+  namp_internal_attach(ATTACH_MUTATIONS, m, 10);
   return NAMP_OK;
 }
 

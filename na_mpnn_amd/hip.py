@@ -247,6 +247,10 @@ _PROTOTYPES = {
     "namp_group_mutations_in_offset": (sz, [i32] * 11),
     "namp_group_mutations_out_offset": (sz, [i32] * 11),
     "namp_group_mutations": (i32, [i32] * 8),
+    "namp_class_mutations_workspace_bytes": (sz, [i32] * 13),
+    "namp_class_mutations_in_offset": (sz, [i32] * 13),
+    "namp_class_mutations_out_offset": (sz, [i32] * 13),
+    "namp_class_mutations": (i32, [i32] * 10),
     "namp_tied_score_workspace_bytes": (sz, [i32] * 6),
     "namp_tied_score_in_offset": (sz, [i32] * 6),
     "namp_tied_score_out_offset": (sz, [i32] * 6),

@@ -85,7 +85,7 @@ def _section_bytes(elems):
 
 def output_section_layout(family, dims):
     """The arrays of the OUTPUT SECTION of an attached namp_decoder_fwd call, in the order include/namp.h lists (and the library
-    carves) them -> [(name, elems, dtype), ...]; needs no device.  family: "library", "mutations", "state_mutations", "group_mutations" or "tied_score";
+    carves) them -> [(name, elems, dtype), ...]; needs no device.  family: "library", "mutations", "state_mutations", "group_mutations", "class_mutations" or "tied_score";
     dims: the ints of the family's size functions.  The 64-word header of "library" / "tied_score" is carved as it stands: 63 (+ 1)."""
     i32, f32 = torch.int32, torch.float32
     if family == "library":
@@ -101,7 +101,8 @@ def output_section_layout(family, dims):
         N, M, ns, nv, rows3 = dims[0], dims[3], dims[4], dims[5], dims[11]
         return [("site_rows", 3 * ns, i32), ("delta", nv, f32), ("state_delta", nv * M, f32), ("row_residue", rows3, i32),
                 ("row_token_log_prob", rows3, f32), ("unit_residue", rows3, i32), ("unit_log_prob", rows3, f32), ("base_units", N // M, f32)]
-    if family == "group_mutations":
+    if family in ("group_mutations", "class_mutations"):            # (the class scan: n_tables, n_classes behind n_dec)
+        dims = dims if family == "group_mutations" else dims[:3] + dims[5:]
         N, ns, nv, rows3 = dims[0], dims[3], dims[4], dims[10]
         return [("site_rows", 3 * ns, i32), ("delta", nv, f32), ("row_residue", rows3, i32), ("row_token_log_prob", rows3, f32),
                 ("unit_residue", rows3, i32), ("unit_log_prob", rows3, f32), ("base_units", N, f32), ("header", 63, i32)]
@@ -464,6 +465,74 @@ def expand_group_sites(st, tk, groups, L):
         tk_x[:, 0] = tk[:, 0]
         tk_x[:, 1:] = np.where(st_x[tk[:, 0]] >= 0, np.take_along_axis(tk[:, 1:], src[tk[:, 0]], 1), 0)
     return st_x, tk_x
+
+
+def class_lane(tables, named):
+    """The class a variant means for one tied unit; needs no device.  tables: the members' class tables in listed
+    order (spec.N_CLASS_LANES entries each, below 0: no such class), named: {listed position: token} -> the LOWEST lane below
+    spec.N_CLASSES every member has an entry on and whose entry equals the token at every named member, or -1.  (The canonical classes
+    lie below the wobble lanes: naming G alone means G-C, naming both members (G, U) the wobble class.)"""
+    for c in range(spec.N_CLASSES):
+        if all(C[c] >= 0 for C in tables) and all(tables[t][c] == tok for t, tok in named.items()):
+            return c
+    return -1
+
+
+def expand_class_sites(st, tk, units, L):
+    """The sites of score_mutations(tied=True, classes=True) on the device; needs no device.  st int [n_sites, s]
+    padded with -1, tk int [n, 1 + s], units: [(members in LISTED order, their class tables)] the tied units, disjoint.  For every
+    unit with a named member the variant's class is class_lane over the named members of that unit, and EVERY member, named or not,
+    gets its table's token for it; a residue in no unit keeps the token it was given -> (st_x int64 [n_sites, s_x], tk_x int64
+    [n, 1 + s_x]), the members in listed order, unit by unit in the order the site first names them.  No lane for the given tokens, or
+    more than MUT_MAX_EDITS flat residues in one expanded site: ValueError."""
+    unit = {}
+    for members, tables in units:
+        for t, r in enumerate(members):
+            unit[int(r)] = ([int(q) for q in members], tables, t)
+    plans = []
+    for s, row in enumerate(st):
+        order, cols = [], {}
+        for c, r in enumerate(row):
+            if r < 0:
+                continue
+            members, tables, t = unit.get(int(r), ([int(r)], None, 0))
+            if members[0] not in cols:
+                order.append((members, tables))
+                cols[members[0]] = {}
+            cols[members[0]][t] = c
+        flat = sum(len(m) for m, _ in order)
+        if flat > MUT_MAX_EDITS:
+            raise ValueError(f"sites[{s}] expands to {flat} flat residues (every member of every named unit); at most {MUT_MAX_EDITS} fit")
+        plans.append([(members, tables, cols[members[0]]) for members, tables in order])
+    width = max([sum(len(m) for m, _, _ in p) for p in plans], default=1) or 1
+    st_x = np.full((len(st), width), -1, np.int64)
+    for s, p in enumerate(plans):
+        flat = [r for members, _, _ in p for r in members]
+        st_x[s, :len(flat)] = flat
+    tk_x = np.zeros((len(tk), 1 + width), np.int64)
+    for v, row in enumerate(tk):
+        tk_x[v, 0], q = row[0], 1
+        for members, tables, named in plans[int(row[0])]:
+            given = {t: int(row[1 + c]) for t, c in named.items()}
+            if tables is None:
+                tk_x[v, q] = given[0]
+            else:
+                lane = class_lane(tables, given)
+                if lane < 0:
+                    raise ValueError(f"site_tokens[{v}]: the unit of residue {members[0]} has no class with " +
+                                     ", ".join(f"token {tok} at residue {members[t]}" for t, tok in sorted(given.items())))
+                tk_x[v, q:q + len(members)] = [C[lane] for C in tables]
+            q += len(members)
+    return st_x, tk_x
+
+
+def polymer_alphabet(prot, dna, rna, s0):
+    """synth.make_complex's ranges for one residue (its polymer flags and its token): the 20 amino acids, the 4 DNA and the 4 RNA letters."""
+    if dna or (not prot and not rna and 21 <= s0 < 26):
+        return range(21, 25)
+    if rna or (not prot and 26 <= s0 < 31):
+        return range(26, 30)
+    return range(0, 20)
 
 
 def mutations_dense(out, L):
@@ -1434,12 +1503,7 @@ class ProteinMPNN(nn.Module):
                 partner[i] = partner[j] = (i, j, spec.token_map(self.restype_to_int, kind))
 
         def alphabet(i):
-            """synth.make_complex's ranges: the 20 amino acids, the 4 DNA and the 4 RNA letters."""
-            if dna[i] or (not prot[i] and not rna[i] and 21 <= S0[i] < 26):
-                return range(21, 25)
-            if rna[i] or (not prot[i] and 26 <= S0[i] < 31):
-                return range(26, 30)
-            return range(0, 20)
+            return polymer_alphabet(prot[i], dna[i], rna[i], S0[i])
         site_list, seen = [], set()
         for p in pos:                                            # a pair is one site, scanned once from its first listed member
             members = partner[p][:2] if p in partner else (p,)
@@ -1469,7 +1533,8 @@ class ProteinMPNN(nn.Module):
         return st, tk, {"positions": [m[0] for m in site_list], "tokens": T, "valid": valid}
 
     @torch.no_grad()
-    def score_mutations(self, feature_dict, positions=None, tokens=None, sites=None, site_tokens=None, pairs=False, method="auto", tied=False):
+    def score_mutations(self, feature_dict, positions=None, tokens=None, sites=None, site_tokens=None, pairs=False, method="auto", tied=False,
+                        classes=False):
         """A mutational scan: for every VARIANT — a SITE of 1 to 8 distinct residues with one token per residue, every other residue
         keeping feature_dict["S"] — the change of the joint log-likelihood score() reports, delta = sum_i w_i (log p_v(S_v[i]) -
         log p(S[i])) with w = mask * chain_mask, under score()'s own decoding order (the same randn, batch_size = 1: the definition
@@ -1503,11 +1568,19 @@ class ProteinMPNN(nn.Module):
         tied=True: the symmetric scan of _score_group_mutations — feature_dict["symmetry_residues"] are read as
         score_tied() reads them, a named residue stands for its whole unit and the deltas are differences of score_tied()'s
         log_likelihood; with state_weights and no listed group the call is the specificity scan as it stands (with both:
-        NotImplementedError).  tied=False reads no symmetry group."""
+        NotImplementedError).  tied=False reads no symmetry group.
+        tied=True, classes=True: the paired scan — every tie score_tied() reads on one backbone (base pairs, wobble,
+        symmetry groups with or without token maps, pairs joined with groups) through class tables: a variant names the class of
+        every unit it touches (class_lane: the lowest matching lane) and every member gets its token; pairs=True scans the class axis
+        of every pair.  classes=True without tied=True: ValueError; with state_weights or pair_terms: NotImplementedError."""
         if method not in ("auto", "cone", "dense"):
             raise ValueError(f"method must be 'auto', 'cone' or 'dense'; got {method!r}")
         fd = feature_dict
         sw = fd.get("state_weights")
+        if classes:
+            if not tied:
+                raise ValueError("score_mutations(classes=True) needs tied=True: class tables belong to the tied scan")
+            return self._score_group_mutations(fd, positions, tokens, sites, site_tokens, pairs, method, True)
         if tied:
             sym = fd.get("symmetry_residues")
             listed = not (sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0))
@@ -1799,7 +1872,76 @@ class ProteinMPNN(nn.Module):
         st_x, tk_x = expand_group_sites(st, tk, groups, L)
         return (ties, groups, leader, st, tk, scan, st_x, tk_x) + flat_sites_and_variants(st_x, tk_x, 1, L)
 
-    def _score_group_mutations(self, fd, positions, tokens, sites, site_tokens, pairs, method):
+    def _class_scan_arguments(self, fd, positions, tokens, sites, site_tokens, pairs):
+        """The checked arguments of the paired scan (no device needed) -> what _group_scan_arguments returns — the ties
+        read with class tables, st / tk as NAMED, st_x / tk_x from expand_class_sites — and the scan form's own result keys.  pairs=True
+        (scan form only, no `tokens`): every scanned unit once from its listed-first member over the class axis, one variant per class
+        every member has and whose first-member token lies in that member's polymer alphabet; a unit of one: lanes = tokens."""
+        if fd.get("state_weights") is not None:
+            raise NotImplementedError("score_mutations(tied=True, classes=True): state_weights are not supported (states joined with "
+                                      "pairs: a pair over M states is 2 M edits of a site's 8)")
+        if fd.get("pair_terms") is not None:
+            raise NotImplementedError("score_mutations(tied=True, classes=True): pair_terms are not supported (score_tied reads none)")
+        _require_one_complex(fd, "score_mutations", None)
+        L = fd["S"].shape[1]
+        ties = self._conditional_arguments(fd, 1, L, None, True, True)
+        units = [([int(r) for r in flat], [list(C) for C in ft]) for flat, _, ft, _, _ in (ties["tied"] if ties is not None else ())]
+        host = lambda key: [int(v) for v in fd[key][0].reshape(-1).tolist()]
+        S0 = host("S")
+        leader, unit_of = list(range(L)), {}
+        for members, tables in units:
+            if class_lane(tables, {t: S0[r] for t, r in enumerate(members)}) < 0:
+                raise ValueError(f"feature_dict['S'] matches no class of the unit of residue {members[0]}: a tied scan has no base there")
+            for r in members:
+                leader[r], unit_of[r] = members[0], (members, tables)
+        w = [a * b for a, b in zip(fd["mask"][0].reshape(-1).tolist(), fd["chain_mask"][0].reshape(-1).tolist())]
+        general = sites is not None or site_tokens is not None
+        if positions is None and not general:
+            positions = torch.tensor([i for i in range(L) if leader[i] == i and w[i] != 0], dtype=torch.long)
+        extra = {}
+        if pairs:
+            if general:
+                raise ValueError("pairs=True belongs to the scan form: a general site lists its residues itself")
+            if tokens is not None:
+                raise ValueError("score_mutations(tied=True, classes=True, pairs=True) scans the class axis: it takes no tokens")
+            prot, dna, rna = host("protein_mask"), host("dna_mask"), host("rna_mask")
+            firsts, seen = [], set()
+            for p in _positions_argument(positions, L):
+                if leader[p] not in seen:
+                    seen.add(leader[p])
+                    firsts.append(leader[p])
+            lanes = []
+            for f in firsts:
+                members, tables = unit_of.get(f, ([f], [list(range(spec.N_CLASS_LANES))]))
+                alpha = polymer_alphabet(prot[f], dna[f], rna[f], S0[f])
+                lanes.append([c for c in range(spec.N_CLASSES if f in unit_of else len(spec.RESTYPES))
+                              if all(C[c] >= 0 for C in tables) and tables[0][c] in alpha])
+            T = sorted({c for ls in lanes for c in ls})
+            valid = np.array([[c in ls for c in T] for ls in lanes], bool).reshape(len(firsts), len(T))
+            st = np.full((len(firsts), 2), -1, np.int64)
+            ctok = np.full((len(firsts), len(T), 2), -1, np.int64)
+            rows = []
+            for q, f in enumerate(firsts):
+                members, tables = unit_of.get(f, ([f], [list(range(spec.N_CLASS_LANES))]))
+                st[q, :min(2, len(members))] = members[:2]
+                for k, c in enumerate(T):
+                    if valid[q, k]:
+                        ctok[q, k, :min(2, len(members))] = [C[c] for C in tables[:2]]
+                        rows.append([q] + [max(int(t), 0) for t in ctok[q, k]])
+            tk = np.array(rows, np.int64).reshape(len(rows), 3)
+            scan = {"positions": firsts, "tokens": T, "valid": valid}
+            extra = {"classes": torch.tensor(T, dtype=torch.long), "class_tokens": torch.from_numpy(ctok)}
+        else:
+            plain = {k: v for k, v in fd.items() if k not in ("symmetry_residues", "symmetry_weights", "symmetry_token_maps", "paired_residues",
+                                                              "paired_weights", "paired_wobble", "paired_wobble_bias")}
+            st, tk, scan = self._mutation_arguments(plain, positions, tokens, sites, site_tokens, False)
+        for r in sorted({int(r) for r in st.reshape(-1) if r >= 0}):
+            if w[r] == 0:
+                raise ValueError(f"residue {r} has mask * chain_mask == 0: score_tied would not apply an edit there")
+        st_x, tk_x = expand_class_sites(st, tk, units, L)
+        return (ties, [m for m, _ in units], leader, st, tk, scan, st_x, tk_x) + flat_sites_and_variants(st_x, tk_x, 1, L) + (extra,)
+
+    def _score_group_mutations(self, fd, positions, tokens, sites, site_tokens, pairs, method, classes=False):
         """score_mutations(tied=True) — the symmetric scan: which point mutations of a tied design change its likelihood
         under the distribution tied sample() draws from.  One complex; feature_dict["symmetry_residues"] / ["symmetry_weights"] are read
         as score_tied() reads them (listed order, a group with a masked member is not tied, the caps of conditional_probs(tied=True));
@@ -1818,9 +1960,19 @@ class ProteinMPNN(nn.Module):
         ascending per variant), "unit_log_prob" float32: one entry per unit with a member in U_3(site).
         method: "cone" — namp_group_mutations (include/namp.h) carried by one decoder call per chunk; "dense" — the explicit library
         [S; S_v ...] through score_tied(method="auto"): every layer count and precision mode; "auto" — the cone where it applies and
-        the mean of sum_l |U_l(site)| over the variants is at most 2 L."""
-        ties, groups, leader_l, st, tk, scan, st_x, tk_x, sites8, tok9 = self._group_scan_arguments(fd, positions, tokens, sites, site_tokens,
-                                                                                                     pairs)
+        the mean of sum_l |U_l(site)| over the variants is at most 2 L.
+        classes=True — the paired scan: the ties are every tie score_tied() reads on one backbone, read with class
+        tables (_class_scan_arguments); the units are total[c] = sum_t weight_t row_t[C_t[c]] + b_u[c] over the classes every member
+        has, clp = log_softmax(total), unit = logsumexp of clp over the classes that match the members' tokens; a variant's class per
+        touched unit is class_lane's and every member gets its token (expand_class_sites).  The cone is namp_class_mutations; the result
+        adds "sites_flat" / "site_tokens_flat" (the expanded sites and the tokens every member received) and, with pairs=True,
+        "classes" int64 [T] and "class_tokens" int64 [P, T, 2] (-1: no such class) beside "delta" [P, T]."""
+        class_keys = {}
+        if classes:
+            *args, class_keys = self._class_scan_arguments(fd, positions, tokens, sites, site_tokens, pairs)
+        else:
+            args = self._group_scan_arguments(fd, positions, tokens, sites, site_tokens, pairs)
+        ties, groups, leader_l, st, tk, scan, st_x, tk_x, sites8, tok9 = args
         S_true, mask = fd["S"], fd["mask"]
         L, n, n_sites, Vn = S_true.shape[1], len(tk), len(st), self.num_letters
         cone_ok = self._item_routes_ok("score_mutations", method, "dense")
@@ -1845,13 +1997,23 @@ class ProteinMPNN(nn.Module):
             if ties is None:
                 nxt = torch.full((L,), -1, dtype=torch.int32)
                 first, gw = torch.zeros(L, dtype=torch.int32), torch.ones(L, dtype=torch.float32)
+                sec = torch.cat((nxt, first, first, gw.view(torch.int32), torch.arange(Vn, dtype=torch.int32),
+                                 torch.full((spec.N_CLASS_LANES - Vn,), -1, dtype=torch.int32), torch.zeros(spec.N_CLASS_LANES, dtype=torch.int32)))
             else:
                 sec = ties["section"]
                 nxt, first, gw = sec[:L], sec[L:2 * L], sec[3 * L:4 * L].view(torch.float32)
-            tail = torch.cat((cm.float(), torch.cat((nxt, first)).view(torch.float32).to(dev), gw.to(dev)))
             base = torch.empty(1, L, Vn, device=dev)
-            route = _ConeRoute("group_mutations", L, K, (L, K, 3), (), f"score_mutations: no workspace for the group scan L={L} K={K}",
-                               sites8, tok9, tail, {"delta": ()}, ("row_residue", "row_token_log_prob", "unit_residue", "unit_log_prob"))
+            per_row = ("row_residue", "row_token_log_prob", "unit_residue", "unit_log_prob")
+            if classes:                                    # (the group section of namp_tied_score as it stands, behind w)
+                n_tab = 1 if ties is None else ties["n_tables"]
+                tail = torch.cat((cm.float(), sec.view(torch.float32).to(dev)))
+                route = _ConeRoute("class_mutations", L, K, (L, K, 3, n_tab, spec.N_CLASSES), (n_tab, spec.N_CLASSES),
+                                   f"score_mutations: no workspace for the class scan L={L} K={K} tables={n_tab}", sites8, tok9, tail,
+                                   {"delta": ()}, per_row)
+            else:
+                tail = torch.cat((cm.float(), torch.cat((nxt, first)).view(torch.float32).to(dev), gw.to(dev)))
+                route = _ConeRoute("group_mutations", L, K, (L, K, 3), (), f"score_mutations: no workspace for the group scan L={L} K={K}",
+                                   sites8, tok9, tail, {"delta": ()}, per_row)
             got = self._cone_scan(route, inputs, base, tk[:, 0], method)         # (the plan call: sizes, base rows, base units)
             out["site_rows"], btlp, use_cone = got["site_rows"], got["base_units"], got["use_cone"] and n > 0
         if use_cone:
@@ -1886,6 +2048,9 @@ class ProteinMPNN(nn.Module):
         denom = counted.float().sum() + 1e-8
         base_loss = -torch.where(counted, btlp, torch.zeros_like(btlp)).sum() / denom
         extra = {"unit_offsets": uoffs, "unit_residue": ures, "unit_log_prob": ulp}
+        if classes:
+            extra.update({"sites_flat": torch.from_numpy(st_x).to(dev), "site_tokens_flat": torch.from_numpy(tk_x).to(dev),
+                          **{k: v.to(dev) for k, v in class_keys.items()}})
         return self._scan_result(out, scan, delta, base_loss, denom, btlp, base, order, (offs, rres, rlp), extra, chunks, use_cone)
 
     @staticmethod

@@ -6,8 +6,11 @@ route's 3 L) and the number of decoder calls.
     python tools/group_scan_time.py [--reps 7] [--prec x3,fp32] [--copies 3] [--residues 300]
         a 3 x 300 homo-trimer (one chain copied under a three-fold rotation), K = 48, everything designed, groups (i, i + 300, i + 600),
         the 20 amino acids at 100 evenly spaced units (n = 2,000, three edits per variant)
+    --pairs         the paired scan, score_mutations(pairs=True, tied=True, classes=True) (namp_class_mutations), in the place of the
+                    symmetric one: a 2 x 150 RNA duplex, K = 48, wobble on, every pair over its 6 classes (n = 900), and a 300-residue
+                    protein beside a 2 x 20 RNA duplex, K = 32 (n = 120); the second strand runs antiparallel 10 A beside the first
     --parent PATH   another build of the library (libnamp_hip.so of the parent commit) as a second library of this process: score(),
-                    the plain and the state scan on their cones, score_tied(items) on the trimer at n = 100, conditional_probs(tied=True)
+                    the plain, the state and the group scan on their cones, score_tied(items) on the trimer at n = 100, conditional_probs(tied=True)
                     and the cfg1 design call (97 residues, K = 32, batch_size 1) run alternated on both builds; per call this build's
                     median - its median beside the larger min-max spread of the two, and whether the results are its bits.
 """
@@ -90,7 +93,57 @@ def states_of(cx, M, seed=5, amplitude=2.0, jitter=0.15):
     return np.stack(out)
 
 
+def duplex(n_prot, n_strand, seed=7):
+    """A protein of n_prot residues (none: 0) and an RNA duplex of 2 x n_strand: the second strand is the first one read backwards, 10 A
+    beside it, with the Watson-Crick complement of its tokens -> (cx, the pairs (first strand k, its partner))."""
+    n = n_prot + n_strand
+    cx = synth.make_complex(seed=seed, n=n, n_chains=1, frac_protein=n_prot / n, frac_dna=0.0)
+    rti = spec.restype_to_int()
+    wc = {rti[a]: rti[b] for a, b in spec.WC_SAME.items()}
+    a = np.arange(n_prot, n)
+    out = {}
+    for k, v in cx.items():
+        tail = v[a][::-1]
+        if k == "X":
+            tail = (tail + np.array([10.0, 0.0, 0.0], np.float32)) * cx["X_m"][a][::-1][:, :, None]
+        elif k == "S":
+            tail = np.array([wc.get(int(t), int(t)) for t in tail], v.dtype)
+        out[k] = np.concatenate((v, tail.astype(v.dtype)))
+    L2 = n + n_strand
+    out["chain_labels"] = np.repeat(np.arange(3, dtype=cx["chain_labels"].dtype), (n_prot, n_strand, n_strand))      # the protein, the two strands
+    out["chain_mask"] = np.ones(L2, np.int32)
+    out["randn"] = np.random.default_rng(seed).standard_normal(L2).astype(np.float32)
+    pairs = [(int(r), L2 - 1 - q) for q, r in enumerate(a)]
+    return out, [p for p in pairs if out["mask"][p[0]] and out["mask"][p[1]]]
+
+
 reps = int(arg("--reps", "7"))
+if "--pairs" in sys.argv:
+    for n_prot, n_strand, Kp in ((0, 150, 48), (300, 20, 32)):
+        cxp, prs = duplex(n_prot, n_strand)
+        Lp = len(cxp["S"])
+        fdp = to_fd(cxp)
+        fdp.update(paired_residues=prs, paired_wobble=True, paired_wobble_bias=0.0, symmetry_residues=[[]], symmetry_weights=[[]],
+                   temperature=1.0, bias=torch.zeros(1, Lp, 33, device=dev))
+        firsts = torch.tensor(sorted(p[0] for p in prs), device=dev)
+        for prec in arg("--prec", "x3,fp32").split(","):
+            m = model(Kp)
+            m.message_precision = prec
+            calls = {"cone": lambda: m.score_mutations(fdp, positions=firsts, pairs=True, method="cone", tied=True, classes=True),
+                     "dense": lambda: m.score_mutations(fdp, positions=firsts, pairs=True, method="dense", tied=True, classes=True)}
+            c, d = calls["cone"](), calls["dense"]()
+            n = len(c["site_index"])
+            diff = float((c["delta_log_likelihood"] - d["delta_log_likelihood"]).abs().max())
+            auto = m.score_mutations(fdp, positions=firsts, pairs=True, tied=True, classes=True)["method"]
+            t = measure(calls, reps)
+            rows = c["site_rows"][c["site_index"]].float()
+            (cm, clo, chi), (dm, dlo, dhi) = t["cone"], t["dense"]
+            print(f"{n_prot} protein + 2 x {n_strand} RNA duplex L={Lp} K={Kp} pairs={len(prs)} n={n} {prec}: cone {cm:.2f} ms [{clo:.2f}, {chi:.2f}] in "
+                  f"{c['chunks']} calls  dense {dm:.2f} ms [{dlo:.2f}, {dhi:.2f}] in {d['chunks']} calls  dense / cone {dm / cm:.2f}x "
+                  f"(dense - cone {dm - cm:+.2f} ms, larger min-max spread {max(chi - clo, dhi - dlo):.2f} ms); rows per variant: mean "
+                  f"{[round(v, 1) for v in rows.mean(0).tolist()]} = {float(rows.sum(1).mean()):.0f}, max {int(rows.sum(1).max())}, dense {3 * Lp}; "
+                  f"'auto' takes {auto}; max|d delta| cone vs dense {diff:.2e}; {reps} alternated calls each, from coordinates", flush=True)
+    sys.exit(0)
 copies, n_res, K = int(arg("--copies", "3")), int(arg("--residues", "300")), 48
 cx, groups = oligomer(n_res, copies)
 L = copies * n_res
@@ -140,6 +193,8 @@ if arg("--parent", ""):
         forms = {"score()": (lambda: m.score(fd0), "log_probs"),
                  "score_mutations(cone), 40 positions": (lambda: m.score_mutations(fd0, method="cone"), "delta_log_likelihood"),
                  "score_mutations(cone), 2 states, 40 positions": (lambda: m.score_mutations(fds, method="cone"), "delta_log_likelihood"),
+                 f"score_mutations(cone, tied=True), {copies} x {n_res} trimer, 100 units x 20":
+                     (lambda: m48.score_mutations(fd, positions=positions, method="cone", tied=True), "delta_log_likelihood"),
                  f"score_tied(items), {copies} x {n_res} trimer, n = 100": (lambda: m48.score_tied(fd, lib, method="items"), "token_log_probs"),
                  "conditional_probs(tied=True), the trimer": (lambda: m48.conditional_probs(fd, tied=True), "log_probs"),
                  "cfg1 design call": (lambda: m.sample(fd1), "log_probs")}

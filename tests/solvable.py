@@ -12,14 +12,13 @@ read from."""
 from __future__ import annotations
 
 import os
-import re
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from na_mpnn_amd import synth
-from oracle import cpu_ref
+from oracle import cpu_ref, cpu_ref_mixed
 
 H = 128
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,10 +108,7 @@ ROUNDINGS = {None: lambda x: x, "bf16": round_bf16, "x3": round_x3}
 
 def gelu4_constants():
     """Q0..Q4 of the bf16 mode's GELU polynomial, parsed from namp_device.h (no second copy of them)."""
-    src = open(os.path.join(ROOT, "na_mpnn_amd", "csrc", "namp_device.h")).read()
-    c = {k: float(np.float32(v)) for k, v in re.findall(r"#define NAMP_GELU4_(Q[0-4]) (-?[0-9.e+-]+)f", src)}
-    assert sorted(c) == ["Q0", "Q1", "Q2", "Q3", "Q4"]
-    return [c[f"Q{i}"] for i in range(5)]
+    return cpu_ref_mixed.gelu4_constants()
 
 
 def gelu_poly(x):

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 from na_mpnn_amd import spec, synth, train
 from na_mpnn_amd.model import ProteinMPNN
 from oracle import cpu_ref
+from solvable_train import _mix32, hash_dropout_factor
 from test_oracle_golden import g7_inputs, g7b_ppm
 
 pytestmark = pytest.mark.gpu
@@ -196,27 +197,6 @@ def test_edge_update_backward_on_chip_weight_gradients(B, N, K, p, monkeypatch):
         worst[name] = rel(b, a)
         assert worst[name] < 1.5e-2, (name, worst[name])
     print(f"edge update, on-chip dW vs row tensors ({B}x{N}x{K}, p={p}):", {k_: f"{v:.1e}" for k_, v in worst.items()})
-
-
-def _mix32(x):
-    """mix32 of csrc/namp_device.h on int64 tensors holding uint32 values."""
-    M = 0xFFFFFFFF
-    x = x ^ (x >> 16); x = (x * 0x7feb352d) & M
-    x = x ^ (x >> 15); x = (x * 0x846ca68b) & M
-    return x ^ (x >> 16)
-
-
-def hash_dropout_factor(seed, E, p, dev):
-    """The training path's counter-based dropout mask (drop_row_key / drop_factor, csrc/namp_device.h) restated in torch: [E,128] of
-    0 or 1 / (1 - p).  Edge rows < 2^32, so the key's high-word term is mix32(0x9E3779B9)."""
-    M = 0xFFFFFFFF
-    e = torch.arange(E, device=dev, dtype=torch.int64)
-    hi = _mix32(torch.full((1,), 0x9E3779B9, device=dev, dtype=torch.int64))
-    key = _mix32((int(seed) & M) ^ e ^ hi)
-    ch = torch.arange(128, device=dev, dtype=torch.int64)
-    h = _mix32((key[:, None] + ch[None, :] * 0x9E3779B9) & M)
-    thresh = int(float(p) * 4294967296.0)
-    return (h >= thresh).double() / (1.0 - p)
 
 
 @pytest.mark.parametrize("kind,prec", [("enc_msg", 1), ("enc_msg", 2), ("dec_msg", 1), ("dec_msg", 2), ("edge", 2)])

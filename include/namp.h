@@ -755,6 +755,40 @@ size_t namp_sample_pair_terms_workspace_bytes(int B_enc, int B_dec, int N, int K
 size_t namp_sample_pair_terms_offset(int B_enc, int B_dec, int N, int K, int n_dec);
 int namp_sample_pair_terms(int D, int n_tables, int members);
 
+/* ---- forbidden motifs: token patterns of 2..8 residues the sampler never completes ---------------------------------
+ * A motif OCCURS at residues r_0 .. r_{n-1} that are consecutive on one chain (the caller's adjacency: window[][] below), all present,
+ * and hold the motif's tokens.  When the group closing at a visit draws, group token / class `a` is BANNED if the following sequence
+ * holds an occurrence that covers a member of the group: every member holds what the draw's assignment loop writes for it under `a`
+ * (through its map or class table; forced and fixed members their own token, which with maps they also pass on), every residue
+ * whose group closed before the group's first visit (rank < v_first) holds its token in S_out, every other residue is PAD.  Banned
+ * candidates get p = 0 where the special tokens are removed and p is renormalised (class tables: before the restriction by pinned
+ * members); a ban that would leave no candidate with p > 0 is skipped for that draw.  probs_out carries the ban, logp_out does not.
+ * The data sits in the pair terms' INPUT SECTION, behind their blocks (without pair terms D = n_tables = 0 and those are empty), in
+ * int32 words, G = B_enc * N, W = 2 * half_width:
+ *     window[G][W]              the chain neighbours of residue i at offsets -half_width .. -1, +1 .. +half_width (local index in its
+ *                               complex; -1: none — chain end, gap, absent residue)
+ *     entries[n_entries][6]     (pattern[3], mask[3]), one per (motif, alignment): the window of a member is 15 slots of 6 bits,
+ *                               slot 7 + o the neighbour at offset o and slot 7 the member itself, slot s at bit 6 * (s % 5) of word
+ *                               s / 5, a slot holding token + 1 (0: none); the entry of motif m_0 .. m_{n-1} with the member at
+ *                               position k has m_q + 1 in slot 7 - k + q and 0x3f in the mask there; it matches when
+ *                               ((window ^ pattern) & mask) == 0 in all three words
+ *     namp_sample_motifs_offset(B_enc, B_dec, N, K, n_dec, D, n_tables, vocab)   byte offset of window[][] in ws (vocab: the weights'
+ *                               own, which places the pair terms' tables; 0 on bad arguments); the entries follow at
+ *                               + 4 * G * W
+ * namp_sample_motifs(n_entries, half_width), 1 <= n_entries <= NAMP_MOTIF_MAX_ENTRIES, 1 <= half_width <= 7 (NAMP_EINVAL otherwise,
+ * and nothing stays attached), attaches them to the calling thread's NEXT sampler call as namp_sample_pair_terms does — beside it or
+ * alone —, which requires ws_bytes >= namp_sample_motifs_workspace_bytes(.., D, n_tables, n_entries, half_width) (sized for vocab = 64;
+ * 0 on bad arguments) and returns NAMP_EINVAL if ws is smaller, the dense pair_bias pointer is given, or K > 128 (the 12-wave
+ * workgroup form carries no motif code: it runs at its register cap).  The attachment is cleared
+ * whether the call succeeds or not.  Validated on the device: a window index outside [0, N) or the residue itself is absent; a token
+ * outside [0, min(vocab, 62)) never fills a slot, so an entry that asks for one never matches.  The level decoders need window[][]
+ * among their dependencies (namp_sample_levels_dep with the partners and the window side by side).  One wave per draw, lane =
+ * candidate; per member W agent-scope loads of S_out, then n_entries scalar entry loads; nothing is written. */
+#define NAMP_MOTIF_MAX_ENTRIES 504   /* 63 motifs x 8 alignments */
+size_t namp_sample_motifs_workspace_bytes(int B_enc, int B_dec, int N, int K, int n_dec, int D, int n_tables, int n_entries, int half_width);
+size_t namp_sample_motifs_offset(int B_enc, int B_dec, int N, int K, int n_dec, int D, int n_tables, int vocab);
+int namp_sample_motifs(int n_entries, int half_width);
+
 /* ---- tied states: the plan of one sequence sampled over M backbone states of the same molecule -------------------
  * M states of N residues, encoded as a batch, are ONE symmetric design on the block-diagonal flattened graph of M * N residues:
  * residue n of state m is flat residue m * N + n, its neighbours are E_idx[m][n][:] + m * N, and the M copies of a residue form a

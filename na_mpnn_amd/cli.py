@@ -52,6 +52,11 @@ def build_parser():
     a("--pair_bias_members", type=str, default="auto", choices=("auto", "closing", "all"), help="which members of a tied group feel "
       "--pair_bias_AA: 'closing' - the group's last member only (the reference's rule); 'all' - every member, each in its own alphabet "
       "(both strands of a base pair feel their neighbours); 'auto' (default) - 'all' when base pairs are given, else 'closing'")
+    a("--forbidden_motifs", type=str, default="", help="sequence motifs of 2..8 residues no design may hold on one chain, e.g. "
+      "'gggg,cccc,dna:GAATTC,rna:GGGG': plain items in the one-letter alphabet of --bias_AA, 'dna:' / 'rna:' items in ACGT / ACGU; goes "
+      "with every tie flag and with --pair_bias_AA; every design's fasta header reports motif_hits")
+    a("--max_homopolymer", type=int, default=0, help="N in 1..7: no run of more than N equal residues (forbids the run of N + 1 of every "
+      "residue type of the polymers being designed)")
     a("--symmetry_residues", type=str, default="", help="tied residues, e.g. 'A12,A13,A14|C2,C3'")
     a("--symmetry_weights", type=str, default="", help="weights matching --symmetry_residues, e.g. '1.0,1.0,1.0|-1.0,2.0'")
     a("--multi_state", type=int, default=0, help="1 - the MODELs of --pdb_path are states of one molecule: ONE sequence is designed "
@@ -176,6 +181,30 @@ def make_pair_terms(chain_labels, R_idx, pair_bias_AA, members="closing"):
     partner[0, i, 1] = (i + 1).to(torch.int32)
     AA = pair_bias_AA.detach().float().cpu()
     return {"partner": partner, "table": table, "tables": torch.stack((AA, AA.t())).contiguous(), "members": members}
+
+
+def parse_forbidden_motifs(forbidden_motifs, max_homopolymer, rti, polymers=("protein", "dna", "rna")):
+    """--forbidden_motifs 'gggg,dna:GAATTC,rna:GGGG' and --max_homopolymer N as the list of token tuples of
+    feature_dict["forbidden_motifs"].  rti: the run's restype_to_int (with --na_shared_tokens 1 the RNA names hold the shared tokens);
+    polymers: the polymer types being designed, whose residue types --max_homopolymer expands over."""
+    one = {spec.RESTYPE_3TO1[k]: int(v) for k, v in rti.items()}
+    named = {"dna": dict(zip("ACGT", ("DA", "DC", "DG", "DT"))), "rna": dict(zip("ACGU", ("A", "C", "G", "U")))}
+    out = []
+    for item in filter(None, (t.strip() for t in forbidden_motifs.split(","))):
+        kind, _, body = item.rpartition(":")
+        if kind and kind not in named:
+            raise ValueError(f"--forbidden_motifs: '{item}': the prefix is 'dna:' or 'rna:'")
+        try:
+            out.append(tuple(int(rti[named[kind][c]]) for c in body.upper()) if kind else tuple(one[c] for c in body))
+        except KeyError as e:
+            raise ValueError(f"--forbidden_motifs: '{item}' holds the unknown letter {e}") from None
+    if max_homopolymer:
+        if not 1 <= max_homopolymer <= 7:
+            raise ValueError(f"--max_homopolymer is in 1..7; got {max_homopolymer}")
+        names = {"protein": spec.RESTYPES[:20], "dna": ("DA", "DC", "DG", "DT"), "rna": ("A", "C", "G", "U")}
+        for tok in sorted({int(rti[n]) for kind in polymers for n in names[kind]}):
+            out.append((tok,) * (max_homopolymer + 1))
+    return list(dict.fromkeys(out))
 
 
 def parse_pairs(paired_residues, paired_strands, encoded, chain_letters):
@@ -308,6 +337,12 @@ def main(argv=None):
     if args.coordinate_gradients and (args.score_fasta or args.conditional_probs_only or args.multi_state or args.mutation_scan):
         raise ValueError("--coordinate_gradients 1 differentiates one structure's likelihood: it does not go with --score_fasta, "
                          "--conditional_probs_only, --multi_state or --mutation_scan")
+    if (args.forbidden_motifs or args.max_homopolymer) and (args.score_fasta or args.conditional_probs_only or args.mutation_scan
+                                                             or args.coordinate_gradients):
+        raise ValueError("--forbidden_motifs / --max_homopolymer constrain designs: they do not go with --score_fasta, "
+                         "--conditional_probs_only, --mutation_scan or --coordinate_gradients")
+    if args.max_homopolymer and not 1 <= args.max_homopolymer <= 7:
+        raise ValueError(f"--max_homopolymer is in 1..7; got {args.max_homopolymer}")
     if args.model_type != "na_mpnn":
         print("Choose --model_type flag from currently available models")
         sys.exit()
@@ -456,6 +491,10 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
         if pair_bias_AA is not None:
             members = args.pair_bias_members if args.pair_bias_members != "auto" else ("all" if pairs else "closing")
             fd["pair_terms"] = make_pair_terms(fd["chain_labels"][0], fd["R_idx"][0], pair_bias_AA, members)
+        if args.forbidden_motifs or args.max_homopolymer:
+            designed = (fd["mask"] * fd["chain_mask"])[0] != 0
+            polymers = [k for k in ("protein", "dna", "rna") if bool(((fd[k + "_mask"][0] != 0) & designed).any())]
+            fd["forbidden_motifs"] = parse_forbidden_motifs(args.forbidden_motifs, args.max_homopolymer, rti, polymers)
         if args.conditional_probs_only:
             # one deterministic leave-one-out profile instead of draws: the decoding order's noise is the only random input
             fd["randn"] = torch.randn(1, L, device=device)
@@ -529,7 +568,7 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
                      residue_norm=out["residue_norm"][0].cpu().numpy(), loss=float(out["loss"]), encoded_residues=encoded,
                      mask=P["mask"], chain_mask=chain_mask, decoding_randn=fd["randn"][0].cpu().numpy())
             return
-        S_l, lp_l, sp_l, loss_l, lpr_l, Ss_l = [], [], [], [], [], []
+        S_l, lp_l, sp_l, loss_l, lpr_l, Ss_l, hits_l = [], [], [], [], [], [], []
         cmask = (fd["mask"] * fd["chain_mask"]).float()
         forced = np.load(args.forced_draws_npz) if args.forced_draws_npz else None
         model.sample_check_walk = True      # verify the persistent level walk's barriers per design call; falls back to per-level launches
@@ -550,6 +589,8 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
             S_l.append(out["S"]); lp_l.append(out["log_probs"]); sp_l.append(out["sampling_probs"])
             if "S_states" in out:
                 Ss_l.append(out["S_states"])
+            if "motif_hits" in out:
+                hits_l.append(out["motif_hits"])
         S_stack, sp_stack, loss_stack, lpr_stack = torch.cat(S_l), torch.cat(sp_l), torch.cat(loss_l), torch.cat(lpr_l)
         rec = ((fd["S"][:1] == S_stack) * cmask).sum(-1) / cmask.sum(-1)               # get_seq_rec, data_utils.py:18-30
 
@@ -557,9 +598,12 @@ def run_one(args, model, pdb, name, fixed_residues, device, seed, ckpt_name, bia
     entries = ['>{}, T={}, seed={}, num_res={}, batch_size={}, number_of_batches={}, model_path={}\n{}'.format(
         name, args.temperature, seed, (fd["mask"] * fd["chain_mask"]).sum().cpu().numpy(), args.batch_size, args.number_of_batches, ckpt_name,
         seq_string(P["S"], rna_flag, int_to_str, dna_to_rna, P["chain_letters"]))]
+    motif_hits = torch.cat(hits_l).cpu().tolist() if hits_l else None
     for ix in range(S_stack.shape[0]):
         conf = np.format_float_positional(np.exp(-loss_stack[ix].cpu().numpy()), unique=False, precision=4)
         srec = np.format_float_positional(rec[ix].cpu().numpy(), unique=False, precision=4)
+        if motif_hits is not None:                                                    # (with --forbidden_motifs / --max_homopolymer only)
+            srec += f" motif_hits={motif_hits[ix]}"
         entries.append('>{}, id={}, T={}, seed={}, overall_confidence={} seq_rec={}\n{}'.format(
             name, ix if args.zero_indexed else ix + 1, args.temperature, seed, conf, srec,
             seq_string(S_stack[ix].cpu().numpy(), rna_flag, int_to_str, dna_to_rna, P["chain_letters"])))

@@ -1293,6 +1293,39 @@ int namp_sample_pair_terms(int D, int n_tables, int members) {
   return NAMP_OK;
 }
 
+// ---- forbidden motifs: two more blocks of that section, behind the pair terms' (include/namp.h) ----
+// the attachment of the calling thread's NEXT sampler call (namp_sample_motifs): taken, and cleared, by sample_prepare
+static thread_local int g_motifs = 0;                            // half_width << 17 | n_entries << 21 (the free bits of SampleArgs.pair_terms)
+
+// bytes from the start of the section to the window block: the pair terms' blocks (vocab: the tables' side as the call's weights give it);
+// D = n_tables = 0 without pair terms
+static size_t motifs_block_offset(size_t G, int D, int n_tables, int vocab) {
+  return 4 * (2 * G * (size_t)D + (size_t)n_tables * vocab * vocab);
+}
+static bool motifs_dims_ok(int D, int n_tables, int n_entries, int half_width) {
+  return ((D == 0 && n_tables == 0) || (D >= 1 && D <= 64 && n_tables >= 1 && n_tables <= 256)) && n_entries >= 1 &&
+         n_entries <= NAMP_MOTIF_MAX_ENTRIES && half_width >= 1 && half_width <= 7;
+}
+size_t namp_sample_motifs_offset(int B_enc, int B_dec, int N, int K, int n_dec, int D, int n_tables, int vocab) {
+  const size_t off = namp_sample_pair_terms_offset(B_enc, B_dec, N, K, n_dec);
+  if (off == 0 || vocab < 1 || vocab > 64 || !((D == 0 && n_tables == 0) || (D >= 1 && D <= 64 && n_tables >= 1 && n_tables <= 256))) return 0;
+  return off + motifs_block_offset((size_t)B_enc * N, D, n_tables, vocab);
+}
+// (sized for the largest vocabulary, as the pair terms' tables are)
+size_t namp_sample_motifs_workspace_bytes(int B_enc, int B_dec, int N, int K, int n_dec, int D, int n_tables, int n_entries, int half_width) {
+  const size_t off = namp_sample_motifs_offset(B_enc, B_dec, N, K, n_dec, D, n_tables, 64);
+  if (off == 0 || !motifs_dims_ok(D, n_tables, n_entries, half_width)) return 0;
+  const size_t G = (size_t)B_enc * N;
+  return off + 4 * (G * 2 * half_width + 6 * (size_t)n_entries);
+}
+int namp_sample_motifs(int n_entries, int half_width) {
+  g_motifs = 0;                                                  // (an invalid attach leaves nothing attached)
+  REQUIRE(n_entries >= 1 && n_entries <= NAMP_MOTIF_MAX_ENTRIES, "namp_sample_motifs: n_entries=%d must be in [1, %d]", n_entries, NAMP_MOTIF_MAX_ENTRIES);
+  REQUIRE(half_width >= 1 && half_width <= 7, "namp_sample_motifs: half_width=%d must be in [1, 7]", half_width);
+  g_motifs = (half_width << 17) | (n_entries << 21);
+  return NAMP_OK;
+}
+
 static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float* h_E, const int32_t* E_idx,
                           const int32_t* mask, const int32_t* mask_dec, const int32_t* chain_mask, const int32_t* S_true, const float* bias,
                           const int32_t* order, const int32_t* rank, const float* uniform, const int32_t* S_forced,
@@ -1305,7 +1338,10 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
   g_tok_maps = nullptr; g_n_maps = 0;                            // (one call only, whatever becomes of it)
   const int pair_terms = g_pair_terms;
   g_pair_terms = 0;
+  const int motifs = g_motifs;
+  g_motifs = 0;
   REQUIRE(pair_terms == 0 || pair_bias == nullptr, "namp_decoder_sample: pair terms and the dense pair_bias do not go together");
+  REQUIRE(motifs == 0 || pair_bias == nullptr, "namp_decoder_sample: forbidden motifs and the dense pair_bias do not go together");
   REQUIRE(w != nullptr, "namp_decoder_sample: null weights");
   REQUIRE(tok_maps == nullptr || pair_bias == nullptr, "namp_decoder_sample: token maps / class tables and pair_bias do not go together");
   REQUIRE((group_first == nullptr) == (group_last == nullptr), "namp_decoder_sample: group_first and group_last go together");
@@ -1328,6 +1364,13 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
     // the section sits behind the carve (and the walk's barrier words, which stay the last 4 KiB of it)
     const size_t need = namp_sample_pair_terms_workspace_bytes(B_enc, B_dec, N, K, nd, pair_terms & 0x7f, (pair_terms >> 8) & 0x1ff);
     REQUIRE(need != 0 && ws_bytes >= need, "namp_decoder_sample: workspace too small for the pair-terms section (%zu bytes, needs %zu)", ws_bytes, need);
+  }
+  if (motifs) {
+    // the motif blocks sit behind the pair terms' (none: D = n_tables = 0), which are placed by the vocabulary of THIS call's weights
+    const int D = pair_terms & 0x7f, n_tab = (pair_terms >> 8) & 0x1ff, hw = (motifs >> 17) & 7, n_ent = (motifs >> 21) & 0x3ff;
+    const size_t off = namp_sample_motifs_offset(B_enc, B_dec, N, K, nd, D, n_tab, w->vocab);
+    const size_t need = off + 4 * ((size_t)Ge * 2 * hw + 6 * (size_t)n_ent);
+    REQUIRE(off != 0 && ws_bytes >= need, "namp_decoder_sample: workspace too small for the motif section (%zu bytes, needs %zu)", ws_bytes, need);
   }
   float* Pfw[NAMP_MAX_LAYERS]; for (int l = 0; l < nd; ++l) Pfw[l] = c.take((size_t)Ge * NAMP_HIDDEN);
   float* Pa0 = c.take((size_t)Ge * NAMP_HIDDEN);
@@ -1368,9 +1411,9 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
   a.uniform = uniform; a.S_forced = S_forced; a.group_first = group_first; a.group_last = group_last;
   a.sym_w = sym_weights; a.pair_bias = pair_bias; a.tok_maps = tok_maps; a.n_maps = n_maps & 0xffff; a.n_classes = n_maps >> 16; a.head_wT = head_wT; a.head_b = w->Wout_b; a.S_out = S_out;
   a.probs_out = probs_out; a.logp_out = logp_out; a.special = special_tokens; a.inv_T = 1.0f / temperature;
-  if (pair_terms) {
+  if (pair_terms | motifs) {
     a.pair_bias = (const float*)((const char*)ws + namp_sample_pair_terms_offset(B_enc, B_dec, N, K, nd));
-    a.pair_terms = pair_terms;
+    a.pair_terms = pair_terms | motifs;
   }
   a.B_dec = B_dec; a.B_enc = B_enc; a.N = N; a.K = K; a.TPN = (K + 15) / 16; a.n_layers = w->n_dec; a.vocab = w->vocab;
   // 8 waves per workgroup (256 VGPRs per lane: no scratch) serve 8 / TPN streams; K > 128 falls back to the 12-wave form
@@ -1379,6 +1422,7 @@ static int sample_prepare(const NampModelW* w, const float* h_V_enc, const float
   a.slots = slots;
   int nwaves = slots * a.TPN; if (nwaves < 8) nwaves = 8;
   REQUIRE(nwaves <= 12, "namp_decoder_sample: K=%d needs %d waves per workgroup (max 12)", K, nwaves);
+  REQUIRE(motifs == 0 || maxw == 8, "namp_decoder_sample: forbidden motifs need K <= 128 (K=%d runs the 12-wave form, which has none)", K);
   for (int l = 0; l < w->n_dec; ++l) {
     const NampDecLayerW* D = &w->dec[l];
     SampleLayer& L = a.l[l];

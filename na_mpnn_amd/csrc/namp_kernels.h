@@ -2253,6 +2253,9 @@ struct SampleArgs {
                                // one).  pair_bias then points to the int32 section partner[G_enc][D] (-1: none), table_idx[G_enc][D],
                                // tables[n_tables][vocab][vocab] (float bits) — the dense tensor is never there together with it, so the section needs no
                                // pointer of its own, and this word fills the last 4 bytes of padding in front of l.
+                               // FORBIDDEN MOTIFS ride in the word's other bits: half_width << 17 | n_entries << 21 (0: none); their blocks —
+                               // window[G_enc][2 * half_width] int32 and the packed entries [n_entries][6] — sit behind the pair terms' in the same section
+                               // (include/namp.h; with motifs alone D = 0 and n_tables = 0).
   SampleLayer l[NAMP_MAX_LAYERS];      // 8 x 480 B: with the scalars and the launch's own 40 argument bytes all 4,096 kernel-argument bytes
 };
 static_assert(sizeof(SampleArgs) + 40 <= 4096, "SampleArgs + the sampler launch's scalar arguments must fit the kernel-argument segment");
@@ -2437,7 +2440,7 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     const int32_t* So = a.S_out + (long)bq * a.N;
     float sum = 0.f;
 #pragma unroll 1
-    for (int v = (pt >> 20) ? v_first : t; v <= t; ++v) {
+    for (int v = ((pt >> 20) & 1) ? v_first : t; v <= t; ++v) {
       const int im = a.order[(long)bq * a.N + v];
       int x = idx ? a.tok_maps[idx[e0 + im] * 64 + lane] : lane;
       x = (x < 0 ? 0 : (x < V ? x : V - 1)) * V;                   // the member's token of `lane`: its row of every table
@@ -2460,8 +2463,77 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     }
     return sum;
   };
+  // Forbidden motifs (SampleArgs.pair_terms, bits 17-30): is group token / class `lane` BANNED for the group closing at visit t of stream bq —
+  // would the running sequence, with every member of the group holding what the assignment loops of `draw` write for it under `lane`, contain
+  // a motif that covers a member?  The window of member m is its up to 7 chain neighbours on either side (window[m][..], the host's adjacency:
+  // -1 absent), 15 slots of 6 bits in three 32-bit words per lane, 5 slots a word, slot 7 + o the neighbour at chain offset o, slot 7 the member itself.
+  // A slot holds token + 1, or 0: absent, PAD (a residue whose group has not closed before v_first and that is no member), out of range.
+  // A neighbour that closed earlier comes from S_out as a scalar; a neighbour that is a member of the open group holds its own token under
+  // `lane`.  The host expanded every (motif, alignment) to one entry (pattern[3], mask[3]) in these coordinates; an entry matches when
+  // ((x ^ pattern) & mask) == 0 in all three words.  Every load is unconditional on clamped indices; no slot ever holds 63.
+  auto motif_ban = [&](const int bq, const int t, const int v_first, const int pt, const int nm) __attribute__((always_inline)) {
+    const int hw = (pt >> 17) & 7, W = 2 * hw, V = a.vocab;
+    const int e0 = (bq % a.B_enc) * a.N;
+    const long Ge = (long)a.B_enc * a.N;
+    const int32_t* win = (const int32_t*)a.pair_bias + (2 * Ge * (pt & 0x7f) + (long)((pt >> 8) & 0x1ff) * V * V);      // (behind the pair terms' blocks)
+    bool banned = false;
+#pragma unroll 1
+    for (int v = v_first; v <= t; ++v) {
+      const int im = a.order[(long)bq * a.N + v];
+      unsigned x0 = 0, x1 = 0, x2 = 0;
+      bool any = false;
+      // the W neighbours, then (d == W) the member itself in slot 7
+#pragma unroll 1
+      for (int d = 0; d <= W; ++d) {
+        const int j = d < W ? win[(long)(e0 + im) * W + d] : -1;
+        const bool there = j >= 0 && j < a.N && j != im;
+        const int jc = d < W ? (there ? j : 0) : im;
+        const int Sj = __builtin_amdgcn_readfirstlane(__hip_atomic_load(a.S_out + (long)bq * a.N + jc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        const int rj = __builtin_amdgcn_readfirstlane(a.rank[(long)bq * a.N + jc]);
+        int tok = rj < v_first ? Sj : -1;
+        if ((there || d == W) && rj >= v_first && rj <= t) {
+          // A member of the open group (visit rj) holds its token under `lane`: class tables — its class token, or its own if it is forced
+          // or fixed; maps (or none) — the running group token, which forced and fixed members replace for themselves and the members
+          // behind them, through its map
+          if (nm >> 16) {
+            const int iu = a.order[(long)bq * a.N + rj];
+            tok = a.tok_maps[a.tok_maps[(nm & 0xffff) * 64 + e0 + iu] * 64 + lane];
+            if (a.S_forced) tok = a.S_forced[(long)bq * a.N + iu];
+            if (!a.chain_mask[e0 + iu]) tok = a.S_true[e0 + iu];
+          } else {
+            tok = lane;
+#pragma unroll 1
+            for (int u = v_first; u <= rj; ++u) {
+              const int iu = a.order[(long)bq * a.N + u];
+              const int32_t* pm = a.tok_maps ? a.tok_maps + a.tok_maps[(nm & 0xffff) * 64 + e0 + iu] * 64 : nullptr;
+              int f = -1;
+              if (a.S_forced) f = a.S_forced[(long)bq * a.N + iu];
+              if (!a.chain_mask[e0 + iu]) f = a.S_true[e0 + iu];
+              if (f >= 0) tok = pm ? pm[f & 63] : f;                     // (the group token of the member's own token: the maps are involutions)
+              if (u == rj) tok = pm ? pm[tok & 63] : tok;
+            }
+          }
+        }
+        const unsigned val = ((there || d == W) && tok >= 0 && tok < V && tok < 62) ? (unsigned)(tok + 1) : 0u;
+        const int s = d == W ? 7 : (d < hw ? 7 - hw + d : 8 - hw + d);   // chain offsets -hw .. -1, +1 .. +hw
+        if (s < 5) x0 |= val << (6 * s); else if (s < 10) x1 |= val << (6 * (s - 5)); else x2 |= val << (6 * (s - 10));
+        any |= there;
+      }
+      if (any) {
+        const unsigned* ent = (const unsigned*)(win + Ge * W);
+        const int n_ent = (pt >> 21) & 0x3ff;
+#pragma unroll 1
+        for (int e = 0; e < n_ent; ++e) {
+          const unsigned* q = ent + 6 * e;
+          banned |= (((x0 ^ q[0]) & q[3]) | ((x1 ^ q[1]) & q[4]) | ((x2 ^ q[2]) & q[5])) == 0u;
+        }
+      }
+    }
+    return banned;
+  };
   // softmax((total + bias_t [+ pair_bias_t]) / T) with bias of the group's last residue (visit t of stream bq), special tokens removed,
   // renormalised (model_utils.py:194-205 / :300-312); inverse-CDF draw; the token goes to every member v_first .. t.  One wave.
+  // Forbidden motifs: the banned candidates lose their p where the special tokens do — unless that would leave none, then the ban is skipped.
   auto draw = [&](const int bq, const int t, const int v_first, const float total) __attribute__((always_inline)) {
     const int iq = a.order[(long)bq * a.N + t];
     const int ne = (bq % a.B_enc) * a.N + iq;
@@ -2470,7 +2542,17 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     // (compact pair terms, once for all three forms: the residues' map / table indices sit behind the maps / tables in either case)
     float pterm = 0.f;
     const int pt = scalar_here(a.pair_terms);
-    if (pt) pterm = pair_term(bq, t, v_first, pt, a.tok_maps ? a.tok_maps + (nm & 0xffff) * 64 : nullptr);
+    if (pt & 0x7f) pterm = pair_term(bq, t, v_first, pt, a.tok_maps ? a.tok_maps + (nm & 0xffff) * 64 : nullptr);
+    // (the 8-wave forms only: the 12-wave forms of K > 128 run at their 168-register cap, where the windows cost scratch; the host entry
+    //  points refuse motifs there)
+    bool ban = false;
+    if constexpr (MAXW == 8) {
+      if (__builtin_expect(pt >> 21, 0)) {
+        asm volatile("" ::: "memory");               // (keeps the loads of the motif loops inside them: no live range of the draw grows)
+        ban = motif_ban(bq, t, v_first, pt, nm);
+        asm volatile("" ::: "memory");
+      }
+    }
     if (nm >> 16) {
       // Class tables: the group draws a PAIR CLASS c = lane, member j holds C_j[c].  Lanes < vocab are the group tokens of the maps (the
       // tables are involutions there), the lanes from vocab on are further classes (G-U wobble) that several classes may share a token with.
@@ -2482,7 +2564,7 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
       const int ce = a.tok_maps[kc * 64 + lane];
       const int bl = ce < 0 ? 0 : ce;                                  // the closing member's token of class `lane` (clamped: loads stay unconditional)
       float add = a.bias[(long)ne * a.vocab + bl] + cls_bias[kc * 64 + lane];
-      if (pt) add += pterm;
+      if (pt & 0x7f) add += pterm;
       const float u = a.uniform[vis];
       // the classes of a group are those of its closing member's table: every member of a group has a token for the same classes (the
       // host builds the tables so), and the sum of any other class — some lane's logit, see the fetch in `step` — is never looked at
@@ -2492,6 +2574,7 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
       float p = ok ? expf(zt - mt) : 0.f;
       p = p / wave_sum64(p);
       if ((a.special >> bl) & 1ull) p = 0.f;
+      if constexpr (MAXW == 8) { if ((pt >> 21) && __ballot(p > 0.f && !ban) && ban) p = 0.f; }
       p = p / wave_sum64(p);
       // a pinned member (fixed, or forced) does not overwrite a running token: it RESTRICTS the classes to those under which it holds its
       // token, in visit order; a restriction that would leave no class is skipped
@@ -2538,7 +2621,7 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     const int bl = a.tok_maps ? a.tok_maps[map_idx[ne] * 64 + lane] : lane;
     float add = (lane < a.vocab) ? a.bias[(long)ne * a.vocab + bl] : 0.f;
     if (pt) {
-      add += pterm;
+      if (pt & 0x7f) add += pterm;
     } else if (a.pair_bias && lane < a.vocab) {
       const float* pb = a.pair_bias + ((long)ne * a.vocab + lane) * a.N * a.vocab;
       float acc_pb = 0.f;
@@ -2559,6 +2642,7 @@ __global__ __launch_bounds__(MAXW * 64) void dec_sample_kernel(const SampleArgs 
     float p = (lane < a.vocab) ? expf(zt - mt) : 0.f;
     p = p / wave_sum64(p);
     if ((a.special >> lane) & 1ull) p = 0.f;
+    if constexpr (MAXW == 8) { if ((pt >> 21) && __ballot(p > 0.f && !ban) && ban) p = 0.f; }
     p = p / wave_sum64(p);
     // inverse CDF: first token whose inclusive prefix sum exceeds u
     const float cdf = wave_scan64(p, lane);

@@ -216,6 +216,9 @@ _PROTOTYPES = {
     "namp_sample_pair_terms_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32]),
     "namp_sample_pair_terms_offset": (sz, [i32, i32, i32, i32, i32]),
     "namp_sample_pair_terms": (i32, [i32, i32, i32]),
+    "namp_sample_motifs_workspace_bytes": (sz, [i32] * 9),
+    "namp_sample_motifs_offset": (sz, [i32] * 8),
+    "namp_sample_motifs": (i32, [i32, i32]),
     "namp_pairs_plan": (i32, [c_ip] * 8 + [i32, i32, vp]),
     "namp_pairs_work_lists": (i32, [c_ip] * 6 + [i32, i32, vp]),
     "namp_states_plan": (i32, [c_ip, c_ip, c_ip, c_fp] + [c_ip] * 5 + [c_fp] + [c_ip] * 7 + [i32, i32, i32, i32, vp]),

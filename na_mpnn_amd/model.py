@@ -366,6 +366,108 @@ def pair_terms_dense(pair_terms, L):
     return out
 
 
+MOTIF_MIN_LEN, MOTIF_MAX_LEN, MOTIF_MAX_COUNT = 2, 8, 63       # namp_sample_motifs' limits: 63 motifs x 8 alignments = 504 entries
+
+
+def forbidden_motifs_arguments(motifs, V, special=(), B=1, tied=False, pair_bias=False):
+    """feature_dict["forbidden_motifs"] checked on the host (needs no device) -> a list of token tuples.  `motifs`: a list of token
+    sequences, or an int tensor [n, Lm] whose rows are padded with -1.  Refused: a token outside [0, V), a special token (`special`: they
+    are never drawn, and PAD stands for "not decoded yet"), a length outside 2..8, more than 63 motifs, the dense pair_bias beside
+    motifs, and several complexes (B != 1) with ties."""
+    if pair_bias:
+        raise ValueError("forbidden_motifs do not go with the dense pair_bias: give the pair bias as pair_terms")
+    if tied and B != 1:
+        raise ValueError(f"forbidden_motifs with ties expect one input complex (B == 1); got B = {B}")
+    if torch.is_tensor(motifs):
+        if motifs.dim() != 2 or motifs.dtype.is_floating_point or motifs.dtype == torch.bool:
+            raise ValueError(f"forbidden_motifs as a tensor must be an integer tensor [n, Lm] padded with -1; got {motifs.dtype} {tuple(motifs.shape)}")
+        rows = []
+        for row in motifs.detach().cpu().tolist():
+            n = len(row)
+            while n and row[n - 1] == -1:
+                n -= 1
+            rows.append(row[:n])
+        motifs = rows
+    elif not isinstance(motifs, (list, tuple)):
+        raise ValueError(f"forbidden_motifs must be a list of token tuples or an int tensor [n, Lm]; got {type(motifs).__name__}")
+    out, bad = [], {int(t) for t in special}
+    for m in motifs:
+        if torch.is_tensor(m):
+            m = m.detach().cpu().tolist()
+        if not isinstance(m, (list, tuple)) or any(isinstance(t, (float, bool, str)) for t in m):
+            raise ValueError(f"forbidden_motifs: a motif is a sequence of integer tokens; got {m!r}")
+        m = tuple(int(t) for t in m)
+        if not MOTIF_MIN_LEN <= len(m) <= MOTIF_MAX_LEN:
+            raise ValueError(f"forbidden_motifs: a motif has {MOTIF_MIN_LEN}..{MOTIF_MAX_LEN} tokens; got {len(m)} in {m}")
+        if any(not 0 <= t < min(V, 62) for t in m):
+            raise ValueError(f"forbidden_motifs: tokens must lie in [0, {min(V, 62)}); got {m}")
+        if any(t in bad for t in m):
+            raise ValueError(f"forbidden_motifs: {m} holds a special token (never drawn; PAD stands for 'not decoded yet')")
+        out.append(m)
+    if len(out) > MOTIF_MAX_COUNT:
+        raise ValueError(f"forbidden_motifs: {len(out)} motifs; at most {MOTIF_MAX_COUNT}")
+    return out
+
+
+def motif_adjacency(chain_labels, R_idx, mask):
+    """[B, L - 1] bool on the inputs' device: residues i and i + 1 are consecutive on one chain (same chain_labels, R_idx one apart:
+    the adjacency of cli.make_pair_terms) and both present (mask)."""
+    m = mask != 0
+    return ((R_idx[:, 1:] - R_idx[:, :-1]) == 1) & (chain_labels[:, 1:] == chain_labels[:, :-1]) & m[:, 1:] & m[:, :-1]
+
+
+def motif_windows(chain_labels, R_idx, mask, half_width):
+    """The windows of the motif section: int32 [B, L, 2 * half_width], the residue at chain offset -half_width .. -1, +1 .. +half_width of
+    every residue, -1 where the run of consecutive present residues (motif_adjacency) ends before it."""
+    B, L = mask.shape
+    hw = int(half_width)
+    adj = motif_adjacency(chain_labels, R_idx, mask)
+    win = torch.full((B, L, 2 * hw), -1, dtype=torch.int32, device=mask.device)
+    ar = torch.arange(L, dtype=torch.int32, device=mask.device)
+    reach = torch.ones(B, L, dtype=torch.bool, device=mask.device)            # reach[i]: i .. i + k are consecutive
+    for k in range(1, hw + 1):
+        if k >= L:
+            break
+        reach = reach[:, :L - k] & adj[:, k - 1:]
+        win[:, :L - k, hw + k - 1] = torch.where(reach, ar[k:], -1)            # i -> i + k
+        win[:, k:, hw - k] = torch.where(reach, ar[:L - k], -1)                # i + k -> i
+    return win
+
+
+def motif_entries(motifs):
+    """The packed entries of the motif section: int32 [n_entries, 6] = (pattern[3], mask[3]), one per motif and alignment k (the member
+    at position k of the motif).  A window is 15 slots of 6 bits, slot 7 the member, slot 7 + o its chain neighbour at offset o, slot s
+    at bit 6 * (s % 5) of word s // 5; token m_q sits in slot 7 - k + q as m_q + 1."""
+    rows = []
+    for m in motifs:
+        for k in range(len(m)):
+            pat, msk = [0, 0, 0], [0, 0, 0]
+            for q, t in enumerate(m):
+                s = 7 - k + q
+                pat[s // 5] |= (int(t) + 1) << (6 * (s % 5))
+                msk[s // 5] |= 0x3f << (6 * (s % 5))
+            rows.append(pat + msk)
+    return torch.tensor(rows, dtype=torch.int32).view(-1, 6)
+
+
+def motif_hits(S, adj, motifs):
+    """Occurrences of the motifs in S [R, L] (adj [R, L - 1] bool: motif_adjacency, a row per row of S) -> int64 [R], with stock torch ops
+    on the device of S."""
+    R, L = S.shape
+    hits = torch.zeros(R, dtype=torch.int64, device=S.device)
+    for m in motifs:
+        n = len(m)
+        if n > L:
+            continue
+        ok = torch.ones(R, L - n + 1, dtype=torch.bool, device=S.device)
+        for q, t in enumerate(m):
+            ok &= S[:, q:L - n + 1 + q] == t
+        for q in range(n - 1):
+            ok &= adj[:, q:L - n + 1 + q]
+        hits += ok.sum(1)
+    return hits
+
+
 MUT_MAX_EDITS = 8     # NAMP_MUT_MAX_EDITS of include/namp.h: residues per site of score_mutations()
 
 # A scan on the per-site cones as ProteinMPNN._cone_scan drives it: the family riding on namp_decoder_fwd; the carrier's N, K; what
@@ -816,33 +918,74 @@ class ProteinMPNN(nn.Module):
             raise ValueError("pair_terms and pair_bias are two forms of one quantity: give one of them")
         return pair_terms_arguments(fd["pair_terms"], B, L, self.num_letters)
 
-    def _pair_terms_section(self, pt, B, B_dec, N, K, dev, counted=None):
-        """The sampler's workspace with the pair-terms INPUT SECTION (include/namp.h) filled: ONE pinned copy — to be enqueued before the
-        encoder's launches, a host-to-device copy waits for the stream —, then the slots of every residue sorted by partner on the device.
-        N > L (tied states: the flattened graph of N = M * L residues): the rows go to state 0's copies, every other copy has no slot.
+    def _motifs_of(self, fd, B, L, tied):
+        """feature_dict["forbidden_motifs"] checked (forbidden_motifs_arguments) with what the section needs, built on the CPU (one
+        read of chain_labels / R_idx / mask): {"motifs", "hw": the windows' half width, "window" int32 [B, L, 2 hw], "entries" int32
+        [n, 6], "adj": motif_adjacency on the device, for motif_hits}; None without the key or with no motif."""
+        if fd.get("forbidden_motifs") is None:
+            return None
+        special = [int(self.restype_to_int[name]) for name in ("UNK", "DX", "RX", "MAS", "PAD")]
+        motifs = forbidden_motifs_arguments(fd["forbidden_motifs"], self.num_letters, special, B, tied, "pair_bias" in fd)
+        if not motifs:
+            return None
+        if min(self.k_neighbors, L) > 128:
+            raise ValueError(f"forbidden_motifs need k_neighbors <= 128 (the sampler's form for K = {min(self.k_neighbors, L)} carries no motif code)")
+        hw = max(len(m) for m in motifs) - 1
+        cl, ri, mk = fd["chain_labels"], fd["R_idx"], fd["mask"]
+        return {"motifs": motifs, "hw": hw, "window": motif_windows(cl.detach().cpu(), ri.detach().cpu(), mk.detach().cpu(), hw),
+                "entries": motif_entries(motifs), "adj": motif_adjacency(cl, ri, mk)}
+
+    def _pair_terms_section(self, pt, B, B_dec, N, K, dev, counted=None, motifs=None):
+        """The sampler's workspace with the INPUT SECTION of the pair terms and / or the forbidden motifs (include/namp.h) filled: ONE
+        pinned copy — to be enqueued before the encoder's launches, a host-to-device copy waits for the stream —, then the slots of every
+        residue sorted by partner on the device.  pt: pair_terms_arguments' tuple or None; motifs: _motifs_of's dict or None.
+        N > L (tied states: the flattened graph of N = M * L residues): the rows go to state 0's copies, every other copy has no slot
+        and an empty window.
         counted (bool per residue, optional): residues whose terms count; the others lose their slots.
-        -> {"ws", "dep": the section's partner block [B * N * D] int32 — namp_sample_levels_dep's dep_idx —, "D", "n_tables", "members"}."""
-        partner, table, tables, members = pt
-        Lb, n_dec = hip.lib(), len(self.decoder_layers)
-        L, D, n_tab, G = partner.shape[1], partner.shape[2], tables.shape[0], B * N
-        need = Lb.namp_sample_pair_terms_workspace_bytes(B, B_dec, N, K, n_dec, D, n_tab)
+        -> {"ws", "dep": [B * N * n_dep] int32 — namp_sample_levels_dep's dep_idx: the partners and the window of every residue side by
+        side —, "n_dep", "D", "n_tables", "members", "motifs": (n_entries, half_width) or None}."""
+        Lb, n_dec, V, G = hip.lib(), len(self.decoder_layers), self.num_letters, B * N
+        D = n_tab = members = n_pt = 0
+        if pt is not None:
+            partner, table, tables, members = pt
+            L, D, n_tab = partner.shape[1], partner.shape[2], tables.shape[0]
+            n_pt = 2 * G * D + tables.numel()
         off = Lb.namp_sample_pair_terms_offset(B, B_dec, N, K, n_dec)
+        if motifs is None:
+            need, words = Lb.namp_sample_pair_terms_workspace_bytes(B, B_dec, N, K, n_dec, D, n_tab), n_pt
+        else:
+            hw, W, E = motifs["hw"], 2 * motifs["hw"], motifs["entries"].shape[0]
+            need = Lb.namp_sample_motifs_workspace_bytes(B, B_dec, N, K, n_dec, D, n_tab, E, hw)
+            w0 = (Lb.namp_sample_motifs_offset(B, B_dec, N, K, n_dec, D, n_tab, V) - off) // 4
+            e0 = w0 + G * W
+            words = e0 + 6 * E
         if need == 0:
-            raise ValueError(f"pair_terms: no sampler workspace for B={B} batch={B_dec} N={N} K={K} D={D} n_tables={n_tab}")
-        host = torch.empty(2 * G * D + tables.numel(), dtype=torch.int32, pin_memory=True)
-        p, t = host[:G * D].view(B, N, D), host[G * D:2 * G * D].view(B, N, D)
-        p.fill_(-1); t.zero_()
-        p[:, :L], t[:, :L] = torch.where(partner < L, partner, torch.full_like(partner, -1)), table
-        if counted is not None:
-            p[:, :L][:, ~torch.as_tensor(counted, dtype=torch.bool)] = -1
-        host[2 * G * D:] = tables.view(-1).view(torch.int32)
+            raise ValueError(f"pair_terms / forbidden_motifs: no sampler workspace for B={B} batch={B_dec} N={N} K={K} D={D} n_tables={n_tab}")
+        host = torch.empty(words, dtype=torch.int32, pin_memory=True)
+        if pt is not None:
+            p, t = host[:G * D].view(B, N, D), host[G * D:2 * G * D].view(B, N, D)
+            p.fill_(-1); t.zero_()
+            p[:, :L], t[:, :L] = torch.where(partner < L, partner, torch.full_like(partner, -1)), table
+            if counted is not None:
+                p[:, :L][:, ~torch.as_tensor(counted, dtype=torch.bool)] = -1
+            host[2 * G * D:n_pt] = tables.view(-1).view(torch.int32)
+        if motifs is not None:
+            host[w0:e0] = -1
+            host[w0:e0].view(B, N, W)[:, :motifs["window"].shape[1]] = motifs["window"]
+            host[e0:] = motifs["entries"].reshape(-1)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         sec = ws[off:off + 4 * host.numel()].view(torch.int32)
         sec.copy_(host, non_blocking=True)
-        pd, td = sec[:G * D].view(B, N, D), sec[G * D:2 * G * D].view(B, N, D)
-        ps, ts = sort_pair_slots(pd, td)
-        pd.copy_(ps); td.copy_(ts)
-        return {"ws": ws, "dep": sec[:G * D], "D": D, "n_tables": n_tab, "members": members}
+        dep, n_dep = sec[:G * D], D
+        if pt is not None:
+            pd, td = sec[:G * D].view(B, N, D), sec[G * D:2 * G * D].view(B, N, D)
+            ps, ts = sort_pair_slots(pd, td)
+            pd.copy_(ps); td.copy_(ts)
+        if motifs is not None:
+            wd = sec[w0:e0]
+            dep, n_dep = (wd if pt is None else torch.cat((pd, wd.view(B, N, W)), 2).reshape(-1)), D + W
+        return {"ws": ws, "dep": dep, "n_dep": n_dep, "D": D, "n_tables": n_tab, "members": members,
+                "motifs": None if motifs is None else (E, hw)}
 
     def _as(self, t, kind):
         """`t` in the dtype / layout the kernels read ("i32": int32, "f32": float32; contiguous), converted ONCE per tensor object: a
@@ -2599,6 +2742,11 @@ class ProteinMPNN(nn.Module):
         ``pair_bias``) as one persistent HIP launch.  ``feature_dict["pair_terms"]`` is the compact form of ``pair_bias`` —
         {"partner", "table": int [B, L, D], "tables": float [n, V, V], "members": "closing" | "all"}, see pair_terms_arguments — and,
         unlike the dense tensor, goes with every tie (symmetry_residues, paired_residues, paired_wobble, state_weights).
+        ``feature_dict["forbidden_motifs"]`` — a list of token tuples, or an int tensor [n, Lm] padded with -1; lengths 2..8, at most 63 —
+        are motifs no draw may complete on consecutive present residues of one chain (with every tie and with
+        ``pair_terms``, not with the dense ``pair_bias`` and not with k_neighbors > 128): a candidate that would complete one on any
+        member of the drawing group gets p = 0 in ``sampling_probs``, a ban that would leave nothing is skipped, and ``motif_hits``
+        int64 [batch] — returned with the key — counts the occurrences left in ``S``.
         With ``state_weights`` one sequence is tied across backbone states, with ``state_S`` / ``state_mask`` beside it the states also
         differ in their fixed tokens and in which residues they have (_sample_states).
         The categorical draw uses torch.rand on the device (seed with torch.manual_seed) through an inverse
@@ -2627,9 +2775,10 @@ class ProteinMPNN(nn.Module):
         self._check_tokens(S_true)
         if fd.get("S_forced") is not None:
             self._check_tokens(fd["S_forced"], "S_forced")
-        if pterms is not None:                                                    # (its one copy goes up before anything is enqueued)
+        motifs = self._motifs_of(fd, B, L, symmetric)
+        if pterms is not None or motifs is not None:                              # (its one copy goes up before anything is enqueued)
             _require_device(fd["X"], "X")
-            pterms = self._pair_terms_section(pterms, B, B * bs, L, int(min(self.k_neighbors, L)), dev)
+            pterms = self._pair_terms_section(pterms, B, B * bs, L, int(min(self.k_neighbors, L)), dev, motifs=motifs)
         o = self._decoding_order(mask, fd["chain_mask"], fd["randn"])               # [max(B, bs), L]; sorted by the featuriser launch
         order, rank = o.order, o.rank
         V, _, h_E, E_idx = self._featurize_hip(fd, want_E=False, want_hE=True, order=o)   # (E_idx stays int32: the kernels' dtype)
@@ -2637,7 +2786,7 @@ class ProteinMPNN(nn.Module):
         B_dec = B * bs
         dims, Lb = (B_dec, B, L, K), hip.lib()
         # (dep_idx, n_dep) of the levels beside the graph's — the pair terms section's partner block IS one; None: the sequential walk
-        deps = (None, 0) if pterms is None else (pterms["dep"], pterms["D"])
+        deps = (None, 0) if pterms is None else (pterms["dep"], pterms["n_dep"])
         on_device = (self.sample_level_parallel and walk and o.order32 is not None and order.shape[0] == B_dec
                      and E_idx.dtype == torch.int32 and E_idx.is_contiguous())
         plan = start = None
@@ -2702,6 +2851,8 @@ class ProteinMPNN(nn.Module):
             out["levels"] = levels
         if walk:
             out["work_items"] = plan.nwork
+        if motifs is not None:                                                 # (stream r samples complex r % B)
+            out["motif_hits"] = motif_hits(out["S"], motifs["adj"].repeat(bs, 1), motifs["motifs"])
         return out
 
     # build the plan of a design whose groups are all base pairs on the device (sampling.pairs_plan: namp_pairs_plan,
@@ -2806,18 +2957,22 @@ class ProteinMPNN(nn.Module):
         S_true, mask = fd["S"], fd["mask"]
         dev, N, Vn = S_true.device, M * L, self.num_letters
         pterms = self._pair_terms_of(fd, 1, L)
+        # (the windows sit on state 0's copies only, as the pair terms' rows do: a residue counts once)
+        motifs = self._motifs_of(fd, 1, L, True)
         _require_device(fd["X"], "X")
+        counted = None
         if pterms is not None:
             # The rows sit on state 0's copies only — a residue counts once, not M times —, so the kernel counts EVERY member of a group
             # (its closing member is a copy of the last state, which has no slots); under "closing" the residues that do not close their
             # group lose their slots instead.  One copy, before anything is enqueued.
-            counted = None
             if pterms[3] == 0 and symmetric:
                 counted = [True] * L
                 for g in sym_groups:
                     for r in list(g)[:-1]:
                         counted[int(r)] = False
-            pterms = self._pair_terms_section(pterms[:3] + (1,), 1, bs, N, int(min(self.k_neighbors, L)), dev, counted)
+            pterms = pterms[:3] + (1,)
+        if pterms is not None or motifs is not None:
+            pterms = self._pair_terms_section(pterms, 1, bs, N, int(min(self.k_neighbors, L)), dev, counted, motifs=motifs)
         self._check_tokens(S_true)
         if fd.get("S_forced") is not None:
             self._check_tokens(fd["S_forced"], "S_forced")
@@ -2849,7 +3004,7 @@ class ProteinMPNN(nn.Module):
                 if i not in tied:
                     groups.append([i + m * L for m in range(M)]); weights.append(list(w))
             E_f = _i32(E_idx + (torch.arange(M, dtype=torch.int32, device=dev) * L)[:, None, None]).view(N, K)
-            plan = sampling.host_plan(self, groups, weights, o.order, o.rank, E_f, dims, (None, 0) if pterms is None else (pterms["dep"], pterms["D"]),
+            plan = sampling.host_plan(self, groups, weights, o.order, o.rank, E_f, dims, (None, 0) if pterms is None else (pterms["dep"], pterms["n_dep"]),
                                       walk, split=bool(walk and self.sample_split_groups), steps=True)
         if uniform is None:
             uniform = torch.rand(bs, L, device=dev)
@@ -2885,6 +3040,8 @@ class ProteinMPNN(nn.Module):
         if ctx is not None:                                                    # (an absent copy scores nothing: its rows are zeros)
             out["log_probs"] = logp.view(bs, N, Vn).masked_fill(absent[None, :, None], 0.0).view(bs, M, L, Vn)
             out["S_states"] = S_out.view(bs, M, L).long()
+        if motifs is not None:
+            out["motif_hits"] = motif_hits(out["S"], motifs["adj"].expand(bs, -1), motifs["motifs"])
         return out
 
     def sample_walk_status(self):

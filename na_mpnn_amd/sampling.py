@@ -241,7 +241,7 @@ def launch(model, plan, arrays, maps, pterms, temperature, dims, walk):
     """One sampler call: namp_decoder_sample (a plan without work lists: the sequential walk), namp_decoder_sample_walk (`walk`: one persistent
     launch walking the levels, nothing read back, the call returns with the whole design enqueued) or namp_decoder_sample_levels (one launch per
     level; counting them is its one host sync).  maps = (tok_maps, n_maps, classes) as _attach_maps takes them and pterms (the dict of
-    _pair_terms_section, whose workspace the call then uses; or None) are attached to THIS call of the thread.  dims = (B_dec, B_enc, n, K).
+    _pair_terms_section — pair terms, forbidden motifs or both —, whose workspace the call then uses; or None) are attached to THIS call of the thread.  dims = (B_dec, B_enc, n, K).
     -> (S int32 [B_dec, n], sampling_probs, log_probs [B_dec, n, V], levels: None, the plan's device scalar or the count of launches), code: the
     walk's barrier status (its words are left in model._walk_sync) if model.sample_check_walk, else 0; non-zero: decode again with walk=False."""
     (B_dec, B_enc, n, K), Lb, dev, V, a = dims, hip.lib(), plan.E.device, model.num_letters, arrays
@@ -259,8 +259,10 @@ def launch(model, plan, arrays, maps, pterms, temperature, dims, walk):
     tail = (float(temperature), special, S_out.data_ptr(), probs.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
             B_dec, B_enc, n, K, hip.current_stream())
     model._attach_maps(*maps)
-    if pterms is not None:
+    if pterms is not None and pterms["D"]:
         hip.check(Lb.namp_sample_pair_terms(pterms["D"], pterms["n_tables"], pterms["members"]), "sample_pair_terms")
+    if pterms is not None and pterms["motifs"] is not None:
+        hip.check(Lb.namp_sample_motifs(*pterms["motifs"]), "sample_motifs")
     levels, code = plan.levels, 0
     if plan.work is None:
         hip.check(Lb.namp_decoder_sample(*common, *tail), "decoder_sample")     # (no host sync: temporaries are stream-ordered, see _featurize_hip)

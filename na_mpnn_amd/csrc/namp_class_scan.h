@@ -1,8 +1,8 @@
 // Class scan (namp_class_mutations, include/namp.h): the group scan of namp_group_scan.h with the combine of the tied
 // score (tied_combine_kernel, namp_tied.h) — the members of a unit speak through CLASS TABLES, so a unit may be a base pair, a wobble
 // pair, a group with token maps or a pair joined with symmetry groups.  Everything in front of the units is the group scan's as it
-// stands: the tied base stream of S, the plan on the keys, gmut_items_kernel (a member's token comes from the variant through
-// mut_token; edge kinds do not depend on tables), the whole-row head.  What is new is the combine.  With row_t the member's log_softmax
+// stands: the tied base stream of S, the plan on the keys, the items with edge kinds (a member's token comes from the variant through
+// mut_token; edge kinds do not depend on tables), the whole-row head, the unit kernels.  What is new is their Combine.  With row_t the member's log_softmax
 // row (the variant's where it has one in U_3(site), else the base row), C_t its table and b the bias of the LAST listed member's table,
 //   total[c] = sum over the members t, listed order, of weight_t * row_t[C_t[c]]  +  b[c]     (classes c < n_classes every member has
 //              a token for, else -inf; every product and sum rounded once, from 0)
@@ -58,66 +58,13 @@ __device__ __forceinline__ float class_unit_row(const MutPlanArgs& a, const Grou
   return m2 + logf(tied_wave_sum(x > -INFINITY ? expf(x - m2) : 0.f));
 }
 
-// one wave per residue; the wave of a unit's listed-first member combines the base rows under S and stores the unit at every member's
-// slot (an ungrouped residue: its own entry at its own slot)
-static __global__ __launch_bounds__(256) void class_base_unit_kernel(const MutPlanArgs a, const GroupScanArgs g, const ClassScanArgs c,
-                                                                      const float* __restrict__ base_lp) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= a.N) return;                                       // (wave-uniform)
-  const bool grouped = g.gl[i] >= 0;
-  if (grouped && g.gl[i] != i) return;                        // (wave-uniform)
-  const float unit = class_unit_row(a, g, c, base_lp, i, grouped, lane, [](int) -> const float* { return nullptr; },
-                                    [&](const int j) -> int { return a.S[j]; });
-  int cur = i;
-  for (int step = 0; step < NAMP_LOO_GROUP_MAX; ++step) {
-    if (lane == 0) g.base_unit[cur] = unit;
-    if (!grouped) break;
-    cur = loo_clamp(g.next[cur], a.N);
-    if (cur == i) break;
+// the Combine of group_unit_kernel / group_base_unit_kernel (namp_group_scan.h) for the class scan: class_unit_row (`own` is not read:
+// every member's token goes through its table)
+struct ClassCombine {
+  ClassScanArgs c;
+  template <class VarRow, class TokOf>
+  __device__ __forceinline__ float unit(const MutPlanArgs& a, const GroupScanArgs& g, const float* __restrict__ base_lp, const int first,
+                                        const bool grouped, const int lane, const int, VarRow var_row, TokOf tok_of) const {
+    return class_unit_row(a, g, c, base_lp, first, grouped, lane, var_row, tok_of);
   }
-}
-
-// one wave per layer-3 item row: the leader rule and the stores of group_unit_kernel, the units through class_unit_row
-static __global__ __launch_bounds__(256) void class_unit_kernel(const MutPlanArgs a, const StateScanArgs s, const GroupScanArgs g,
-                                                                 const ClassScanArgs c) {
-  const int lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= a.icap[2]) return;                                 // (wave-uniform)
-  const int32_t* io = a.ioff[2];
-  bool lead = a.n_var > 0 && r < io[a.n_var];
-  const int v = lead ? mut_variant_of(io, a.n_var, (int)r) : 0;
-  const int site = a.n_var > 0 ? mut_site_of(a, v) : 0;
-  const int b = a.n_var > 0 ? a.loff[2][site] : 0, e = a.n_var > 0 ? a.loff[2][site + 1] : 0;
-  const int row0 = a.n_var > 0 ? io[v] : 0, row1 = a.n_var > 0 ? io[v + 1] : 0;
-  const int f = loo_clamp(s.ctr[r], a.N);
-  const bool grouped = g.gl[f] >= 0;
-  const int first = grouped ? loo_clamp(g.gl[f], a.N) : f;
-  auto var_row = [&](const int j) -> const float* {
-    const int p = mut_find(a.list[2], b, e, j);
-    const int row = row0 + (p - b);
-    return (p >= 0 && row < row1) ? s.rows + (long)row * 64 : nullptr;
-  };
-  lead = lead && a.mask[f] != 0;
-  if (grouped) {
-    int cur = first;
-    for (int step = 0; step < NAMP_LOO_GROUP_MAX; ++step) {
-      if (cur == f) break;
-      if (var_row(cur) != nullptr) lead = false;
-      cur = loo_clamp(g.next[cur], a.N);
-    }
-  }
-  if (!lead) {                                                // (wave-uniform)
-    if (lane == 0) { s.term[r] = 0.f; s.unit_res[r] = -1; s.unit_lp[r] = 0.f; }
-    return;
-  }
-  const float unit_v = class_unit_row(a, g, c, s.base_lp, first, grouped, lane, var_row,
-                                      [&](const int j) -> int { return a.n_var > 0 ? mut_token(a, v, site, j) : a.S[j]; });
-  const float unit_b = class_unit_row(a, g, c, s.base_lp, first, grouped, lane, [](int) -> const float* { return nullptr; },
-                                      [&](const int j) -> int { return a.S[j]; });
-  if (lane == 0) {
-    s.term[r] = __fmul_rn(a.w[first], __fsub_rn(unit_v, unit_b));
-    s.unit_res[r] = first;
-    s.unit_lp[r] = unit_v;
-  }
-}
+};

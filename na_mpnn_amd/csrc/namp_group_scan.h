@@ -3,15 +3,16 @@
 // The base stream is the tied stream of S run as items over all N residues (tied_item_stream at n_chunk = 1) with every layer's
 // tables kept: centres, rows projected with the token at j and without it at N + j of ONE table, Pfw, states, log_softmax rows.  The
 // plan is that of namp_mutations.h, unchanged, with the KEYS of tied_keys_kernel as its ranks: "key(j) < key(i) and (j in the site or
-// level(j) < l)" — a hidden-backward edge counts like a backward one, a superset of the rows that can differ.  gmut_items_kernel is
-// mut_items_kernel with edge kinds: for key(j) < key(i)
+// level(j) < l)" — a hidden-backward edge counts like a backward one, a superset of the rows that can differ.  The items are
+// mut_items_kernel's with the edge kinds of GroupScanArgs: for key(j) < key(i)
 //   backward (leader[j] != leader[i])   the variant's with-token row (LOO_OV | r) if j has one in U_{l-1}(site), else base row j
 //   hidden, layer 1                     Pfw_1[j]                    (the encoder state: no token, the same in every variant)
 //   hidden, layers 2 and 3              the variant's without-token row (LOO_OV | R_{l-1} + r), else base row N + j
 // so dec_items_kernel (namp_loo.h, unchanged) reads five sources through its three tables.  Behind layer 3 state_head_kernel keeps the
-// whole row; group_unit_kernel combines the members of a unit in listed order through group_unit_row — the one device function the
-// base units come from too, every product and sum rounded once — and state_delta_kernel sums the leader terms.  Plain stores, one
-// wave owns a row, bounded loops, every index read from a section or a table is clamped.
+// whole row; group_unit_kernel combines the members of a unit in listed order through its Combine — GroupCombine here (group_unit_row),
+// ClassCombine in namp_class_scan.h: the one device function the base units come from too, every product and sum rounded once — and
+// state_delta_kernel sums the leader terms.  Plain stores, one wave owns a row, bounded loops, every index read from a section or a
+// table is clamped.
 #pragma once
 #include "namp_state_scan.h"
 #include "namp_tied.h"
@@ -23,49 +24,15 @@ struct GroupScanArgs {
   const uint32_t* key;      // [N] tied_keys_kernel
   const int32_t* leader;    // [N] tied_keys_kernel: the listed-first member of the residue's unit
   float* base_unit;         // [N] output section: the unit of S at every member
-};
 
-// the index tables of layer l's items: mut_items_kernel with edge kinds (a.rank holds the keys); one thread per (item row, edge)
-static __global__ __launch_bounds__(256) void gmut_items_kernel(const MutPlanArgs a, const GroupScanArgs g, const MutItemTables t, const int l) {
-  const long R = mut_pick(a.icap, l);
-  const long u = (long)blockIdx.x * 256 + threadIdx.x;
-  if (u >= R * a.K) return;
-  const int r = (int)(u / a.K);
-  const int e = (int)(u - (long)r * a.K);
-  const int32_t* io = mut_pick(a.ioff, l);
-  const bool on = a.n_var > 0 && r < io[a.n_var];
-  const int v = on ? mut_variant_of(io, a.n_var, r) : 0;
-  const int site = a.n_var > 0 ? mut_site_of(a, v) : 0;
-  const int i = on ? loo_clamp(mut_pick(a.list, l)[mut_pick(a.loff, l)[site] + (r - io[v])], a.N) : 0;
-  const int Rprev = l ? mut_pick(a.icap, l - 1) : 0;
-  auto prev_row = [&](const int j) -> int {                      // (mut_items_kernel's)
-    if (!on) return -1;
-    if (l == 0) { const int q = mut_edit(a, site, j); return q >= 0 ? v * MUT_E + q : -1; }
-    const int32_t* lo = mut_pick(a.loff, l - 1);
-    const int32_t* po = mut_pick(a.ioff, l - 1);
-    const int p = mut_find(mut_pick(a.list, l - 1), lo[site], lo[site + 1], j);
-    if (p < 0) return -1;
-    const int row = po[v] + (p - lo[site]);
-    return row < po[v + 1] ? row : -1;
-  };
-  const int j = loo_clamp(a.E_idx[(long)i * a.K + e], a.N);
-  int code = LOO_FW | j;
-  if (g.key[j] < g.key[i]) {
-    const bool hid = g.leader[j] == g.leader[i];
-    const int pj = prev_row(j);
-    if (l == 0) code = hid ? (LOO_FW | j) : (pj >= 0 ? (LOO_OV | pj) : j);
-    else code = pj >= 0 ? (LOO_OV | (hid ? Rprev + pj : pj)) : (hid ? a.N + j : j);
+  // mut_items_kernel's Edges: j lies behind i by its key; the code by the edge's kind (pj: j's row in U_{l-1}(site), or -1)
+  __device__ __forceinline__ bool behind(const MutPlanArgs&, const int j, const int i) const { return key[j] < key[i]; }
+  __device__ __forceinline__ int code(const MutPlanArgs& a, const int l, const int j, const int i, const int pj) const {
+    const bool hid = leader[j] == leader[i];
+    if (l == 0) return hid ? (LOO_FW | j) : (pj >= 0 ? (LOO_OV | pj) : j);
+    return pj >= 0 ? (LOO_OV | (hid ? mut_pick(a.icap, l - 1) + pj : pj)) : (hid ? a.N + j : j);
   }
-  t.esrc[u] = code;
-  if (e == 0) {
-    const int pi = l ? prev_row(i) : -1;
-    t.act[r] = on ? 1 : 0;
-    t.ctr[r] = i;
-    t.cen[r] = pi >= 0 ? (LOO_CEN_OV | pi) : i;
-    t.msk[r] = a.mask[i];
-    t.tok[r] = on ? mut_token(a, v, site, i) : a.S[i];
-  }
-}
+};
 
 // one wave per residue: the base stream's log_softmax row from its layer-3 state (state_head_kernel's arithmetic)
 static __global__ __launch_bounds__(256) void group_base_head_kernel(const float* __restrict__ h3, const float* __restrict__ head_w,
@@ -74,7 +41,7 @@ static __global__ __launch_bounds__(256) void group_base_head_kernel(const float
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= N) return;                                         // (wave-uniform)
-  const float lp = state_head_row(h3 + r * NAMP_H, head_w, head_b, vocab, lane);
+  const float lp = mut_head_row(h3 + r * NAMP_H, head_w, head_b, vocab, lane);
   if (lane < vocab) log_probs[r * vocab + lane] = lp;
 }
 
@@ -99,26 +66,32 @@ __device__ __forceinline__ float group_unit_row(const MutPlanArgs& a, const Grou
     cur = loo_clamp(g.next[cur], a.N);
     if (cur == first) break;
   }
-  if (lane >= a.vocab) z = -INFINITY;
-  float mx = z;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  float ex = (lane < a.vocab) ? expf(z - mx) : 0.f;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) ex += __shfl_xor(ex, o);
-  return (z - mx) - logf(ex);
+  return mut_wave_log_softmax(lane < a.vocab ? z : -INFINITY, lane < a.vocab);
 }
 
-// one wave per residue; the wave of a unit's listed-first member combines the base rows and stores the unit, at the token of that
-// member, at every member's slot (an ungrouped residue: its own entry at its own slot)
-static __global__ __launch_bounds__(256) void group_base_unit_kernel(const MutPlanArgs a, const GroupScanArgs g, const float* __restrict__ base_lp) {
+// A Combine gives the value of the unit whose listed-first member is `first`, the same in every lane: unit(a, g, base_lp, first, grouped,
+// lane, own, var_row, tok_of) with var_row(j) as above, tok_of(j) the token of member j and `own` the token that picks the entry where
+// the members speak without tables.  The symmetric scan's: the entry of group_unit_row at `own` (identity maps: one token per unit)
+struct GroupCombine {
+  template <class VarRow, class TokOf>
+  __device__ __forceinline__ float unit(const MutPlanArgs& a, const GroupScanArgs& g, const float* __restrict__ base_lp, const int first,
+                                        const bool grouped, const int lane, const int own, VarRow var_row, TokOf) const {
+    return __shfl(group_unit_row(a, g, base_lp, first, grouped, lane, var_row), loo_clamp(own, a.vocab));
+  }
+};
+
+// one wave per residue; the wave of a unit's listed-first member combines the base rows under S and stores the unit, at the token of
+// that member, at every member's slot (an ungrouped residue: its own entry at its own slot)
+template <class Combine>
+static __global__ __launch_bounds__(256) void group_base_unit_kernel(const MutPlanArgs a, const GroupScanArgs g, const Combine c,
+                                                                      const float* __restrict__ base_lp) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= a.N) return;                                       // (wave-uniform)
   const bool grouped = g.gl[i] >= 0;
   if (grouped && g.gl[i] != i) return;                        // (wave-uniform)
-  const float row = group_unit_row(a, g, base_lp, i, grouped, lane, [](int) -> const float* { return nullptr; });
-  const float unit = __shfl(row, loo_clamp(a.S[i], a.vocab));
+  const float unit = c.unit(a, g, base_lp, i, grouped, lane, a.S[i], [](int) -> const float* { return nullptr; },
+                            [&](const int j) -> int { return a.S[j]; });
   int cur = i;
   for (int step = 0; step < NAMP_LOO_GROUP_MAX; ++step) {
     if (lane == 0) g.base_unit[cur] = unit;
@@ -132,7 +105,8 @@ static __global__ __launch_bounds__(256) void group_base_unit_kernel(const MutPl
 // row in the site's list_3 segment within the variant's capacity.  The leader walks the cycle from the listed-first member, takes the
 // variant's row where the member has one, else the base row, and stores w * (unit_v - unit) at its row and the unit into the sparse
 // units (unit_res: the listed-first member); every other row stores 0 and -1
-static __global__ __launch_bounds__(256) void group_unit_kernel(const MutPlanArgs a, const StateScanArgs s, const GroupScanArgs g) {
+template <class Combine>
+static __global__ __launch_bounds__(256) void group_unit_kernel(const MutPlanArgs a, const StateScanArgs s, const GroupScanArgs g, const Combine c) {
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= a.icap[2]) return;                                 // (wave-uniform)
@@ -163,10 +137,10 @@ static __global__ __launch_bounds__(256) void group_unit_kernel(const MutPlanArg
     if (lane == 0) { s.term[r] = 0.f; s.unit_res[r] = -1; s.unit_lp[r] = 0.f; }
     return;
   }
-  const float uv = group_unit_row(a, g, s.base_lp, first, grouped, lane, var_row);
-  const float ub = group_unit_row(a, g, s.base_lp, first, grouped, lane, [](int) -> const float* { return nullptr; });
-  const float unit_v = __shfl(uv, loo_clamp(s.tok[r], a.vocab));
-  const float unit_b = __shfl(ub, loo_clamp(a.S[first], a.vocab));
+  const float unit_v = c.unit(a, g, s.base_lp, first, grouped, lane, s.tok[r], var_row,
+                              [&](const int j) -> int { return a.n_var > 0 ? mut_token(a, v, site, j) : a.S[j]; });
+  const float unit_b = c.unit(a, g, s.base_lp, first, grouped, lane, a.S[first], [](int) -> const float* { return nullptr; },
+                              [&](const int j) -> int { return a.S[j]; });
   if (lane == 0) {
     s.term[r] = __fmul_rn(a.w[first], __fsub_rn(unit_v, unit_b));
     s.unit_res[r] = first;

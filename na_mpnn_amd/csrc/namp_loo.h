@@ -64,6 +64,19 @@ struct LooPrepArgs {
 
 __device__ __forceinline__ int loo_clamp(const int v, const int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
+// the wave's max / sum in every lane: one butterfly order (o = 1, 2, .. 32) for the tied score and every scan; all 64 lanes take part
+__device__ __forceinline__ float tied_wave_max(float v) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+__device__ __forceinline__ float tied_wave_sum(float v) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 // The caller's table is device data, a successor cycle in LISTED order (next[g] = local index of the member listed after g, the last
 // names the first) with first[g] = 1 on the listed-first member.  One thread per residue walks its cycle, at most NAMP_LOO_GROUP_MAX
 // steps.  g is grouped only if the walk returns to it, every successor on the way is inside [0, N), exactly one member carries

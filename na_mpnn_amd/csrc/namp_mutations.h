@@ -212,8 +212,19 @@ struct MutItemTables {
   int32_t* esrc;            // [R][K] edge codes
 };
 
-// the index tables of layer l's items (R = icap[l] rows, laid out by ioff_l); one thread per (item row, edge)
-static __global__ __launch_bounds__(256) void mut_items_kernel(const MutPlanArgs a, const MutItemTables t, const int l) {
+// the plain scan's edges: j lies behind i by its rank; a backward edge reads the variant's row of j where U_{l-1}(site) holds one (pj),
+// else base row j
+struct MutPlainEdges {
+  __device__ __forceinline__ bool behind(const MutPlanArgs& a, const int j, const int i) const { return a.rank[j] < a.rank[i]; }
+  __device__ __forceinline__ int code(const MutPlanArgs&, const int, const int j, const int, const int pj) const {
+    return pj >= 0 ? (LOO_OV | pj) : j;
+  }
+};
+
+// the index tables of layer l's items (R = icap[l] rows, laid out by ioff_l); one thread per (item row, edge).  Edges: which edges lie
+// behind their centre and the code of such an edge (MutPlainEdges; the group scan's kinds: GroupScanArgs, namp_group_scan.h)
+template <class Edges>
+static __global__ __launch_bounds__(256) void mut_items_kernel(const MutPlanArgs a, const Edges g, const MutItemTables t, const int l) {
   const long R = mut_pick(a.icap, l);
   const long u = (long)blockIdx.x * 256 + threadIdx.x;
   if (u >= R * a.K) return;
@@ -237,12 +248,7 @@ static __global__ __launch_bounds__(256) void mut_items_kernel(const MutPlanArgs
     return row < po[v + 1] ? row : -1;
   };
   const int j = loo_clamp(a.E_idx[(long)i * a.K + e], a.N);
-  int code = LOO_FW | j;
-  if (a.rank[j] < a.rank[i]) {
-    const int pj = prev_row(j);
-    code = pj >= 0 ? (LOO_OV | pj) : j;
-  }
-  t.esrc[u] = code;
+  t.esrc[u] = g.behind(a, j, i) ? g.code(a, l, j, i, prev_row(j)) : (LOO_FW | j);
   if (e == 0) {
     const int pi = l ? prev_row(i) : -1;                                     // (layer 1's input is the encoder state of every variant)
     t.act[r] = on ? 1 : 0;
@@ -253,8 +259,34 @@ static __global__ __launch_bounds__(256) void mut_items_kernel(const MutPlanArgs
   }
 }
 
-// one wave per layer-3 item row: log_softmax(W_out . h + b) of the item's state (lib_head_kernel's sums), of which the lane of the
-// variant's own token stores its entry at the item's row; lane 0 stores the residue.  A row outside every variant: residue -1, entry 0
+// lane = token: log_softmax of z over the lanes that are `on` (the others hold -inf).  The one copy every scan's head and combine goes
+// through; called by all 64 lanes of a wave, never under a branch that splits it
+__device__ __forceinline__ float mut_wave_log_softmax(const float z, const bool on) {
+  const float mx = tied_wave_max(z);
+  const float ex = tied_wave_sum(on ? expf(z - mx) : 0.f);
+  return (z - mx) - logf(ex);
+}
+
+// lane = token: log_softmax(W_out . y + b) of one state row y [128] (lib_head_kernel's sums); lanes >= vocab hold -inf
+__device__ __forceinline__ float mut_head_row(const float* __restrict__ y, const float* __restrict__ head_w, const float* __restrict__ head_b,
+                                              const int vocab, const int lane) {
+  float z = -INFINITY;
+  if (lane < vocab) {
+    const float* w = head_w + (long)lane * NAMP_H;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll 8
+    for (int c = 0; c < NAMP_H; c += 4) {
+      const f4 wv = *(const f4*)(w + c);
+      const f4 yv = *(const f4*)(y + c);
+      s0 = fmaf(wv.x, yv.x, s0); s1 = fmaf(wv.y, yv.y, s1); s2 = fmaf(wv.z, yv.z, s2); s3 = fmaf(wv.w, yv.w, s3);
+    }
+    z = (s0 + s1) + (s2 + s3) + head_b[lane];
+  }
+  return mut_wave_log_softmax(z, lane < vocab);
+}
+
+// one wave per layer-3 item row: the log_softmax row of the item's state, of which the lane of the variant's own token stores its entry
+// at the item's row; lane 0 stores the residue.  A row outside every variant: residue -1, entry 0
 static __global__ __launch_bounds__(256) void mut_head_kernel(const MutPlanArgs a, const int32_t* __restrict__ ctr, const int32_t* __restrict__ tok,
                                                                const float* __restrict__ h3, const float* __restrict__ head_w,
                                                                const float* __restrict__ head_b, int32_t* __restrict__ row_res,
@@ -266,26 +298,8 @@ static __global__ __launch_bounds__(256) void mut_head_kernel(const MutPlanArgs 
     if (lane == 0) { row_res[r] = -1; row_lp[r] = 0.f; }
     return;
   }
-  const float* y = h3 + r * NAMP_H;
-  float z = -INFINITY;
-  if (lane < a.vocab) {
-    const float* w = head_w + (long)lane * NAMP_H;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll 8
-    for (int c = 0; c < NAMP_H; c += 4) {
-      const f4 wv = *(const f4*)(w + c);
-      const f4 yv = *(const f4*)(y + c);
-      s0 = fmaf(wv.x, yv.x, s0); s1 = fmaf(wv.y, yv.y, s1); s2 = fmaf(wv.z, yv.z, s2); s3 = fmaf(wv.w, yv.w, s3);
-    }
-    z = (s0 + s1) + (s2 + s3) + head_b[lane];
-  }
-  float mx = z;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  float ex = (lane < a.vocab) ? expf(z - mx) : 0.f;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) ex += __shfl_xor(ex, o);
-  if (lane == loo_clamp(tok[r], a.vocab)) row_lp[r] = (z - mx) - logf(ex);
+  const float lp = mut_head_row(h3 + r * NAMP_H, head_w, head_b, a.vocab, lane);
+  if (lane == loo_clamp(tok[r], a.vocab)) row_lp[r] = lp;
   if (lane == 0) row_res[r] = ctr[r];
 }
 

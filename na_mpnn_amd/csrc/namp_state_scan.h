@@ -42,14 +42,7 @@ __device__ __forceinline__ float state_unit_row(const MutPlanArgs& a, const Stat
     const float u = solo ? (m == 0 ? 1.f : 0.f) : s.unit_w[j];
     if (solo ? m == 0 : a.mask[j] != 0) z = __fadd_rn(z, __fmul_rn(u, x));
   }
-  if (lane >= a.vocab) z = -INFINITY;
-  float mx = z;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  float ex = (lane < a.vocab) ? expf(z - mx) : 0.f;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) ex += __shfl_xor(ex, o);
-  return (z - mx) - logf(ex);
+  return mut_wave_log_softmax(lane < a.vocab ? z : -INFINITY, lane < a.vocab);
 }
 
 // one wave per shared residue: unit[i] of S from the base rows, at the token of the first present copy (none present: copy 0's)
@@ -65,31 +58,7 @@ static __global__ __launch_bounds__(256) void state_base_unit_kernel(const MutPl
   if (lane == tk) s.base_unit[i] = row;
 }
 
-// lane = token: log_softmax(W_out . y + b) of one state row y [128] (mut_head_kernel's sums); lanes >= vocab hold -inf
-__device__ __forceinline__ float state_head_row(const float* __restrict__ y, const float* __restrict__ head_w, const float* __restrict__ head_b,
-                                                const int vocab, const int lane) {
-  float z = -INFINITY;
-  if (lane < vocab) {
-    const float* w = head_w + (long)lane * NAMP_H;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll 8
-    for (int c = 0; c < NAMP_H; c += 4) {
-      const f4 wv = *(const f4*)(w + c);
-      const f4 yv = *(const f4*)(y + c);
-      s0 = fmaf(wv.x, yv.x, s0); s1 = fmaf(wv.y, yv.y, s1); s2 = fmaf(wv.z, yv.z, s2); s3 = fmaf(wv.w, yv.w, s3);
-    }
-    z = (s0 + s1) + (s2 + s3) + head_b[lane];
-  }
-  float mx = z;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  float ex = (lane < vocab) ? expf(z - mx) : 0.f;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) ex += __shfl_xor(ex, o);
-  return (z - mx) - logf(ex);
-}
-
-// one wave per layer-3 item row: mut_head_kernel's sums, the whole log_softmax row kept beside the own entry
+// one wave per layer-3 item row: mut_head_kernel's row (mut_head_row), the whole log_softmax row kept beside the own entry
 static __global__ __launch_bounds__(256) void state_head_kernel(const MutPlanArgs a, const StateScanArgs s, const float* __restrict__ h3,
                                                                  const float* __restrict__ head_w, const float* __restrict__ head_b) {
   const int lane = threadIdx.x & 63;
@@ -100,7 +69,7 @@ static __global__ __launch_bounds__(256) void state_head_kernel(const MutPlanArg
     if (lane == 0) { s.row_res[r] = -1; s.row_lp[r] = 0.f; }
     return;
   }
-  const float lp = state_head_row(h3 + r * NAMP_H, head_w, head_b, a.vocab, lane);
+  const float lp = mut_head_row(h3 + r * NAMP_H, head_w, head_b, a.vocab, lane);
   s.rows[r * 64 + lane] = lane < a.vocab ? lp : 0.f;
   if (lane == loo_clamp(s.tok[r], a.vocab)) s.row_lp[r] = lp;
   if (lane == 0) s.row_res[r] = s.ctr[r];

@@ -184,18 +184,6 @@ static inline int tied_item_stream(const NampModelW* w, const int prec, const fl
   return NAMP_OK;
 }
 
-__device__ __forceinline__ float tied_wave_max(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-__device__ __forceinline__ float tied_wave_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // One wave per (sequence k, residue g), lane = class; only the wave of a unit's leader works.  It walks the cycle (an ungrouped
 // residue is a cycle of one) in listed order: per member the own log-softmax of its logits row (its own entry -> member_lp, with
 // k = 0 the row -> log_probs) and, in a group, total[c] = sum_t w_t z_t[C_t[c]] (fma chain) + b[c] through the table of the LAST

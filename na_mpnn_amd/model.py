@@ -94,18 +94,18 @@ def output_section_layout(family, dims):
     if family == "tied_score":
         N, n_chunk = dims[0], dims[5]
         return [("header", 63, i32), ("unit_log_probs", n_chunk * N, f32), ("member_log_probs", n_chunk * N, f32)]
-    if family == "mutations":
-        ns, nv, rows3 = dims[3], dims[4], dims[10]
-        return [("site_rows", 3 * ns, i32), ("delta", nv, f32), ("row_residue", rows3, i32), ("row_token_log_prob", rows3, f32)]
-    if family == "state_mutations":
-        N, M, ns, nv, rows3 = dims[0], dims[3], dims[4], dims[5], dims[11]
-        return [("site_rows", 3 * ns, i32), ("delta", nv, f32), ("state_delta", nv * M, f32), ("row_residue", rows3, i32),
-                ("row_token_log_prob", rows3, f32), ("unit_residue", rows3, i32), ("unit_log_prob", rows3, f32), ("base_units", N // M, f32)]
-    if family in ("group_mutations", "class_mutations"):            # (the class scan: n_tables, n_classes behind n_dec)
-        dims = dims if family == "group_mutations" else dims[:3] + dims[5:]
-        N, ns, nv, rows3 = dims[0], dims[3], dims[4], dims[10]
-        return [("site_rows", 3 * ns, i32), ("delta", nv, f32), ("row_residue", rows3, i32), ("row_token_log_prob", rows3, f32),
-                ("unit_residue", rows3, i32), ("unit_log_prob", rows3, f32), ("base_units", N, f32), ("header", 63, i32)]
+    at = {"mutations": 3, "state_mutations": 4, "group_mutations": 3, "class_mutations": 5}     # where n_sites stands (behind n_dec and the family's own ints)
+    if family in at:                                                # one scan: a base list, and the tails of the family
+        q, N, M = at[family], dims[0], dims[3] if family == "state_mutations" else 1
+        ns, nv, rows3 = dims[q], dims[q + 1], dims[q + 7]
+        head = [("site_rows", 3 * ns, i32), ("delta", nv, f32)]
+        rows = [("row_residue", rows3, i32), ("row_token_log_prob", rows3, f32)]
+        units = [("unit_residue", rows3, i32), ("unit_log_prob", rows3, f32), ("base_units", N // M, f32)]
+        if family == "mutations":
+            return head + rows
+        if family == "state_mutations":
+            return head + [("state_delta", nv * M, f32)] + rows + units
+        return head + rows + units + [("header", 63, i32)]
     raise ValueError(f"no output section is described for {family!r}")
 
 
@@ -139,6 +139,58 @@ def _require_one_complex(fd, who, states_note):
         raise ValueError(f"{who} expects one input complex (B == 1); got S of shape {tuple(S.shape)}")
     if states_note is not None and fd.get("state_weights") is not None:
         raise NotImplementedError(f"{who} does not take state_weights ({states_note})")
+
+
+def _listed(v):
+    """Whether a tie list of a feature_dict names anything (None, [] and [[]] do not)."""
+    return v is not None and len(v) > 0 and not (len(v) == 1 and hasattr(v[0], "__len__") and len(v[0]) == 0)
+
+
+def _counted_weights(fd):
+    """w = mask * chain_mask of the one complex as a host list [L]."""
+    return [a * b for a, b in zip(fd["mask"][0].reshape(-1).tolist(), fd["chain_mask"][0].reshape(-1).tolist())]
+
+
+def _require_counted(st, w):
+    """Every residue the sites st name is counted (w != 0): the tied scans are differences of score_tied(), which edits no other."""
+    for r in sorted({int(r) for r in st.reshape(-1) if r >= 0}):
+        if w[r] == 0:
+            raise ValueError(f"residue {r} has mask * chain_mask == 0: score_tied would not apply an edit there")
+
+
+def _variant_library(S_true, st, tk, base_row=None):
+    """The explicit library of a scan's dense route -> int64 [n (+ 1), L]: per variant S with the tokens tk[v, 1:] at the residues of
+    its site st[tk[v, 0]] (padding -1 skipped); S itself in front of them (base_row "first"), behind them ("last") or absent (None)."""
+    n, L, dev = len(tk), S_true.shape[1], S_true.device
+    S_full = S_true.long().expand(n + (base_row is not None), L).clone()
+    res = st[tk[:, 0]].reshape(-1)
+    keep = res >= 0
+    vi = torch.from_numpy((base_row == "first") + np.repeat(np.arange(n), st.shape[1])[keep]).to(dev)
+    S_full[vi, torch.from_numpy(res[keep]).to(dev)] = torch.from_numpy(tk[:, 1:].reshape(-1)[keep]).to(dev)
+    return S_full
+
+
+def _scan_head(st, tk, dev, **own):
+    """What every route of score_mutations() reports of its arguments, and the `own` keys of the route."""
+    return {"site_index": torch.from_numpy(tk[:, 0].copy()).to(dev), "sites": torch.from_numpy(st).to(dev),
+            "site_tokens": torch.from_numpy(tk).to(dev), "site_rows": None, **own}
+
+
+def _empty_rows(dev):
+    """No variants -> (delta [0], row_offsets [1], row_residue [0], row_token_log_prob [0]); the sparse units have the same shapes."""
+    return (torch.zeros(0, device=dev), torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+            torch.zeros(0, device=dev))
+
+
+def _sparse_units(got, n, L):
+    """The sparse units of a cone scan: the leader rows of _cone_scan's "unit_residue" / "unit_log_prob", per variant ascending in the
+    unit's residue -> (unit_offsets int64 [n + 1], unit_residue, unit_log_prob)."""
+    ures, ulp = got["unit_residue"], got["unit_log_prob"]
+    vid = torch.repeat_interleave(torch.arange(n), got["row_counts"]).to(ures.device)
+    lead = ures >= 0
+    srt = torch.argsort(vid[lead] * L + ures[lead].long(), stable=True)
+    uoffs = torch.cat((torch.zeros(1, dtype=torch.int64, device=ures.device), torch.bincount(vid[lead], minlength=n).cumsum(0)))
+    return uoffs, ures[lead][srt], ulp[lead][srt]
 
 
 def tied_stream_keys(rank0, groups):
@@ -1628,7 +1680,7 @@ class ProteinMPNN(nn.Module):
                 self._check_tokens(torch.from_numpy(tk[:, 1:]), "site_tokens")
             return st, tk, None
         host = lambda key: [int(v) for v in fd[key][0].reshape(-1).tolist()]
-        w = [a * b for a, b in zip(fd["mask"][0].reshape(-1).tolist(), fd["chain_mask"][0].reshape(-1).tolist())]
+        w = _counted_weights(fd)
         if positions is None:
             pos = [i for i in range(L) if w[i] != 0]
         else:
@@ -1725,9 +1777,7 @@ class ProteinMPNN(nn.Module):
                 raise ValueError("score_mutations(classes=True) needs tied=True: class tables belong to the tied scan")
             return self._score_group_mutations(fd, positions, tokens, sites, site_tokens, pairs, method, True)
         if tied:
-            sym = fd.get("symmetry_residues")
-            listed = not (sym is None or len(sym) == 0 or (len(sym) == 1 and len(sym[0]) == 0))
-            if sw is not None and listed:
+            if sw is not None and _listed(fd.get("symmetry_residues")):
                 raise NotImplementedError("score_mutations(tied=True): symmetry_residues joined with state_weights are not supported")
             if sw is None:
                 return self._score_group_mutations(fd, positions, tokens, sites, site_tokens, pairs, method)
@@ -1737,13 +1787,12 @@ class ProteinMPNN(nn.Module):
                 return self._score_state_mutations(fd, positions, tokens, sites, site_tokens, pairs, method)
         st, tk, scan = self._mutation_arguments(fd, positions, tokens, sites, site_tokens, pairs)
         S_true, mask = fd["S"], fd["mask"]
-        L, n, n_sites, M = S_true.shape[1], len(tk), st.shape[0], st.shape[1]
+        L, n, n_sites = S_true.shape[1], len(tk), st.shape[0]
         cone_ok = self._item_routes_ok("score_mutations", method, "dense")
         _require_device(fd["X"], "X")
         dev = fd["X"].device
         w = (mask * fd["chain_mask"])[0].float()
-        out = {"site_index": torch.from_numpy(tk[:, 0].copy()).to(dev), "sites": torch.from_numpy(st).to(dev),
-               "site_tokens": torch.from_numpy(tk).to(dev), "site_rows": None}
+        out = _scan_head(st, tk, dev)
         use_cone, base = False, None
         if cone_ok and method != "dense" and n_sites:
             o = self._decoding_order(mask, fd["chain_mask"], fd["randn"])
@@ -1760,21 +1809,13 @@ class ProteinMPNN(nn.Module):
         if n == 0:
             sc = self.score(dict(fd, batch_size=1))
             base, order = sc["log_probs"], sc["decoding_order"]
-            delta = torch.zeros(0, device=dev)
-            rres, rlp = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev)
-            offs = torch.zeros(1, dtype=torch.int64, device=dev)
-            chunks = 0
+            (delta, offs, rres, rlp), chunks = _empty_rows(dev), 0
         elif use_cone:
             order = o.order[0]
             delta, offs, rres, rlp, chunks = (got[k] for k in ("delta", "row_offsets", "row_residue", "row_token_log_prob", "chunks"))
         else:
-            S_full = S_true.long().expand(n, L).clone()
-            vi = torch.from_numpy(np.repeat(np.arange(n), M)[(st[tk[:, 0]] >= 0).reshape(-1)]).to(dev)
-            res = st[tk[:, 0]].reshape(-1)
-            keep = res >= 0
-            S_full[vi, torch.from_numpy(res[keep]).to(dev)] = torch.from_numpy(tk[:, 1:].reshape(-1)[keep]).to(dev)
-            union = torch.tensor(sorted({int(r) for r in res[keep]}), dtype=torch.long)
-            lib = self.score_sequences(fd, S_full, union, method="dense")
+            union = torch.tensor(sorted({int(r) for r in st[tk[:, 0]].reshape(-1) if r >= 0}), dtype=torch.long)
+            lib = self.score_sequences(fd, _variant_library(S_true, st, tk), union, method="dense")
             base, order = lib["base_log_probs"], lib["decoding_order"]
             tlp = lib["token_log_probs"]
             btlp = base[0].gather(1, S_true[0].long()[:, None])[:, 0]
@@ -1865,8 +1906,7 @@ class ProteinMPNN(nn.Module):
         """The checked arguments of the specificity scan (no device needed) -> (state weights, M, L, ctx, sites [n_sites, s], site_tokens
         [n, 1 + s], scan: _mutation_arguments over SHARED residues; flat sites int32 [n_sites, 8] and flat variants int32 [n, 9]: the
         edit of shared residue r goes to all M copies m * L + r, absent ones too)."""
-        listed = lambda v: v is not None and len(v) > 0 and not (len(v) == 1 and hasattr(v[0], "__len__") and len(v[0]) == 0)
-        if pairs or any(listed(fd.get(k)) for k in ("symmetry_residues", "paired_residues")) or fd.get("pair_terms") is not None \
+        if pairs or any(_listed(fd.get(k)) for k in ("symmetry_residues", "paired_residues")) or fd.get("pair_terms") is not None \
                 or self._wobble_arguments(fd)[2]:
             raise NotImplementedError("score_mutations with state_weights scans backbone states alone: pairs=True, symmetry_residues, "
                                       "paired_residues, paired_wobble and pair_terms are not supported beside them")
@@ -1877,10 +1917,8 @@ class ProteinMPNN(nn.Module):
         s = int((st >= 0).sum(1).max()) if len(st) else 1
         if s * M > MUT_MAX_EDITS:
             raise ValueError(f"a site of {s} residues in {M} states is {s * M} edits on the flattened graph; at most {MUT_MAX_EDITS} fit")
-        w = [a * b for a, b in zip(fd["mask"][0].reshape(-1).tolist(), fd["chain_mask"][0].reshape(-1).tolist())]
-        for r in sorted({int(r) for r in st.reshape(-1) if r >= 0}):
-            if w[r] == 0:
-                raise ValueError(f"residue {r} has mask * chain_mask == 0: score_tied would not apply an edit there")
+        w = _counted_weights(fd)
+        _require_counted(st, w)
         return (state_w, M, L, ctx, st, tk, scan) + flat_sites_and_variants(st, tk, M, L)
 
     def _score_state_mutations(self, fd, positions, tokens, sites, site_tokens, pairs, method):
@@ -1910,9 +1948,7 @@ class ProteinMPNN(nn.Module):
         sw = torch.tensor(state_w if M > 1 else [1.0], dtype=torch.float32, device=dev)     # (M = 1: the own entry, as score_tied has it)
         w_flat = (counted[None] & present).reshape(N).float()
         unit_w = (sw[:, None] * present).reshape(N).float()
-        out = {"site_index": torch.from_numpy(tk[:, 0].copy()).to(dev), "sites": torch.from_numpy(st).to(dev),
-               "site_tokens": torch.from_numpy(tk).to(dev), "site_rows": None,
-               "state_weights": torch.tensor(state_w, dtype=torch.float32, device=dev)}
+        out = _scan_head(st, tk, dev, state_weights=torch.tensor(state_w, dtype=torch.float32, device=dev))
         o = self._decoding_order(mask, fd["chain_mask"], fd["randn"][:1])
         h_V, h_E, E_idx = self._encode_side_by_side(fd, o, state_w, M, L, ctx)
         self._check_tokens(S_true)
@@ -1929,29 +1965,14 @@ class ProteinMPNN(nn.Module):
             got = self._cone_scan(route, inputs, base, tk[:, 0], method)         # (the plan call: sizes, base rows, base units)
             out["site_rows"], btlp, use_cone = got["site_rows"], got["base_units"], got["use_cone"] and n > 0
         if use_cone:
-            delta, sdelta, offs, rres, rlp, ures, ulp, chunks = (got[k] for k in (
-                "delta", "state_delta", "row_offsets", "row_residue", "row_token_log_prob", "unit_residue", "unit_log_prob", "chunks"))
-            # the sparse units: the leader rows, per variant ascending in the shared residue
-            vid = torch.repeat_interleave(torch.arange(n), got["row_counts"]).to(dev)
-            lead = ures >= 0
-            key = vid[lead] * L + ures[lead].long()
-            srt = torch.argsort(key, stable=True)
-            ures, ulp = ures[lead][srt], ulp[lead][srt]
-            uoffs = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.bincount(vid[lead], minlength=n).cumsum(0)))
+            delta, sdelta, offs, rres, rlp, chunks = (got[k] for k in (
+                "delta", "state_delta", "row_offsets", "row_residue", "row_token_log_prob", "chunks"))
+            uoffs, ures, ulp = _sparse_units(got, n, L)                          # (ascending in the shared residue)
         elif n == 0:
-            delta, sdelta = torch.zeros(0, device=dev), torch.zeros(0, M, device=dev)
-            rres, rlp = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev)
-            ures, ulp = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev)
-            offs = uoffs = torch.zeros(1, dtype=torch.int64, device=dev)
-            chunks = 0
+            (delta, offs, rres, rlp), (_, uoffs, ures, ulp) = _empty_rows(dev), _empty_rows(dev)
+            sdelta, chunks = torch.zeros(0, M, device=dev), 0
         else:
-            S_full = S_true.long().expand(n + 1, L).clone()                      # the variants, and S itself as the last row
-            s_w = st.shape[1]
-            res = st[tk[:, 0]].reshape(-1)
-            keep = res >= 0
-            vi = torch.from_numpy(np.repeat(np.arange(n), s_w)[keep]).to(dev)
-            S_full[vi, torch.from_numpy(res[keep]).to(dev)] = torch.from_numpy(tk[:, 1:].reshape(-1)[keep]).to(dev)
-            lib = self.score_tied(fd, S_full, method="stream")
+            lib = self.score_tied(fd, _variant_library(S_true, st, tk, "last"), method="stream")
             own = lib["member_log_probs"]                                          # [n + 1, M, L]
             state_ll = torch.where((counted[None] & present)[None], own, torch.zeros_like(own)).sum(-1)
             delta = lib["log_likelihood"][:n] - lib["log_likelihood"][n]
@@ -1988,8 +2009,7 @@ class ProteinMPNN(nn.Module):
         """The checked arguments of the symmetric scan (no device needed) -> (ties: _conditional_arguments(tied=True) or None, groups:
         the validly tied groups in listed order, leader [L] as a list, st [n_sites, s] and tk [n, 1 + s] as NAMED, scan, st_x / tk_x:
         expand_group_sites, sites8 int32 [n_sites, 8], tok9 int32 [n, 9])."""
-        listed = lambda v: v is not None and len(v) > 0 and not (len(v) == 1 and hasattr(v[0], "__len__") and len(v[0]) == 0)
-        if pairs or fd.get("symmetry_token_maps") is not None or listed(fd.get("paired_residues")) or fd.get("pair_terms") is not None \
+        if pairs or fd.get("symmetry_token_maps") is not None or _listed(fd.get("paired_residues")) or fd.get("pair_terms") is not None \
                 or self._wobble_arguments(fd)[2]:
             raise NotImplementedError("score_mutations(tied=True) scans symmetry groups with identity token maps: symmetry_token_maps, "
                                       "paired_residues, pairs=True, paired_wobble and pair_terms are not supported")
@@ -2004,14 +2024,12 @@ class ProteinMPNN(nn.Module):
                 raise ValueError(f"feature_dict['S'] is not tie-consistent on the group of residue {g[0]}: a tied scan has no base there")
             for r in g:
                 leader[r] = g[0]
-        w = [a * b for a, b in zip(fd["mask"][0].reshape(-1).tolist(), fd["chain_mask"][0].reshape(-1).tolist())]
+        w = _counted_weights(fd)
         if positions is None and sites is None and site_tokens is None:
             positions = torch.tensor([i for i in range(L) if leader[i] == i and w[i] != 0], dtype=torch.long)
         plain = {k: v for k, v in fd.items() if k not in ("symmetry_residues", "symmetry_weights")}
         st, tk, scan = self._mutation_arguments(plain, positions, tokens, sites, site_tokens, False)
-        for r in sorted({int(r) for r in st.reshape(-1) if r >= 0}):
-            if w[r] == 0:
-                raise ValueError(f"residue {r} has mask * chain_mask == 0: score_tied would not apply an edit there")
+        _require_counted(st, w)
         st_x, tk_x = expand_group_sites(st, tk, groups, L)
         return (ties, groups, leader, st, tk, scan, st_x, tk_x) + flat_sites_and_variants(st_x, tk_x, 1, L)
 
@@ -2037,7 +2055,7 @@ class ProteinMPNN(nn.Module):
                 raise ValueError(f"feature_dict['S'] matches no class of the unit of residue {members[0]}: a tied scan has no base there")
             for r in members:
                 leader[r], unit_of[r] = members[0], (members, tables)
-        w = [a * b for a, b in zip(fd["mask"][0].reshape(-1).tolist(), fd["chain_mask"][0].reshape(-1).tolist())]
+        w = _counted_weights(fd)
         general = sites is not None or site_tokens is not None
         if positions is None and not general:
             positions = torch.tensor([i for i in range(L) if leader[i] == i and w[i] != 0], dtype=torch.long)
@@ -2078,9 +2096,7 @@ class ProteinMPNN(nn.Module):
             plain = {k: v for k, v in fd.items() if k not in ("symmetry_residues", "symmetry_weights", "symmetry_token_maps", "paired_residues",
                                                               "paired_weights", "paired_wobble", "paired_wobble_bias")}
             st, tk, scan = self._mutation_arguments(plain, positions, tokens, sites, site_tokens, False)
-        for r in sorted({int(r) for r in st.reshape(-1) if r >= 0}):
-            if w[r] == 0:
-                raise ValueError(f"residue {r} has mask * chain_mask == 0: score_tied would not apply an edit there")
+        _require_counted(st, w)
         st_x, tk_x = expand_class_sites(st, tk, units, L)
         return (ties, [m for m, _ in units], leader, st, tk, scan, st_x, tk_x) + flat_sites_and_variants(st_x, tk_x, 1, L) + (extra,)
 
@@ -2126,8 +2142,7 @@ class ProteinMPNN(nn.Module):
         counted = torch.zeros(L, dtype=torch.bool, device=dev)
         counted[leader] = True
         counted &= cm
-        out = {"site_index": torch.from_numpy(tk[:, 0].copy()).to(dev), "sites": torch.from_numpy(st).to(dev),
-               "site_tokens": torch.from_numpy(tk).to(dev), "site_rows": None, "leader": leader}
+        out = _scan_head(st, tk, dev, leader=leader)
         use_cone, base, btlp, order = False, None, None, None
         if cone_ok and method != "dense" and n_sites:
             o = self._decoding_order(mask, fd["chain_mask"], fd["randn"])
@@ -2160,21 +2175,10 @@ class ProteinMPNN(nn.Module):
             got = self._cone_scan(route, inputs, base, tk[:, 0], method)         # (the plan call: sizes, base rows, base units)
             out["site_rows"], btlp, use_cone = got["site_rows"], got["base_units"], got["use_cone"] and n > 0
         if use_cone:
-            delta, offs, rres, rlp, ures, ulp, chunks = (got[k] for k in (
-                "delta", "row_offsets", "row_residue", "row_token_log_prob", "unit_residue", "unit_log_prob", "chunks"))
-            # the sparse units: the leader rows, per variant ascending in the unit's listed-first member
-            vid = torch.repeat_interleave(torch.arange(n), got["row_counts"]).to(dev)
-            lead = ures >= 0
-            srt = torch.argsort(vid[lead] * L + ures[lead].long(), stable=True)
-            ures, ulp = ures[lead][srt], ulp[lead][srt]
-            uoffs = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.bincount(vid[lead], minlength=n).cumsum(0)))
+            delta, offs, rres, rlp, chunks = (got[k] for k in ("delta", "row_offsets", "row_residue", "row_token_log_prob", "chunks"))
+            uoffs, ures, ulp = _sparse_units(got, n, L)                          # (ascending in the unit's listed-first member)
         else:
-            S_full = S_true.long().expand(n + 1, L).clone()                      # S itself, then the variants
-            res = st_x[tk_x[:, 0]].reshape(-1)
-            keep = res >= 0
-            vi = torch.from_numpy(1 + np.repeat(np.arange(n), st_x.shape[1])[keep]).to(dev)
-            S_full[vi, torch.from_numpy(res[keep]).to(dev)] = torch.from_numpy(tk_x[:, 1:].reshape(-1)[keep]).to(dev)
-            lib = self.score_tied(fd, S_full, method="auto")
+            lib = self.score_tied(fd, _variant_library(S_true, st_x, tk_x, "first"), method="auto")
             tlp, own = lib["token_log_probs"], lib["member_log_probs"][:, 0]
             if not torch.equal(lib["leader"], leader):
                 raise RuntimeError("score_mutations(tied=True): score_tied reads other units than the scan")

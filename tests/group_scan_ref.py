@@ -33,7 +33,7 @@ def expand(sites, groups):
 
 
 def lead_rows(u3, leader, gpos, mask):
-    """The leader rule of group_unit_kernel on one variant's ascending layer-3 list: row r leads if it is unmasked and no earlier-listed
+    """The leader rule of group_unit_kernel<Combine> on one variant's ascending layer-3 list: row r leads if it is unmasked and no earlier-listed
     member of its unit is in the list -> bool [len(u3)]."""
     here = set(int(r) for r in u3)
     out = []

@@ -10,7 +10,7 @@ route's 3 L) and the number of decoder calls.
                     symmetric one: a 2 x 150 RNA duplex, K = 48, wobble on, every pair over its 6 classes (n = 900), and a 300-residue
                     protein beside a 2 x 20 RNA duplex, K = 32 (n = 120); the second strand runs antiparallel 10 A beside the first
     --parent PATH   another build of the library (libnamp_hip.so of the parent commit) as a second library of this process: score(),
-                    the plain, the state and the group scan on their cones, score_tied(items) on the trimer at n = 100, conditional_probs(tied=True)
+                    the plain, the state, the group and the paired scan on their cones, score_tied(items) on the trimer at n = 100, conditional_probs(tied=True)
                     and the cfg1 design call (97 residues, K = 32, batch_size 1) run alternated on both builds; per call this build's
                     median - its median beside the larger min-max spread of the two, and whether the results are its bits.
 """
@@ -188,6 +188,11 @@ if arg("--parent", ""):
         fd1 = to_fd(cx1)
         fd1.update(temperature=0.1, bias=torch.zeros(1, 97, 33, device=dev), symmetry_residues=[[]], symmetry_weights=[[]],
                    S_forced=fd1["S"].long())                           # (forced draws: the two builds' results can be compared bit for bit)
+        cxp, prs = duplex(0, 150)                                      # (the first duplex of --pairs)
+        fdp = to_fd(cxp)
+        fdp.update(paired_residues=prs, paired_wobble=True, paired_wobble_bias=0.0, symmetry_residues=[[]], symmetry_weights=[[]],
+                   temperature=1.0, bias=torch.zeros(1, len(cxp["S"]), 33, device=dev))
+        firsts = torch.tensor(sorted(p[0] for p in prs), device=dev)
         m, m48 = model(32), model(K)
         m.message_precision = m48.message_precision = prec
         forms = {"score()": (lambda: m.score(fd0), "log_probs"),
@@ -195,6 +200,8 @@ if arg("--parent", ""):
                  "score_mutations(cone), 2 states, 40 positions": (lambda: m.score_mutations(fds, method="cone"), "delta_log_likelihood"),
                  f"score_mutations(cone, tied=True), {copies} x {n_res} trimer, 100 units x 20":
                      (lambda: m48.score_mutations(fd, positions=positions, method="cone", tied=True), "delta_log_likelihood"),
+                 f"score_mutations(cone, pairs=True, tied=True, classes=True), 2 x 150 RNA duplex, {len(prs)} pairs x 6 classes":
+                     (lambda: m48.score_mutations(fdp, positions=firsts, pairs=True, method="cone", tied=True, classes=True), "delta_log_likelihood"),
                  f"score_tied(items), {copies} x {n_res} trimer, n = 100": (lambda: m48.score_tied(fd, lib, method="items"), "token_log_probs"),
                  "conditional_probs(tied=True), the trimer": (lambda: m48.conditional_probs(fd, tied=True), "log_probs"),
                  "cfg1 design call": (lambda: m.sample(fd1), "log_probs")}
